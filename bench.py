@@ -2,6 +2,7 @@
 """bench.py -- QuakeIndex::search() hot path on MI355X: queries/sec at recall@10 >= 0.9.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + everything below the headline (rooflines, CPU legs, workloads)
     python bench.py --gpus N --steps K --warmup W          # N = 2, 4, 8: starts its own N ranks (launch_ranks), or, equivalently,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -9,10 +10,14 @@
 Headline workload (BASELINE.json configs[1], SURVEY.md section 8d "C2"): synthetic 10M x 128 f32 Gaussian mixture (4096
 centres ~N(0,1), within-cluster sigma 0.3), L2, nlist=4096 built with the GPU k-means, batches of 1024 queries, k=10.
 One "step" = one qk_search() of a whole batch (coarse + partition scan + merge) with queries, index and outputs resident
-in HBM; the timed region rotates over 4 different query batches.  nprobe = the smallest of {1,2,4,...,64} reaching
-recall@10 >= 0.9 against exact brute force.
+in HBM; the timed region rotates over 4 different query batches and is exactly `--steps` steps between synchronisations.
+nprobe = the smallest of {1,2,4,...,64} reaching recall@10 >= 0.9 against exact brute force.
 
-Next to the headline line the same JSON object carries (N = 1 only, `--no-extra` skips them):
+A plain run sets up, warms up, times the steps and prints the headline line (`value`, `ms_per_step`); `--dump-outputs DIR`
+also writes the ids and distances of the last timed step (DIR/ids.npy as float64, DIR/distances.npy as float32): the inputs
+are seeded, so two builds can be compared output for output.  Everything else is measured with `--full` only.
+
+With `--full`, next to the headline line the same JSON object carries (N = 1 only, `--no-extra` skips them):
   workloads.hard      the same sizes on a corpus WITHOUT cluster structure (x = zA + noise, latent dimension 10: a smooth
                       low-intrinsic-dimension density like SIFT / embeddings): the recall target NEEDS nprobe >> 1 -- the
                       regime where a probed partition is shared by many queries of the batch; reported with its own
@@ -26,7 +31,7 @@ all ranks (local assign + accumulate, all-reduce of sums and counts per iteratio
 nlist = 8192*N global centroids, replicated; list p lives on rank p % N; the batch is 512*N queries; every rank computes
 the coarse step, scans the probed lists it owns and the per-rank top-k meet in one all-to-all + merge.
 
-`roofline` is for the dominant kernel (k_scan, HBM-bound): algorithmic bytes per launch (sum over unique probed
+With `--full`, `roofline` is for the dominant kernel (k_scan, HBM-bound): algorithmic bytes per launch (sum over unique probed
 partitions of n_p*d*4) / the kernel's mean duration measured with HIP events recorded on the launch stream inside the
 timed region.  `cpu_baseline` times oracle/ (the CPU port of the reference path) on the host cores on a bounded sample
 of the same queries; the ids of the bench batch must equal the batched oracle's, bit for bit, or the run fails.
@@ -165,6 +170,29 @@ def recall_at_k(ids, gt, k):
     return hit.mean().item()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def keep_outputs(out):
+    """what a step returned (ids, distances), copied before any later step reuses the output buffers"""
+    return tuple(t.clone(memory_format=torch.contiguous_format) for t in out[:2])
+
+
+def dump_outputs(path, ids, dists):
+    """--dump-outputs DIR: the answer of the last timed step as DIR/ids.npy (float64: every id is exact below 2^53) and
+    DIR/distances.npy (float32).  Above DUMP_LIMIT_BYTES in all, the same seeded sample of query rows is written from both."""
+    ids = ids.cpu().numpy().astype(np.float64)
+    dists = dists.cpu().numpy().astype(np.float32)
+    total = ids.nbytes + dists.nbytes
+    if total > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], ids.shape[0] * DUMP_LIMIT_BYTES // total, replace=False))
+        ids, dists = ids[rows], dists[rows]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ids.npy"), ids)
+    np.save(os.path.join(path, "distances.npy"), dists)
+    log(f"outputs of the last timed step: {ids.shape[0]} x {ids.shape[1]} ids and distances in {path}")
+
+
 # ---- single-GPU index build (untimed) -------------------------------------------------------------------------------------
 def build_single(ctx, dev, x, nlist, metric, niter, keep_host):
     """k-means on the GPU, vectors bucketed by list, device store + flat parent over the centroids."""
@@ -238,22 +266,24 @@ def pick_nprobe(step, batches, gts, k, target, fixed, recall_fn):
     return nprobe, rec(nprobe), sweep
 
 
-MIN_TIMED_STEPS = 200  # a 20-step region of a 0.3 ms step is 6 ms: one clock excursion moves it by 2-3 %
+EXTRA_TIMED_STEPS = 200  # the extra workloads of --full: median of groups of steps, 200 in all (a 20-step region of a 0.3 ms step is
+# 6 ms: one clock excursion moves it by 2-3 %)
 
 
-def timed_region(ctx, step, nprobe, steps, warmup, settle, dist, dev, ctxs=None, groups=None, sync=None):
-    """settle + warmup untimed, then EXACTLY `steps` steps between barrier + synchronize; one HIP event pair per step around
-    the scan kernel (timing mode 3).  ctxs: the contexts the steps rotate over (step i runs on ctxs[i % len]; each has its own
-    stream and output buffers, so len(ctxs) batches are in flight at a time); default [ctx].
-    The region is run `groups` times (default: as many as it takes to time MIN_TIMED_STEPS steps in all, at most 10) -- every
-    group is exactly `steps` steps between barrier + synchronize on both sides -- and the MEDIAN group is the one reported:
-    `elapsed` is its wall time (max over ranks); group_times lists them all.
+def timed_region(ctx, step, nprobe, steps, warmup, settle, dist, dev, ctxs=None, groups=1, sync=None, measure=True, on_last=None):
+    """settle + warmup untimed, then EXACTLY `steps` steps between barrier + synchronize.  ctxs: the contexts the steps rotate
+    over (step i runs on ctxs[i % len]; each has its own stream and output buffers, so len(ctxs) batches are in flight at a
+    time); default [ctx].
+    The region is run `groups` times (default once: the headline times exactly `steps` steps) -- every group is exactly `steps`
+    steps between barrier + synchronize on both sides -- and the MEDIAN group is the one reported: `elapsed` is its wall time
+    (max over ranks); group_times lists them all.
+    measure: one HIP event pair per step around the scan kernel (timing mode 3) and, after the region, a short untimed pass
+    with events around every phase; off, the event sums are None.
     sync: extra synchronisation of the path under test (the device group's members), called beside the contexts'.
+    on_last: called with what the last timed step returned, once the region is over and before any other step runs.
     Returns (elapsed seconds, scan-kernel event sums over all groups, phase sums, group_times)."""
     ctxs = ctxs or [ctx]
     nc = len(ctxs)
-    if groups is None:
-        groups = max(1, min(10, -(-MIN_TIMED_STEPS // max(steps, 1))))
 
     def sync_all():
         for c in ctxs:
@@ -276,25 +306,31 @@ def timed_region(ctx, step, nprobe, steps, warmup, settle, dist, dev, ctxs=None,
         step(nprobe, i % N_BATCHES, i % nc)
     for i in range(warmup):
         step(nprobe, i % N_BATCHES, i % nc)
-    for c in ctxs:
-        c.set_timing(3)
+    if measure:
+        for c in ctxs:
+            c.set_timing(3)
     times = []
+    last = None
     for _ in range(groups):
         if dist is not None:
             dist.barrier()
         sync_all()
         t0 = time.perf_counter()
         for i in range(steps):
-            step(nprobe, i % N_BATCHES, i % nc)
+            last = step(nprobe, i % N_BATCHES, i % nc)
         if dist is not None:
             dist.barrier()
         sync_all()
         times.append(time.perf_counter() - t0)
+    if on_last is not None:
+        on_last(last)
     if dist is not None:  # a group's time is the slowest rank's
         tt = torch.tensor(times, dtype=torch.float64, device=dev if str(dist.get_backend()).lower() != "gloo" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         times = tt.tolist()
     elapsed = sorted(times)[(len(times) - 1) // 2]  # the median group (the lower one of an even count)
+    if not measure:
+        return elapsed, None, None, times
     ev = None
     for c in ctxs:  # the scan-kernel event pairs of all streams
         e = c.read_timing()
@@ -491,10 +527,13 @@ def cpu_sgemm_search(qh, hc, hv, hi, ho, nprobe, k, metric, threads):
 
 
 def run_single_workload(ctx, dev, args, name, sigma, fixed_nprobe, steps, warmup, settle, cpu_seconds, traffic_file=None,
-                        manifold=0, sweep_nprobes=(), with_aps=None):
-    """Build, sweep nprobe, time, verify against the oracle.  Returns the result dict of one single-GPU workload.
+                        manifold=0, sweep_nprobes=(), with_aps=None, groups=1):
+    """Build, sweep nprobe, time; with args.full also measure beside the timed region and verify against the oracle.  Returns
+    the result dict of one single-GPU workload; its "outputs" are the (ids, distances) of the last timed step.
+    groups: timed groups of `steps` steps, the median one reported (timed_region).
     manifold > 0: the low-intrinsic-dimension corpus (gen_manifold, latent dimension `manifold`) instead of the mixture."""
     n, d, nlist, k, Q, metric = args.nvec, args.dim, args.nlist, args.k, args.batch, args.metric
+    full = args.full
     unit = metric == "ip"
     t0 = time.time()
     sift = None
@@ -516,7 +555,7 @@ def run_single_workload(ctx, dev, args, name, sigma, fixed_nprobe, steps, warmup
         desc = f"Gaussian mixture (sigma {sigma})"
     torch.cuda.synchronize()
     log(f"[{name}] generated {n}x{d} ({desc}) in {time.time() - t0:.1f}s")
-    want_cpu = not args.no_cpu
+    want_cpu = full and not args.no_cpu
     idx = build_single(ctx, dev, x, nlist, metric, args.niter, keep_host=want_cpu)
     parent, store = idx["parent"], idx["store"]
     if sift is not None:
@@ -539,7 +578,7 @@ def run_single_workload(ctx, dev, args, name, sigma, fixed_nprobe, steps, warmup
     # stores -- so the small kernels of one batch (prep, nearest centroid, group + seed, merge) run under the partition
     # scan of another.  (The extra contexts use the library's private non-blocking streams.)
     from quake_amd.capi import Context
-    inflight = max(1, int(args.inflight))
+    inflight = max(1, int(args.inflight)) if full else 1
     ctxs = [ctx] + [Context(dev.index) for _ in range(inflight - 1)]
     outs = [(torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
             for _ in range(inflight)]
@@ -550,11 +589,34 @@ def run_single_workload(ctx, dev, args, name, sigma, fixed_nprobe, steps, warmup
     nprobe, recall, sweep = pick_nprobe(step, batches, gts, k, args.recall_target, fixed_nprobe,
                                         lambda ri, b: recall_at_k(ri, gts[b], k))
     log(f"[{name}] nprobe={nprobe} recall@{k}={recall:.4f} sweep={sweep}")
-    ctx.set_timing(1)
-    _, _, tinfo = ctx.search(parent, store, batches[0], nprobe, k, metric, timing=True)
-    log(f"[{name}] phases (ms):", {kk: round(v, 4) if isinstance(v, float) else v for kk, v in tinfo.items()})
+    if full:
+        ctx.set_timing(1)
+        _, _, tinfo = ctx.search(parent, store, batches[0], nprobe, k, metric, timing=True)
+        log(f"[{name}] phases (ms):", {kk: round(v, 4) if isinstance(v, float) else v for kk, v in tinfo.items()})
     # the timed region of the contract: one batch at a time on one stream
-    elapsed, ev, ev_ph, gtimes = timed_region(ctx, step, nprobe, steps, warmup, settle, None, dev, ctxs=[ctx])
+    last = []
+    elapsed, ev, ev_ph, gtimes = timed_region(ctx, step, nprobe, steps, warmup, settle, None, dev, ctxs=[ctx], groups=groups,
+                                              measure=full, on_last=lambda out: last.append(keep_outputs(out)))
+    res = {
+        "value": round(Q * steps / elapsed, 1), "unit": "queries/s", "ms_per_step": round(1e3 * elapsed / steps, 4),
+        "steps": steps, "warmup": warmup, "timed_groups": groups_of(gtimes, steps, Q),
+        "config": {
+            "workload": (f"{os.path.basename(os.path.normpath(args.sift_dir))} {n} x {d} f32 {metric.upper()} ({desc}), " if sift is not None else
+                         f"Synthetic {n // 1_000_000}M x {d} f32 {metric.upper()} {'unit-norm ' if unit else ''}{desc}, ")
+                        + f"nlist={nlist}, batch={Q} queries, k={k}, nprobe={nprobe}",
+            "data": "dataset files (--sift-dir)" if sift is not None else "synthetic",
+            "nvec": n, "dim": d, "metric_type": metric, "nlist": nlist, "batch": Q, "k": k, "nprobe": nprobe,
+            "sigma": None if manifold else sigma, "latent_dim": manifold or None,
+            "recall_at_k": round(recall, 4), "recall_sweep": sweep, "settle_steps": max(settle, 0),
+            "query_batches_rotated": N_BATCHES,
+        },
+        "build": {"kmeans_s": round(idx["kmeans_s"], 2), "niter": args.niter, "last_iteration": idx.get("kmeans_kernels")},
+        "outputs": last[0],
+    }
+    if not full:
+        store.close()
+        parent.close()
+        return res
     piped = None
     if inflight > 1:  # the same steps with `inflight` batches in flight, reported beside the headline figure (never `value`)
         n2 = max(steps // 2, 10)
@@ -621,25 +683,12 @@ def run_single_workload(ctx, dev, args, name, sigma, fixed_nprobe, steps, warmup
                           "steps": 30, "recall_at_k": round(recall_at_k(ri, gts[0], k), 4),
                           "roofline": roofline_of(sb, ev_s, mt["bytes_per_launch"] if mt else None, kernel=kern, pair_rows=pair_rows_of(npb), d=d,
                                                   traffic_source=f"rocprofv3 --pmc FETCH_SIZE in this run ({mt['kernel']}, {mt['launches']} launches)" if mt else None)})
-    res = {
-        "value": round(Q * steps / elapsed, 1), "unit": "queries/s", "ms_per_step": round(1e3 * elapsed / steps, 4),
-        "steps": steps, "warmup": warmup, "timed_groups": groups_of(gtimes, steps, Q),
-        "config": {
-            "workload": (f"{os.path.basename(os.path.normpath(args.sift_dir))} {n} x {d} f32 {metric.upper()} ({desc}), " if sift is not None else
-                         f"Synthetic {n // 1_000_000}M x {d} f32 {metric.upper()} {'unit-norm ' if unit else ''}{desc}, ")
-                        + f"nlist={nlist}, batch={Q} queries, k={k}, nprobe={nprobe}",
-            "data": "dataset files (--sift-dir)" if sift is not None else "synthetic",
-            "nvec": n, "dim": d, "metric_type": metric, "nlist": nlist, "batch": Q, "k": k, "nprobe": nprobe,
-            "sigma": None if manifold else sigma, "latent_dim": manifold or None,
-            "recall_at_k": round(recall, 4), "recall_sweep": sweep, "settle_steps": max(settle, 0),
-            "query_batches_rotated": N_BATCHES,
-        },
+    res.update({
         "batches_in_flight": piped,
         "roofline": roofline_of(scan_bytes, ev, traffic, kernel=scan_kernel, pair_rows=pair_rows, d=d, traffic_source=traffic_source),
         "host_api": host_api,
         "phases_ms": phases_of(ev_ph),
-        "build": {"kmeans_s": round(idx["kmeans_s"], 2), "niter": args.niter, "last_iteration": idx.get("kmeans_kernels")},
-    }
+    })
     if sweep_res:
         res["nprobe_sweep"] = sweep_res
     # the recall-target search (adaptive partition scanning, SearchParams.recall_target > 0) on the same index: rounds on the
@@ -998,7 +1047,34 @@ def run_sharded(ctx, dev, args, dist, rank, world):
 
     nprobe, recall, sweep = pick_nprobe(step, batches, gts, k, args.recall_target, args.nprobe, rec)
     log(f"nprobe={nprobe} recall@{k}={recall:.4f} sweep={sweep}")
-    elapsed, ev, ev_ph, gtimes = timed_region(ctx, step, nprobe, args.steps, args.warmup, args.settle, dist, dev)
+    last = []
+    elapsed, ev, ev_ph, gtimes = timed_region(ctx, step, nprobe, args.steps, args.warmup, args.settle, dist, dev, measure=args.full,
+                                              on_last=lambda out: last.append(keep_outputs(out)))
+    outputs = None
+    if args.dump_outputs:  # the answer of the last timed step for the whole batch: every rank holds the slice of the queries it owns
+        li, ld = last[0]
+        all_i, all_d = [torch.empty_like(li) for _ in range(world)], [torch.empty_like(ld) for _ in range(world)]
+        _all_gather(dist, all_i, li)
+        _all_gather(dist, all_d, ld)
+        outputs = (torch.cat(all_i), torch.cat(all_d))
+    res = {
+        "value": round(Q * args.steps / elapsed, 1), "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "timed_groups": groups_of(gtimes, args.steps, Q),
+        "config": {
+            "workload": f"Synthetic {n * world // 1_000_000}M x {d} f32 {metric.upper()} Gaussian mixture, nlist={nlist_g} "
+                        f"(one k-means over all ranks), lists sharded by number over {world} ranks, batch={Q} queries, k={k}, "
+                        f"nprobe={nprobe} (BASELINE.json configs[3] shape: 12.5M vectors, 8192 lists and 512 queries per GPU)",
+            "nvec_per_gpu": n, "dim": d, "metric_type": metric, "nlist": nlist_g, "batch": Q, "k": k, "nprobe": nprobe,
+            "recall_at_k": round(recall, 4), "recall_sweep": sweep, "settle_steps": max(args.settle, 0),
+            "query_batches_rotated": N_BATCHES,
+            "sharding": "list p on rank p % N, centroids replicated; every rank computes the coarse step, scans the probed "
+                        "lists it owns; all-to-all of the per-rank top-k, merge on the rank that owns the query",
+        },
+        "build": {"sharded_kmeans_s": round(t_kmeans, 2), "niter": args.niter},
+        "outputs": outputs,
+    }
+    if not args.full:
+        return res
     ctx.set_timing(1)
     sb = torch.tensor([float(sharded.engine.last_scan_bytes(batches[0], nprobe, k))], device=dev, dtype=torch.float64)
     ctx.set_timing(0)
@@ -1028,27 +1104,15 @@ def run_sharded(ctx, dev, args, dist, rank, world):
                             "record": "12 bytes per entry (int64 id + float32 key), block j = the results for the queries rank j owns"},
         "collectives_per_step": 2,
     }
-    return {
-        "value": round(Q * args.steps / elapsed, 1), "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-        "timed_groups": groups_of(gtimes, args.steps, Q),
+    res.update({
         "per_rank": seen, "exchange": exchange,
         "rccl_ranks_seen": {"backend": str(dist.get_backend()), "ranks": world,
                             "distinct_devices": len({(r_["pci_bus_id"], r_["uuid"], r_["device_index"]) for r_ in seen}),
                             "ranks_described": len(seen)},
-        "config": {
-            "workload": f"Synthetic {n * world // 1_000_000}M x {d} f32 {metric.upper()} Gaussian mixture, nlist={nlist_g} "
-                        f"(one k-means over all ranks), lists sharded by number over {world} ranks, batch={Q} queries, k={k}, "
-                        f"nprobe={nprobe} (BASELINE.json configs[3] shape: 12.5M vectors, 8192 lists and 512 queries per GPU)",
-            "nvec_per_gpu": n, "dim": d, "metric_type": metric, "nlist": nlist_g, "batch": Q, "k": k, "nprobe": nprobe,
-            "recall_at_k": round(recall, 4), "recall_sweep": sweep, "settle_steps": max(args.settle, 0),
-            "query_batches_rotated": N_BATCHES,
-            "sharding": "list p on rank p % N, centroids replicated; every rank computes the coarse step, scans the probed "
-                        "lists it owns; all-to-all of the per-rank top-k, merge on the rank that owns the query",
-        },
         "roofline": my_roof,
         "phases_ms": phases_of(ev_ph),
-        "build": {"sharded_kmeans_s": round(t_kmeans, 2), "niter": args.niter},
-    }
+    })
+    return res
 
 
 # ---- one rank's step of BASELINE.json configs[3] (8 x MI355X), on ONE GPU, without the exchange ---------------------------------
@@ -1203,15 +1267,9 @@ def run_group(ctx, dev, args, world):
     nprobe, recall, sweep = pick_nprobe(step, batches, gts, k, args.recall_target, args.nprobe, lambda ri, b: recall_at_k(ri, gts[b], k))
     log(f"[group] nprobe={nprobe} recall@{k}={recall:.4f} sweep={sweep}")
     # parity: the group's answer == the one-store search over the same lists (when the whole index also fits one store: N small)
-    elapsed, _, _, gtimes = timed_region(ctx, step, nprobe, args.steps, args.warmup, args.settle, None, dev, sync=grp.synchronize)
-    _, _, tm = grp.search(parent, batches[0], nprobe, k, metric, timing=True)
-    sb = 0
-    for b in range(N_BATCHES):
-        sb += int(grp.search(parent, batches[b], nprobe, k, metric, timing=True)[2]["scan_bytes"])
-    sb //= N_BATCHES
-    # every member streams its share of the unique bytes concurrently: aggregate bytes / the lead's scan phase against N x peak
-    scan_ms = tm["scan_ms"]
-    agg = sb / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+    last = []
+    elapsed, _, _, gtimes = timed_region(ctx, step, nprobe, args.steps, args.warmup, args.settle, None, dev, sync=grp.synchronize,
+                                         measure=args.full, on_last=lambda out: last.append(keep_outputs(out)))
     distinct = len(set(devices))
     res = {
         "value": round(Q * args.steps / elapsed, 1), "ms_per_step": round(1e3 * elapsed / args.steps, 4),
@@ -1228,6 +1286,22 @@ def run_group(ctx, dev, args, world):
                         "the lead; " + ("members SHARE devices: a functional run, not a scaling figure" if distinct < world else
                                         "one member per GPU"),
         },
+        "build": {"kmeans_s": round(t_kmeans, 2), "niter": args.niter},
+        "outputs": last[0],
+    }
+    if not args.full:
+        grp.close()
+        parent.close()
+        return res
+    _, _, tm = grp.search(parent, batches[0], nprobe, k, metric, timing=True)
+    sb = 0
+    for b in range(N_BATCHES):
+        sb += int(grp.search(parent, batches[b], nprobe, k, metric, timing=True)[2]["scan_bytes"])
+    sb //= N_BATCHES
+    # every member streams its share of the unique bytes concurrently: aggregate bytes / the lead's scan phase against N x peak
+    scan_ms = tm["scan_ms"]
+    agg = sb / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+    res.update({
         "roofline": {"kernel": "partition scan of every member (lead's scan phase: entry of the scans to the arrival of the last block)",
                      "bound": "hbm", "achieved": round(agg, 1), "peak": HBM_PEAK_GBS * distinct, "unit": "GB/s",
                      "frac": round(agg / (HBM_PEAK_GBS * distinct), 4), "traffic": None, "algorithmic_bytes_per_launch": int(sb),
@@ -1236,8 +1310,7 @@ def run_group(ctx, dev, args, world):
                              f"{distinct} x the HBM peak"},
         "phases_ms": {"coarse": round(tm["coarse_ms"], 4), "group": 0.0, "scan": round(tm["scan_ms"], 4), "merge": round(tm["merge_ms"], 4),
                       "note": "events on the lead's stream: coarse = batch in to list numbers everywhere; scan = to the last packed block; merge"},
-        "build": {"kmeans_s": round(t_kmeans, 2), "niter": args.niter},
-    }
+    })
     grp.close()
     parent.close()
     return res
@@ -1305,7 +1378,16 @@ def main():
     ap.add_argument("--sift-dir", default="", help="directory with <name>_base.fvecs / _query.fvecs [/ _groundtruth.ivecs] (e.g. TEXMEX sift/): "
                     "the headline workload runs on these vectors verbatim instead of the synthetic mixture (use --nlist 1024 for configs[0]'s index)")
     ap.add_argument("--only", default="", help="comma-separated subset of the extra workloads (hard,configs0,configs2,configs3_rank_step)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: rooflines (with the in-run rocprofv3 pass), phases, batches in "
+                         "flight, host-buffer rate, nprobe sweep, recall-target search, CPU legs with the oracle parity check, the extra "
+                         "workloads (N > 1: every rank's roofline, devices, exchange bytes); --no-cpu, --no-extra, --no-pmc, "
+                         "--no-host-api, --inflight and --only trim it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the answer of the last timed step: DIR/ids.npy (float64) and DIR/distances.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.single_process:
         return main_single_process(args)
@@ -1365,25 +1447,24 @@ def main():
         main_res["config"]["sharding"] = "single GPU"
     else:
         main_res = run_sharded(ctx, dev, args, dist, rank, world)
+    outputs = main_res.pop("outputs")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *outputs)
+    del outputs
 
     result = {
         "metric": METRIC_NAME, "value": main_res["value"], "unit": "queries/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"], "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": main_res["config"].get("data", "synthetic"), "config": main_res["config"],
-        # (`steps` is the contract's K: `value` is the median over `timed_steps_total` / K groups of exactly K steps, each between
-        #  barrier + synchronise -- timed_groups lists every group)
-        "timed_steps_total": (main_res.get("timed_groups") or {}).get("groups", 1) * args.steps if isinstance(main_res.get("timed_groups"), dict) else args.steps,
-        "roofline": main_res["roofline"], "phases_ms": main_res["phases_ms"], "build": main_res["build"],
-        "timed_groups": main_res.get("timed_groups"),
+        # (`steps` is the contract's K: `value` and `ms_per_step` come from exactly K steps between barrier + synchronise)
+        "timed_steps_total": args.steps,
+        "build": main_res["build"], "timed_groups": main_res.get("timed_groups"),
     }
-    if main_res.get("batches_in_flight"):
-        result["batches_in_flight"] = main_res["batches_in_flight"]
-    if main_res.get("host_api"):
-        result["host_api"] = main_res["host_api"]
-    for key in ("per_rank", "exchange", "rccl_ranks_seen"):  # the N > 1 path: every rank's own roofline, the devices, the exchange
+    # --full: the scan kernel's roofline and the phases (N > 1: every rank's own roofline, the devices, the exchange)
+    for key in ("roofline", "phases_ms", "batches_in_flight", "host_api", "per_rank", "exchange", "rccl_ranks_seen"):
         if main_res.get(key):
             result[key] = main_res[key]
-    if world == 1 and not force_sharded:
+    if world == 1 and not force_sharded and args.full:
         result["cpu_baseline"] = main_res.get("cpu_baseline")
         if "speedup_vs_cpu" in main_res:
             result["speedup_vs_cpu"] = main_res["speedup_vs_cpu"]
@@ -1391,10 +1472,12 @@ def main():
             extra = {}
             only = set(v for v in args.only.split(",") if v)
             hard_steps = max(20, min(args.steps, 100))
+            hard_groups = min(10, -(-EXTRA_TIMED_STEPS // hard_steps))
             if not only or "hard" in only:
                 extra["hard"] = run_single_workload(ctx, dev, args, "hard", 0.0, 0, hard_steps, min(args.warmup, 10),
                                                     min(args.settle, 50), args.cpu_seconds * 0.5, traffic_file="r05_pmc_k_scan_hard.json",
-                                                    manifold=args.hard_latent, with_aps=True)
+                                                    manifold=args.hard_latent, with_aps=True, groups=hard_groups)
+                del extra["hard"]["outputs"]
             if not only or "configs0" in only:
                 extra["configs0"] = run_configs0(ctx, dev, args)
             if (not only or "configs2" in only) and cfg_no == 1:
@@ -1403,7 +1486,8 @@ def main():
                 a2 = argparse.Namespace(**vars(args))
                 a2.dim, a2.metric, a2.k, a2.inflight = 768, "ip", 100, 1
                 extra["configs2"] = run_single_workload(ctx, dev, a2, "configs2", args.sigma, 0, hard_steps, min(args.warmup, 10),
-                                                        min(args.settle, 50), args.cpu_seconds * 0.5)
+                                                        min(args.settle, 50), args.cpu_seconds * 0.5, groups=hard_groups)
+                del extra["configs2"]["outputs"]
                 extra["configs2"]["config"]["workload"] += " (BASELINE.json configs[2])"
             if (not only or "configs3_rank_step" in only) and cfg_no == 1:
                 extra["configs3_rank_step"] = run_rank_step(ctx, dev, args, int(main_res["config"]["nprobe"]))
@@ -1438,12 +1522,17 @@ def main_single_process(args):
     log("device", ctx.device_info(), "| GPUs visible:", torch.cuda.device_count())
     t_all = time.time()
     r = run_group(ctx, dev, args, world)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *r["outputs"])
     result = {
         "metric": METRIC_NAME, "value": r["value"], "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic", "config": r["config"], "roofline": r["roofline"], "phases_ms": r["phases_ms"], "build": r["build"],
+        "data": "synthetic", "config": r["config"], "build": r["build"],
         "timed_groups": r["timed_groups"], "launch": "single process, device group (qk_group_*)",
     }
+    for key in ("roofline", "phases_ms"):  # --full
+        if key in r:
+            result[key] = r[key]
     log(f"total bench wall {time.time() - t_all:.1f}s")
     print(json.dumps(result), flush=True)
 

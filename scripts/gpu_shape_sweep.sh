@@ -1,7 +1,7 @@
 #!/bin/bash
 # the bench step on shapes beside the configs (run on the GPU box): one line each -- d, metric, k, nprobe -> queries/s, kernel, fraction
 cd $GRAFT_REPO_ROOT
-run() { python bench.py --no-cpu --no-extra --no-pmc --steps 20 "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu --no-extra --no-pmc --steps 20 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 c = d['config']; r = d['roofline']

@@ -197,7 +197,7 @@ def test_bench_starts_its_own_ranks(nranks):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(QUAKE_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--steps", "5", "--warmup", "2", "--settle", "5",
-                        "--nvec-sharded", "300000", "--nlist-sharded", "128", "--batch-sharded", "128", "--no-cpu", "--no-extra"],
+                        "--nvec-sharded", "300000", "--nlist-sharded", "128", "--batch-sharded", "128", "--full", "--no-cpu", "--no-extra"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     import json
