@@ -439,11 +439,13 @@ int group_search(qk_group *g, qk_store *parent, const float *x, int64_t Q, const
         timing->merge_ms = ms;
         QK_HIP(hipEventElapsedTime(&ms, g->tev[0], g->tev[3]));
         timing->total_ms = ms;
+        bool one_launch = false;
         for (int j = 0; j < G; j++) {
             Member &mb = g->m[j];
             qk_timing &t = mt[(size_t)j];
             if (t.n_items < 0) {  // the one-launch small-batch search leaves no scalars
                 t.n_items = 0;
+                one_launch = true;
             } else {
                 QK_HIP(hipSetDevice(mb.ctx->device));
                 QK_TRY(qk_finish_timing(mb.ctx, mb.store, &t, false, 4));
@@ -452,6 +454,8 @@ int group_search(qk_group *g, qk_store *parent, const float *x, int64_t Q, const
             timing->scan_bytes += t.scan_bytes;
             timing->partitions_scanned += t.partitions_scanned;
         }
+        // that search counts no pairs: it reports the call's nominal Q x nprobe, which holds for the whole group, not per member
+        if (one_launch) timing->partitions_scanned = Q * (int64_t)kk;
     }
     if (tm || mem == QK_MEM_HOST)
         for (auto &mb : g->m) QK_TRY(qk_check_overflow(mb.ctx));

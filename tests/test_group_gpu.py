@@ -55,7 +55,7 @@ def _build(capi, ivf, G, metric="l2", mem="host"):
     return ctx, parent, single, grp
 
 
-@pytest.mark.parametrize("G", [1, 2, 4, 7])
+@pytest.mark.parametrize("G", [1, 2, 4, 7, 8])
 @pytest.mark.parametrize("metric", ["l2", "ip"])
 def test_group_search_equals_single_store_and_oracle(capi, G, metric):
     ivf = make_ivf(60000, 64, 96, seed=3, metric=metric, empty=(5, 17))
@@ -82,7 +82,7 @@ def test_group_search_equals_single_store_and_oracle(capi, G, metric):
         assert (_np(di) == si).all() and (_bits(dd) == _bits(sd)).all()
 
 
-@pytest.mark.parametrize("G,k", [(2, 961), (3, 1500), (4, 4000)])
+@pytest.mark.parametrize("G,k", [(2, 961), (3, 1500), (4, 4000), (8, 1200)])
 def test_group_large_k_equals_single_store(capi, G, k):
     """k beyond the LDS pools of the cross-member merge (k > 960): the sorted-run merge (k_merge_ranks_large, qk_merge.hip) -- the
     reference has no k limit with workers (query_coordinator.cpp:243-469), and one store serves k up to 8192.  Also k larger than
@@ -97,6 +97,26 @@ def test_group_large_k_equals_single_store(capi, G, k):
         assert (_bits(gd) == _bits(sd)).all()
         if nprobe == 1:
             assert (gi[:, -1] == -1).all()  # one list of ~625 rows: fewer than k entries, the rest is padding
+    grp.close()
+    single.close()
+    parent.close()
+    ctx.close()
+
+
+@pytest.mark.parametrize("G", [3, 8])
+def test_group_ids_beyond_32_bits(capi, G):
+    """ids >= 2^40 through the members' packed 12-byte top-k records and the lead's merge, both merge forms (the other tests
+    here number rows below 2^32, where an id field cut to 32 bits would go unseen)"""
+    ivf = make_ivf(30000, 32, 64, seed=61, id_base=(1 << 40) + 12345)
+    ctx, parent, single, grp = _build(capi, ivf, G)
+    for Q, nprobe, k in [(64 * G, 6, 10), (5, 64, 100), (300, 3, 1200)]:
+        q = make_queries(Q, 32, seed=62 + Q, like=ivf["x"])
+        si, sd = ctx.search(parent, single, q, nprobe, k, "l2")
+        gi, gd = grp.search(parent, q, nprobe, k, "l2")
+        assert (gi == si).all() and (_bits(gd) == _bits(sd)).all(), (G, Q, nprobe, k)
+        oi, od = O.search(q, ivf["centroids"], ivf["vecs"], ivf["ids"], ivf["offsets"], nprobe, k, "l2", batched_scan=True)
+        assert (gi == oi).all() and (_bits(gd) == _bits(od)).all(), (G, Q, nprobe, k)
+        assert (gi[:, 0] >= (1 << 40)).all()
     grp.close()
     single.close()
     parent.close()
@@ -145,6 +165,13 @@ def test_group_counters_sum_over_members(capi):
     _, _, tg = grp.search(parent, q, 6, 10, "l2", timing=True)
     assert tg["partitions_scanned"] == ts["partitions_scanned"]
     assert tg["scan_bytes"] == ts["scan_bytes"]  # every probed list is read once, by the member that holds it
+    # a small batch: the one-launch search on the store and on every member counts no pairs and reports the call's nominal
+    # Q x nprobe -- once for the group, not once per member
+    _, _, ts = ctx.search(parent, single, q[:3], 6, 10, "l2", timing=True)
+    assert ctx.last_scan_kernel() == "k_search_small"
+    _, _, tg = grp.search(parent, q[:3], 6, 10, "l2", timing=True)
+    assert tg["partitions_scanned"] == ts["partitions_scanned"] == 3 * 6
+    assert tg["scan_bytes"] == ts["scan_bytes"]
 
 
 def test_group_scan_seam_and_padding(capi):

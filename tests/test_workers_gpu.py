@@ -52,7 +52,7 @@ def _params(mod, k, nprobe, batched=False):
 
 
 @pytest.mark.parametrize("mirror", ["compiled", "python"])
-@pytest.mark.parametrize("G", [2, 4])
+@pytest.mark.parametrize("G", [2, 4, 8])  # 8: the member count of configs[3]
 def test_num_workers_equals_no_workers(qb, mirror, G):
     import quake_amd as qa
     mod = qb if mirror == "compiled" else qa
