@@ -52,6 +52,9 @@ typedef enum {
                       * (slower, exact) */
 #define QK_MAX_NPROBE 8192 /* largest nprobe / number of APS candidate partitions: the coarse step selects them with a
                               * bisection select + sort beyond QK_MAX_K (flat parent index) */
+#define QK_MAX_D 8192 /* largest dimension, for every entry point and every k.  Up to d ~ 2500 (less with large k) the scan,
+                       * dense and k-means kernels stage their 16-query tile in LDS; wider rows go to the wide-row siblings,
+                       * which read the queries from global memory (same bits).  Larger d: QK_ERR_UNSUPPORTED */
 
 typedef struct qk_ctx qk_ctx;     /* device + stream + scratch workspace                     */
 typedef struct qk_store qk_store; /* device mirror of faiss::DynamicInvertedLists (one level) */

@@ -907,7 +907,10 @@ int qk_dense_device(qk_ctx *ctx, qk_store *s, int64_t list_no, const qk_scan_arg
     int NQ = 4;
     while (NQ > 1 && (size_t)NQ * nblk * 1024 > 64 * 1024) NQ >>= 1;
     const size_t lds = (size_t)NQ * nblk * 1024 + (size_t)NQ * 16 * 4 + 64;
-    if (lds > 160 * 1024) QK_FAIL(QK_ERR_UNSUPPORTED, "dense scan: d=%d too large for the LDS query tile", s->d);
+    // wide rows: the query tile does not fit the LDS -- k_dense_wide (qk_scan_wide.hip) reads the queries from global memory
+    const bool wide = lds > 160 * 1024;
+    if (wide && s->d > QK_MAX_D) QK_FAIL(QK_ERR_UNSUPPORTED, "dense scan: d=%d exceeds QK_MAX_D=%d", s->d, QK_MAX_D);
+    if (wide) ctx->last_scan_kernel = "k_dense_wide";
     // (from 32768 rows on the prefiltered form below is the faster nearest-centroid search too -- 1024 queries: 32768 rows 84 -> 71 us,
     //  65536 rows 154 -> 96 us; at 16384 rows 50 against 54 us the fused fp32 argmin stays)
     const bool pf_k1 = k == 1 && nrows >= 32768 && Q <= 16384 && a.x && a.out_ids && !qk_env_set("QK_NO_DENSE_PF") && qk_dense_pf_supported(ctx, s, Q, nrows, 1);
@@ -916,7 +919,7 @@ int qk_dense_device(qk_ctx *ctx, qk_store *s, int64_t list_no, const qk_scan_arg
                             !qk_env_set("QK_NO_DENSE_APF");
     // a query preparation left pending by the caller (qk_prep_queries(.., defer)) is folded into the fp32 nearest-centroid kernel;
     // every other form below wants the prepared queries in place
-    const bool fuse_prep = ctx->prep_pending && to_argmin && !argmin_apf && a.x == ctx->prep_x && Q == ctx->prep_Q &&
+    const bool fuse_prep = ctx->prep_pending && to_argmin && !argmin_apf && !wide && a.x == ctx->prep_x && Q == ctx->prep_Q &&
                            ((uintptr_t)a.x & 15) == 0 && s->d % 4 == 0 && a.xq4 == (const float4 *)ctx->qprep &&
                            !qk_env_set("QK_NO_FUSED_PREP");
     if (!fuse_prep) QK_TRY(qk_prep_flush(ctx));
@@ -952,6 +955,20 @@ int qk_dense_device(qk_ctx *ctx, qk_store *s, int64_t list_no, const qk_scan_arg
             QK_TRY(qk_assign_pf_launch(ctx, a.x, Q, rm, nrows, s->d, a.metric, s->norms + pt.row_off, s->ids + pt.row_off, nullptr, nullptr,
                                        best64, a.out_dist != nullptr, apf_scratch));
             ctx->last_scan_kernel = "k_assign_pf";
+        } else if (wide) {
+            if (!preinit) QK_HIP(hipMemsetAsync(best64, 0xFF, (size_t)Q * 8, st));
+            QkDenseWideParams wp{};
+            wp.vecs = (const float4 *)s->vecs;
+            wp.norms = s->norms;
+            wp.ids = s->ids + pt.row_off;
+            wp.row_off = pt.row_off;
+            wp.nrows = nrows;
+            wp.nblk = nblk;
+            wp.xq4 = a.xq4;
+            wp.xn = a.xn;
+            wp.Q = Q;
+            wp.best64 = best64;
+            QK_TRY(qk_launch_dense_wide(st, wp, true, a.metric, num_cus_a));
         } else {
         if (!preinit) QK_HIP(hipMemsetAsync(best64, 0xFF, (size_t)Q * 8, st));
         ArgminParams ap;
@@ -1018,7 +1035,7 @@ int qk_dense_device(qk_ctx *ctx, qk_store *s, int64_t list_no, const qk_scan_arg
         }
         return QK_OK;
     }
-    if (a.x && a.out_ids && s->min_id_seen >= 0 && qk_coarse_small_supported(s, Q, nrows, k)) {
+    if (!wide && a.x && a.out_ids && s->min_id_seen >= 0 && qk_coarse_small_supported(s, Q, nrows, k)) {
         // a few dozen queries against a few thousand rows: keys + selection in one launch (k_coarse_small, qk_small.hip)
         QK_TRY(pe.mark(0));
         QK_TRY(pe.mark(1));
@@ -1145,7 +1162,20 @@ int qk_dense_device(qk_ctx *ctx, qk_store *s, int64_t list_no, const qk_scan_arg
         tiles_per_wg = qk_round_up(tiles_per_wg, 4);
         dp.tiles_per_wg = tiles_per_wg;
         const int rchunks = std::max(1, (ntile + tiles_per_wg - 1) / tiles_per_wg);
-        if (nrows > 0) {
+        if (nrows > 0 && wide) {
+            QkDenseWideParams wp{};
+            wp.vecs = dp.vecs;
+            wp.norms = dp.norms;
+            wp.row_off = dp.row_off;
+            wp.nrows = nrows;
+            wp.nblk = nblk;
+            wp.xq4 = dp.xq4;
+            wp.xn = dp.xn;
+            wp.Q = nq;
+            wp.D = D;
+            wp.ld = ld;
+            QK_TRY(qk_launch_dense_wide(st, wp, false, a.metric, num_cus));
+        } else if (nrows > 0) {
             dim3 grid((unsigned)qgroups, (unsigned)rchunks);
 #define DN_CASE(D_, N_) \
     if (DB == D_ && NQ == N_) QK_TRY((launch_dense_t<D_, N_>(st, grid, lds, dp)));

@@ -372,6 +372,37 @@ int qk_launch_merge_slices(qk_ctx *ctx, const int64_t *sl_ids, const uint32_t *s
 // k > QK_MAX_K over several lists: emit every key (qk_scan_device in emission mode), then exact selection per query.  qk_dense.hip
 int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base);
 constexpr int QK_MAX_WIDE_K = 8192;  // = the reference's TOP_K_BUFFER_CAPACITY (list_scanning.h:39)
+// wide rows (a 16-query tile no longer fits the LDS next to what the kernel keeps there): the queries are read from global
+// memory instead (qk_scan_wide.hip).  k_dense_wide: every query against one list -- keys into D, or (argmin) the packed
+// minimum (key << 32 | id) into best64; k_assign_wide: k_assign's nearest centroid of every row of x
+struct QkDenseWideParams {
+    const float4 *vecs;  // arena
+    const float *norms;
+    const int64_t *ids;  // ids of the list (argmin)
+    int64_t row_off;     // first arena row of the list (multiple of 16)
+    int nrows;
+    int nblk;
+    const float4 *xq4;   // [Q][nblk][4] fragment-ordered queries
+    const float *xn;     // [Q]
+    int64_t Q;
+    uint32_t *D;         // [Q][ld] keys (!argmin)
+    int64_t ld;
+    unsigned long long *best64;  // [Q] (argmin), ~0 = nothing yet
+    int tiles_per_wg;    // (set by the launcher)
+};
+int qk_launch_dense_wide(hipStream_t st, const QkDenseWideParams &p, bool argmin, int metric, int num_cus);
+struct QkAssignWideParams {
+    const float *x;       // [n][d] row-major
+    int64_t n;
+    int d;
+    int nblk;
+    const float4 *cvecs;  // centroids, tile-major
+    const float *cnorms;  // [mt*16]
+    int m;
+    int64_t *assign;      // [n]
+    float *val;           // [n] or nullptr
+};
+int qk_launch_assign_wide(hipStream_t st, const QkAssignWideParams &p, int metric);
 
 // phase events of one pipeline run: per-call mode (ctx->ev[ev_base..]) and/or deferred mode (parked in the ctx)
 struct qk_phase_events {

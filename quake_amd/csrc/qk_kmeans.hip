@@ -759,7 +759,12 @@ static int assign_device(qk_ctx *ctx, const float *x, int64_t n, const float *c,
     while (NQ > 1 && (size_t)NQ * nblk * 1024 > 64 * 1024) NQ >>= 1;
     if (n <= 16) NQ = 1;
     const size_t lds = (size_t)NQ * nblk * 1024 + (size_t)NQ * 16 * 4 + (size_t)4 * NQ * 16 * 8 + 64;
-    if (lds > 160 * 1024) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_kmeans_assign: d=%d too large for the LDS query tile", d);
+    if (lds > 160 * 1024) {
+        // wide rows: the x tile does not fit the LDS -- k_assign_wide (qk_scan_wide.hip) reads the rows from global memory
+        if (d > QK_MAX_D) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_kmeans_assign: d=%d exceeds QK_MAX_D=%d", d, QK_MAX_D);
+        QkAssignWideParams wp{x, n, d, nblk, (const float4 *)ctile, cnorm, (int)m, assign, val};
+        return qk_launch_assign_wide(ctx->stream, wp, metric);
+    }
     const unsigned grid = km_grid(n, NQ * 16);
 #define KM_CASE(D, N) \
     if (DB == D && NQ == N) QK_TRY((launch_assign_t<D, N>(ctx->stream, grid, lds, ap)));

@@ -1342,7 +1342,9 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     const HotCost hot = plan.hot;
     qk_ctx::form_stat *fmeasure = plan.measure;
     const int maxch = pick_maxch(C);
-    const size_t lds_scan = use_rl ? ((qk_scan_rl_lds_per_wave(nblk, C, rlc.qb) + 15) & ~(size_t)15)
+    const bool wide = plan.wide;  // k_scan_wide: the pools alone in LDS
+    const size_t lds_scan = wide ? (size_t)16 * C * 12
+                            : use_rl ? ((qk_scan_rl_lds_per_wave(nblk, C, rlc.qb) + 15) & ~(size_t)15)
                             : qshare ? (size_t)nw * (q_bytes + (size_t)16 * C * 12) : q_bytes + (size_t)nw * 16 * C * 12;
     const int Cm = qk_round_up(k + 64, 64);
     const int maxch_m = Cm <= 128 ? 2 : Cm <= 256 ? 4 : Cm <= 512 ? 8 : 16;
@@ -1668,7 +1670,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         // dynamic tail: measured wave end times spread over 65-100 % of the kernel with a purely static cut
         static const int dyn_pct = qk_env_int("QK_SCAN_DYN_PCT", QK_DYN_PCT_DEFAULT);
         static const int dyn_chunk = qk_env_int("QK_SCAN_DYN_CHUNK", QK_DYN_CHUNK_DEFAULT);
-        sp.dyn_counter = (nw == 1 && dyn_pct > 0 && !use_rl) ? (unsigned long long *)(scal + 16) : nullptr;  // zeroed with the counters
+        sp.dyn_counter = (nw == 1 && dyn_pct > 0 && !use_rl && !wide) ? (unsigned long long *)(scal + 16) : nullptr;  // zeroed with the counters
         sp.dyn_chunk = std::max(1, dyn_chunk);
         sp.dyn_pct = std::min(90, std::max(0, dyn_pct));
         if (use_rl) {  // row-per-lane form: dynamic tail in ranges of rl_dyn_chunk units (>= tail / QK_RL_DYN_MAX)
@@ -1689,7 +1691,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         }
         // single-wave workgroups are bundled four to a hardware workgroup: one wave per SIMD, guaranteed (see k_scan)
         static const bool no_pack = qk_env_set("QK_SCAN_NO_PACK");
-        const bool pack4 = use_rl || (nw == 1 && !qshare && !no_pack && (wgs_per_cu == 4 || wgs_per_cu == 8) && lds_launch % 16 == 0);
+        const bool pack4 = use_rl || (nw == 1 && !qshare && !wide && !no_pack && (wgs_per_cu == 4 || wgs_per_cu == 8) && lds_launch % 16 == 0);
         const int pk = use_rl ? rl_waves : 4;
         sp.pack = pack4 ? pk : 1;
         sp.pack_lds = (int)lds_launch;
@@ -1730,7 +1732,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         sp.xcd_on = 0;
         sp.xcd_stat = nullptr;
         for (int c = 0; c < 8; c++) sp.xcd_w[c] = 1024;
-        if (xcd_adapt && (sp.dyn_counter == nullptr || use_rl) && grid >= 64 && tiles_est >= (int64_t)grid * wpw * 32) {
+        if (xcd_adapt && !wide && (sp.dyn_counter == nullptr || use_rl) && grid >= 64 && tiles_est >= (int64_t)grid * wpw * 32) {
             qk_ctx::xcd_state &xs = ctx->xcd[s->uid];
             sp.xcd_on = 1;
             for (int c = 0; c < 8; c++) sp.xcd_w[c] = std::max(1, (int)(xs.w[c] * 1024.0 + 0.5));
@@ -1752,8 +1754,10 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             QK_HIP(hipMemsetAsync(d_clock, 0, (size_t)grid * wpw * 64 * 2, st));
             sp.wave_clock = d_clock;
         }
-        ctx->last_scan_kernel = use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
-        if (use_rl)
+        ctx->last_scan_kernel = wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
+        if (wide)
+            QK_TRY(qk_launch_scan_wide(maxch, (unsigned)grid, lds_launch, st, sp));
+        else if (use_rl)
             QK_TRY(qk_launch_scan_rl(nblk, dim3((unsigned)grid), lds_launch, st, sp));
         else
             QK_TRY(launch_scan(DB, maxch, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));

@@ -121,8 +121,24 @@ int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int
 #endif
     int C = qk_round_up(k + std::max(slack_min, std::min(k, QK_SLACK_CAP)), 4);
     while ((size_t)16 * C * 12 + q_bytes > lds_budget && C > k + 4) C -= 4;
-    if ((size_t)16 * C * 12 + q_bytes > lds_budget || C < k + 4 || C > 512)
-        QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: k=%d with d=%d does not fit the LDS top-k pools", k, s->d);
+    if ((size_t)16 * C * 12 + q_bytes > lds_budget || C < k + 4 || C > 512) {
+        // the query tile and the pools do not fit side by side: k_scan_wide (qk_scan_wide.hip) keeps only the pools in LDS and
+        // reads the queries from global memory.  The one form of these shapes -- no form feedback.
+        if (s->d > QK_MAX_D) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: d=%d exceeds QK_MAX_D=%d", s->d, QK_MAX_D);
+        C = qk_round_up(k + std::max(slack_min, std::min(k, QK_SLACK_CAP)), 4);
+        while ((size_t)16 * C * 12 > lds_budget && C > k + 4) C -= 4;
+        if ((size_t)16 * C * 12 > lds_budget || C < k + 4 || C > 512)
+            QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: k=%d with d=%d does not fit the LDS top-k pools", k, s->d);
+        pl->DB = DB;
+        pl->C = C;
+        pl->nw = 1;
+        pl->qshare = 0;
+        pl->use_rl = false;
+        pl->form = 0;
+        pl->measure = nullptr;
+        pl->wide = true;
+        return QK_OK;
+    }
     // waves per workgroup: 1 unless the wave-private query tile keeps a CU below 4 resident waves; then 2 or 4 waves
     // share the tile (and, if that is what it takes to reach 4 waves, the pools give up part of their slack)
     int nw = 1;

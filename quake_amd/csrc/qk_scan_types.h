@@ -206,5 +206,8 @@ struct ScanPlan {
     int rl_app = 32, rl_waves = 4;
     HotCost hot{0, 0, 0, 0, 0, 0, 0, 0};
     qk_ctx::form_stat *measure = nullptr;  // form feedback: this call is timed (e0 is already on the stream; the caller records e1)
+    bool wide = false;       // the query tile does not fit next to the pools: k_scan_wide (qk_scan_wide.hip), the only form
 };
 int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int k, int P, int64_t npairs, ScanPlan *pl);
+// wide-row scan (qk_scan_wide.hip): one wave per workgroup, lds = its 16 pools of sp.C entries
+int qk_launch_scan_wide(int maxch, unsigned grid, size_t lds, hipStream_t st, const ScanParams &sp);
