@@ -205,6 +205,52 @@ QK_API int qk_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x,
 QK_API int qk_search_tracked(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
                              int64_t *out_ids, float *out_dist, int64_t *out_probed, int mem, qk_timing *timing);
 
+/* ---- filtered search ---------------------------------------------------------------------------
+ * No reference counterpart (its SearchParams ends at aps_flush_period_us): search restricted to a set of ids.
+ * A filter is a set of ids S and a mode -- QK_FILTER_ALLOW: a row is a candidate iff its id is in S; QK_FILTER_DENY: iff it is
+ * not.  The coarse step is not filtered: a filtered search probes the lists the unfiltered one probes and returns the k best
+ * CANDIDATE rows of those lists under the total order (key, id), with the same distance bits -- it equals the unfiltered search
+ * over a store that holds the same lists without the other rows.  Fewer than k candidates in the probed lists: padded like any
+ * short result (id -1, +inf / -inf).  Ids of S the store does not hold are ignored; every copy of an id stored twice follows the
+ * filter; rows added after the filter was made follow the mode (absent from an allow-set: not a candidate).
+ *
+ * A filter belongs to ONE store (another store's: QK_ERR_INVALID) but is defined by ids, not rows: inside, it keeps S sorted on
+ * the device and a row mask -- one bit per arena row, cap_rows / 8 bytes -- stamped with the store's version.  Whatever moves rows
+ * (add, remove, list relocation, compaction, refinement, maintenance) changes that version, and the next filtered call re-derives
+ * the mask (k_filter_build: one pass over the stored ids, a binary search each) on ITS context's stream, in front of its scan.
+ * Ordering: a mask is read by the scans enqueued behind its build on that stream; a filtered call on another context waits for
+ * the build by event.  A caller that rebinds a context to streams of its own (qk_ctx_set_stream) must order a stream behind the
+ * one that ran the last filtered call after a store change before it issues filtered calls on it -- and, as for every search,
+ * nobody mutates the store while searches are in flight.
+ * The filter holds everything it needs: it may be destroyed after its store (it can no longer be used then).
+ *
+ * Limits, all QK_ERR_UNSUPPORTED: k > QK_MAX_K (no wide-k path), and there is no filtered form of qk_search_aps (recall target:
+ * its recall model counts volume, not candidate rows) nor of the device group (qk_group_search).  With a filter the scan is the
+ * 16 x 16 tile form (k_scan_filt, or k_scan_wide_filt for wide rows) without bound seeding -- a bound from a row that is not a
+ * candidate would drop rows that are -- whatever form the unfiltered call of the same shape takes; tiles without a candidate
+ * are not read.  A flat index (parent == NULL) takes the same scan, not the dense forms. */
+typedef struct qk_filter qk_filter;
+#define QK_FILTER_ALLOW 0
+#define QK_FILTER_DENY 1
+/* ids [n] in `mem` (any order, duplicates allowed; n == 0: the empty set).  Builds the first mask on the store's context. */
+QK_API int qk_filter_create(qk_store *s, const int64_t *ids, int64_t n, int mode, int mem, qk_filter **out);
+QK_API int qk_filter_destroy(qk_filter *f);
+/* Any pointer may be NULL.  n_ids: distinct ids of S; rows_allowed: candidate rows of the store as of the last mask build
+ * (synchronises with that build); store_version: the stamp of the mask; rebuilds: mask builds after the first, one per filtered
+ * call that found the store changed; device_bytes: HBM held by the filter (not part of qk_store_device_bytes). */
+QK_API int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t *store_version, int64_t *rebuilds,
+                          int64_t *device_bytes);
+/* qk_search / qk_search_tracked / qk_scan restricted to the filter's candidates; timing is filled as for the unfiltered calls
+ * (partitions_scanned = lists probed, scan_bytes = the algorithmic bytes of those lists, not what the mask left to read).
+ * qk_ctx_last_scan_kernel names "k_scan (filtered)" / "k_scan_wide (filtered)" afterwards. */
+QK_API int qk_search_filtered(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
+                              qk_filter *f, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_search_filtered_tracked(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k,
+                                      int metric, qk_filter *f, int64_t *out_ids, float *out_dist, int64_t *out_probed, int mem,
+                                      qk_timing *timing);
+QK_API int qk_scan_filtered(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric,
+                            qk_filter *f, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+
 /* QueryCoordinator::search with SearchParams::recall_target > 0 and batched_scan == false: adaptive partition
  * scanning (query_coordinator.cpp:612-657 picks M = max((int)(nlist * initial_search_fraction), 1) candidate partitions
  * from the parent; the use_aps branch of serial_scan, :471-611, scans them in rank order and stops a query once the

@@ -77,6 +77,13 @@ SIGNATURES = {
     "qk_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search_tracked": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_filter_create": (_int, [_vp, _vp, _i64, _int, _int, C.POINTER(_vp)]),
+    "qk_filter_destroy": (_int, [_vp]),
+    "qk_filter_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_uint64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "qk_search_filtered": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_search_filtered_tracked": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _int,
+                                   C.POINTER(QkTiming)]),
+    "qk_scan_filtered": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search_aps": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, C.c_float, _int, C.c_float, _vp, _vp, _vp, _int,
                       C.POINTER(QkTiming)]),
     "qk_merge_topk": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp]),

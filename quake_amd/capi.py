@@ -166,7 +166,8 @@ class Context:
                                  _ptr(out_d) if values else None, mem))
         return out_p, out_d
 
-    def scan(self, store, x, pids, k, metric, timing=False):
+    def scan(self, store, x, pids, k, metric, timing=False, filter=None):
+        """filter: a Filter of `store` -- only its candidates are returned (qk_scan_filtered)"""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
         if pids.ndim == 1:  # same set for every query (query_coordinator.cpp:506-508)
@@ -176,6 +177,11 @@ class Context:
         out_i = _empty_like_mem((Q, k), np.int64, x)
         out_d = _empty_like_mem((Q, k), np.float32, x)
         t = QkTiming()
+        if filter is not None:
+            check(self.lib.qk_scan_filtered(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None,
+                                            int(pids.shape[1]), int(k), metric_code(metric), filter.h, _ptr(out_i), _ptr(out_d),
+                                            mem, C.byref(t) if timing else None))
+            return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
         check(self.lib.qk_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]),
                                int(k), metric_code(metric), _ptr(out_i), _ptr(out_d), mem, C.byref(t) if timing else None))
         return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
@@ -189,7 +195,8 @@ class Context:
                                _ptr(out_i), _ptr(out_d), _mem_of(x, pids), None))
         return out_i, out_d
 
-    def search(self, parent, store, x, nprobe, k, metric, timing=False, out=None):
+    def search(self, parent, store, x, nprobe, k, metric, timing=False, out=None, filter=None):
+        """filter: a Filter of `store` -- the k best of its candidates in the probed lists (qk_search_filtered)"""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
@@ -199,13 +206,19 @@ class Context:
         else:
             out_i, out_d = out
         t = QkTiming()
+        if filter is not None:
+            check(self.lib.qk_search_filtered(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe),
+                                              int(k), metric_code(metric), filter.h, _ptr(out_i), _ptr(out_d), mem,
+                                              C.byref(t) if timing else None))
+            return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
         check(self.lib.qk_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), int(k),
                                  metric_code(metric), _ptr(out_i), _ptr(out_d), mem, C.byref(t) if timing else None))
         return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
 
-    def search_tracked(self, parent, store, x, nprobe, k, metric, timing=False):
+    def search_tracked(self, parent, store, x, nprobe, k, metric, timing=False, filter=None):
         """qk_search_tracked: search + the [Q, min(nprobe, parent lists)] list numbers every query scanned, one enqueue.
-        Returns (ids, dist, probed[, timing])."""
+        Returns (ids, dist, probed[, timing]).  filter: a Filter of `store` (qk_search_filtered_tracked; the probed lists are
+        those of the unfiltered search)."""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
@@ -214,8 +227,13 @@ class Context:
         out_d = _empty_like_mem((Q, k), np.float32, x)
         out_p = _empty_like_mem((Q, max(width, 1)), np.int64, x)
         t = QkTiming()
-        check(self.lib.qk_search_tracked(self.h, parent.h, store.h, _ptr(x), Q, int(nprobe), int(k), metric_code(metric),
-                                         _ptr(out_i), _ptr(out_d), _ptr(out_p), mem, C.byref(t) if timing else None))
+        if filter is not None:
+            check(self.lib.qk_search_filtered_tracked(self.h, parent.h, store.h, _ptr(x), Q, int(nprobe), int(k),
+                                                      metric_code(metric), filter.h, _ptr(out_i), _ptr(out_d), _ptr(out_p), mem,
+                                                      C.byref(t) if timing else None))
+        else:
+            check(self.lib.qk_search_tracked(self.h, parent.h, store.h, _ptr(x), Q, int(nprobe), int(k), metric_code(metric),
+                                             _ptr(out_i), _ptr(out_d), _ptr(out_p), mem, C.byref(t) if timing else None))
         out_p = out_p[:, :width]
         return (out_i, out_d, out_p, timing_dict(t)) if timing else (out_i, out_d, out_p)
 
@@ -499,6 +517,44 @@ class Store:
         out = np.zeros(8, np.int64)
         check(self.lib.qk_store_counters(self.h, _ptr(out), 8))
         return dict(zip(self.COUNTER_NAMES, (int(v) for v in out)))
+
+
+class Filter:
+    """A set of ids of one Store and a mode: "allow" (a row is a candidate iff its id is in the set) or "deny" (iff it is not).
+    Pass it as `filter=` to Context.search / search_tracked / scan.  Defined by ids, not rows: it stays correct while the store
+    changes (the row mask inside is re-derived at the next filtered call).  ids: numpy or torch, host or device."""
+
+    MODES = {"allow": 0, "deny": 1}
+
+    def __init__(self, store, ids, mode="allow"):
+        if mode not in self.MODES:
+            raise ValueError("Filter mode must be 'allow' or 'deny'")
+        self.lib = store.lib
+        self.store = store  # (keeps the store alive; the C object itself does not need it)
+        self.mode = mode
+        self.h = C.c_void_p()
+        ids = _i64(ids).reshape(-1)
+        check(self.lib.qk_filter_create(store.h, _ptr(ids) if ids.shape[0] > 0 else None, int(ids.shape[0]), self.MODES[mode],
+                                        _mem_of(ids), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h:
+            self.lib.qk_filter_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{n_ids, rows_allowed, store_version, rebuilds, device_bytes} (qk_filter_info)"""
+        n, ra, rb, db = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        ver = C.c_uint64()
+        check(self.lib.qk_filter_info(self.h, C.byref(n), C.byref(ra), C.byref(ver), C.byref(rb), C.byref(db)))
+        return {"n_ids": n.value, "rows_allowed": ra.value, "store_version": ver.value, "rebuilds": rb.value,
+                "device_bytes": db.value}
 
 
 class Group:

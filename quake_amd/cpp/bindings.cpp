@@ -58,6 +58,8 @@ PYBIND11_MODULE(_bindings, m) {
         .def("maintenance", &QuakeIndex::maintenance)
         .def("initialize_maintenance_policy", &QuakeIndex::initialize_maintenance_policy)
         .def("refine_partitions", &QuakeIndex::refine_partitions, py::arg("partition_ids"), py::arg("iterations") = 0)
+        .def("make_filter", &QuakeIndex::make_filter, py::arg("ids"), py::arg("exclude") = false,
+             "extension: a SearchFilter over this index's vector ids for SearchParams.filter")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)
@@ -120,6 +122,21 @@ PYBIND11_MODULE(_bindings, m) {
             return Repr().kv("nlist", p.nlist).kv("niter", p.niter).kv("metric", p.metric).kv("num_workers", p.num_workers).str();
         });
 
+    py::class_<SearchFilter, std::shared_ptr<SearchFilter>>(m, "SearchFilter")
+        .def_readonly("exclude", &SearchFilter::exclude)
+        .def("info", [](const SearchFilter &f) {  // qk_filter_info
+            int64_t n = 0, ra = 0, rb = 0, db = 0;
+            uint64_t ver = 0;
+            qk_check(qk_filter_info(f.h, &n, &ra, &ver, &rb, &db));
+            py::dict d;
+            d["n_ids"] = n;
+            d["rows_allowed"] = ra;
+            d["store_version"] = ver;
+            d["rebuilds"] = rb;
+            d["device_bytes"] = db;
+            return d;
+        });
+
     py::class_<SearchParams, std::shared_ptr<SearchParams>>(m, "SearchParams")
         .def(py::init<>())
         .def_readwrite("k", &SearchParams::k)
@@ -131,6 +148,7 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("initial_search_fraction", &SearchParams::initial_search_fraction)
         .def_readwrite("recompute_threshold", &SearchParams::recompute_threshold)
         .def_readwrite("aps_flush_period_us", &SearchParams::aps_flush_period_us)
+        .def_readwrite("filter", &SearchParams::filter)  // extension; not part of the summary below
         .def("__repr__", [](const SearchParams &p) {  // wrap.cpp:173-186
             return Repr().kv("k", p.k).kv("nprobe", p.nprobe).kv("recall_target", p.recall_target).kv("batched_scan", p.batched_scan)
                 .kv("use_precomputed", p.use_precomputed).kv("initial_search_fraction", p.initial_search_fraction)

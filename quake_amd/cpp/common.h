@@ -57,6 +57,20 @@ struct IndexBuildParams {  // common.h:123-143
     shared_ptr<IndexBuildParams> parent_params = nullptr;
 };
 
+// extension (no reference counterpart): a set of vector ids of ONE index and a mode, made by QuakeIndex::make_filter -- with
+// exclude == false a stored vector is a candidate iff its id is in the set, with exclude == true iff it is not (qk_filter).
+// Defined by ids: it stays valid while the index changes.  Not persisted by save().
+struct SearchFilter {
+    qk_filter *h = nullptr;
+    bool exclude = false;
+    SearchFilter() = default;
+    SearchFilter(const SearchFilter &) = delete;
+    SearchFilter &operator=(const SearchFilter &) = delete;
+    ~SearchFilter() {
+        if (h) (void)qk_filter_destroy(h);
+    }
+};
+
 struct SearchParams {  // common.h:171-184
     int nprobe = DEFAULT_NPROBE;
     int k = DEFAULT_K;
@@ -68,6 +82,7 @@ struct SearchParams {  // common.h:171-184
     float recompute_threshold = 0.001f;
     float initial_search_fraction = 0.02f;
     int aps_flush_period_us = 100;
+    shared_ptr<SearchFilter> filter = nullptr;  // extension, not part of the summary: search only the filter's candidates
 };
 
 struct BuildTimingInfo {  // common.h:189-198

@@ -124,6 +124,22 @@ shared_ptr<SearchResult> QuakeIndex::search(Tensor x, shared_ptr<SearchParams> s
     return query_coordinator_->search(x, sp);
 }
 
+shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
+    require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?");
+    qk_store *s = partition_manager_->store();
+    if (!s) throw std::runtime_error("[QuakeIndex::make_filter()] filtered search is not supported with num_workers > 0");
+    auto f = std::make_shared<SearchFilter>();
+    f->exclude = exclude;
+    const bool on_dev = ids.defined() && ids.is_cuda();
+    Tensor idl = !ids.defined() ? torch::empty({0}, torch::kInt64)
+                 : on_dev     ? ids.reshape({-1}).to(torch::kInt64).contiguous()
+                              : host_i64(ids.reshape({-1}));
+    if (on_dev) torch::cuda::synchronize();  // (torch's stream made the ids; the library copies them out on its own)
+    qk_check(qk_filter_create(s, idl.numel() > 0 ? idl.data_ptr<int64_t>() : nullptr, idl.numel(), exclude ? QK_FILTER_DENY : QK_FILTER_ALLOW,
+                              on_dev ? QK_MEM_DEVICE : QK_MEM_HOST, &f->h));
+    return f;
+}
+
 Tensor QuakeIndex::get(Tensor ids) {
     require_built("[QuakeIndex::get()] No partition manager. Index not built?");
     return partition_manager_->get(ids);

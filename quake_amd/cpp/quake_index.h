@@ -39,6 +39,8 @@ public:
     void initialize_maintenance_policy(shared_ptr<MaintenancePolicyParams> maintenance_policy_params);
     shared_ptr<MaintenanceTimingInfo> maintenance();
     void refine_partitions(Tensor partition_ids, int iterations);
+    // extension: a filter over this index's vector ids for SearchParams::filter (ids: any integer tensor, host or device)
+    shared_ptr<SearchFilter> make_filter(Tensor ids, bool exclude = false);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

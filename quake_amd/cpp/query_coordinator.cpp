@@ -116,6 +116,16 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
         }
     } timing_mode(ctx, !on_dev || device_timing_);
     qk_timing *tmp = (!on_dev || device_timing_) ? &tm : nullptr;  // device tensors: asynchronous unless the caller opted in
+    qk_filter *flt = nullptr;
+    if (sp->filter) {
+        // filtered search (extension): the fixed-nprobe branch of one device; the rest is refused, not approximated
+        if (sp->recall_target > 0.0f)
+            throw std::runtime_error("[QuakeIndex::search()] a filter cannot be combined with recall_target > 0 "
+                                     "(the recall model counts volume, not allowed rows): not supported");
+        if (group) throw std::runtime_error("[QuakeIndex::search()] filtered search is not supported with num_workers > 0");
+        if (!sp->filter->h) throw std::runtime_error("[QuakeIndex::search()] SearchParams.filter must come from make_filter()");
+        flt = sp->filter->h;
+    }
     if (sp->recall_target > 0.0f && parent_ && !sp->batched_scan) {
         // adaptive partition scanning (:502,637-641): candidates = nlist * initial_search_fraction; with workers the rounds run on
         // the group's lead and every member scans the pairs whose partitions it holds (the APS hook of worker_scan, :364-428)
@@ -139,6 +149,9 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
             qk_check(qk_coarse(ctx, parent_->store(), xq.data_ptr<float>(), Q, nprobe, (int)metric_, pids.data_ptr<int64_t>(), nullptr, mem));
             qk_check(qk_group_scan(group, xq.data_ptr<float>(), Q, pids.data_ptr<int64_t>(), kk, k, (int)metric_,
                                    res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, &tm));
+        } else if (flt) {  // (the probed lists are the unfiltered search's: the policy sees the same hits)
+            qk_check(qk_search_filtered_tracked(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_, flt,
+                                                res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), pids.data_ptr<int64_t>(), mem, &tm));
         } else {
             qk_check(qk_search_tracked(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_,
                                        res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), pids.data_ptr<int64_t>(), mem, &tm));
@@ -156,8 +169,12 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
         ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
         ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
     } else {
-        qk_check(qk_search(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_,
-                           res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, tmp));
+        if (flt)
+            qk_check(qk_search_filtered(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_,
+                                        flt, res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, tmp));
+        else
+            qk_check(qk_search(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_,
+                               res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, tmp));
         ti->partitions_scanned = (int)tm.partitions_scanned;
         ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
         ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);

@@ -62,7 +62,7 @@ int check_metric(int metric) {
 // `timing` are requested but read later, by qk_finish_timing, once every member of the group has been enqueued.
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
-                  bool defer_finish, int64_t *probed_out) {
+                  bool defer_finish, int64_t *probed_out, qk_filter *filter) {
     QK_TRY(qk_check_overflow(ctx));  // a record-buffer overflow of an earlier launch is reported by the next call
     QK_HIP(hipSetDevice(ctx->device));
     if (timing) memset(timing, 0, sizeof(*timing));
@@ -144,7 +144,8 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
         }
     }
     // small batches: the whole search in one launch (qk_small.hip) -- no prep / group / seed / merge launches
-    if (use_parent && !coarse_only && kk > 0 && !probed_out && qk_small_supported(ctx, parent, s, Q, kk, k)) {
+    // (not a filtered search: that kernel seeds its bound from a sample of rows)
+    if (use_parent && !coarse_only && kk > 0 && !probed_out && !filter && qk_small_supported(ctx, parent, s, Q, kk, k)) {
         const bool tm = ctx->timing && timing;
         // one event pair around the one kernel (an event record costs the stream a few microseconds): ev[4], ev[7] per call,
         // the scan pair of a deferred group otherwise
@@ -229,6 +230,8 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
             }
         }
         sa.sqrt_l2 = !ctx->squared_l2;
+        // filtered search: the row mask, re-derived here (on this stream, in front of the scan) if the store changed
+        if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &sa.mask));
         if (use_parent && kk <= 0) {  // empty parent: nothing to probe -> padding only
             QK_HIP(hipMemsetAsync((void *)sv.pids, 0xFF, (size_t)Q * 8, ctx->stream));
             sa.P = 1;

@@ -1,0 +1,263 @@
+// qk_filter.hip -- filtered search: the filter object of the C ABI (include/quake_hip.h, "filtered search") and the kernel that
+// turns its id set into the row mask the scan kernels read (k_scan_filt, qk_scan.hip; k_scan_wide_filt, qk_scan_wide.hip).
+//
+// A filter is a set of ids S and a mode (allow / deny).  What the scan needs is a statement about ROWS: the lists of a store are
+// extents of 16-row tiles of its arena (qk_part::row_off and cap are multiples of 16), so one 16-bit word per arena tile says which
+// rows of the tile are candidates -- cap_rows / 8 bytes, 1.25 MB at 10M rows.  The word of a tile has one writer (16 lanes of one
+// wave combine their bits with a ballot), so the build needs no atomics on the mask; rows behind a list's size and abandoned
+// extents keep the 0 of the memset in front of the kernel.
+//
+// The mask is stamped with the store's (uid, version, cap_rows): every operation that changes which id sits in which arena row --
+// append, in-place removal (swap with last), list relocation, both arena compactions, qk_store_refine_lists (remove + re-add),
+// list creation / removal, bulk builds -- sets qk_store::table_dirty, and the table sync in front of every scan turns that into a
+// new version.  qk_filter_ensure compares the stamp after that sync and re-derives the mask from the ids when it differs: a filter
+// is defined by ids and stays correct whatever moves rows.
+#include "qk_internal.h"
+
+#include <algorithm>
+#include <vector>
+
+struct qk_filter {
+    uint64_t store_uid = 0;  // the store it was made for (never dereferenced: the store may be destroyed first)
+    int device = 0;
+    int mode = QK_FILTER_ALLOW;
+    int64_t n_ids = 0;
+    int64_t *d_ids = nullptr;  // [n_ids] ascending, no duplicates
+    uint16_t *mask = nullptr;  // [mask_words] one word per arena tile
+    int64_t mask_words = 0;    // capacity
+    bool built = false;
+    uint64_t version = 0;      // stamp: the store's version and arena capacity the mask was derived for
+    int64_t cap_rows = 0;
+    int64_t rebuilds = 0;      // builds after the first
+    unsigned long long *d_allowed = nullptr;  // [1] candidates of the last build
+    hipEvent_t built_ev = nullptr;            // behind the last build, on the stream that ran it
+    qk_ctx *built_ctx = nullptr;
+};
+
+namespace {
+
+struct FilterBuildParams {
+    const int64_t *ids;      // arena ids
+    const int64_t *pt_off;   // [npids] first arena row of every list
+    const int32_t *pt_size;  // [npids] rows, -1 = absent
+    const int64_t *set;      // [n] sorted id set
+    int64_t n;
+    int deny;
+    uint16_t *mask;
+    int64_t mask_words;
+    unsigned long long *allowed;
+};
+
+// blockIdx.x = list, blockIdx.y strides over its chunks of 16 tiles (one tile per 16 lanes of the 256-thread block)
+__global__ __launch_bounds__(256) void k_filter_build(FilterBuildParams F) {
+    const int p = blockIdx.x;
+    const int size = F.pt_size[p];
+    if (size <= 0) return;
+    const int64_t row_off = F.pt_off[p];
+    const int ntl = (size + 15) >> 4;
+    const int lane = threadIdx.x & 63, j = lane & 15;
+    const int sub = threadIdx.x >> 4;  // tile of the chunk
+    unsigned long long mine = 0;
+    for (int t0 = blockIdx.y * 16; t0 < ntl; t0 += gridDim.y * 16) {
+        const int tile = t0 + sub;
+        const int row = tile * 16 + j;
+        bool bit = false;
+        if (tile < ntl && row < size) {
+            const int64_t id = F.ids[row_off + row];
+            int64_t lo = 0, hi = F.n;  // first element >= id
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (F.set[mid] < id) lo = mid + 1;
+                else hi = mid;
+            }
+            const bool found = lo < F.n && F.set[lo] == id;
+            bit = F.deny ? !found : found;
+        }
+        const uint64_t b = __ballot(bit);
+        const uint32_t word = (uint32_t)((b >> (16 * (lane >> 4))) & 0xFFFFull);
+        const int64_t w = (row_off >> 4) + tile;
+        if (j == 0 && tile < ntl && w < F.mask_words) {
+            F.mask[w] = (uint16_t)word;
+            mine += __popc(word);
+        }
+    }
+    // one atomic per wave
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
+    if (lane == 0 && mine) atomicAdd(F.allowed, mine);
+}
+
+int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
+    const int64_t words = s->cap_rows / 16;
+    if (words > f->mask_words || !f->mask) {
+        // (the old mask may still be read by a scan in flight on some context: hipFree waits for the device)
+        if (f->mask) QK_HIP(hipFree(f->mask));
+        f->mask = nullptr;
+        f->mask_words = 0;
+        const int64_t cap = std::max<int64_t>(words + words / 4, 64);
+        if (hipMalloc((void **)&f->mask, (size_t)cap * sizeof(uint16_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            QK_FAIL(QK_ERR_OOM, "qk_filter: no memory for a row mask of %lld tiles", (long long)cap);
+        }
+        f->mask_words = cap;
+    }
+    hipStream_t st = ctx->stream;
+    // a build on another context than the last one: behind that one's (its scans may still read the mask it wrote)
+    if (f->built_ctx && f->built_ctx != ctx) QK_HIP(hipStreamWaitEvent(st, f->built_ev, 0));
+    QK_HIP(hipMemsetAsync(f->mask, 0, (size_t)f->mask_words * sizeof(uint16_t), st));
+    QK_HIP(hipMemsetAsync(f->d_allowed, 0, sizeof(unsigned long long), st));
+    const int64_t npids = (int64_t)s->parts.size();
+    if (npids > 0 && s->ntotal > 0) {
+        FilterBuildParams F;
+        F.ids = s->ids;
+        F.pt_off = s->d_off;
+        F.pt_size = s->d_size;
+        F.set = f->d_ids;
+        F.n = f->n_ids;
+        F.deny = f->mode == QK_FILTER_DENY ? 1 : 0;
+        F.mask = f->mask;
+        F.mask_words = f->mask_words;
+        F.allowed = f->d_allowed;
+        const int64_t max_tiles = (std::max<int64_t>(1, s->max_size) + 15) / 16;
+        const unsigned gy = (unsigned)std::min<int64_t>(65535, (max_tiles + 15) / 16);
+        hipLaunchKernelGGL(k_filter_build, dim3((unsigned)npids, gy), dim3(256), 0, st, F);
+        QK_HIP(hipGetLastError());
+    }
+    QK_HIP(hipEventRecord(f->built_ev, st));
+    if (f->built) f->rebuilds++;
+    f->built = true;
+    f->built_ctx = ctx;
+    f->version = s->version;
+    f->cap_rows = s->cap_rows;
+    return QK_OK;
+}
+
+}  // namespace
+
+int qk_filter_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const uint16_t **mask) {
+    if (!f || !s) QK_FAIL(QK_ERR_INVALID, "filtered search: null filter");
+    if (f->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "filtered search: the filter was made for another store");
+    if (f->device != ctx->device) QK_FAIL(QK_ERR_INVALID, "filtered search: the filter lives on device %d, the context on %d", f->device, ctx->device);
+    QK_TRY(qk_store_sync_table(s));
+    if (!f->built || f->version != s->version || f->cap_rows != s->cap_rows) {
+        QK_TRY(filter_build(ctx, s, f));
+    } else if (f->built_ctx != ctx) {
+        QK_HIP(hipStreamWaitEvent(ctx->stream, f->built_ev, 0));  // the build ran on another context's stream
+    }
+    *mask = f->mask;
+    return QK_OK;
+}
+
+extern "C" {
+
+int qk_filter_create(qk_store *s, const int64_t *ids, int64_t n, int mode, int mem, qk_filter **out) {
+    if (!s || !out || n < 0 || (n > 0 && !ids)) QK_FAIL(QK_ERR_INVALID, "qk_filter_create: bad argument");
+    if (mode != QK_FILTER_ALLOW && mode != QK_FILTER_DENY) QK_FAIL(QK_ERR_INVALID, "qk_filter_create: mode must be QK_FILTER_ALLOW or QK_FILTER_DENY");
+    qk_ctx *c = s->ctx;
+    QK_HIP(hipSetDevice(c->device));
+    // the request sorted and de-duplicated on the host (the product path has no device library)
+    std::vector<int64_t> h((size_t)n);
+    if (n > 0) {
+        if (mem == QK_MEM_DEVICE) {
+            QK_HIP(hipStreamSynchronize(c->stream));
+            QK_HIP(hipMemcpy(h.data(), ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        } else {
+            std::copy(ids, ids + n, h.begin());
+        }
+        std::sort(h.begin(), h.end());
+        h.erase(std::unique(h.begin(), h.end()), h.end());
+    }
+    qk_filter *f = new qk_filter();
+    f->store_uid = s->uid;
+    f->device = c->device;
+    f->mode = mode;
+    f->n_ids = (int64_t)h.size();
+    bool ok = hipMalloc((void **)&f->d_ids, std::max<size_t>(h.size(), 1) * sizeof(int64_t)) == hipSuccess &&
+              hipMalloc((void **)&f->d_allowed, sizeof(unsigned long long)) == hipSuccess &&
+              hipEventCreateWithFlags(&f->built_ev, hipEventDisableTiming) == hipSuccess;
+    if (ok && !h.empty()) ok = hipMemcpy(f->d_ids, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        qk_filter_destroy(f);
+        QK_FAIL(QK_ERR_OOM, "qk_filter_create: no device memory for %lld ids", (long long)n);
+    }
+    // the first mask now, on the store's context: the first filtered search does not pay for it
+    QK_TRY(qk_store_sync_table(s));
+    const int rc = filter_build(c, s, f);
+    if (rc != QK_OK) {
+        qk_filter_destroy(f);
+        return rc;
+    }
+    *out = f;
+    return QK_OK;
+}
+
+int qk_filter_destroy(qk_filter *f) {
+    if (!f) return QK_OK;
+    hipSetDevice(f->device);
+    if (f->built_ev) {
+        hipEventSynchronize(f->built_ev);
+        hipEventDestroy(f->built_ev);
+    }
+    if (f->mask) hipFree(f->mask);  // (hipFree waits for the device: no scan still reads the mask)
+    if (f->d_ids) hipFree(f->d_ids);
+    if (f->d_allowed) hipFree(f->d_allowed);
+    (void)hipGetLastError();
+    delete f;
+    return QK_OK;
+}
+
+int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t *store_version, int64_t *rebuilds, int64_t *device_bytes) {
+    if (!f) QK_FAIL(QK_ERR_INVALID, "qk_filter_info: null filter");
+    QK_HIP(hipSetDevice(f->device));
+    if (n_ids) *n_ids = f->n_ids;
+    if (rows_allowed) {
+        unsigned long long v = 0;
+        QK_HIP(hipEventSynchronize(f->built_ev));
+        QK_HIP(hipMemcpy(&v, f->d_allowed, sizeof(v), hipMemcpyDeviceToHost));
+        *rows_allowed = (int64_t)v;
+    }
+    if (store_version) *store_version = f->version;
+    if (rebuilds) *rebuilds = f->rebuilds;
+    if (device_bytes) *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t) + std::max<int64_t>(f->n_ids, 1) * sizeof(int64_t) + 8);
+    return QK_OK;
+}
+
+int qk_search_filtered(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
+                       qk_filter *f, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+    if (!ctx || !s || !f || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered: null argument");
+    if (k <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered: k must be positive");
+    if (k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_search_filtered: k=%d exceeds QK_MAX_K=%d (filtered search has no wide-k path)", k, QK_MAX_K);
+    if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered: nprobe must be positive");
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, f);
+}
+
+int qk_search_filtered_tracked(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
+                               qk_filter *f, int64_t *out_ids, float *out_dist, int64_t *out_probed, int mem, qk_timing *timing) {
+    if (!ctx || !s || !f || !parent || (Q > 0 && (!x || !out_ids || !out_probed))) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_tracked: null argument");
+    if (k <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_tracked: k must be positive");
+    if (k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_search_filtered_tracked: k=%d exceeds QK_MAX_K=%d (filtered search has no wide-k path)", k, QK_MAX_K);
+    if (nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_tracked: nprobe must be positive");
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, out_ids, out_dist, mem, timing, false, false, out_probed, f);
+}
+
+int qk_scan_filtered(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric, qk_filter *f,
+                     int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+    if (!ctx || !s || !f || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "qk_scan_filtered: null argument");
+    if (P <= 0 || !pids) QK_FAIL(QK_ERR_INVALID, "qk_scan_filtered: bad partition id list");
+    if (k <= 0) QK_FAIL(QK_ERR_INVALID, "qk_scan_filtered: k must be positive");
+    if (k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan_filtered: k=%d exceeds QK_MAX_K=%d (filtered search has no wide-k path)", k, QK_MAX_K);
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    if (mem == QK_MEM_HOST) {
+        for (int64_t i = 0; i < Q * (int64_t)P; i++) {
+            const int64_t p = pids[i];
+            if (p < 0) continue;
+            if (p >= (int64_t)s->parts.size() || !s->parts[p].present)
+                QK_FAIL(QK_ERR_NOT_FOUND, "List does not exist in get_codes (list %lld)", (long long)p);
+        }
+    }
+    return qk_run_search(ctx, nullptr, s, x, Q, pids, P, 0, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, f);
+}
+
+}  // extern "C"

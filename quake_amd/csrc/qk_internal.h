@@ -303,7 +303,14 @@ struct qk_scan_args {
     const unsigned long long **packed_out = nullptr;
     const float4 *xq4 = nullptr;  // [Q][nblk][4] fragment-ordered queries (qk_prep_queries), required
     const float *xn = nullptr;    // [Q] squared norms, required
+    // filtered scan: the row mask of a qk_filter that qk_filter_ensure has just brought up to date for this store (one 16-bit
+    // word per arena tile).  Turns off everything that learns a bound from rows it did not test against the mask.
+    const uint16_t *mask = nullptr;
 };
+// filters (qk_filter.hip)
+struct qk_filter;
+// the filter's row mask, rebuilt on ctx's stream if the store changed since it was made; QK_ERR_INVALID for another store's filter
+int qk_filter_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const uint16_t **mask);
 // x[Q][d] -> ctx->qprep (xq4 then xn); returns the two device pointers
 // zero_bytes > 0: the kernel also clears that many bytes for the scan of this batch (qk_scan_zero_bytes)
 int qk_prep_queries(qk_ctx *ctx, const float *x, int64_t Q, int d, const float4 **xq4, const float **xn, size_t zero_bytes = 0,
@@ -322,7 +329,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
 // the body of qk_coarse / qk_scan / qk_search (qk_api.hip) and the read-back of its scalars; see there
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
-                  bool defer_finish, int64_t *probed_out = nullptr);
+                  bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr);
 int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, int scan_ev_base);
 // adaptive (recall-target) search: the rounds run on `ctx`; a round's (query, list) pairs are scanned by `scan` (qk_aps.hip)
 struct qk_aps_round {

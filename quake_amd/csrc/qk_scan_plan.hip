@@ -163,6 +163,19 @@ int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int
             if ((w == 1 || w == 2 || w == 4) && waves_for(w, C) > 0) nw = w;
         }
     }
+    if (a.mask) {
+        // filtered call: the tile form with one query tile per workgroup (k_scan_filt), nothing else.  The query-sharing, per-wave,
+        // mixed and hot forms either learn bounds from rows they have not tested against the mask (bf16 prefilter) or have no
+        // filtered instantiation; form feedback neither measures such a call nor is consulted for it.
+        pl->DB = DB;
+        pl->C = C;
+        pl->nw = nw;
+        pl->qshare = 0;
+        pl->use_rl = false;
+        pl->form = 0;
+        pl->measure = nullptr;
+        return QK_OK;
+    }
     // query-sharing workgroups: narrow rows and many queries per probed partition (a partition is otherwise streamed once
     // per 16-query tile).  The host only knows the average (pairs per present list); a batch whose queries cluster on few
     // partitions is hotter than that, so the threshold is low.

@@ -140,6 +140,9 @@ struct ScanParams {
     int hot_first_pct;            // the hot-first workgroups' share of the grid = hot / (hot + walk) cost with the items' cost taken at
                                   // this percentage: > 100 puts more workgroups on items at the start, so that the ITEMS (47 us
                                   // apiece) run out first and the launch ends in the fine-grained dynamic tail of the per-wave walk
+    // filtered scan (k_scan_filt, k_scan_wide_filt): one word per 16-row arena tile, bit r = row r of the tile is a candidate
+    // (qk_filter.hip); nullptr = no filter
+    const uint16_t *mask;
 };
 
 // ---- merge stage (qk_merge.hip) ------------------------------------------------------------------------------------------

@@ -116,6 +116,27 @@ class SearchParams(_Summary):  # common.h:171-184, wrap.cpp:153-186
         self.recompute_threshold = DEFAULT_RECOMPUTE_THRESHOLD
         self.initial_search_fraction = DEFAULT_INITIAL_SEARCH_FRACTION
         self.aps_flush_period_us = DEFAULT_APS_FLUSH_PERIOD_US
+        # extension (no reference counterpart, not part of the summary): a SearchFilter of the searched index
+        # (QuakeIndex.make_filter) -- the search returns the k best of the filter's candidates in the probed lists
+        self.filter = None
+
+
+class SearchFilter:
+    """A set of vector ids of ONE index and a mode (QuakeIndex.make_filter): with exclude=False a stored vector is a candidate
+    iff its id is in the set, with exclude=True iff it is not.  Defined by ids, so it stays valid across add / remove / modify /
+    maintenance; it is not persisted by save().  info(): {n_ids, rows_allowed, store_version, rebuilds, device_bytes}."""
+
+    def __init__(self, index, ids, exclude=False):
+        if isinstance(index._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::make_filter()] filtered search is not supported with num_workers > 0")
+        self.exclude = bool(exclude)
+        ids = ids if torch.is_tensor(ids) else torch.as_tensor(np.asarray(ids))
+        ids = ids.reshape(-1).to(torch.int64)
+        self._store = index._store
+        self._h = capi.Filter(index._store, ids if ids.is_cuda else ids.numpy(), "deny" if exclude else "allow")
+
+    def info(self):
+        return self._h.info()
 
 
 class SearchTimingInfo(_Summary):  # common.h:214-228, wrap.cpp:279-320; device phases come from HIP events (qk_timing)
@@ -464,6 +485,19 @@ class QuakeIndex:
         use_aps = (search_params.recall_target is not None and search_params.recall_target > 0.0 and self.parent is not None
                    and not search_params.batched_scan)  # query_coordinator.cpp:502,637-641,659-673
         grp = self._store if isinstance(self._store, capi.Group) else None
+        flt = getattr(search_params, "filter", None)
+        if flt is not None:
+            # filtered search (extension): the fixed-nprobe branch of one device; the rest is refused, not approximated
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.filter must come from make_filter()")
+            if search_params.recall_target is not None and search_params.recall_target > 0.0:
+                raise RuntimeError("[QuakeIndex::search()] a filter cannot be combined with recall_target > 0 "
+                                   "(the recall model counts volume, not allowed rows): not supported")
+            if grp is not None:
+                raise RuntimeError("[QuakeIndex::search()] filtered search is not supported with num_workers > 0")
+            if flt._store is not self._store:
+                raise RuntimeError("[QuakeIndex::search()] the filter was made for another index")
+            flt = flt._h
         if grp is not None:
             grp.set_stream(torch.cuda.current_stream(grp.device).cuda_stream)  # the lead's stream (see _context)
         if use_aps:
@@ -499,7 +533,7 @@ class QuakeIndex:
                     ids, dist, tm = grp.scan(xd, pids, int(k), self.metric_, timing=True)
                 else:  # one enqueue: the nearest-centroid step writes the list numbers where the policy will read them
                     ids, dist, pids, tm = self._ctx.search_tracked(self.parent._store, self._store, xd, nprobe, int(k), self.metric_,
-                                                                   timing=True)
+                                                                   timing=True, filter=flt)
                 self._pending_hits.append(pids)
                 if len(self._pending_hits) >= 64:
                     self._flush_hits()
@@ -507,7 +541,7 @@ class QuakeIndex:
                 ids, dist, tm = grp.search(self.parent._store, xd, nprobe, int(k), self.metric_, timing=True)
             else:
                 ids, dist, tm = self._ctx.search(self.parent._store if self.parent is not None else None, self._store, xd,
-                                                 nprobe, int(k), self.metric_, timing=True)
+                                                 nprobe, int(k), self.metric_, timing=True, filter=flt)
         finally:
             self._ctx.set_timing(0)
         ti.n_queries = int(x.shape[0])
@@ -525,6 +559,11 @@ class QuakeIndex:
         res.ids = ids if on_dev else ids.cpu()
         res.distances = dist if on_dev else dist.cpu()
         return res
+
+    def make_filter(self, ids, exclude=False):
+        """extension: a SearchFilter over this index's vector ids for SearchParams.filter"""
+        self._require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?")
+        return SearchFilter(self, ids, exclude)
 
     # -- get / get_ids (partition_manager.cpp:322-343) --------------------------------------------------------------------
     def get(self, ids):
