@@ -251,6 +251,32 @@ QK_API int qk_search_filtered_tracked(qk_ctx *ctx, qk_store *parent, qk_store *s
 QK_API int qk_scan_filtered(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric,
                             qk_filter *f, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
 
+/* One filter per QUERY of a batch (a server has one filter per user or tenant; its batches mix them): query i is answered under
+ * filters[qfilter[i]].  Row i of the result equals row 0 of the single-filter call above made with query i alone and that
+ * filter -- ids and distance bits -- so everything said there holds per query: the coarse step is not filtered, a short row is
+ * padded, ids that are not stored are ignored, a filter follows its ids through add / remove / refine / maintenance, and no bound
+ * is learned from a row that was not tested against that query's filter.
+ *   filters [F]  HOST array of handles of this store (1 <= F <= QK_MAX_BATCH_FILTERS), each brought up to date like the single one;
+ *   qfilter [Q]  int32 in `mem` like the other buffers.  There is no "unfiltered" code: a query that should see every row names a
+ *                QK_FILTER_DENY filter of the empty set.
+ * QK_ERR_INVALID: F < 1, a null handle, a filter of another store or device, a host qfilter value outside [0, F).  A DEVICE
+ * qfilter is not read by the host: a value outside [0, F) gives that query an all-padding row (the kernel checks the range before
+ * it indexes the table).  QK_ERR_UNSUPPORTED: k > QK_MAX_K, F > QK_MAX_BATCH_FILTERS.
+ * Inside: the kernels k_scan_filtq / k_scan_wide_filtq test every row against the mask word of its lane's own query, and read the
+ * tiles that hold a candidate of at least one of the F filters -- the OR of the masks (k_filter_union), kept on the context
+ * together with the device table of the mask pointers and reused while the same filters come in the same order and neither they
+ * nor the store changed.  qk_ctx_last_scan_kernel names "k_scan (filtered, per query)" / "k_scan_wide (filtered, per query)". */
+#define QK_MAX_BATCH_FILTERS 4096
+QK_API int qk_search_filtered_batch(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k,
+                                    int metric, qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids,
+                                    float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_search_filtered_batch_tracked(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k,
+                                            int metric, qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids,
+                                            float *out_dist, int64_t *out_probed, int mem, qk_timing *timing);
+QK_API int qk_scan_filtered_batch(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric,
+                                  qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids, float *out_dist,
+                                  int mem, qk_timing *timing);
+
 /* QueryCoordinator::search with SearchParams::recall_target > 0 and batched_scan == false: adaptive partition
  * scanning (query_coordinator.cpp:612-657 picks M = max((int)(nlist * initial_search_fraction), 1) candidate partitions
  * from the parent; the use_aps branch of serial_scan, :471-611, scans them in rank order and stops a query once the

@@ -63,6 +63,33 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _i32_with(a, ref):
+    """`a` as a contiguous int32 vector in the memory space of `ref` (numpy on the host, torch on ref's device)"""
+    if _is_torch(ref) and ref.is_cuda:
+        import torch
+        a = a if _is_torch(a) else torch.as_tensor(np.ascontiguousarray(a))
+        return a.reshape(-1).to(device=ref.device, dtype=torch.int32).contiguous()
+    if _is_torch(a):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+
+
+def _filter_batch(filter, filters, query_filter, x):
+    """the (handle array, F, qfilter) of a per-query call, or None: filters= / query_filter= come together and exclude filter="""
+    if filters is None and query_filter is None:
+        return None
+    if filter is not None:
+        raise ValueError("filter= and filters= / query_filter= are exclusive")
+    if filters is None or query_filter is None:
+        raise ValueError("filters= and query_filter= must be given together")
+    filters = list(filters)
+    qf = _i32_with(query_filter, x)
+    if qf.shape[0] != x.shape[0]:
+        raise ValueError("query_filter must have one entry per query: %d != %d" % (qf.shape[0], x.shape[0]))
+    harr = (C.c_void_p * max(len(filters), 1))(*[f.h if f is not None else None for f in filters])
+    return harr, len(filters), qf
+
+
 def _empty_like_mem(shape, dtype, ref):
     if _is_torch(ref) and ref.is_cuda:
         import torch
@@ -166,8 +193,10 @@ class Context:
                                  _ptr(out_d) if values else None, mem))
         return out_p, out_d
 
-    def scan(self, store, x, pids, k, metric, timing=False, filter=None):
-        """filter: a Filter of `store` -- only its candidates are returned (qk_scan_filtered)"""
+    def scan(self, store, x, pids, k, metric, timing=False, filter=None, filters=None, query_filter=None):
+        """filter: a Filter of `store` -- only its candidates are returned (qk_scan_filtered).
+        filters + query_filter: one filter per query -- query i sees the candidates of filters[query_filter[i]]; query_filter is
+        an int32 array / tensor of shape [Q], on the host or on the device with x (qk_scan_filtered_batch)"""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
         if pids.ndim == 1:  # same set for every query (query_coordinator.cpp:506-508)
@@ -177,6 +206,12 @@ class Context:
         out_i = _empty_like_mem((Q, k), np.int64, x)
         out_d = _empty_like_mem((Q, k), np.float32, x)
         t = QkTiming()
+        fb = _filter_batch(filter, filters, query_filter, x)
+        if fb is not None:
+            check(self.lib.qk_scan_filtered_batch(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None,
+                                                  int(pids.shape[1]), int(k), metric_code(metric), fb[0], fb[1], _ptr(fb[2]),
+                                                  _ptr(out_i), _ptr(out_d), mem, C.byref(t) if timing else None))
+            return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
         if filter is not None:
             check(self.lib.qk_scan_filtered(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None,
                                             int(pids.shape[1]), int(k), metric_code(metric), filter.h, _ptr(out_i), _ptr(out_d),
@@ -195,8 +230,9 @@ class Context:
                                _ptr(out_i), _ptr(out_d), _mem_of(x, pids), None))
         return out_i, out_d
 
-    def search(self, parent, store, x, nprobe, k, metric, timing=False, out=None, filter=None):
-        """filter: a Filter of `store` -- the k best of its candidates in the probed lists (qk_search_filtered)"""
+    def search(self, parent, store, x, nprobe, k, metric, timing=False, out=None, filter=None, filters=None, query_filter=None):
+        """filter: a Filter of `store` -- the k best of its candidates in the probed lists (qk_search_filtered).
+        filters + query_filter: one filter per query, as in scan() (qk_search_filtered_batch)"""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
@@ -206,6 +242,12 @@ class Context:
         else:
             out_i, out_d = out
         t = QkTiming()
+        fb = _filter_batch(filter, filters, query_filter, x)
+        if fb is not None:
+            check(self.lib.qk_search_filtered_batch(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q,
+                                                    int(nprobe), int(k), metric_code(metric), fb[0], fb[1], _ptr(fb[2]),
+                                                    _ptr(out_i), _ptr(out_d), mem, C.byref(t) if timing else None))
+            return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
         if filter is not None:
             check(self.lib.qk_search_filtered(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe),
                                               int(k), metric_code(metric), filter.h, _ptr(out_i), _ptr(out_d), mem,
@@ -215,10 +257,10 @@ class Context:
                                  metric_code(metric), _ptr(out_i), _ptr(out_d), mem, C.byref(t) if timing else None))
         return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
 
-    def search_tracked(self, parent, store, x, nprobe, k, metric, timing=False, filter=None):
+    def search_tracked(self, parent, store, x, nprobe, k, metric, timing=False, filter=None, filters=None, query_filter=None):
         """qk_search_tracked: search + the [Q, min(nprobe, parent lists)] list numbers every query scanned, one enqueue.
         Returns (ids, dist, probed[, timing]).  filter: a Filter of `store` (qk_search_filtered_tracked; the probed lists are
-        those of the unfiltered search)."""
+        those of the unfiltered search).  filters + query_filter: one filter per query (qk_search_filtered_batch_tracked)."""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
@@ -227,7 +269,12 @@ class Context:
         out_d = _empty_like_mem((Q, k), np.float32, x)
         out_p = _empty_like_mem((Q, max(width, 1)), np.int64, x)
         t = QkTiming()
-        if filter is not None:
+        fb = _filter_batch(filter, filters, query_filter, x)
+        if fb is not None:
+            check(self.lib.qk_search_filtered_batch_tracked(self.h, parent.h, store.h, _ptr(x), Q, int(nprobe), int(k),
+                                                            metric_code(metric), fb[0], fb[1], _ptr(fb[2]), _ptr(out_i),
+                                                            _ptr(out_d), _ptr(out_p), mem, C.byref(t) if timing else None))
+        elif filter is not None:
             check(self.lib.qk_search_filtered_tracked(self.h, parent.h, store.h, _ptr(x), Q, int(nprobe), int(k),
                                                       metric_code(metric), filter.h, _ptr(out_i), _ptr(out_d), _ptr(out_p), mem,
                                                       C.byref(t) if timing else None))
@@ -517,6 +564,9 @@ class Store:
         out = np.zeros(8, np.int64)
         check(self.lib.qk_store_counters(self.h, _ptr(out), 8))
         return dict(zip(self.COUNTER_NAMES, (int(v) for v in out)))
+
+
+QK_MAX_BATCH_FILTERS = 4096  # include/quake_hip.h: most filters of one per-query call
 
 
 class Filter:

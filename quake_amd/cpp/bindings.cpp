@@ -149,6 +149,14 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("recompute_threshold", &SearchParams::recompute_threshold)
         .def_readwrite("aps_flush_period_us", &SearchParams::aps_flush_period_us)
         .def_readwrite("filter", &SearchParams::filter)  // extension; not part of the summary below
+        .def_readwrite("filters", &SearchParams::filters)  // extension: one filter per query, with query_filter
+        .def_property(
+            "query_filter",
+            [](const SearchParams &p) -> py::object {
+                if (!p.query_filter.defined()) return py::none();
+                return py::cast(p.query_filter);
+            },
+            [](SearchParams &p, py::object v) { p.query_filter = v.is_none() ? Tensor() : v.cast<Tensor>(); })
         .def("__repr__", [](const SearchParams &p) {  // wrap.cpp:173-186
             return Repr().kv("k", p.k).kv("nprobe", p.nprobe).kv("recall_target", p.recall_target).kv("batched_scan", p.batched_scan)
                 .kv("use_precomputed", p.use_precomputed).kv("initial_search_fraction", p.initial_search_fraction)

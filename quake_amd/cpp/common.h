@@ -63,6 +63,7 @@ struct IndexBuildParams {  // common.h:123-143
 struct SearchFilter {
     qk_filter *h = nullptr;
     bool exclude = false;
+    const void *owner = nullptr;  // the store of the index that made it (compared, never dereferenced)
     SearchFilter() = default;
     SearchFilter(const SearchFilter &) = delete;
     SearchFilter &operator=(const SearchFilter &) = delete;
@@ -83,6 +84,10 @@ struct SearchParams {  // common.h:171-184
     float initial_search_fraction = 0.02f;
     int aps_flush_period_us = 100;
     shared_ptr<SearchFilter> filter = nullptr;  // extension, not part of the summary: search only the filter's candidates
+    // extension, not part of the summary: one filter per query of the batch -- query i sees the candidates of
+    // filters[query_filter[i]] (query_filter: integer tensor [Q]).  Given together, exclusive with `filter`
+    std::vector<shared_ptr<SearchFilter>> filters;
+    Tensor query_filter;
 };
 
 struct BuildTimingInfo {  // common.h:189-198

@@ -130,6 +130,7 @@ shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     if (!s) throw std::runtime_error("[QuakeIndex::make_filter()] filtered search is not supported with num_workers > 0");
     auto f = std::make_shared<SearchFilter>();
     f->exclude = exclude;
+    f->owner = s;
     const bool on_dev = ids.defined() && ids.is_cuda();
     Tensor idl = !ids.defined() ? torch::empty({0}, torch::kInt64)
                  : on_dev     ? ids.reshape({-1}).to(torch::kInt64).contiguous()

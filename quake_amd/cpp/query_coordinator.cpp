@@ -126,6 +126,33 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
         if (!sp->filter->h) throw std::runtime_error("[QuakeIndex::search()] SearchParams.filter must come from make_filter()");
         flt = sp->filter->h;
     }
+    // one filter per query (extension): the same branch, the same refusals
+    std::vector<qk_filter *> flts;
+    Tensor qflt;
+    if (!sp->filters.empty() || sp->query_filter.defined()) {
+        if (sp->filter) throw std::runtime_error("[QuakeIndex::search()] SearchParams.filter and SearchParams.filters are exclusive");
+        if (sp->filters.empty() || !sp->query_filter.defined())
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.filters and SearchParams.query_filter must be given together");
+        for (const auto &f : sp->filters)
+            if (!f || !f->h) throw std::runtime_error("[QuakeIndex::search()] SearchParams.filters must come from make_filter()");
+        if (sp->recall_target > 0.0f)
+            throw std::runtime_error("[QuakeIndex::search()] a filter cannot be combined with recall_target > 0 "
+                                     "(the recall model counts volume, not allowed rows): not supported");
+        if (group) throw std::runtime_error("[QuakeIndex::search()] filtered search is not supported with num_workers > 0");
+        for (const auto &f : sp->filters)
+            if (f->owner != store) throw std::runtime_error("[QuakeIndex::search()] the filter was made for another index");
+        const Tensor &qf = sp->query_filter;
+        if (qf.dim() != 1 || qf.size(0) != Q)
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.query_filter must have one entry per query (" +
+                                     std::to_string(qf.dim() >= 1 ? qf.size(0) : 0) + " != " + std::to_string(Q) + ")");
+        if (!qf.is_cuda() && qf.numel() > 0 &&
+            (qf.min().item<int64_t>() < 0 || qf.max().item<int64_t>() >= (int64_t)sp->filters.size()))
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.query_filter holds a value outside [0, " +
+                                     std::to_string(sp->filters.size()) + ")");
+        for (const auto &f : sp->filters) flts.push_back(f->h);
+        qflt = qf.to(xq.device(), torch::kInt32).contiguous();
+    }
+    const int F = (int)flts.size();
     if (sp->recall_target > 0.0f && parent_ && !sp->batched_scan) {
         // adaptive partition scanning (:502,637-641): candidates = nlist * initial_search_fraction; with workers the rounds run on
         // the group's lead and every member scans the pairs whose partitions it holds (the APS hook of worker_scan, :364-428)
@@ -149,6 +176,10 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
             qk_check(qk_coarse(ctx, parent_->store(), xq.data_ptr<float>(), Q, nprobe, (int)metric_, pids.data_ptr<int64_t>(), nullptr, mem));
             qk_check(qk_group_scan(group, xq.data_ptr<float>(), Q, pids.data_ptr<int64_t>(), kk, k, (int)metric_,
                                    res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, &tm));
+        } else if (F) {
+            qk_check(qk_search_filtered_batch_tracked(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_,
+                                                      flts.data(), F, qflt.data_ptr<int32_t>(), res->ids.data_ptr<int64_t>(),
+                                                      res->distances.data_ptr<float>(), pids.data_ptr<int64_t>(), mem, &tm));
         } else if (flt) {  // (the probed lists are the unfiltered search's: the policy sees the same hits)
             qk_check(qk_search_filtered_tracked(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_, flt,
                                                 res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), pids.data_ptr<int64_t>(), mem, &tm));
@@ -169,7 +200,11 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
         ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
         ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
     } else {
-        if (flt)
+        if (F)
+            qk_check(qk_search_filtered_batch(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k,
+                                              (int)metric_, flts.data(), F, qflt.data_ptr<int32_t>(), res->ids.data_ptr<int64_t>(),
+                                              res->distances.data_ptr<float>(), mem, tmp));
+        else if (flt)
             qk_check(qk_search_filtered(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_,
                                         flt, res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, tmp));
         else

@@ -62,7 +62,7 @@ int check_metric(int metric) {
 // `timing` are requested but read later, by qk_finish_timing, once every member of the group has been enqueued.
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
-                  bool defer_finish, int64_t *probed_out, qk_filter *filter) {
+                  bool defer_finish, int64_t *probed_out, qk_filter *filter, const qk_filter_batch *fbatch) {
     QK_TRY(qk_check_overflow(ctx));  // a record-buffer overflow of an earlier launch is reported by the next call
     QK_HIP(hipSetDevice(ctx->device));
     if (timing) memset(timing, 0, sizeof(*timing));
@@ -145,7 +145,7 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
     }
     // small batches: the whole search in one launch (qk_small.hip) -- no prep / group / seed / merge launches
     // (not a filtered search: that kernel seeds its bound from a sample of rows)
-    if (use_parent && !coarse_only && kk > 0 && !probed_out && !filter && qk_small_supported(ctx, parent, s, Q, kk, k)) {
+    if (use_parent && !coarse_only && kk > 0 && !probed_out && !filter && !fbatch && qk_small_supported(ctx, parent, s, Q, kk, k)) {
         const bool tm = ctx->timing && timing;
         // one event pair around the one kernel (an event record costs the stream a few microseconds): ev[4], ev[7] per call,
         // the scan pair of a deferred group otherwise
@@ -232,6 +232,25 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
         sa.sqrt_l2 = !ctx->squared_l2;
         // filtered search: the row mask, re-derived here (on this stream, in front of the scan) if the store changed
         if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &sa.mask));
+        if (fbatch) {
+            // one filter per query: every mask brought up to date, then the table of their pointers and their union (kept on the
+            // context while nothing changes); a host qfilter -- range-checked by the entry point -- goes to the device behind them
+            QK_TRY(qk_filter_batch_ensure(ctx, s, fbatch->filters, fbatch->F, &sa.qmasks, &sa.mask));
+            sa.F = fbatch->F;
+            sa.qfilter = fbatch->qfilter;
+            if (mem == QK_MEM_HOST) {
+                if (Q > ctx->fb_qfilter_cap) {
+                    if (ctx->fb_qfilter) QK_HIP(hipFree(ctx->fb_qfilter));
+                    ctx->fb_qfilter = nullptr;
+                    ctx->fb_qfilter_cap = 0;
+                    const int64_t cap = std::max<int64_t>(Q + Q / 2, 1024);
+                    QK_HIP(hipMalloc((void **)&ctx->fb_qfilter, (size_t)cap * sizeof(int32_t)));
+                    ctx->fb_qfilter_cap = cap;
+                }
+                QK_HIP(hipMemcpyAsync(ctx->fb_qfilter, fbatch->qfilter, (size_t)Q * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+                sa.qfilter = ctx->fb_qfilter;
+            }
+        }
         if (use_parent && kk <= 0) {  // empty parent: nothing to probe -> padding only
             QK_HIP(hipMemsetAsync((void *)sv.pids, 0xFF, (size_t)Q * 8, ctx->stream));
             sa.P = 1;

@@ -15,9 +15,11 @@
 #include "qk_internal.h"
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 struct qk_filter {
+    uint64_t serial = 0;     // unique per filter object of the process: a freed and re-allocated handle is another filter
     uint64_t store_uid = 0;  // the store it was made for (never dereferenced: the store may be destroyed first)
     int device = 0;
     int mode = QK_FILTER_ALLOW;
@@ -131,19 +133,100 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     return QK_OK;
 }
 
-}  // namespace
-
-int qk_filter_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const uint16_t **mask) {
-    if (!f || !s) QK_FAIL(QK_ERR_INVALID, "filtered search: null filter");
-    if (f->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "filtered search: the filter was made for another store");
-    if (f->device != ctx->device) QK_FAIL(QK_ERR_INVALID, "filtered search: the filter lives on device %d, the context on %d", f->device, ctx->device);
-    QK_TRY(qk_store_sync_table(s));
+// the mask of a filter of this store and device, current for the store's table (the caller has synced it)
+int filter_current(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     if (!f->built || f->version != s->version || f->cap_rows != s->cap_rows) {
         QK_TRY(filter_build(ctx, s, f));
     } else if (f->built_ctx != ctx) {
         QK_HIP(hipStreamWaitEvent(ctx->stream, f->built_ev, 0));  // the build ran on another context's stream
     }
+    return QK_OK;
+}
+
+int filter_belongs(qk_ctx *ctx, qk_store *s, qk_filter *f) {
+    if (!f || !s) QK_FAIL(QK_ERR_INVALID, "filtered search: null filter");
+    if (f->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "filtered search: the filter was made for another store");
+    if (f->device != ctx->device) QK_FAIL(QK_ERR_INVALID, "filtered search: the filter lives on device %d, the context on %d", f->device, ctx->device);
+    return QK_OK;
+}
+
+// ---- one filter per query: the OR of the call's F masks ------------------------------------------------------------------------
+// The scan of a per-query call walks the tiles that hold a candidate of ANY of its filters (ScanParams::mask) and tests every row
+// against its own query's word (ScanParams::qmasks): the first is this kernel's output.  One lane per word, a loop over the F
+// masks -- the 64 lanes of a wave read 128 consecutive bytes of each -- plain vector stores, no atomics.
+__global__ __launch_bounds__(256) void k_filter_union(const uint16_t *const *masks, int F, int64_t words, uint16_t *out) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= words) return;
+    uint32_t acc = 0;
+    for (int f = 0; f < F; f++) acc |= (uint32_t)masks[f][w];
+    out[w] = (uint16_t)acc;
+}
+
+}  // namespace
+
+int qk_filter_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const uint16_t **mask) {
+    QK_TRY(filter_belongs(ctx, s, f));
+    QK_TRY(qk_store_sync_table(s));
+    QK_TRY(filter_current(ctx, s, f));
     *mask = f->mask;
+    return QK_OK;
+}
+
+int qk_filter_batch_ensure(qk_ctx *ctx, qk_store *s, qk_filter *const *filters, int F, const uint16_t *const **table, const uint16_t **uni) {
+    for (int i = 0; i < F; i++) QK_TRY(filter_belongs(ctx, s, filters[i]));
+    QK_TRY(qk_store_sync_table(s));  // once: every filter is compared with the same version
+    for (int i = 0; i < F; i++) QK_TRY(filter_current(ctx, s, filters[i]));
+    // what the table and the union were derived from; a mask that was re-derived has another version (or capacity), a handle that
+    // was freed and allocated again another serial
+    std::vector<uint64_t> key;
+    key.reserve((size_t)F * 4);
+    for (int i = 0; i < F; i++) {
+        const qk_filter *f = filters[i];
+        key.push_back(f->serial);
+        key.push_back(f->version);
+        key.push_back((uint64_t)f->cap_rows);
+        key.push_back((uint64_t)(uintptr_t)f->mask);
+    }
+    const int64_t words = s->cap_rows / 16;
+    if (key != ctx->fb_key || !ctx->fb_table || !ctx->fb_union) {
+        hipStream_t st = ctx->stream;
+        ctx->fb_key.clear();
+        if (F > ctx->fb_table_cap || !ctx->fb_table) {
+            // (scans in flight may still read the old table: hipFree waits for the device)
+            if (ctx->fb_table) QK_HIP(hipFree((void *)ctx->fb_table));
+            ctx->fb_table = nullptr;
+            ctx->fb_table_cap = 0;
+            const int64_t cap = std::max<int64_t>(F, 64);
+            if (hipMalloc((void **)&ctx->fb_table, (size_t)cap * sizeof(uint16_t *)) != hipSuccess) {
+                (void)hipGetLastError();
+                QK_FAIL(QK_ERR_OOM, "filtered search: no memory for a table of %lld masks", (long long)cap);
+            }
+            ctx->fb_table_cap = cap;
+        }
+        if (words > ctx->fb_union_words || !ctx->fb_union) {
+            if (ctx->fb_union) QK_HIP(hipFree(ctx->fb_union));
+            ctx->fb_union = nullptr;
+            ctx->fb_union_words = 0;
+            const int64_t cap = std::max<int64_t>(words + words / 4, 64);
+            if (hipMalloc((void **)&ctx->fb_union, (size_t)cap * sizeof(uint16_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                QK_FAIL(QK_ERR_OOM, "filtered search: no memory for the union of the masks (%lld tiles)", (long long)cap);
+            }
+            ctx->fb_union_words = cap;
+        }
+        // stream-ordered, no synchronisation: the source is pageable, so it has been copied out when the call returns
+        std::vector<const uint16_t *> h((size_t)F);
+        for (int i = 0; i < F; i++) h[i] = filters[i]->mask;
+        QK_HIP(hipMemcpyAsync((void *)ctx->fb_table, h.data(), (size_t)F * sizeof(uint16_t *), hipMemcpyHostToDevice, st));
+        if (words > 0) {
+            hipLaunchKernelGGL(k_filter_union, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st,
+                               (const uint16_t *const *)ctx->fb_table, F, words, ctx->fb_union);
+            QK_HIP(hipGetLastError());
+        }
+        ctx->fb_key = std::move(key);
+    }
+    *table = (const uint16_t *const *)ctx->fb_table;
+    *uni = ctx->fb_union;
     return QK_OK;
 }
 
@@ -166,7 +249,9 @@ int qk_filter_create(qk_store *s, const int64_t *ids, int64_t n, int mode, int m
         std::sort(h.begin(), h.end());
         h.erase(std::unique(h.begin(), h.end()), h.end());
     }
+    static std::atomic<uint64_t> next_serial{1};
     qk_filter *f = new qk_filter();
+    f->serial = next_serial.fetch_add(1);
     f->store_uid = s->uid;
     f->device = c->device;
     f->mode = mode;
@@ -258,6 +343,63 @@ int qk_scan_filtered(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const 
         }
     }
     return qk_run_search(ctx, nullptr, s, x, Q, pids, P, 0, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, f);
+}
+
+// ---- one filter per query ------------------------------------------------------------------------------------------------------
+static int check_filter_batch(const char *who, qk_filter *const *filters, int F, const int32_t *qfilter, int64_t Q, int k, int mem) {
+    if (!filters || F < 1) QK_FAIL(QK_ERR_INVALID, "%s: at least one filter is required (F=%d)", who, F);
+    if (F > QK_MAX_BATCH_FILTERS) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: F=%d exceeds QK_MAX_BATCH_FILTERS=%d", who, F, QK_MAX_BATCH_FILTERS);
+    for (int i = 0; i < F; i++)
+        if (!filters[i]) QK_FAIL(QK_ERR_INVALID, "%s: filter %d of %d is null", who, i, F);
+    if (Q > 0 && !qfilter) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
+    if (k <= 0) QK_FAIL(QK_ERR_INVALID, "%s: k must be positive", who);
+    if (k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds QK_MAX_K=%d (filtered search has no wide-k path)", who, k, QK_MAX_K);
+    if (mem == QK_MEM_HOST)
+        for (int64_t i = 0; i < Q; i++)
+            if (qfilter[i] < 0 || qfilter[i] >= F)
+                QK_FAIL(QK_ERR_INVALID, "%s: qfilter[%lld]=%d is outside [0, F=%d)", who, (long long)i, (int)qfilter[i], F);
+    return QK_OK;
+}
+
+int qk_search_filtered_batch(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
+                             qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids, float *out_dist, int mem,
+                             qk_timing *timing) {
+    if (!ctx || !s || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_batch: null argument");
+    QK_TRY(check_filter_batch("qk_search_filtered_batch", filters, F, qfilter, Q, k, mem));
+    if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_batch: nprobe must be positive");
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    const qk_filter_batch fb{filters, F, qfilter};
+    return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, nullptr, &fb);
+}
+
+int qk_search_filtered_batch_tracked(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
+                                     qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids, float *out_dist,
+                                     int64_t *out_probed, int mem, qk_timing *timing) {
+    if (!ctx || !s || !parent || (Q > 0 && (!x || !out_ids || !out_probed))) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_batch_tracked: null argument");
+    QK_TRY(check_filter_batch("qk_search_filtered_batch_tracked", filters, F, qfilter, Q, k, mem));
+    if (nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_batch_tracked: nprobe must be positive");
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    const qk_filter_batch fb{filters, F, qfilter};
+    return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, out_ids, out_dist, mem, timing, false, false, out_probed, nullptr, &fb);
+}
+
+int qk_scan_filtered_batch(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric,
+                           qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids, float *out_dist, int mem,
+                           qk_timing *timing) {
+    if (!ctx || !s || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "qk_scan_filtered_batch: null argument");
+    if (P <= 0 || !pids) QK_FAIL(QK_ERR_INVALID, "qk_scan_filtered_batch: bad partition id list");
+    QK_TRY(check_filter_batch("qk_scan_filtered_batch", filters, F, qfilter, Q, k, mem));
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    if (mem == QK_MEM_HOST) {
+        for (int64_t i = 0; i < Q * (int64_t)P; i++) {
+            const int64_t p = pids[i];
+            if (p < 0) continue;
+            if (p >= (int64_t)s->parts.size() || !s->parts[p].present)
+                QK_FAIL(QK_ERR_NOT_FOUND, "List does not exist in get_codes (list %lld)", (long long)p);
+        }
+    }
+    const qk_filter_batch fb{filters, F, qfilter};
+    return qk_run_search(ctx, nullptr, s, x, Q, pids, P, 0, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, nullptr, &fb);
 }
 
 }  // extern "C"

@@ -174,6 +174,15 @@ struct qk_ctx {
     bool xcd_pending = false;
     uint64_t xcd_key = 0;
     double xcd_wsnap[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    // one filter per query (qk_filter.hip, qk_filter_batch_ensure): the device table of the last call's F mask pointers and the OR
+    // of those masks, valid while fb_key -- (serial, version, cap_rows, mask) of every filter in order -- is what the next call brings
+    std::vector<uint64_t> fb_key;
+    const uint16_t **fb_table = nullptr;  // [fb_table_cap]
+    int64_t fb_table_cap = 0;
+    uint16_t *fb_union = nullptr;         // [fb_union_words]
+    int64_t fb_union_words = 0;
+    int32_t *fb_qfilter = nullptr;        // [fb_qfilter_cap] device copy of a host qfilter
+    int64_t fb_qfilter_cap = 0;
 };
 
 int qk_ws_reserve(qk_ctx *ctx, size_t bytes);          // make sure the workspace can hold `bytes` (may sync+realloc)
@@ -306,11 +315,25 @@ struct qk_scan_args {
     // filtered scan: the row mask of a qk_filter that qk_filter_ensure has just brought up to date for this store (one 16-bit
     // word per arena tile).  Turns off everything that learns a bound from rows it did not test against the mask.
     const uint16_t *mask = nullptr;
+    // one filter per query (qk_filter_batch_ensure): query i is answered under qmasks[qfilter[i]], `mask` is then the OR of the F
+    // masks (which tiles are read); qfilter [Q] on the device, a value outside [0, F) gives that query no candidates
+    const uint16_t *const *qmasks = nullptr;
+    const int32_t *qfilter = nullptr;
+    int F = 0;
 };
 // filters (qk_filter.hip)
 struct qk_filter;
 // the filter's row mask, rebuilt on ctx's stream if the store changed since it was made; QK_ERR_INVALID for another store's filter
 int qk_filter_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const uint16_t **mask);
+// one filter per query: the filters of a qk_*_filtered_batch call (qfilter lives in the call's `mem`)
+struct qk_filter_batch {
+    qk_filter *const *filters = nullptr;
+    int F = 0;
+    const int32_t *qfilter = nullptr;
+};
+// every one of the F masks brought up to date like qk_filter_ensure does (one table sync), then the device table of the F mask
+// pointers and the OR of the masks, both kept on the context and reused while the filters and the store are unchanged
+int qk_filter_batch_ensure(qk_ctx *ctx, qk_store *s, qk_filter *const *filters, int F, const uint16_t *const **table, const uint16_t **uni);
 // x[Q][d] -> ctx->qprep (xq4 then xn); returns the two device pointers
 // zero_bytes > 0: the kernel also clears that many bytes for the scan of this batch (qk_scan_zero_bytes)
 int qk_prep_queries(qk_ctx *ctx, const float *x, int64_t Q, int d, const float4 **xq4, const float **xn, size_t zero_bytes = 0,
@@ -329,7 +352,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
 // the body of qk_coarse / qk_scan / qk_search (qk_api.hip) and the read-back of its scalars; see there
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
-                  bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr);
+                  bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr, const qk_filter_batch *fbatch = nullptr);
 int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, int scan_ev_base);
 // adaptive (recall-target) search: the rounds run on `ctx`; a round's (query, list) pairs are scanned by `scan` (qk_aps.hip)
 struct qk_aps_round {

@@ -815,6 +815,16 @@ __global__ __launch_bounds__(256) void k_scan_filt(ScanParams P) {
 #undef QK_SCAN_FILT
 }
 
+// One filter per query (ScanParams::qmasks / qfilter): the filtered body once more, with the epilogue's mask word taken from the
+// lane's own query's filter and the walk driven by the OR of the call's masks.  Its own kernel again: k_scan_filt does not change.
+template <int DB, int MAXCH, bool L2>
+__global__ __launch_bounds__(256) void k_scan_filtq(ScanParams P) {
+    constexpr int MODE = 0;
+#define QK_SCAN_FILT 2
+#include "qk_scan_body.inc"
+#undef QK_SCAN_FILT
+}
+
 // ---- host orchestration -------------------------------------------------------------------------------------
 // row-per-lane form (qk_scan_rl.hip)
 int qk_launch_merge(qk_ctx *ctx, MergeParams mp, dim3 mgrid);  // qk_merge.hip
@@ -847,8 +857,18 @@ static int launch_scan_emit(dim3 grid, dim3 block, size_t lds, hipStream_t st, c
     return launch_scan_m<DB, 1, 4>(grid, block, lds, st, sp);
 }
 
+template <int DB, int MAXCH, bool L2>
+static int launch_scan_filtq(dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp) {
+    QK_HIP(hipFuncSetAttribute((const void *)k_scan_filtq<DB, MAXCH, L2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_scan_filtq<DB, MAXCH, L2>), grid, block, lds, st, sp);
+    return QK_OK;
+}
+
 template <int DB, int MAXCH>
 static int launch_scan_filt(dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp) {
+    if (sp.qmasks)  // one filter per query
+        return sp.metric == QK_METRIC_L2 ? launch_scan_filtq<DB, MAXCH, true>(grid, block, lds, st, sp)
+                                         : launch_scan_filtq<DB, MAXCH, false>(grid, block, lds, st, sp);
     if (sp.metric == QK_METRIC_L2) {
         QK_HIP(hipFuncSetAttribute((const void *)k_scan_filt<DB, MAXCH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((k_scan_filt<DB, MAXCH, true>), grid, block, lds, st, sp);
@@ -1264,6 +1284,9 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         sp.key_out = a.key_out;
         sp.pair_base = a.pair_base;
         sp.mask = a.mask;
+        sp.qmasks = a.qmasks;
+        sp.qfilter = a.qfilter;
+        sp.F = a.F;
         sp.pair_slots = pair_slots;
         sp.rec_counter = rec_counter;
         sp.max_recs = (int32_t)max_recs;
@@ -1370,7 +1393,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             QK_HIP(hipMemsetAsync(d_clock, 0, (size_t)grid * wpw * 64 * 2, st));
             sp.wave_clock = d_clock;
         }
-        ctx->last_scan_kernel = filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
+        ctx->last_scan_kernel = a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
         if (wide)
             QK_TRY(qk_launch_scan_wide(maxch, (unsigned)grid, lds_launch, st, sp));
         else if (use_rl)

@@ -4,6 +4,10 @@
 // candidate" (qk_filter.hip): a wave walks only the tiles of its share whose word is not 0 -- the loads of the others are never
 // issued -- and a row passes the epilogue only with its bit set.  Which tiles are skipped depends on the tile index alone, and the
 // barriers of the multi-wave forms sit at the query staging, once per segment, outside the tile loop: every wave reaches them.
+// QK_SCAN_FILT 2 = k_scan_filtq, one filter per QUERY: ScanParams::mask is the OR of the call's F masks and drives the walk alone
+// (which tiles are read); the word that reaches the epilogue is the lane's own, qmasks[qfilter[myq]][tile] -- lane (j, g) holds
+// rows 4g..4g+3 of the tile for query j, so the 16 queries of a tile are answered under 16 different filters in one pass.  The
+// four g groups of a query read the same word: at most 16 distinct 2-byte addresses per tile.
 // Expects: template parameters DB, MAXCH, MODE, L2 and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     // nw waves per workgroup (1, 2 or 4) share ONE LDS query tile and split every segment's tiles between them; each
@@ -168,6 +172,22 @@
             const float4 *nsrcL = (const float4 *)(P.norms + row_off) + g;
             const longlong2 *isrcL = (const longlong2 *)(P.ids + row_off) + 2 * g;
             const uint16_t *mrow = P.mask + (row_off >> 4);
+#if QK_SCAN_FILT == 2
+            // this lane's own mask row, resolved once per segment.  A lane without a query, or whose filter number is outside
+            // [0, F) (a device qfilter is not validated by the host), reads the union's word and drops it: qm_keep = 0
+            const uint16_t *qmrow = mrow;
+            uint32_t qm_keep = 0u;
+            if (myq >= 0) {
+                const int fi_ = P.qfilter[myq];
+                if ((unsigned)fi_ < (unsigned)P.F) {
+                    qmrow = P.qmasks[fi_] + (row_off >> 4);
+                    qm_keep = 0xFFFFu;
+                }
+            }
+#define QK_MASK_WORD(T) ((uint32_t)qmrow[T] & qm_keep)
+#else
+#define QK_MASK_WORD(T) (uint32_t)mrow[T]
+#endif
             int fl_base = tl, lt = min(tl, tend_wg - 1), lt_issued = lt;
             uint64_t fl_bits = 0;
             uint32_t y0_m = 0, y1_m = 0;  // the tile's word, double-buffered with its norms (y0 / y1) and ids
@@ -224,7 +244,7 @@
         Y = nsrcL[(int64_t)lt * 4];                                   \
         I0 = isrcL[(int64_t)lt * 8];                                  \
         I1 = isrcL[(int64_t)lt * 8 + 1];                              \
-        Y##_m = (uint32_t)mrow[lt];                                   \
+        Y##_m = QK_MASK_WORD(lt);                                     \
         lt_issued = lt;                                               \
         if (lS < nsteps - 1) {                                        \
             lS++;                                                     \
@@ -418,6 +438,9 @@
 #undef QK_STEP
 #undef QK_EPI_M
 #undef QK_NEXT_TILE
+#if QK_SCAN_FILT
+#undef QK_MASK_WORD
+#endif
             if (!PRODUCT && probe_sink == 12345.678f) my_ord[0] = 1;  // keep the probe's loads alive
         }
         // ---- segment end: final compaction (sorts, caps at k), publish bound, emit records ---------------------------

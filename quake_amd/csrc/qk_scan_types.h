@@ -143,6 +143,11 @@ struct ScanParams {
     // filtered scan (k_scan_filt, k_scan_wide_filt): one word per 16-row arena tile, bit r = row r of the tile is a candidate
     // (qk_filter.hip); nullptr = no filter
     const uint16_t *mask;
+    // one filter per query (k_scan_filtq, k_scan_wide_filtq): query i is answered under the mask qmasks[qfilter[i]]; `mask` above
+    // is then the OR of the F masks and decides only which tiles are read.  qfilter[i] outside [0, F): no candidates.  nullptr = off
+    const uint16_t *const *qmasks;  // [F] device table of mask pointers
+    const int32_t *qfilter;         // [Q]
+    int F;
 };
 
 // ---- merge stage (qk_merge.hip) ------------------------------------------------------------------------------------------

@@ -94,6 +94,21 @@ __global__ __launch_bounds__(64) void k_scan_wide_filt(ScanParams P) {
 #include "qk_scan_wide_body.inc"
 #undef QK_SCAN_FILT
 }
+// one filter per query (ScanParams::qmasks / qfilter): see qk_scan_wide_body.inc
+template <bool L2, int MAXCH>
+__global__ __launch_bounds__(64) void k_scan_wide_filtq(ScanParams P) {
+    constexpr bool EMIT = false;
+#define QK_SCAN_FILT 2
+#include "qk_scan_wide_body.inc"
+#undef QK_SCAN_FILT
+}
+
+template <bool L2, int MAXCH>
+static int launch_scan_wide_fq(unsigned grid, size_t lds, hipStream_t st, const ScanParams &sp) {
+    QK_HIP(hipFuncSetAttribute((const void *)k_scan_wide_filtq<L2, MAXCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_scan_wide_filtq<L2, MAXCH>), dim3(grid), dim3(64), lds, st, sp);
+    return QK_OK;
+}
 
 template <bool L2, int MAXCH>
 static int launch_scan_wide_f(unsigned grid, size_t lds, hipStream_t st, const ScanParams &sp) {
@@ -112,6 +127,12 @@ template <bool L2>
 static int launch_scan_wide_m(int maxch, unsigned grid, size_t lds, hipStream_t st, const ScanParams &sp) {
     if (sp.mask) {
         if (sp.key_out) QK_FAIL(QK_ERR_UNSUPPORTED, "no filtered wide-row scan kernel for key emission");
+        if (sp.qmasks) {  // one filter per query
+            if (maxch == 1) return launch_scan_wide_fq<L2, 1>(grid, lds, st, sp);
+            if (maxch == 2) return launch_scan_wide_fq<L2, 2>(grid, lds, st, sp);
+            if (maxch == 4) return launch_scan_wide_fq<L2, 4>(grid, lds, st, sp);
+            return launch_scan_wide_fq<L2, 8>(grid, lds, st, sp);
+        }
         if (maxch == 1) return launch_scan_wide_f<L2, 1>(grid, lds, st, sp);
         if (maxch == 2) return launch_scan_wide_f<L2, 2>(grid, lds, st, sp);
         if (maxch == 4) return launch_scan_wide_f<L2, 4>(grid, lds, st, sp);

@@ -1,7 +1,9 @@
 // qk_scan_wide_body.inc -- the body of k_scan_wide (qk_scan_wide.hip), included once per kernel: QK_SCAN_FILT 0 = k_scan_wide as it
 // always was (same preprocessed text, so its code does not move), QK_SCAN_FILT 1 = k_scan_wide_filt, which reads ScanParams::mask
 // (one 16-bit word per arena tile, qk_filter.hip): a row passes the epilogue only with its bit set, and the walk jumps over tiles
-// whose word is 0 (a tile of a wide row is 16 x d x 4 bytes: 192 KB at d = 3072).
+// whose word is 0 (a tile of a wide row is 16 x d x 4 bytes: 192 KB at d = 3072).  QK_SCAN_FILT 2 = k_scan_wide_filtq, one filter
+// per query: the walk jumps by ScanParams::mask, the OR of the call's masks; the epilogue's word is the lane's own query's
+// (qmasks[qfilter[myq]], see qk_scan_body.inc).
 // Expects: template parameters L2, MAXCH, EMIT and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int R = QK_WIDE_R;
@@ -64,6 +66,18 @@
             if (l2) xnj = P.xn[myq];
         }
         int cnt = 0;
+#if QK_SCAN_FILT == 2
+        // this lane's own mask, resolved once per segment; no query / a filter number outside [0, F): the union's word, dropped
+        const uint16_t *qmask = P.mask;
+        uint32_t qm_keep = 0u;
+        if (myq >= 0) {
+            const int fi_ = P.qfilter[myq];
+            if ((unsigned)fi_ < (unsigned)P.F) {
+                qmask = P.qmasks[fi_];
+                qm_keep = 0xFFFFu;
+            }
+        }
+#endif
         const float4 *qsrc = P.xq4 + (int64_t)qsafe * nblk * 4 + g;
         auto bload = [&](int c) { return qsrc[c * 4]; };
 
@@ -85,7 +99,9 @@
             const longlong2 ia = ((const longlong2 *)(P.ids + (tile_abs << 4)))[2 * g];
             const longlong2 ib = ((const longlong2 *)(P.ids + (tile_abs << 4)))[2 * g + 1];
             const int64_t idv[4] = {ia.x, ia.y, ib.x, ib.y};
-#if QK_SCAN_FILT
+#if QK_SCAN_FILT == 2
+            const uint32_t mw = (uint32_t)qmask[tile_abs] & qm_keep;  // this tile's word under this lane's query's filter
+#elif QK_SCAN_FILT
             const uint32_t mw = (uint32_t)P.mask[tile_abs];  // this tile's word: bit r = row r is a candidate
 #endif
             if (P.gtau && P.tau_refresh && (tile & 7) == 7 && myq >= 0)

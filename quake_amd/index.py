@@ -119,6 +119,10 @@ class SearchParams(_Summary):  # common.h:171-184, wrap.cpp:153-186
         # extension (no reference counterpart, not part of the summary): a SearchFilter of the searched index
         # (QuakeIndex.make_filter) -- the search returns the k best of the filter's candidates in the probed lists
         self.filter = None
+        # extension: one filter per query of the batch -- `filters` is a list of SearchFilter, `query_filter` an integer tensor of
+        # shape [Q]; query i sees the candidates of filters[query_filter[i]].  Given together, exclusive with `filter`
+        self.filters = []
+        self.query_filter = None
 
 
 class SearchFilter:
@@ -498,6 +502,32 @@ class QuakeIndex:
             if flt._store is not self._store:
                 raise RuntimeError("[QuakeIndex::search()] the filter was made for another index")
             flt = flt._h
+        flts = getattr(search_params, "filters", None)
+        flts = list(flts) if flts is not None else []
+        qflt = getattr(search_params, "query_filter", None)
+        fb = {}
+        if flts or qflt is not None:
+            # one filter per query (extension): the same branch, the same refusals
+            if flt is not None:
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.filter and SearchParams.filters are exclusive")
+            if not flts or qflt is None:
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.filters and SearchParams.query_filter must be given together")
+            if any(not isinstance(f, SearchFilter) for f in flts):
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.filters must come from make_filter()")
+            if search_params.recall_target is not None and search_params.recall_target > 0.0:
+                raise RuntimeError("[QuakeIndex::search()] a filter cannot be combined with recall_target > 0 "
+                                   "(the recall model counts volume, not allowed rows): not supported")
+            if grp is not None:
+                raise RuntimeError("[QuakeIndex::search()] filtered search is not supported with num_workers > 0")
+            if any(f._store is not self._store for f in flts):
+                raise RuntimeError("[QuakeIndex::search()] the filter was made for another index")
+            qflt = qflt if torch.is_tensor(qflt) else torch.as_tensor(np.asarray(qflt))
+            if qflt.dim() != 1 or qflt.shape[0] != x.shape[0]:
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.query_filter must have one entry per query "
+                                   "(%d != %d)" % (qflt.shape[0] if qflt.dim() >= 1 else 0, x.shape[0]))
+            if not qflt.is_cuda and qflt.numel() > 0 and (int(qflt.min()) < 0 or int(qflt.max()) >= len(flts)):
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.query_filter holds a value outside [0, %d)" % len(flts))
+            fb = dict(filters=[f._h for f in flts], query_filter=qflt.to(device=xd.device, dtype=torch.int32))
         if grp is not None:
             grp.set_stream(torch.cuda.current_stream(grp.device).cuda_stream)  # the lead's stream (see _context)
         if use_aps:
@@ -533,7 +563,7 @@ class QuakeIndex:
                     ids, dist, tm = grp.scan(xd, pids, int(k), self.metric_, timing=True)
                 else:  # one enqueue: the nearest-centroid step writes the list numbers where the policy will read them
                     ids, dist, pids, tm = self._ctx.search_tracked(self.parent._store, self._store, xd, nprobe, int(k), self.metric_,
-                                                                   timing=True, filter=flt)
+                                                                   timing=True, filter=flt, **fb)
                 self._pending_hits.append(pids)
                 if len(self._pending_hits) >= 64:
                     self._flush_hits()
@@ -541,7 +571,7 @@ class QuakeIndex:
                 ids, dist, tm = grp.search(self.parent._store, xd, nprobe, int(k), self.metric_, timing=True)
             else:
                 ids, dist, tm = self._ctx.search(self.parent._store if self.parent is not None else None, self._store, xd,
-                                                 nprobe, int(k), self.metric_, timing=True, filter=flt)
+                                                 nprobe, int(k), self.metric_, timing=True, filter=flt, **fb)
         finally:
             self._ctx.set_timing(0)
         ti.n_queries = int(x.shape[0])
