@@ -277,6 +277,38 @@ QK_API int qk_scan_filtered_batch(qk_ctx *ctx, qk_store *s, const float *x, int6
                                   qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids, float *out_dist,
                                   int mem, qk_timing *timing);
 
+/* ---- range search --------------------------------------------------------------------------------
+ * No reference counterpart (every search of the reference is a top-k): all rows of the probed lists within a radius of each query.
+ * Lists: qk_range_search probes what the unfiltered qk_search probes -- the same min(nprobe, parent lists) lists in the same rank
+ * order, every list with parent == NULL; qk_range_scan takes pids [Q][P] like qk_scan (distinct list numbers per row), where -1,
+ * absent and empty lists contribute nothing (no QK_ERR_NOT_FOUND here).
+ * Hits: a row of a probed list is a hit iff the float32 distance qk_search would report for it -- sqrt L2, squared L2 after
+ * qk_ctx_set_squared_l2(ctx, 1), the dot product for IP -- satisfies dist <= radius (L2) / dist >= radius (IP), inclusive, in
+ * float32; a NaN distance is never a hit; radius = +inf (L2) / -inf (IP) returns every probed row whose distance is not NaN; a NaN
+ * radius is QK_ERR_INVALID.  The host turns the radius into one closed interval of the integer keys the scan emits (L2 with sqrt:
+ * the largest float t >= 0 with sqrtf(t) <= radius, found by stepping ulps around radius * radius), so the test is exact.
+ * `filter`: a qk_filter of this store or NULL; a hit must also be a candidate of the filter (brought up to date like any
+ * filtered call; another store's filter: QK_ERR_INVALID).
+ * Order: query q's hits are out_ids / out_dist [lims[q], lims[q+1]), lims[0] = 0; inside a query in scan order -- the probed
+ * lists in rank order (the order of its pids row), the rows of a list in stored order.  Ids are the stored ids, distances the bits
+ * qk_search returns for those rows.  No atomic decides a position: the result is a pure function of the store and the call.
+ * Capacity: out_lims [Q + 1] is always written in full and exact, whatever cap is; ids and distances are written at positions
+ * < cap only -- a prefix of the global order -- and nothing beyond min(cap, lims[Q]) is touched.  lims[Q] > cap is still QK_OK: the
+ * caller compares and calls again with larger buffers.  cap == 0 with NULL out_ids / out_dist counts only (out_dist may be NULL
+ * with any cap).  cap < 0 or out_lims == NULL: QK_ERR_INVALID.  Q == 0: QK_OK, lims[0] = 0.
+ * Inside: the key-emission scan of the wide-k path (one launch per pass of queries, the only kernel that reads the vectors), then
+ * k_range_count / k_range_qscan / k_range_offsets / k_range_write (qk_range.hip): count per slice, exclusive scans -- per query,
+ * then over the queries, continued across passes on the device -- and a stable compaction.  timing: coarse_ms the coarse step, scan_ms the emission scan, merge_ms counting + compaction (of
+ * the last pass when there are several), n_items the number of query passes, scan_bytes / partitions_scanned as for qk_search.
+ * qk_ctx_last_scan_kernel names "k_scan (range)" / "k_scan_wide (range)".  There is no range form of qk_search_aps, of the device
+ * group or of per-query filter tables. */
+QK_API int qk_range_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int metric, float radius,
+                           qk_filter *filter, int64_t cap, int64_t *out_lims, int64_t *out_ids, float *out_dist, int mem,
+                           qk_timing *timing);
+QK_API int qk_range_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric, float radius,
+                         qk_filter *filter, int64_t cap, int64_t *out_lims, int64_t *out_ids, float *out_dist, int mem,
+                         qk_timing *timing);
+
 /* QueryCoordinator::search with SearchParams::recall_target > 0 and batched_scan == false: adaptive partition
  * scanning (query_coordinator.cpp:612-657 picks M = max((int)(nlist * initial_search_fraction), 1) candidate partitions
  * from the parent; the use_aps branch of serial_scan, :471-611, scans them in rank order and stops a query once the

@@ -90,6 +90,8 @@ SIGNATURES = {
                                          _int, C.POINTER(QkTiming)]),
     "qk_scan_filtered_batch": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, C.POINTER(_vp), _int, _vp, _vp, _vp, _int,
                                C.POINTER(QkTiming)]),
+    "qk_range_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, _vp, _i64, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_range_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _i64, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search_aps": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, C.c_float, _int, C.c_float, _vp, _vp, _vp, _int,
                       C.POINTER(QkTiming)]),
     "qk_merge_topk": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp]),

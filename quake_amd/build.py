@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libquake_hip.so")
-SOURCES = ["qk_ctx.hip", "qk_store.hip", "qk_scan.hip", "qk_scan_plan.hip", "qk_merge.hip", "qk_scan_rl.hip", "qk_small.hip", "qk_dense.hip", "qk_dense_pf.hip", "qk_dense_fused.hip", "qk_kmeans.hip", "qk_assign_pf.hip", "qk_aps.hip", "qk_api.hip", "qk_group.hip", "qk_scan_wide.hip", "qk_filter.hip"]
+SOURCES = ["qk_ctx.hip", "qk_store.hip", "qk_scan.hip", "qk_scan_plan.hip", "qk_merge.hip", "qk_scan_rl.hip", "qk_small.hip", "qk_dense.hip", "qk_dense_pf.hip", "qk_dense_fused.hip", "qk_kmeans.hip", "qk_assign_pf.hip", "qk_aps.hip", "qk_api.hip", "qk_group.hip", "qk_scan_wide.hip", "qk_filter.hip", "qk_range.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value"]
@@ -50,6 +50,10 @@ def build_lib(force=False, verbose=False, variant=None, extra_flags=()):
     flag_text = " ".join(flags)
     if not os.path.exists(flag_file) or open(flag_file).read() != flag_text:
         force = True
+    # the library is newer than every source and header and was linked with these flags: nothing to do, whether or not the
+    # object files are still around (a tree that was copied without them)
+    if not force and not _stale(lib, [os.path.join(CSRC, s) for s in srcs] + headers):
+        return lib
     objs = []
     jobs = []
     for s in srcs:

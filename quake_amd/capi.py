@@ -284,6 +284,74 @@ class Context:
         out_p = out_p[:, :width]
         return (out_i, out_d, out_p, timing_dict(t)) if timing else (out_i, out_d, out_p)
 
+    # ---- range search ---------------------------------------------------------------------------------
+    def _range(self, call, x, cap, timing, out):
+        """the capacity protocol of qk_range_search / qk_range_scan around `call(cap, lims, ids, dist, timing)`: with cap=None a
+        guess, then one more call only if lims[Q] says it was short; ids / dist come back trimmed to what was written"""
+        Q = x.shape[0]
+        lims = _empty_like_mem((Q + 1,), np.int64, x)
+        t = QkTiming()
+        self.last_range_calls = 0
+
+        def run(c, ids, dist):
+            self.last_range_calls += 1
+            call(int(c), lims, ids, dist, C.byref(t) if timing else None)
+            if _is_torch(lims) and lims.is_cuda:
+                self.synchronize()
+            return int(lims[Q])
+
+        if out is not None:
+            ids, dist = out
+            if cap is None:
+                cap = 0 if ids is None else int(ids.shape[0])
+            total = run(cap, ids, dist)
+        elif cap is not None:
+            ids = _empty_like_mem((int(cap),), np.int64, x) if cap > 0 else None
+            dist = _empty_like_mem((int(cap),), np.float32, x) if cap > 0 else None
+            total = run(cap, ids, dist)
+        else:
+            cap = max(4096, 64 * Q)
+            ids, dist = _empty_like_mem((cap,), np.int64, x), _empty_like_mem((cap,), np.float32, x)
+            total = run(cap, ids, dist)
+            if total > cap:
+                cap = total
+                ids, dist = _empty_like_mem((cap,), np.int64, x), _empty_like_mem((cap,), np.float32, x)
+                total = run(cap, ids, dist)
+        n = min(int(cap), total)
+        ids = ids[:n] if ids is not None else _empty_like_mem((0,), np.int64, x)
+        dist = dist[:n] if dist is not None else _empty_like_mem((0,), np.float32, x)
+        return (lims, ids, dist, timing_dict(t)) if timing else (lims, ids, dist)
+
+    def range_search(self, parent, store, x, nprobe, radius, metric, filter=None, cap=None, timing=False, out=None):
+        """qk_range_search: every row of the lists qk_search probes whose distance passes `radius` (L2: <=, IP: >=), in scan
+        order.  Returns (lims [Q + 1], ids, dist[, timing]): query q's hits are [lims[q], lims[q+1]).  cap=None: the wrapper
+        sizes the buffers (a second call only when the first guess was short) and returns everything; a given cap (or
+        out=(ids, dist) buffers of the caller, untouched behind the written prefix) returns the first min(cap, lims[Q]) hits
+        while lims stays exact; cap=0 counts only.  filter: a Filter of `store`."""
+        x = _f32(x)
+        mem = _mem_of(x)
+
+        def call(c, lims, ids, dist, t):
+            check(self.lib.qk_range_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), x.shape[0], int(nprobe),
+                                           metric_code(metric), float(radius), filter.h if filter is not None else None, c,
+                                           _ptr(lims), _ptr(ids), _ptr(dist), mem, t))
+        return self._range(call, x, cap, timing, out)
+
+    def range_scan(self, store, x, pids, radius, metric, filter=None, cap=None, timing=False, out=None):
+        """qk_range_scan: range_search over the given lists -- pids [Q, P] (or [P] for every query), -1 / absent / empty lists
+        contribute nothing; a query's hits follow the order of its pids row."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        if pids.ndim == 1:
+            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
+                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        mem = _mem_of(x, pids)
+
+        def call(c, lims, ids, dist, t):
+            check(self.lib.qk_range_scan(self.h, store.h, _ptr(x), Q, _ptr(pids), int(pids.shape[1]), metric_code(metric), float(radius),
+                                         filter.h if filter is not None else None, c, _ptr(lims), _ptr(ids), _ptr(dist), mem, t))
+        return self._range(call, x, cap, timing, out)
+
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):
         """recall-target search (adaptive partition scanning).  Returns (ids, dist, nscanned[, timing])."""

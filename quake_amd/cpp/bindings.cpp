@@ -60,6 +60,8 @@ PYBIND11_MODULE(_bindings, m) {
         .def("refine_partitions", &QuakeIndex::refine_partitions, py::arg("partition_ids"), py::arg("iterations") = 0)
         .def("make_filter", &QuakeIndex::make_filter, py::arg("ids"), py::arg("exclude") = false,
              "extension: a SearchFilter over this index's vector ids for SearchParams.filter")
+        .def("range_search", &QuakeIndex::range_search, py::arg("x"), py::arg("radius"), py::arg("search_params"),
+             "extension: every vector of the nprobe nearest partitions within `radius` of each query (lims, ids, distances)")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)
@@ -245,6 +247,13 @@ PYBIND11_MODULE(_bindings, m) {
             if (t.parent_info) r.kv("parent_scan_time_ns", t.parent_info->total_time_ns);
             return r.kv("n_queries", t.n_queries).kv("n_clusters", t.n_clusters).kv("partitions_scanned", t.partitions_scanned).str();
         });
+
+    py::class_<RangeSearchResult, std::shared_ptr<RangeSearchResult>>(m, "RangeSearchResult")
+        .def(py::init<>())
+        .def_readwrite("lims", &RangeSearchResult::lims)
+        .def_readwrite("ids", &RangeSearchResult::ids)
+        .def_readwrite("distances", &RangeSearchResult::distances)
+        .def_readwrite("timing_info", &RangeSearchResult::timing_info);
 
     py::class_<SearchResult, std::shared_ptr<SearchResult>>(m, "SearchResult")
         .def(py::init<>())

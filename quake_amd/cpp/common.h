@@ -121,6 +121,14 @@ struct SearchResult {  // common.h:243-247
     shared_ptr<SearchTimingInfo> timing_info;
 };
 
+// extension (QuakeIndex::range_search): query i's hits are ids / distances [lims[i], lims[i+1]), in scan order
+struct RangeSearchResult {
+    Tensor lims;
+    Tensor ids;
+    Tensor distances;
+    shared_ptr<SearchTimingInfo> timing_info;
+};
+
 struct Clustering {  // common.h:249-276
     Tensor centroids;
     Tensor partition_ids;

@@ -124,6 +124,11 @@ shared_ptr<SearchResult> QuakeIndex::search(Tensor x, shared_ptr<SearchParams> s
     return query_coordinator_->search(x, sp);
 }
 
+shared_ptr<RangeSearchResult> QuakeIndex::range_search(Tensor x, float radius, shared_ptr<SearchParams> sp) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::range_search()] No query coordinator. Did you build the index?");
+    return query_coordinator_->range_search(x, radius, sp);
+}
+
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?");
     qk_store *s = partition_manager_->store();

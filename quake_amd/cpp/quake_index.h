@@ -41,6 +41,8 @@ public:
     void refine_partitions(Tensor partition_ids, int iterations);
     // extension: a filter over this index's vector ids for SearchParams::filter (ids: any integer tensor, host or device)
     shared_ptr<SearchFilter> make_filter(Tensor ids, bool exclude = false);
+    // extension: every vector of the search_params->nprobe nearest partitions within `radius` of each query (qk_range_search)
+    shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

@@ -35,6 +35,8 @@ public:
     ~QueryCoordinator();
 
     shared_ptr<SearchResult> search(Tensor x, shared_ptr<SearchParams> search_params);
+    // extension (qk_range_search): all vectors of the nprobe nearest partitions within `radius`, restricted to sp->filter if set
+    shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

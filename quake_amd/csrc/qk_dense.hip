@@ -1279,6 +1279,13 @@ __global__ __launch_bounds__(1024) void k_exclusive_scan_i64(const int64_t *__re
     }
 }
 
+// sizes[i] = rows of pair i's list (0: -1, absent, empty), pair_base = their exclusive prefix sums, [npairs + 1] entries each
+void qk_launch_pair_offsets(qk_ctx *ctx, qk_store *s, const int64_t *pids, int64_t npairs, int P, int64_t *sizes, int64_t *pair_base) {
+    hipLaunchKernelGGL(k_pair_sizes, dim3((unsigned)((npairs + 256) / 256)), dim3(256), 0, ctx->stream, pids, npairs, P, s->d_size,
+                       (int)s->parts.size(), sizes);
+    hipLaunchKernelGGL(k_exclusive_scan_i64, dim3(1), dim3(1024), 0, ctx->stream, sizes, pair_base, npairs + 1);
+}
+
 int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base) {
     const int64_t Q = a.Q;
     const int k = a.k;
@@ -1291,8 +1298,8 @@ int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *
     int kp = 1;
     while (kp < k) kp <<= 1;
     // queries per pass: the keys of one pass stay under 2^29 (2 GiB)
-    const int64_t per_query_ub = std::max<int64_t>(1, (int64_t)P * std::max<int64_t>(1, s->max_size));
-    const int64_t qc = std::max<int64_t>(1, std::min<int64_t>(Q, ((int64_t)1 << 29) / per_query_ub));
+    int64_t per_query_ub;
+    const int64_t qc = qk_emit_pass_queries(Q, P, s->max_size, &per_query_ub);
     if (per_query_ub > ((int64_t)1 << 30)) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: k=%d with %d lists per query is too large", k, P);
     const int nblk = s->nblk;
     // per-call phase events of THIS pipeline (the inner qk_scan_device runs without a qk_timing, so it records none):
@@ -1316,8 +1323,7 @@ int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *
         int64_t *sizes = (int64_t *)(B + o_sizes), *pair_base = (int64_t *)(B + o_base);
         uint32_t *keys = (uint32_t *)(B + o_keys);
         const int64_t *pids = a.pids ? a.pids + q0 * P : nullptr;
-        hipLaunchKernelGGL(k_pair_sizes, dim3((unsigned)((npairs + 256) / 256)), dim3(256), 0, st, pids, npairs, P, s->d_size, npids, sizes);
-        hipLaunchKernelGGL(k_exclusive_scan_i64, dim3(1), dim3(1024), 0, st, sizes, pair_base, npairs + 1);
+        qk_launch_pair_offsets(ctx, s, pids, npairs, P, sizes, pair_base);
         if (q0 == 0) QK_TRY(pe.mark(1));
         qk_scan_args e = a;
         e.x = a.x + q0 * s->d;

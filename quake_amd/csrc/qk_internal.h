@@ -3,6 +3,7 @@
 #include "qk_idmap.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -402,6 +403,19 @@ int qk_launch_merge_slices(qk_ctx *ctx, const int64_t *sl_ids, const uint32_t *s
 // k > QK_MAX_K over several lists: emit every key (qk_scan_device in emission mode), then exact selection per query.  qk_dense.hip
 int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base);
 constexpr int QK_MAX_WIDE_K = 8192;  // = the reference's TOP_K_BUFFER_CAPACITY (list_scanning.h:39)
+// Pass size of a key-emission pipeline (qk_widek_device, qk_range_device): every query of a pass gets room for the keys of P
+// lists of the store's largest size, and the keys of one pass stay under 2^29 (2 GiB).  *per_query_ub: that room, in keys;
+// beyond 2^30 a single query no longer fits an int index and the callers refuse.
+static inline int64_t qk_emit_pass_queries(int64_t Q, int P, int64_t max_size, int64_t *per_query_ub) {
+    *per_query_ub = std::max<int64_t>(1, (int64_t)P * std::max<int64_t>(1, max_size));
+    return std::max<int64_t>(1, std::min<int64_t>(Q, ((int64_t)1 << 29) / *per_query_ub));
+}
+// the pair offsets both pipelines start a pass with (qk_dense.hip: k_pair_sizes + k_exclusive_scan_i64)
+void qk_launch_pair_offsets(qk_ctx *ctx, qk_store *s, const int64_t *pids, int64_t npairs, int P, int64_t *sizes, int64_t *pair_base);
+// range search (qk_range.hip): every row of the probed lists whose key lies in [key_lo, key_hi] (and is a candidate of `mask`),
+// in scan order; `a` as for qk_widek_device (k unused).  lims [Q + 1], out_ids / out_dist [cap] on the device.
+int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask,
+                    int64_t cap, int64_t *lims, int64_t *out_ids, float *out_dist, qk_timing *timing, int64_t *n_passes);
 // wide rows (a 16-query tile no longer fits the LDS next to what the kernel keeps there): the queries are read from global
 // memory instead (qk_scan_wide.hip).  k_dense_wide: every query against one list -- keys into D, or (argmin) the packed
 // minimum (key << 32 | id) into best64; k_assign_wide: k_assign's nearest centroid of every row of x

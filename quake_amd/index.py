@@ -221,6 +221,16 @@ class SearchResult:  # common.h:243-247
         self.timing_info = None
 
 
+class RangeSearchResult:
+    """extension (QuakeIndex.range_search): query i's hits are ids / distances [lims[i], lims[i+1]), in scan order"""
+
+    def __init__(self):
+        self.lims = None
+        self.ids = None
+        self.distances = None
+        self.timing_info = None
+
+
 _CONTEXTS = {}
 
 
@@ -586,6 +596,66 @@ class QuakeIndex:
             pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
             ti.parent_info = pi
         ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.ids = ids if on_dev else ids.cpu()
+        res.distances = dist if on_dev else dist.cpu()
+        return res
+
+    def range_search(self, x, radius, search_params):
+        """extension (no reference counterpart): every vector of the search_params.nprobe nearest partitions whose distance to
+        the query passes `radius` -- L2: distance <= radius, IP: distance >= radius, inclusive, on the float32 distance search()
+        reports -- restricted to search_params.filter if one is set.  Returns a RangeSearchResult: query i's hits are
+        ids / distances [lims[i], lims[i+1]), the probed partitions in rank order, each in stored order (not sorted by
+        distance).  Tensors on x's device."""
+        self._require_built("[QuakeIndex::range_search()] No query coordinator. Did you build the index?")
+        sp = search_params
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError("[QuakeIndex::range_search()] SearchParams.filters / query_filter (one filter per query) are not "
+                               "supported by range_search")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError("[QuakeIndex::range_search()] range_search is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::range_search()] range_search is not supported with num_workers > 0")
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError("[QuakeIndex::range_search()] SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError("[QuakeIndex::range_search()] the filter was made for another index")
+            flt = flt._h
+        res = RangeSearchResult()
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        nq = 0 if x is None else int(x.shape[0])
+        if nq == 0:
+            res.lims = torch.zeros((1,), dtype=torch.int64)
+            res.ids = torch.empty((0,), dtype=torch.int64)
+            res.distances = torch.empty((0,), dtype=torch.float32)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        self._ctx.set_timing(1)
+        try:
+            lims, ids, dist, tm = self._ctx.range_search(self.parent._store if self.parent is not None else None, self._store, xd,
+                                                         nprobe, float(radius), self.metric_, filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(0)
+        ti.n_queries = nq
+        ti.partitions_scanned = int(tm["partitions_scanned"])
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.lims = lims if on_dev else lims.cpu()
         res.ids = ids if on_dev else ids.cpu()
         res.distances = dist if on_dev else dist.cpu()
         return res
