@@ -309,6 +309,58 @@ QK_API int qk_range_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, co
                          qk_filter *filter, int64_t cap, int64_t *out_lims, int64_t *out_ids, float *out_dist, int mem,
                          qk_timing *timing);
 
+/* ---- attribute filters ---------------------------------------------------------------------------
+ * No reference counterpart.  A COLUMN (qk_attr) is a partial map id -> int64 that belongs to one store and lives on its device.  It
+ * is keyed by id, not by row: add, remove, relocation, compaction, refinement and maintenance never touch it; removing a vector
+ * leaves its values in place (an id that is not stored is never a candidate), so remove + add of an id keeps its attributes.
+ * A PREDICATE filter is a qk_filter made from 1 .. QK_MAX_CLAUSES clauses {column, op, a, b} instead of an id list.  A stored row
+ * is a candidate iff, for EVERY clause, its id has a value v in the clause's column and
+ *   QK_OP_RANGE      a <= v <= b, signed and inclusive (a > b: the empty interval, matches nothing)
+ *   QK_OP_NOT_RANGE  the complement of QK_OP_RANGE
+ *   QK_OP_ANY_BITS   (v & a) != 0          QK_OP_ALL_BITS  (v & a) == a          QK_OP_NO_BITS  (v & a) == 0
+ * holds.  An id without a value fails every op, NOT_RANGE and NO_BITS included (SQL's NULL); every copy of an id stored twice
+ * follows its id; the order of the clauses does not matter.  At any moment the filter answers exactly like the QK_FILTER_ALLOW
+ * filter over {id : every clause holds for id} -- ids, distance bits and padding -- so everything said under "filtered search"
+ * holds, and it is passed to the same entry points: qk_search_filtered*, qk_scan_filtered*, the per-query table (mixed freely
+ * with id-set filters), qk_range_search / qk_range_scan.  It holds no ids: creating it costs one mask build (k_filter_build_where:
+ * per stored row the id, then per clause a lookup in the column and the op, stopping at the first clause that fails).
+ * Liveness: the mask is stamped with the store's (uid, version, cap_rows) AND (serial, version) of every clause's column;
+ * qk_attr_set / qk_attr_unset bump the column's version, and the next filtered call that uses the filter re-derives the mask once,
+ * on its own stream, in front of its scan.  Column updates are enqueued on the store's context stream; a mask build on another
+ * context waits for the column's last update by event.  As for store mutations, nobody updates a column while searches that use it
+ * are in flight.  A filter shares ownership of its columns' device data: qk_attr_destroy while filters are alive is legal, those
+ * filters keep answering with the last values.
+ * Layout (never visible in a result): a direct table -- values[id] and one presence bit per id -- while max_id < 4 * n_ids + 65536,
+ * else ascending (id, value) pairs looked up by binary search; re-decided on every set / unset and converted when the rule flips. */
+typedef struct qk_attr qk_attr;
+#define QK_OP_RANGE 0
+#define QK_OP_NOT_RANGE 1
+#define QK_OP_ANY_BITS 2
+#define QK_OP_ALL_BITS 3
+#define QK_OP_NO_BITS 4
+#define QK_MAX_CLAUSES 8
+#define QK_ATTR_TABLE 0
+#define QK_ATTR_SORTED 1
+typedef struct {
+    qk_attr *attr;
+    int op;
+    int64_t a, b; /* b is read by the RANGE ops only */
+} qk_clause;
+QK_API int qk_attr_create(qk_store *s, qk_attr **out);
+QK_API int qk_attr_destroy(qk_attr *a);
+/* upsert values[i] for ids[i] (an id given twice: the last value wins); a negative id: QK_ERR_INVALID, nothing is changed */
+QK_API int qk_attr_set(qk_attr *a, const int64_t *ids, const int64_t *values, int64_t n, int mem);
+/* the ids lose their values; ids that have none are ignored */
+QK_API int qk_attr_unset(qk_attr *a, const int64_t *ids, int64_t n, int mem);
+/* values_out_host[i], found[i] (0 / 1) for ids_host[i], read back from the device (synchronises; either output may be NULL) */
+QK_API int qk_attr_get(qk_attr *a, const int64_t *ids_host, int64_t n, int64_t *values_out_host, int *found);
+/* n_ids: ids that have a value; version: bumped by every set / unset; layout: QK_ATTR_TABLE / QK_ATTR_SORTED; device_bytes: HBM
+ * held by the column (not part of qk_store_device_bytes) */
+QK_API int qk_attr_info(qk_attr *a, int64_t *n_ids, uint64_t *version, int *layout, int64_t *device_bytes);
+/* QK_ERR_INVALID: n_clauses < 1, a null column, a column of another store, an unknown op; QK_ERR_UNSUPPORTED: n_clauses >
+ * QK_MAX_CLAUSES.  qk_filter_info of the result: n_ids = -1, device_bytes = the mask only. */
+QK_API int qk_filter_create_where(qk_store *s, const qk_clause *clauses, int n_clauses, qk_filter **out);
+
 /* QueryCoordinator::search with SearchParams::recall_target > 0 and batched_scan == false: adaptive partition
  * scanning (query_coordinator.cpp:612-657 picks M = max((int)(nlist * initial_search_fraction), 1) candidate partitions
  * from the parent; the use_aps branch of serial_scan, :471-611, scans them in rank order and stops a query once the

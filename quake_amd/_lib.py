@@ -13,6 +13,9 @@ QK_MEM_HOST = 0
 QK_MEM_DEVICE = 1
 QK_MAX_K = 448
 QK_MAX_NPROBE = 8192
+QK_OP_RANGE, QK_OP_NOT_RANGE, QK_OP_ANY_BITS, QK_OP_ALL_BITS, QK_OP_NO_BITS = 0, 1, 2, 3, 4
+QK_MAX_CLAUSES = 8
+QK_ATTR_TABLE, QK_ATTR_SORTED = 0, 1
 
 STATUS_NAMES = {1: "QK_ERR_INVALID", 2: "QK_ERR_NOT_FOUND", 3: "QK_ERR_HIP", 4: "QK_ERR_UNSUPPORTED", 5: "QK_ERR_OOM"}
 
@@ -21,6 +24,10 @@ class QkTiming(C.Structure):
     _fields_ = [("coarse_ms", C.c_float), ("group_ms", C.c_float), ("scan_ms", C.c_float), ("merge_ms", C.c_float),
                 ("total_ms", C.c_float), ("n_items", C.c_int64), ("scan_bytes", C.c_int64),
                 ("partitions_scanned", C.c_int64)]
+
+
+class QkClause(C.Structure):  # qk_clause: one clause of a predicate filter
+    _fields_ = [("attr", C.c_void_p), ("op", C.c_int), ("a", C.c_int64), ("b", C.c_int64)]
 
 
 class QuakeHipError(RuntimeError):
@@ -92,6 +99,13 @@ SIGNATURES = {
                                C.POINTER(QkTiming)]),
     "qk_range_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, _vp, _i64, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_range_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _i64, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_attr_create": (_int, [_vp, C.POINTER(_vp)]),
+    "qk_attr_destroy": (_int, [_vp]),
+    "qk_attr_set": (_int, [_vp, _vp, _vp, _i64, _int]),
+    "qk_attr_unset": (_int, [_vp, _vp, _i64, _int]),
+    "qk_attr_get": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "qk_attr_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_uint64), C.POINTER(_int), C.POINTER(_i64)]),
+    "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
     "qk_search_aps": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, C.c_float, _int, C.c_float, _vp, _vp, _vp, _int,
                       C.POINTER(QkTiming)]),
     "qk_merge_topk": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp]),

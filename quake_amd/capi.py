@@ -655,6 +655,30 @@ class Filter:
         check(self.lib.qk_filter_create(store.h, _ptr(ids) if ids.shape[0] > 0 else None, int(ids.shape[0]), self.MODES[mode],
                                         _mem_of(ids), C.byref(self.h)))
 
+    OPS = {"range": _lib.QK_OP_RANGE, "not_range": _lib.QK_OP_NOT_RANGE, "any_bits": _lib.QK_OP_ANY_BITS,
+           "all_bits": _lib.QK_OP_ALL_BITS, "no_bits": _lib.QK_OP_NO_BITS}
+
+    @classmethod
+    def where(cls, store, clauses):
+        """A predicate filter (qk_filter_create_where): `clauses` is a sequence of (attr, op, a[, b]) -- attr an Attr of `store`,
+        op one of OPS (or its QK_OP_* code), a / b int64 -- and a stored row is a candidate iff its id has a value in every
+        clause's column that satisfies the clause.  It holds no ids and follows later Attr.set / unset and store changes."""
+        clauses = list(clauses)
+        arr = (_lib.QkClause * max(len(clauses), 1))()
+        for i, cl in enumerate(clauses):
+            attr, op, a = cl[0], cl[1], cl[2]
+            b = cl[3] if len(cl) > 3 else 0
+            arr[i].attr = attr.h if attr is not None else None
+            arr[i].op = cls.OPS[op] if isinstance(op, str) else int(op)
+            arr[i].a, arr[i].b = int(a), int(b)
+        self = cls.__new__(cls)
+        self.lib = store.lib
+        self.store = store
+        self.mode = "where"
+        self.h = C.c_void_p()
+        check(self.lib.qk_filter_create_where(store.h, arr, len(clauses), C.byref(self.h)))
+        return self
+
     def close(self):
         if getattr(self, "h", None) and self.h:
             self.lib.qk_filter_destroy(self.h)
@@ -673,6 +697,62 @@ class Filter:
         check(self.lib.qk_filter_info(self.h, C.byref(n), C.byref(ra), C.byref(ver), C.byref(rb), C.byref(db)))
         return {"n_ids": n.value, "rows_allowed": ra.value, "store_version": ver.value, "rebuilds": rb.value,
                 "device_bytes": db.value}
+
+
+class Attr:
+    """An attribute column of one Store (qk_attr_*): a partial map vector id -> int64 kept on the device, keyed by id (nothing
+    that moves or removes rows touches it).  Clauses of Filter.where name it.  ids / values: numpy or torch, host or device."""
+
+    LAYOUTS = {_lib.QK_ATTR_TABLE: "table", _lib.QK_ATTR_SORTED: "sorted"}
+
+    def __init__(self, store):
+        self.lib = store.lib
+        self.store = store
+        self.h = C.c_void_p()
+        check(self.lib.qk_attr_create(store.h, C.byref(self.h)))
+
+    def close(self):
+        """(filters that name the column keep its values and go on answering)"""
+        if getattr(self, "h", None) and self.h:
+            self.lib.qk_attr_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set(self, ids, values):
+        """upsert; of an id given twice the last value wins"""
+        ids, values = _i64(ids).reshape(-1), _i64(values).reshape(-1)
+        if ids.shape[0] != values.shape[0]:
+            raise ValueError("Attr.set: %d ids, %d values" % (ids.shape[0], values.shape[0]))
+        n = int(ids.shape[0])
+        check(self.lib.qk_attr_set(self.h, _ptr(ids) if n else None, _ptr(values) if n else None, n, _mem_of(ids, values)))
+
+    def unset(self, ids):
+        ids = _i64(ids).reshape(-1)
+        n = int(ids.shape[0])
+        check(self.lib.qk_attr_unset(self.h, _ptr(ids) if n else None, n, _mem_of(ids)))
+
+    def get(self, ids):
+        """(values int64 [n], found bool [n]) as the device holds them; values are 0 where found is False"""
+        if _is_torch(ids):
+            ids = ids.detach().cpu().numpy()
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        vals = np.zeros(ids.shape[0], np.int64)
+        found = np.zeros(ids.shape[0], np.int32)
+        check(self.lib.qk_attr_get(self.h, _ptr(ids) if ids.shape[0] else None, int(ids.shape[0]), _ptr(vals), _ptr(found)))
+        return vals, found.astype(bool)
+
+    def info(self):
+        """{n_ids, version, layout ("table" / "sorted"), device_bytes} (qk_attr_info)"""
+        n, db = C.c_int64(), C.c_int64()
+        ver = C.c_uint64()
+        lay = C.c_int()
+        check(self.lib.qk_attr_info(self.h, C.byref(n), C.byref(ver), C.byref(lay), C.byref(db)))
+        return {"n_ids": n.value, "version": ver.value, "layout": self.LAYOUTS[lay.value], "device_bytes": db.value}
 
 
 class Group:

@@ -41,6 +41,50 @@ public:
     }
     std::string str(bool trailing = false) const { return "{" + os_.str() + (trailing ? ", }" : "}"); }
 };
+
+// an operand of a where clause: a Python integer of any size (`mask`: values in [2^63, 2^64) are bit patterns)
+WhereOperand parse_operand(const py::handle &h, bool mask) {
+    if (!PyLong_Check(h.ptr()) || PyBool_Check(h.ptr())) {
+        if (!PyIndex_Check(h.ptr()) || PyBool_Check(h.ptr()))
+            throw std::runtime_error("[QuakeIndex::make_filter()] operands must be integers, got " + std::string(py::repr(h)));
+    }
+    py::object i = py::reinterpret_steal<py::object>(PyNumber_Index(h.ptr()));
+    if (!i) throw py::error_already_set();
+    WhereOperand o;
+    int over = 0;
+    o.v = (int64_t)PyLong_AsLongLongAndOverflow(i.ptr(), &over);
+    if (over > 0 && mask) {
+        const unsigned long long u = PyLong_AsUnsignedLongLong(i.ptr());
+        if (!PyErr_Occurred()) {
+            o.v = (int64_t)u;
+            return o;
+        }
+        PyErr_Clear();
+    }
+    o.over = over;
+    if (over) o.v = 0;
+    return o;
+}
+
+std::vector<WhereTerm> parse_where(const py::object &where) {
+    std::vector<WhereTerm> out;
+    for (py::handle h : where) {
+        if (!py::isinstance<py::tuple>(h) && !py::isinstance<py::list>(h))
+            throw std::runtime_error("[QuakeIndex::make_filter()] a where clause is (name, op, a[, b]), got " + std::string(py::repr(h)));
+        py::sequence cl = py::reinterpret_borrow<py::sequence>(h);
+        if (cl.size() < 3 || cl.size() > 4 || !py::isinstance<py::str>(cl[0]) || !py::isinstance<py::str>(cl[1]))
+            throw std::runtime_error("[QuakeIndex::make_filter()] a where clause is (name, op, a[, b]), got " + std::string(py::repr(h)));
+        WhereTerm t;
+        t.name = cl[0].cast<std::string>();
+        t.op = cl[1].cast<std::string>();
+        const bool mask = t.op == "any_bits" || t.op == "all_bits" || t.op == "no_bits";
+        t.n_operands = (int)cl.size() - 2;
+        t.a = parse_operand(cl[2], mask);
+        if (cl.size() == 4) t.b = parse_operand(cl[3], false);
+        out.push_back(t);
+    }
+    return out;
+}
 }  // namespace
 
 PYBIND11_MODULE(_bindings, m) {
@@ -58,8 +102,20 @@ PYBIND11_MODULE(_bindings, m) {
         .def("maintenance", &QuakeIndex::maintenance)
         .def("initialize_maintenance_policy", &QuakeIndex::initialize_maintenance_policy)
         .def("refine_partitions", &QuakeIndex::refine_partitions, py::arg("partition_ids"), py::arg("iterations") = 0)
-        .def("make_filter", &QuakeIndex::make_filter, py::arg("ids"), py::arg("exclude") = false,
-             "extension: a SearchFilter over this index's vector ids for SearchParams.filter")
+        .def("make_filter", [](QuakeIndex &q, py::object ids, bool exclude, py::object where) {
+                 if (ids.is_none() == where.is_none())
+                     throw std::runtime_error("[QuakeIndex::make_filter()] exactly one of ids and where must be given");
+                 if (where.is_none()) return q.make_filter(ids.cast<Tensor>(), exclude);
+                 if (exclude) throw std::runtime_error("[QuakeIndex::make_filter()] exclude applies to ids, not to where (negate the clauses)");
+                 return q.make_filter_where(parse_where(where));
+             }, py::arg("ids") = py::none(), py::arg("exclude") = false, py::arg("where") = py::none(),
+             "extension: a SearchFilter for SearchParams.filter -- over vector ids (ids, exclude) or a predicate over the attribute "
+             "columns: where = [(name, op, a[, b]), ...], all of which must hold")
+        .def("set_attribute", &QuakeIndex::set_attribute, py::arg("name"), py::arg("ids"), py::arg("values"),
+             "extension: int64 values keyed by vector id in column `name` (created on first use)")
+        .def("unset_attribute", &QuakeIndex::unset_attribute, py::arg("name"), py::arg("ids"))
+        .def("get_attribute", &QuakeIndex::get_attribute, py::arg("name"), py::arg("ids"), "(values int64 [n], found bool [n])")
+        .def("attribute_names", &QuakeIndex::attribute_names)
         .def("range_search", &QuakeIndex::range_search, py::arg("x"), py::arg("radius"), py::arg("search_params"),
              "extension: every vector of the nprobe nearest partitions within `radius` of each query (lims, ids, distances)")
         .def("save", &QuakeIndex::save)

@@ -46,7 +46,7 @@ int str_to_metric_type(std::string metric) {
 }
 
 QuakeIndex::QuakeIndex(int current_level) : current_level_(current_level) {}
-QuakeIndex::~QuakeIndex() = default;
+QuakeIndex::~QuakeIndex() { drop_attributes(); }
 
 void QuakeIndex::require_built(const char *msg) const {
     if (!partition_manager_ || !partition_manager_->has_lists()) throw std::runtime_error(msg);
@@ -59,6 +59,7 @@ void QuakeIndex::make_coordinator(int num_workers) {
 
 shared_ptr<BuildTimingInfo> QuakeIndex::build(Tensor x, Tensor ids, shared_ptr<IndexBuildParams> build_params) {  // quake_index.cpp:29-90
     auto t_total = clk::now();
+    drop_attributes();  // (columns belong to the store that is replaced here)
     build_params_ = build_params;
     metric_ = str_to_metric_type(build_params_->metric);
     if (x.dim() != 2) throw std::runtime_error("[QuakeIndex::build] x must be 2-D [num_vectors, dimension]");
@@ -143,6 +144,154 @@ shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     if (on_dev) torch::cuda::synchronize();  // (torch's stream made the ids; the library copies them out on its own)
     qk_check(qk_filter_create(s, idl.numel() > 0 ? idl.data_ptr<int64_t>() : nullptr, idl.numel(), exclude ? QK_FILTER_DENY : QK_FILTER_ALLOW,
                               on_dev ? QK_MEM_DEVICE : QK_MEM_HOST, &f->h));
+    return f;
+}
+
+// ---- attribute columns and predicate filters (extension) -------------------------------------------------------------------------
+std::vector<LoweredClause> lower_where(const std::vector<WhereTerm> &where) {
+    const char *who = "[QuakeIndex::make_filter()]";
+    constexpr int64_t MIN = INT64_MIN, MAX = INT64_MAX;
+    if (where.empty()) throw std::runtime_error(std::string(who) + " where needs at least one clause");
+    if (where.size() > QK_MAX_CLAUSES)
+        throw std::runtime_error(std::string(who) + " where has " + std::to_string(where.size()) + " clauses, at most " +
+                                 std::to_string(QK_MAX_CLAUSES) + " are supported");
+    std::vector<LoweredClause> out;
+    for (const WhereTerm &t : where) {
+        LoweredClause c;
+        c.name = t.name;
+        const bool between = t.op == "between";
+        const bool bits = t.op == "any_bits" || t.op == "all_bits" || t.op == "no_bits";
+        if (!(between || bits || t.op == "==" || t.op == "!=" || t.op == "<" || t.op == "<=" || t.op == ">" || t.op == ">="))
+            throw std::runtime_error(std::string(who) + " unknown where op '" + t.op + "'");
+        if (t.n_operands != (between ? 2 : 1))
+            throw std::runtime_error(std::string(who) + " where op '" + t.op + "' takes " + (between ? "2 operands" : "1 operand"));
+        if (bits) {
+            if (t.a.over) throw std::runtime_error(std::string(who) + " the mask of '" + t.op + "' does not fit 64 bits");
+            c.op = t.op == "any_bits" ? QK_OP_ANY_BITS : t.op == "all_bits" ? QK_OP_ALL_BITS : QK_OP_NO_BITS;
+            c.a = t.a.v;
+            out.push_back(c);
+            continue;
+        }
+        // the interval over the integers, cut to int64; (1, 0) if nothing is left
+        bool empty = false;
+        int64_t lo = MIN, hi = MAX;
+        auto at_least = [&](const WhereOperand &o) {  // lo = o
+            if (o.over > 0) empty = true;
+            else if (o.over == 0) lo = o.v;
+        };
+        auto at_most = [&](const WhereOperand &o) {  // hi = o
+            if (o.over < 0) empty = true;
+            else if (o.over == 0) hi = o.v;
+        };
+        if (t.op == "==" || t.op == "!=") {
+            at_least(t.a);
+            at_most(t.a);
+        } else if (t.op == "<") {
+            if (t.a.over == 0 && t.a.v == MIN) empty = true;
+            else at_most(t.a.over ? t.a : WhereOperand{t.a.v - 1, 0});
+        } else if (t.op == "<=") {
+            at_most(t.a);
+        } else if (t.op == ">") {
+            if (t.a.over == 0 && t.a.v == MAX) empty = true;
+            else at_least(t.a.over ? t.a : WhereOperand{t.a.v + 1, 0});
+        } else if (t.op == ">=") {
+            at_least(t.a);
+        } else {
+            at_least(t.a);
+            at_most(t.b);
+        }
+        if (empty || lo > hi) lo = 1, hi = 0;
+        c.op = t.op == "!=" ? QK_OP_NOT_RANGE : QK_OP_RANGE;
+        c.a = lo;
+        c.b = hi;
+        out.push_back(c);
+    }
+    return out;
+}
+
+void QuakeIndex::drop_attributes() {
+    for (auto &kv : attrs_) (void)qk_attr_destroy(kv.second);  // (filters that name a column keep its values)
+    attrs_.clear();
+    attrs_store_ = nullptr;
+}
+
+std::map<std::string, qk_attr *> &QuakeIndex::attributes(const char *who) {
+    const std::string w = std::string("[QuakeIndex::") + who + "()] ";
+    if (!partition_manager_ || !partition_manager_->has_lists()) throw std::runtime_error(w + "No partition manager. Index not built?");
+    qk_store *s = partition_manager_->store();
+    if (!s) throw std::runtime_error(w + "filtered search is not supported with num_workers > 0");
+    if (attrs_store_ != s) {
+        drop_attributes();
+        attrs_store_ = s;
+    }
+    return attrs_;
+}
+
+namespace {
+// ids / values of an attribute call: int64, flat, where they are (the library copies device data out on its own)
+Tensor attr_arg(const Tensor &t, bool on_dev) {
+    return on_dev ? t.reshape({-1}).to(torch::kInt64).contiguous() : host_i64(t.reshape({-1}));
+}
+}  // namespace
+
+void QuakeIndex::set_attribute(const std::string &name, Tensor ids, Tensor values) {
+    auto &cols = attributes("set_attribute");
+    if (ids.numel() != values.numel()) throw std::runtime_error("[QuakeIndex::set_attribute()] ids and values must have the same length");
+    const bool on_dev = ids.is_cuda() && values.is_cuda();
+    Tensor idl = attr_arg(ids, on_dev), vl = attr_arg(values, on_dev);
+    if (on_dev) torch::cuda::synchronize();
+    auto it = cols.find(name);
+    if (it == cols.end()) {
+        qk_attr *a = nullptr;
+        qk_check(qk_attr_create(attrs_store_, &a));
+        it = cols.emplace(name, a).first;
+    }
+    const int64_t n = idl.numel();
+    qk_check(qk_attr_set(it->second, n ? idl.data_ptr<int64_t>() : nullptr, n ? vl.data_ptr<int64_t>() : nullptr, n,
+                         on_dev ? QK_MEM_DEVICE : QK_MEM_HOST));
+}
+
+void QuakeIndex::unset_attribute(const std::string &name, Tensor ids) {
+    auto &cols = attributes("unset_attribute");
+    auto it = cols.find(name);
+    if (it == cols.end()) throw std::runtime_error("[QuakeIndex::unset_attribute()] unknown attribute column '" + name + "'");
+    const bool on_dev = ids.is_cuda();
+    Tensor idl = attr_arg(ids, on_dev);
+    if (on_dev) torch::cuda::synchronize();
+    const int64_t n = idl.numel();
+    qk_check(qk_attr_unset(it->second, n ? idl.data_ptr<int64_t>() : nullptr, n, on_dev ? QK_MEM_DEVICE : QK_MEM_HOST));
+}
+
+std::pair<Tensor, Tensor> QuakeIndex::get_attribute(const std::string &name, Tensor ids) {
+    auto &cols = attributes("get_attribute");
+    auto it = cols.find(name);
+    if (it == cols.end()) throw std::runtime_error("[QuakeIndex::get_attribute()] unknown attribute column '" + name + "'");
+    Tensor idl = host_i64(ids.reshape({-1}));
+    const int64_t n = idl.numel();
+    Tensor vals = torch::zeros({n}, torch::kInt64);
+    Tensor found = torch::zeros({n}, torch::kInt32);
+    if (n) qk_check(qk_attr_get(it->second, idl.data_ptr<int64_t>(), n, vals.data_ptr<int64_t>(), found.data_ptr<int>()));
+    return {vals, found.to(torch::kBool)};
+}
+
+std::vector<std::string> QuakeIndex::attribute_names() {
+    std::vector<std::string> names;
+    if (!partition_manager_ || !partition_manager_->has_lists() || partition_manager_->store() != attrs_store_) return names;
+    for (const auto &kv : attrs_) names.push_back(kv.first);
+    return names;
+}
+
+shared_ptr<SearchFilter> QuakeIndex::make_filter_where(const std::vector<WhereTerm> &where) {
+    auto &cols = attributes("make_filter");
+    std::vector<qk_clause> cl;
+    for (const LoweredClause &c : lower_where(where)) {
+        auto it = cols.find(c.name);
+        if (it == cols.end()) throw std::runtime_error("[QuakeIndex::make_filter()] unknown attribute column '" + c.name + "'");
+        cl.push_back(qk_clause{it->second, c.op, c.a, c.b});
+    }
+    auto f = std::make_shared<SearchFilter>();
+    f->owner = attrs_store_;
+    qk_check(qk_filter_create_where(attrs_store_, cl.data(), (int)cl.size(), &f->h));
     return f;
 }
 
@@ -244,6 +393,7 @@ void QuakeIndex::save(const std::string &dir_path) {
 
 void QuakeIndex::load(const std::string &dir_path, int n_workers) {
     namespace fs = std::filesystem;
+    drop_attributes();  // (attributes are not persisted)
     if (!fs::exists(dir_path) || !fs::is_directory(dir_path)) throw std::runtime_error("Cannot load QuakeIndex, directory does not exist: " + dir_path);
     {
         std::ifstream ifs((fs::path(dir_path) / "metadata.txt").string());

@@ -10,7 +10,29 @@
 #include "partition_manager.h"
 #include "query_coordinator.h"
 
+#include <map>
+
 namespace quake_amd {
+
+// extension: one clause of make_filter_where -- (name, op, a[, b]) with op one of "==" "!=" "<" "<=" ">" ">=" "between" "any_bits"
+// "all_bits" "no_bits".  An operand is an integer of any size: `over` says it lies below (-1) / above (+1) int64 (v is then
+// unused, except that a bit mask in [2^63, 2^64) arrives as its two's complement with over == 0); lowering saturates, never wraps.
+struct WhereOperand {
+    int64_t v = 0;
+    int over = 0;
+};
+struct WhereTerm {
+    std::string name, op;
+    WhereOperand a, b;
+    int n_operands = 1;
+};
+struct LoweredClause {
+    std::string name;
+    int op = QK_OP_RANGE;
+    int64_t a = 0, b = 0;
+};
+// the C clauses of a predicate (the Python mirror's quake_amd/where.py: same rules, same errors as std::runtime_error)
+std::vector<LoweredClause> lower_where(const std::vector<WhereTerm> &where);
 
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
@@ -41,6 +63,15 @@ public:
     void refine_partitions(Tensor partition_ids, int iterations);
     // extension: a filter over this index's vector ids for SearchParams::filter (ids: any integer tensor, host or device)
     shared_ptr<SearchFilter> make_filter(Tensor ids, bool exclude = false);
+    // extension: a predicate filter over the attribute columns below -- every clause must hold; it holds no ids and follows
+    // later set_attribute / add calls (qk_filter_create_where)
+    shared_ptr<SearchFilter> make_filter_where(const std::vector<WhereTerm> &where);
+    // extension: attribute columns -- int64 values keyed by vector id, on the device (qk_attr_*); a column is created by its
+    // first set_attribute; ids need not be stored, remove / modify keep the values; not persisted by save()
+    void set_attribute(const std::string &name, Tensor ids, Tensor values);
+    void unset_attribute(const std::string &name, Tensor ids);
+    std::pair<Tensor, Tensor> get_attribute(const std::string &name, Tensor ids);  // (values int64 [n], found bool [n])
+    std::vector<std::string> attribute_names();
     // extension: every vector of the search_params->nprobe nearest partitions within `radius` of each query (qk_range_search)
     shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
@@ -60,6 +91,10 @@ public:
     qk_store *store() { return partition_manager_ ? partition_manager_->store() : nullptr; }
 
 private:
+    std::map<std::string, qk_attr *> attrs_;  // columns of attrs_store_ (a rebuilt or loaded index starts without columns)
+    qk_store *attrs_store_ = nullptr;
+    std::map<std::string, qk_attr *> &attributes(const char *who);
+    void drop_attributes();
     void require_built(const char *msg) const;
     void make_coordinator(int num_workers);
 };

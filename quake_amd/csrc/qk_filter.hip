@@ -12,29 +12,15 @@
 // list creation / removal, bulk builds -- sets qk_store::table_dirty, and the table sync in front of every scan turns that into a
 // new version.  qk_filter_ensure compares the stamp after that sync and re-derives the mask from the ids when it differs: a filter
 // is defined by ids and stays correct whatever moves rows.
-#include "qk_internal.h"
+//
+// A filter is of one of two kinds (qk_attr.h): an id set, as above, or a PREDICATE over attribute columns (qk_attr.hip), whose
+// mask k_filter_build_where derives and whose stamp also holds the version of every column it names.  Everything behind the mask
+// -- the scans, the per-query table, the union -- is the same for both.
+#include "qk_attr.h"
 
 #include <algorithm>
 #include <atomic>
 #include <vector>
-
-struct qk_filter {
-    uint64_t serial = 0;     // unique per filter object of the process: a freed and re-allocated handle is another filter
-    uint64_t store_uid = 0;  // the store it was made for (never dereferenced: the store may be destroyed first)
-    int device = 0;
-    int mode = QK_FILTER_ALLOW;
-    int64_t n_ids = 0;
-    int64_t *d_ids = nullptr;  // [n_ids] ascending, no duplicates
-    uint16_t *mask = nullptr;  // [mask_words] one word per arena tile
-    int64_t mask_words = 0;    // capacity
-    bool built = false;
-    uint64_t version = 0;      // stamp: the store's version and arena capacity the mask was derived for
-    int64_t cap_rows = 0;
-    int64_t rebuilds = 0;      // builds after the first
-    unsigned long long *d_allowed = nullptr;  // [1] candidates of the last build
-    hipEvent_t built_ev = nullptr;            // behind the last build, on the stream that ran it
-    qk_ctx *built_ctx = nullptr;
-};
 
 namespace {
 
@@ -88,7 +74,8 @@ __global__ __launch_bounds__(256) void k_filter_build(FilterBuildParams F) {
     if (lane == 0 && mine) atomicAdd(F.allowed, mine);
 }
 
-int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
+// the mask sized for the store and cleared, the counter cleared, on ctx's stream
+int filter_build_prepare(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     const int64_t words = s->cap_rows / 16;
     if (words > f->mask_words || !f->mask) {
         // (the old mask may still be read by a scan in flight on some context: hipFree waits for the device)
@@ -107,6 +94,11 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     if (f->built_ctx && f->built_ctx != ctx) QK_HIP(hipStreamWaitEvent(st, f->built_ev, 0));
     QK_HIP(hipMemsetAsync(f->mask, 0, (size_t)f->mask_words * sizeof(uint16_t), st));
     QK_HIP(hipMemsetAsync(f->d_allowed, 0, sizeof(unsigned long long), st));
+    return QK_OK;
+}
+
+int filter_build_ids(qk_ctx *ctx, qk_store *s, qk_filter *f) {
+    hipStream_t st = ctx->stream;
     const int64_t npids = (int64_t)s->parts.size();
     if (npids > 0 && s->ntotal > 0) {
         FilterBuildParams F;
@@ -124,6 +116,15 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
         hipLaunchKernelGGL(k_filter_build, dim3((unsigned)npids, gy), dim3(256), 0, st, F);
         QK_HIP(hipGetLastError());
     }
+    return QK_OK;
+}
+
+int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
+    QK_TRY(filter_build_prepare(ctx, s, f));
+    // (a predicate's clauses are stamped with their columns' versions even when there is no row to look at)
+    if (f->kind == QK_FILTER_KIND_WHERE) QK_TRY(qk_launch_filter_build_where(ctx, s, f));
+    else QK_TRY(filter_build_ids(ctx, s, f));
+    hipStream_t st = ctx->stream;
     QK_HIP(hipEventRecord(f->built_ev, st));
     if (f->built) f->rebuilds++;
     f->built = true;
@@ -135,7 +136,8 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
 
 // the mask of a filter of this store and device, current for the store's table (the caller has synced it)
 int filter_current(qk_ctx *ctx, qk_store *s, qk_filter *f) {
-    if (!f->built || f->version != s->version || f->cap_rows != s->cap_rows) {
+    if (!f->built || f->version != s->version || f->cap_rows != s->cap_rows ||
+        (f->kind == QK_FILTER_KIND_WHERE && !qk_filter_where_current(f))) {
         QK_TRY(filter_build(ctx, s, f));
     } else if (f->built_ctx != ctx) {
         QK_HIP(hipStreamWaitEvent(ctx->stream, f->built_ev, 0));  // the build ran on another context's stream
@@ -176,16 +178,18 @@ int qk_filter_batch_ensure(qk_ctx *ctx, qk_store *s, qk_filter *const *filters, 
     for (int i = 0; i < F; i++) QK_TRY(filter_belongs(ctx, s, filters[i]));
     QK_TRY(qk_store_sync_table(s));  // once: every filter is compared with the same version
     for (int i = 0; i < F; i++) QK_TRY(filter_current(ctx, s, filters[i]));
-    // what the table and the union were derived from; a mask that was re-derived has another version (or capacity), a handle that
-    // was freed and allocated again another serial
+    // what the table and the union were derived from; a mask that was re-derived has another version (or capacity) or -- a
+    // predicate whose column changed under an unchanged store -- another build count, a handle that was freed and allocated again
+    // another serial
     std::vector<uint64_t> key;
-    key.reserve((size_t)F * 4);
+    key.reserve((size_t)F * 5);
     for (int i = 0; i < F; i++) {
         const qk_filter *f = filters[i];
         key.push_back(f->serial);
         key.push_back(f->version);
         key.push_back((uint64_t)f->cap_rows);
         key.push_back((uint64_t)(uintptr_t)f->mask);
+        key.push_back((uint64_t)f->rebuilds);
     }
     const int64_t words = s->cap_rows / 16;
     if (key != ctx->fb_key || !ctx->fb_table || !ctx->fb_union) {
@@ -230,6 +234,16 @@ int qk_filter_batch_ensure(qk_ctx *ctx, qk_store *s, qk_filter *const *filters, 
     return QK_OK;
 }
 
+uint64_t qk_filter_next_serial() {
+    static std::atomic<uint64_t> next_serial{1};
+    return next_serial.fetch_add(1);
+}
+
+int qk_filter_first_build(qk_store *s, qk_filter *f) {
+    QK_TRY(qk_store_sync_table(s));
+    return filter_build(s->ctx, s, f);
+}
+
 extern "C" {
 
 int qk_filter_create(qk_store *s, const int64_t *ids, int64_t n, int mode, int mem, qk_filter **out) {
@@ -249,9 +263,8 @@ int qk_filter_create(qk_store *s, const int64_t *ids, int64_t n, int mode, int m
         std::sort(h.begin(), h.end());
         h.erase(std::unique(h.begin(), h.end()), h.end());
     }
-    static std::atomic<uint64_t> next_serial{1};
     qk_filter *f = new qk_filter();
-    f->serial = next_serial.fetch_add(1);
+    f->serial = qk_filter_next_serial();
     f->store_uid = s->uid;
     f->device = c->device;
     f->mode = mode;
@@ -266,8 +279,7 @@ int qk_filter_create(qk_store *s, const int64_t *ids, int64_t n, int mode, int m
         QK_FAIL(QK_ERR_OOM, "qk_filter_create: no device memory for %lld ids", (long long)n);
     }
     // the first mask now, on the store's context: the first filtered search does not pay for it
-    QK_TRY(qk_store_sync_table(s));
-    const int rc = filter_build(c, s, f);
+    const int rc = qk_filter_first_build(s, f);
     if (rc != QK_OK) {
         qk_filter_destroy(f);
         return rc;
@@ -294,7 +306,7 @@ int qk_filter_destroy(qk_filter *f) {
 int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t *store_version, int64_t *rebuilds, int64_t *device_bytes) {
     if (!f) QK_FAIL(QK_ERR_INVALID, "qk_filter_info: null filter");
     QK_HIP(hipSetDevice(f->device));
-    if (n_ids) *n_ids = f->n_ids;
+    if (n_ids) *n_ids = f->kind == QK_FILTER_KIND_WHERE ? -1 : f->n_ids;
     if (rows_allowed) {
         unsigned long long v = 0;
         QK_HIP(hipEventSynchronize(f->built_ev));
@@ -303,7 +315,10 @@ int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t
     }
     if (store_version) *store_version = f->version;
     if (rebuilds) *rebuilds = f->rebuilds;
-    if (device_bytes) *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t) + std::max<int64_t>(f->n_ids, 1) * sizeof(int64_t) + 8);
+    if (device_bytes) {
+        if (f->kind == QK_FILTER_KIND_WHERE) *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t));  // (no ids: the mask only)
+        else *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t) + std::max<int64_t>(f->n_ids, 1) * sizeof(int64_t) + 8);
+    }
     return QK_OK;
 }
 

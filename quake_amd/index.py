@@ -18,6 +18,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError
+from .where import lower_where
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -130,13 +131,28 @@ class SearchFilter:
     iff its id is in the set, with exclude=True iff it is not.  Defined by ids, so it stays valid across add / remove / modify /
     maintenance; it is not persisted by save().  info(): {n_ids, rows_allowed, store_version, rebuilds, device_bytes}."""
 
-    def __init__(self, index, ids, exclude=False):
+    def __init__(self, index, ids=None, exclude=False, where=None):
         if isinstance(index._store, capi.Group):
             raise RuntimeError("[QuakeIndex::make_filter()] filtered search is not supported with num_workers > 0")
+        if (ids is None) == (where is None):
+            raise RuntimeError("[QuakeIndex::make_filter()] exactly one of ids and where must be given")
         self.exclude = bool(exclude)
+        self._store = index._store
+        if where is not None:
+            # a predicate over the index's attribute columns (set_attribute): no ids are held, later set_attribute / add calls
+            # are seen by the next search
+            if exclude:
+                raise RuntimeError("[QuakeIndex::make_filter()] exclude applies to ids, not to where (negate the clauses)")
+            cols = index._attributes()
+            clauses = []
+            for name, op, a, b in lower_where(where):
+                if name not in cols:
+                    raise RuntimeError("[QuakeIndex::make_filter()] unknown attribute column '%s'" % name)
+                clauses.append((cols[name], op, a, b))
+            self._h = capi.Filter.where(index._store, clauses)
+            return
         ids = ids if torch.is_tensor(ids) else torch.as_tensor(np.asarray(ids))
         ids = ids.reshape(-1).to(torch.int64)
-        self._store = index._store
         self._h = capi.Filter(index._store, ids if ids.is_cuda else ids.numpy(), "deny" if exclude else "allow")
 
     def info(self):
@@ -660,10 +676,62 @@ class QuakeIndex:
         res.distances = dist if on_dev else dist.cpu()
         return res
 
-    def make_filter(self, ids, exclude=False):
-        """extension: a SearchFilter over this index's vector ids for SearchParams.filter"""
+    def make_filter(self, ids=None, exclude=False, where=None):
+        """extension: a SearchFilter for SearchParams.filter -- over this index's vector ids (`ids`, `exclude`), or a predicate
+        over its attribute columns: `where` is a list of (name, op, a[, b]), all of which must hold (quake_amd/where.py: "=="
+        "!=" "<" "<=" ">" ">=" "between" "any_bits" "all_bits" "no_bits"); a vector without a value in a named column is no
+        candidate.  Exactly one of ids / where."""
         self._require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?")
-        return SearchFilter(self, ids, exclude)
+        return SearchFilter(self, ids, exclude, where)
+
+    # -- attribute columns (extension): int64 values keyed by vector id, on the device; not persisted by save() ---------------
+    def _attributes(self):
+        """name -> capi.Attr of the current store (a rebuilt or loaded index starts without columns)"""
+        if getattr(self, "_attrs_store", None) is not self._store:
+            self._attrs, self._attrs_store = {}, self._store
+        return self._attrs
+
+    def _require_attributes(self, who):
+        self._require_built("[QuakeIndex::%s()] No partition manager. Index not built?" % who)
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::%s()] filtered search is not supported with num_workers > 0" % who)
+        return self._attributes()
+
+    @staticmethod
+    def _attr_arg(a):
+        a = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+        a = a.reshape(-1).to(torch.int64)
+        return a if a.is_cuda else a.numpy()
+
+    def set_attribute(self, name, ids, values):
+        """values[i] becomes the value of vector id ids[i] in column `name` (created on first use); the id need not be stored
+        (yet), and remove / modify keep it"""
+        cols = self._require_attributes("set_attribute")
+        ids, values = self._attr_arg(ids), self._attr_arg(values)
+        if ids.shape[0] != values.shape[0]:
+            raise RuntimeError("[QuakeIndex::set_attribute()] ids and values must have the same length")
+        if torch.is_tensor(ids) != torch.is_tensor(values):
+            ids, values = (v.cpu().numpy() if torch.is_tensor(v) else v for v in (ids, values))
+        if name not in cols:
+            cols[name] = capi.Attr(self._store)
+        cols[name].set(ids, values)
+
+    def unset_attribute(self, name, ids):
+        cols = self._require_attributes("unset_attribute")
+        if name not in cols:
+            raise RuntimeError("[QuakeIndex::unset_attribute()] unknown attribute column '%s'" % name)
+        cols[name].unset(self._attr_arg(ids))
+
+    def get_attribute(self, name, ids):
+        """(values int64 [n], found bool [n]) of the ids in column `name`"""
+        cols = self._require_attributes("get_attribute")
+        if name not in cols:
+            raise RuntimeError("[QuakeIndex::get_attribute()] unknown attribute column '%s'" % name)
+        vals, found = cols[name].get(self._attr_arg(ids))
+        return torch.from_numpy(vals), torch.from_numpy(found)
+
+    def attribute_names(self):
+        return sorted(self._attributes()) if self._store is not None else []
 
     # -- get / get_ids (partition_manager.cpp:322-343) --------------------------------------------------------------------
     def get(self, ids):
