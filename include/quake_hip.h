@@ -18,6 +18,13 @@
  *   - L2 results are sqrt distances, like the reference (list_scanning.h:260,286,353-357).
  *   - fewer than k results: ids -1, distances +inf (L2) / -inf (IP) (query_coordinator.cpp:589-601,774-788).
  *   - ordering is the total order (key, id) -- DESIGN.md section 3.
+ *   - non-finite values: a (query, row) pair whose canonical float32 value -- the k-ordered fmaf chain; for L2 the
+ *     expanded form with the clamp -- is NaN is NEVER a candidate: in qk_search, qk_scan, their filtered / per-query-filtered /
+ *     tracked forms, wide rows, k > QK_MAX_K and qk_range_*, whatever the NaN's sign or payload, the row's position or the scan form.
+ *     qk_coarse follows it: a NaN centroid is never probed, and the row is padded with -1 when fewer than kk centroids remain.
+ *     +-inf are ordinary values, ordered as floats: a row at +inf (L2) / -inf (IP) is returned with its own id in front of the
+ *     padding.  -0.0 and +0.0 tie and the lower id goes first; which sign a returned zero carries is unspecified.  Outside this
+ *     rule: k-means on non-finite input (qk_kmeans*), qk_search_aps and the device group.
  *   - all work is enqueued on the context's HIP stream; host-memory outputs are complete on return,
  *     device-memory outputs are complete after qk_ctx_synchronize() (or stream order).
  */

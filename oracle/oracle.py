@@ -18,7 +18,7 @@ METRIC_L2 = 1  # faiss::METRIC_L2
 
 __all__ = [
     "METRIC_IP", "METRIC_L2", "build", "lib", "metric_code", "ip", "l2sqr_direct", "row_norms", "TopkBuffer",
-    "scan_list", "batched_scan_list", "serial_scan", "batched_serial_scan", "coarse", "search", "rand_perm",
+    "scan_list", "batched_scan_list", "pair_values", "serial_scan", "batched_serial_scan", "coarse", "search", "rand_perm",
     "kmeans_assign", "kmeans_accumulate", "kmeans", "kmeans_update", "normalize_rows", "kmeans_refine_partitions", "recall", "csr_from_partitions",
     "max_threads", "effective_cores", "incomplete_beta", "incomplete_beta_table", "incomplete_beta_lookup", "log_cap_volume", "recall_profile",
     "boundary_distances", "search_aps",
@@ -62,6 +62,7 @@ def lib():
         L.qo_scan_list_fast.argtypes = [_f32p, _f32p, _i64p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.qo_batched_scan_list.argtypes = [_f32p, _f32p, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                            C.c_int, C.c_int]
+        L.qo_pair_values.argtypes = [_f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p]
         L.qo_serial_scan.argtypes = [_f32p, C.c_int64, _f32p, _i64p, _i64p, C.c_int64, C.c_int, _i64p, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_int, _i64p, _f32p]
         L.qo_batched_serial_scan.argtypes = [_f32p, C.c_int64, _f32p, _i64p, _i64p, C.c_int64, C.c_int, _i64p,
@@ -202,6 +203,17 @@ def batched_scan_list(queries, vecs, ids, bufs, metric, squared_domain=False):
     arr = (C.c_void_p * nq)(*[b.h for b in bufs])
     lib().qo_batched_scan_list(_pf(queries), _pf(vecs) if vecs.shape[0] else None, _pi(ids), nq, vecs.shape[0], d, arr,
                                metric_code(metric), int(squared_domain))
+
+
+def pair_values(queries, vecs, metric):
+    """[nq, n] canonical value of every (query, row) pair: IP the fmaf chain, L2 the expanded SQUARED form with the clamp -- what
+    the batched scan selects on, NaN included."""
+    queries = _f32(queries)
+    nq, d = queries.shape
+    vecs = _f32(vecs).reshape(-1, d)
+    out = np.empty((nq, vecs.shape[0]), np.float32)
+    lib().qo_pair_values(_pf(queries), nq, _pf(vecs), vecs.shape[0], d, metric_code(metric), _pf(out))
+    return out
 
 
 def csr_from_partitions(part_vecs, part_ids, d):

@@ -33,6 +33,13 @@
  * IP descending inner product then ascending id.  L2 results are selected on the SQUARED distance and
  * sqrt is applied to what is returned -- a refinement of the reference's order on sqrt(d2) (sqrt is monotone).
  *
+ * Non-finite values.  This is where the restatement DEPARTS from list_scanning.h: topk_add drops a
+ * NaN value.  The reference's comparators are not an order once a value is NaN, so what its partial_sort returns depends on
+ * where the NaN row sits in the buffer (first in every answer from row 3 of 200, never returned from row 150) -- there is no
+ * behaviour to restate.  The rule here: a (query, row) pair whose value is NaN is never a candidate, whatever the NaN's sign,
+ * payload or position; +-inf are ordinary floats and are ordered as such; -0 == +0, so the lower id goes first.  Nothing
+ * changes on finite input.
+ *
  * Pinning.  The reference cannot be built here (FAISS absent), so this oracle is pinned against
  * (a) the hand-computed vectors of test/cpp/list_scanning.cpp and test/cpp/topk_buffer.cpp transcribed
  * as data in tests/golden/, (b) torch brute force (the reference tests' own ground truth,
@@ -218,6 +225,7 @@ static void topk_flush(qo_topk *t) {
 
 /* add(): list_scanning.h:117-122 */
 static inline void topk_add(qo_topk *t, float v, int64_t id) {
+    if (v != v) return; /* NaN is never a candidate (file header, "Non-finite values"): not in the reference */
     if (t->curr >= t->cap) topk_flush(t);
     t->buf[t->curr].v = v;
     t->buf[t->curr].id = id;
@@ -417,6 +425,21 @@ static void batched_values(const float *queries, const float *qnorm, int nq, con
         }
     }
     free(xT);
+}
+
+/* the value of every (query, row) pair of one list, out [nq][n]: IP the chain, L2 the expanded form with the clamp (squared) --
+ * what batched_scan_list selects on, before any selection (so a NaN is still there).  For yardsticks that need every pair. */
+QO_API void qo_pair_values(const float *queries, int nq, const float *vecs, int n, int d, int metric, float *out) {
+    if (nq <= 0 || n <= 0) return;
+    float *qnorm = (float *)malloc(sizeof(float) * (size_t)nq);
+    float *ynorm = (float *)malloc(sizeof(float) * (size_t)n);
+    if (metric == QO_METRIC_L2) {
+        qo_row_norms(queries, nq, d, qnorm);
+        qo_row_norms(vecs, n, d, ynorm);
+    }
+    batched_values(queries, qnorm, nq, vecs, ynorm, n, d, metric, out);
+    free(qnorm);
+    free(ynorm);
 }
 
 QO_API void qo_batched_scan_list(const float *queries, const float *vecs, const int64_t *ids, int nq, int n, int d,

@@ -184,6 +184,7 @@ shared_ptr<ModifyTimingInfo> PartitionManager::add(const Tensor &vectors, const 
     } else if (parent_) {  // parent_->search(x, {k = 1}) (:219-230) == the coarse step with nprobe 1
         assign = torch::empty({n}, torch::kInt64);
         qk_check(qk_coarse(ctx_, parent_->store(), xh.data_ptr<float>(), n, 1, metric_, assign.data_ptr<int64_t>(), nullptr, QK_MEM_HOST));
+        assign = nearest_or_first(assign);
     } else {  // flat index: its single partition
         Tensor only = get_partition_ids();
         assign = torch::full({n}, only.numel() ? only[0].item<int64_t>() : 0, torch::kInt64);
@@ -225,6 +226,15 @@ Tensor PartitionManager::get(const Tensor &ids) {
         if (!found) throw std::runtime_error("ID not found in any partition");
     }
     return out;
+}
+
+// The list of every row to store, given its nearest list: a row with a NaN coordinate has no nearest list (the coarse step answers
+// -1: a NaN value is never a candidate) and goes to the list of the lowest number (non-finite rows are not rejected at add).
+Tensor PartitionManager::nearest_or_first(const Tensor &assign) {
+    if (!(assign < 0).any().item<bool>()) return assign;
+    Tensor all = get_partition_ids();
+    const int64_t first = all.numel() ? all.min().item<int64_t>() : 0;
+    return torch::where(assign < 0, torch::full_like(assign, first), assign).contiguous();
 }
 
 Tensor PartitionManager::get_partition_ids() {
@@ -423,6 +433,7 @@ bool PartitionManager::delete_partitions_in_place(const Tensor &partition_ids) {
     for (int64_t i = 0; i < np; i++) qk_check(lists_.remove_list(pp[i]));
     // PartitionManager::add(vectors, ids, {}, check_uniques = false) (:533-552): the nearest remaining centroid of every row
     qk_check(qk_coarse(ctx_, parent_->store(), x.data_ptr<float>(), total, 1, metric_, assign.data_ptr<int64_t>(), nullptr, QK_MEM_DEVICE));
+    assign = nearest_or_first(assign);
     qk_check(lists_.add_batch(total, idd.data_ptr<int64_t>(), x.data_ptr<float>(), assign.data_ptr<int64_t>(), QK_MEM_DEVICE));
     return true;  // (the rows' ids never left the index: resident_ids_ is unchanged)
 }

@@ -167,6 +167,7 @@ public:
     std::vector<int64_t> get_partition_sizes(std::vector<int64_t> partition_ids);
     int64_t get_partition_size(int64_t partition_id);
     Tensor get_partition_ids();
+    Tensor nearest_or_first(const Tensor &assign);  // -1 (a row without a nearest list: NaN) -> the lowest list number
     Tensor get_ids();
     bool validate();
     void save(const std::string &path);

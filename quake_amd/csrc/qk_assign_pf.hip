@@ -160,7 +160,11 @@ __device__ __forceinline__ void apf_exact(const float *__restrict__ x, const flo
             }
         }
         for (int p = 0; p < npad; p++) acc = __fmaf_rn(0.0f, 0.0f, acc);  // (the MFMA path runs over the zero columns of the last block)
-        const uint32_t o = L2 ? ord_from_l2(l2_expanded(xn_w[xl], cnorm[min(ci, m - 1)], acc)) : ord_from_ip(acc);
+        // the nearest-list form (ids given: a search's coarse step) ranks with the search keys -- a NaN value is no candidate, -0 ties
+        // with +0 --; k-means keeps the plain bit keys k_assign ranks with.  Non-finite data makes every centroid a
+        // candidate (header), so this exact key is what decides either way.
+        const float kv = L2 ? l2_expanded(xn_w[xl], cnorm[min(ci, m - 1)], acc) : acc;
+        const uint32_t o = ids ? (L2 ? ord_from_l2(kv) : ord_from_ip(kv)) : (L2 ? ord_bits_l2(kv) : ord_bits_ip(kv));
         const uint32_t low = ids ? (uint32_t)ids[min(ci, m - 1)] : (uint32_t)ci;  // what breaks a tie of keys (and what is returned)
         if (has) atomicMin(&best[xl], ((unsigned long long)o << 32) | (unsigned long long)low);
     }
@@ -426,7 +430,8 @@ __global__ __launch_bounds__(64 * APF_WAVES) void k_assign_pf(AssignPfParams P) 
     for (int rr = lane; rr < WR; rr += 64) {
         const int64_t row = wrow0 + rr;
         if (row >= P.n) continue;
-        const unsigned long long v = best_w[rr];
+        unsigned long long v = best_w[rr];
+        if (P.ids && (uint32_t)(v >> 32) == 0xFFFFFFFFu) v = ~0ull;  // (nearest-list form: only NaN values -- no list, like k_dense_argmin)
         const uint32_t o = (uint32_t)(v >> 32);
         const bool only = v == ~0ull && !P.want_keys && ncand[rr] == 1;
         const uint32_t low1 = only ? (P.ids ? (uint32_t)P.ids[onlyc[rr]] : (uint32_t)onlyc[rr]) : 0u;

@@ -451,7 +451,10 @@ __device__ __forceinline__ void select_large(const Src &src, int k, int kp, int 
     const int n = src.n;
     uint32_t *e_ord = (uint32_t *)smem;                     // [kp]
     int64_t *e_id = (int64_t *)(smem + (size_t)kp * 4);     // [kp]
-    const int kk = min(k, n);  // fewer rows than k: everything is kept, the rest is padding
+    // fewer rows than k: everything is kept, the rest is padding -- everything but the keys of all ones (NaN values: no candidates)
+    int live = 0;
+    for (int i = tid; i < n; i += 256) live += src.key(i) != 0xFFFFFFFFu ? 1 : 0;
+    const int kk = min(k, block_sum_256(live, s_red));
     // 1. k-th smallest key
     uint32_t T = 0;
     for (int b = 31; b >= 0; b--) {
@@ -824,7 +827,8 @@ __global__ __launch_bounds__(256) void k_dense_argmin(ArgminParams P) {
             v = o < v ? o : v;
         }
         const int64_t q = q_base + tid;
-        if (q < P.Q && v != ~0ull) atomicMin(&P.best64[q], v);
+        // (a key of all ones is a NaN value, never a candidate: it is the minimum only when no row has another key)
+        if (q < P.Q && (uint32_t)(v >> 32) != 0xFFFFFFFFu) atomicMin(&P.best64[q], v);
     }
 }
 

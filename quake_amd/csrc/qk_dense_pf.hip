@@ -324,7 +324,7 @@ __global__ __launch_bounds__(64) void k_pf_finish(PfFinish F) {
         const float yn = F.norms[arow];
         uint32_t o = L2 ? ord_from_l2(l2_expanded(xnq, yn, acc)) : ord_from_ip(acc);
         if (!has) o = 0xFFFFFFFFu;
-        const bool pass = has && o <= tau;
+        const bool pass = has && o <= tau && o != 0xFFFFFFFFu;  // (all ones: a NaN value, never a candidate -- tau may be all ones too)
         const uint64_t m = __ballot(pass);
         if (m) {
             if (pass) {

@@ -7,11 +7,26 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- orderable keys: smaller = better --------------------------------------------------------------
-__device__ __forceinline__ uint32_t ord_from_l2(float d2) { return __float_as_uint(d2); }  // d2 >= +0
+// Non-finite values (include/quake_hip.h): a NaN value maps to 0xFFFFFFFF, the key every selection, merge and epilogue
+// reads as "no candidate" and no seed accepts as a bound -- whatever the NaN's sign or payload (a positive NaN used to sort in
+// front of +inf under IP).  +-inf are ordinary keys.  -0 and +0 share the key of +0, so the id decides between them.  No other
+// value has the key 0xFFFFFFFF: under L2 it is a NaN's bit pattern, under IP the image of one.
+__device__ __forceinline__ uint32_t ord_from_l2(float d2) {  // d2 >= +0, or NaN
+    return d2 != d2 ? 0xFFFFFFFFu : __float_as_uint(d2);
+}
 __device__ __forceinline__ uint32_t ord_from_ip(float ip) {
     uint32_t b = __float_as_uint(ip);
+    b = b == 0x80000000u ? 0u : b;  // -0 -> +0
     uint32_t asc = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-    return ~asc;
+    return ip != ip ? 0xFFFFFFFFu : ~asc;
+}
+// The k-means assign (qk_assign_pf.hip without ids, k_assign_wide; km_ord_* of qk_kmeans.hip is the same map) keeps the plain bit maps:
+// k-means on non-finite input is outside the search contract, and its kernels agree with each other on these.  The nearest-list form of
+// qk_assign_pf.hip (a search's coarse step over 40960+ queries) uses ord_from_*.
+__device__ __forceinline__ uint32_t ord_bits_l2(float d2) { return __float_as_uint(d2); }
+__device__ __forceinline__ uint32_t ord_bits_ip(float ip) {
+    const uint32_t b = __float_as_uint(ip);
+    return ~(b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u));
 }
 __device__ __forceinline__ float ip_from_ord(uint32_t o) {
     uint32_t asc = ~o;

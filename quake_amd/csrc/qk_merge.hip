@@ -539,7 +539,7 @@ __global__ __launch_bounds__(64) void k_merge_ranks(const int64_t *__restrict__ 
                 const float v = in_key[base0 + e];
                 o = metric == QK_METRIC_L2 ? ord_from_l2(v) : ord_from_ip(v);
             }
-            const bool pass = id >= 0 && o <= tau;
+            const bool pass = id >= 0 && o <= tau && o != 0xFFFFFFFFu;  // (a NaN key is no candidate)
             const uint64_t m = __ballot(pass);
             if (m) {
                 if (pass) {

@@ -260,17 +260,19 @@ inline uint32_t f2u(float f) {
 
 // host copy of ord_from_ip (qk_device.h)
 inline uint32_t host_ord_from_ip(float ip) {
-    const uint32_t b = f2u(ip);
+    uint32_t b = f2u(ip);
+    if (ip != ip) return 0xFFFFFFFFu;  // NaN: no candidate
+    if (b == 0x80000000u) b = 0u;      // -0 -> +0
     const uint32_t asc = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
     return ~asc;
 }
 
-// The closed key interval of "dist <= radius" (L2) / "dist >= radius" (IP) on the float32 distance the caller sees.  Keys of NaN
-// distances lie outside every interval: above the key of +inf for L2 (and for an IP of negative NaN), below the key of +inf for
-// an IP of positive NaN.  Returns false when no distance can pass.
+// The closed key interval of "dist <= radius" (L2) / "dist >= radius" (IP) on the float32 distance the caller sees.  The key of a
+// NaN distance (0xFFFFFFFF, qk_device.h) lies outside every interval: the widest one ends at the key of +inf (L2) / -inf (IP).
+// Returns false when no distance can pass.
 bool range_key_bounds(int metric, bool sqrt_l2, float radius, uint32_t *lo, uint32_t *hi) {
     if (metric == QK_METRIC_IP) {
-        if (radius == 0.0f) radius = -0.0f;  // +0 >= -0 and -0 >= +0 in float32: the lower of the two keys
+        // (+0 >= -0 and -0 >= +0 in float32: both zeros have one key)
         *lo = host_ord_from_ip(INFINITY);
         *hi = host_ord_from_ip(radius);
         return true;

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void k_dense_wide(QkDenseWideParams P) {
 #pragma unroll
         for (int w = 1; w < 4; w++) v = red[w][tid] < v ? red[w][tid] : v;
         const int64_t qq = (int64_t)blockIdx.x * 16 + tid;
-        if (qq < P.Q && v != ~0ull) atomicMin(&P.best64[qq], v);
+        if (qq < P.Q && (uint32_t)(v >> 32) != 0xFFFFFFFFu) atomicMin(&P.best64[qq], v);  // (all ones: a NaN value, no candidate)
     }
 }
 
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void k_assign_wide(QkAssignWideParams P) {
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
                 const int idx = ((tb + r) << 4) + 4 * g + reg;
-                const uint32_t o = l2 ? ord_from_l2(l2_expanded(xnj, yv[reg], acc[r][reg])) : ord_from_ip(acc[r][reg]);
+                const uint32_t o = l2 ? ord_bits_l2(l2_expanded(xnj, yv[reg], acc[r][reg])) : ord_bits_ip(acc[r][reg]);  // (k-means' keys)
                 if (idx < P.m && o < best_ord) {
                     best_ord = o;
                     best_idx = idx;

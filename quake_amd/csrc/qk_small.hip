@@ -330,7 +330,7 @@ __global__ __launch_bounds__(QK_SMALL_THREADS) void k_search_small(SmallParams P
         int64_t off = 0;
         if (tid < np) {
             const int64_t p = s_pid[tid];
-            if (p >= 0 && p < P.npids) {
+            if (p >= 0 && p < P.npids && s_pord[tid] != 0xFFFFFFFFu) {  // (all ones: a NaN centroid, never probed)
                 sz = max(P.pt_size[p], 0);  // absent lists have size -1
                 off = P.pt_off[p];
             }
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(QK_SMALL_THREADS) void k_coarse_small(CoarseSmallPa
     for (int e = tid; e < P.k; e += QK_SMALL_THREADS) {
         int64_t oid = -1;
         float od = l2 ? INFINITY : -INFINITY;
-        if (e < nn) {
+        if (e < nn && s_ck[e] != 0xFFFFFFFFu) {  // (all ones: a NaN value, no candidate -- sorted behind every other key)
             oid = s_cid[e];
             const uint32_t o = s_ck[e];
             if (l2) {

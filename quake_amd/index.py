@@ -792,7 +792,7 @@ class QuakeIndex:
         else:
             # parent_->search(x, {k = 1, nprobe = parent nlist}) (:219-230) == coarse step with nprobe 1
             pids, _ = self._ctx.coarse(self.parent._store, xd, 1, self.metric_, values=False)
-            assign = pids.reshape(-1)
+            assign = self._nearest_or_first(pids.reshape(-1))
         info.find_partition_time_us = _us(t0)
         t0 = time.perf_counter()
         self._store.add_batch(idd, xd, assign.contiguous())  # per-list append order = input order (:245-258)
@@ -907,6 +907,15 @@ class QuakeIndex:
 
     def _list_ids(self):
         return [int(p) for p in self._store.list_ids()]
+
+    def _nearest_or_first(self, assign):
+        """the list of every row to store, given its nearest list: a row with a NaN coordinate has no nearest list (the coarse step
+        answers -1: a NaN value is never a candidate) and goes to the list of the lowest number; non-finite rows are
+        not rejected at add()"""
+        if not bool((assign < 0).any()):
+            return assign
+        first = int(self._store.list_ids().min())
+        return torch.where(assign < 0, torch.full_like(assign, first), assign)
 
     def _reassign_targets(self, pid):
         """where would the vectors of partition `pid` go if it were deleted: the other partitions among every vector's two
@@ -1094,7 +1103,7 @@ class QuakeIndex:
                 xd = torch.cat([v for v, _ in keep], 0)
                 idd = torch.from_numpy(np.concatenate([i for _, i in keep])).cuda(self._device)
                 near, _ = self._ctx.coarse(self.parent._store, xd, 1, self.metric_, values=False)
-                self._store.add_batch(idd, xd, near.reshape(-1).contiguous())
+                self._store.add_batch(idd, xd, self._nearest_or_first(near.reshape(-1)).contiguous())
 
     # -- sizes ---------------------------------------------------------------------------------------------------------------
     def ntotal(self):

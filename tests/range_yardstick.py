@@ -1,8 +1,8 @@
 """The yardstick of range search (shared by tests/test_range_oracle.py and tests/test_range_search.py).
 
-Expected values come from the oracle as it is: for every list p and the queries that probe it, batched_serial_scan over that one
-list with k = size(p) returns the canonical distance of EVERY row of the list (sorted); unique ids map them back to stored row
-order.  A query's lists are then walked in the order of its pids row (O.coarse's rank order for a search) and the rows that pass
+Expected values come from the oracle as it is: for every list p and the queries that probe it, O.pair_values gives the canonical
+distance of EVERY row of the list in stored row order -- the values the batched scan selects on, before its top-k drops a NaN
+(DESIGN 5.8.1), so a NaN pair is still here and passes() is what refuses it.  A query's lists are then walked in the order of its pids row (O.coarse's rank order for a search) and the rows that pass
 the radius in float32 are kept.  A filter: the same over the reduced CSR of tests/filter_yardstick.py.  Nothing here knows about
 keys, slices or kernels."""
 import numpy as np
@@ -39,13 +39,12 @@ def all_pairs(q, vecs, ids, offsets, pids, metric):
         assert np.unique(qi).shape[0] == qi.shape[0], "a pids row names list %d twice" % p
         lid = ids[offsets[p]:offsets[p + 1]]
         assert np.unique(lid).shape[0] == n, "ids must be unique"
-        oi, od = O.batched_serial_scan(q[qi], vecs, ids, offsets, np.full((qi.shape[0], 1), p, np.int64), n, metric)
-        assert (oi >= 0).all()
-        order = np.argsort(lid, kind="stable")
-        pos = order[np.searchsorted(lid[order], oi)]                # [nq, n] stored row of every sorted entry
-        dst = pair_base[qi, ri][:, None] + pos
+        val = O.pair_values(q[qi], vecs[offsets[p]:offsets[p + 1]], metric)   # [nq, n] in stored row order, NaN included
+        with np.errstate(invalid="ignore"):
+            od = np.sqrt(val) if metric == "l2" else val                     # (what a search returns: sqrt of the squared form)
+        dst = pair_base[qi, ri][:, None] + np.arange(n, dtype=np.int64)[None, :]
         dist[dst] = od
-        rows[dst] = offsets[p] + pos
+        rows[dst] = offsets[p] + np.arange(n, dtype=np.int64)[None, :]
     return lims, rows, dist
 
 
