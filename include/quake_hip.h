@@ -368,6 +368,48 @@ QK_API int qk_attr_info(qk_attr *a, int64_t *n_ids, uint64_t *version, int *layo
  * QK_MAX_CLAUSES.  qk_filter_info of the result: n_ids = -1, device_bytes = the mask only. */
 QK_API int qk_filter_create_where(qk_store *s, const qk_clause *clauses, int n_clauses, qk_filter **out);
 
+/* ---- grouped search -------------------------------------------------------------------------------
+ * No reference counterpart.  The k best GROUPS of a column per query, every group represented by its best row: results that are
+ * distinct by an attribute (the 10 best documents of a store of chunks, each by its best chunk), exact -- what oversampling
+ * qk_search and de-duplicating on the host cannot give.
+ * Lists: qk_search_grouped probes what the unfiltered qk_search probes (every list with parent == NULL); qk_scan_grouped takes
+ * pids [Q][P] like qk_range_scan: -1, absent and empty lists contribute nothing.
+ * Candidates of a query: the rows of its probed lists whose id has a value in `group_by` (an id without a value is never a
+ * candidate, as for predicate filters), whose key is not that of a NaN value (0xFFFFFFFF), and which `filter` -- a qk_filter of
+ * this store or NULL -- allows.  The representative of a value g is the candidate with that value that is smallest under the
+ * library's total order (key, id); the result is the k smallest representatives under (key, id): out_ids / out_dist [Q][k] with the
+ * distance bits qk_search reports for those rows, out_groups [Q][k] (may be NULL) the value of each entry.  Fewer than k groups:
+ * padded like qk_search (id -1, distance +inf / -inf), out_groups 0 there.  With every id in a group of its own the result is
+ * qk_search's bit for bit; with a filter a group is represented by its best ALLOWED row; +-inf are ordinary values; -0 and +0
+ * have one key and tie on the id.  Ids are unique within a store and, having values, non-negative.
+ * Liveness: the values are looked up when the call runs.  The column keeps its value of every arena row of the store, stamped with
+ * the store's (version, cap_rows) and its own version; a call that finds a stamp moved -- add, remove, anything that moves rows,
+ * qk_attr_set / qk_attr_unset -- re-derives them once (k_grouped_rowvals: one lookup per stored row) on its stream in front of its
+ * scan, otherwise nothing is done (qk_attr_group_info counts the derivations).  Ordering across contexts and streams as for filters.
+ * 1 <= k <= 8192; every k goes through key emission (there is no fused form for small k): the emission scan of the wide-k path,
+ * then per pass of queries an open-addressing table per query -- k_grouped_claim / k_grouped_minid / k_grouped_rewrite
+ * (qk_grouped.hip): atomicCAS claims a value's slot, atomicMin folds keys, then ids; every key that is not its group's (min key,
+ * min id) becomes 0xFFFFFFFF -- then the exact selection of the wide-k path and k_grouped_values.  No kernel waits or spins; the
+ * result is a pure function of the store, the column and the call.
+ * Workspace: per query of a pass 8 bytes per key it has room for (P lists of the store's largest size: per_query_ub) and 20 per
+ * table slot, T + 1 slots with T = the power of two >= max(16, 2 * min(per_query_ub, ids that have a value)).  Queries per pass =
+ * min(the wide-k rule: 2^29 / per_query_ub, QK_GROUPED_PASS_BYTES / that many bytes), at least 1; tables are cleared on the stream,
+ * nothing synchronises between passes.  QK_ERR_INVALID: group_by == NULL, a column or filter of another store, k < 1;
+ * QK_ERR_UNSUPPORTED: k > 8192, a single query whose bytes exceed QK_GROUPED_PASS_BYTES (or whose keys exceed 2^30).
+ * timing: coarse_ms / group_ms / scan_ms / merge_ms / total_ms as for the wide-k path (merge_ms: reduction + selection of the last
+ * pass), n_items = the number of query passes; no list statistics.  qk_ctx_last_scan_kernel names "k_scan (grouped)" /
+ * "k_scan_wide (grouped)".  There is no grouped form of per-query filters, of qk_search_aps or of the device group. */
+#define QK_GROUPED_PASS_BYTES ((int64_t)1 << 31)
+QK_API int qk_search_grouped(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
+                             qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
+                             qk_timing *timing);
+QK_API int qk_scan_grouped(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric,
+                           qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
+                           qk_timing *timing);
+/* builds: derivations of the column's row values so far (one per grouped call that found the store or the column changed);
+ * device_bytes: HBM they hold (not part of qk_attr_info).  Either pointer may be NULL. */
+QK_API int qk_attr_group_info(qk_attr *a, int64_t *builds, int64_t *device_bytes);
+
 /* QueryCoordinator::search with SearchParams::recall_target > 0 and batched_scan == false: adaptive partition
  * scanning (query_coordinator.cpp:612-657 picks M = max((int)(nlist * initial_search_fraction), 1) candidate partitions
  * from the parent; the use_aps branch of serial_scan, :471-611, scans them in rank order and stops a query once the

@@ -352,6 +352,43 @@ class Context:
                                          filter.h if filter is not None else None, c, _ptr(lims), _ptr(ids), _ptr(dist), mem, t))
         return self._range(call, x, cap, timing, out)
 
+    # ---- grouped search ---------------------------------------------------------------------------------
+    def search_grouped(self, parent, store, x, nprobe, k, metric, group_by, filter=None, timing=False, out=None):
+        """qk_search_grouped: the k best groups of the Attr `group_by` per query over the lists qk_search probes, every group
+        represented by its best row.  Returns (ids [Q, k], dist [Q, k], groups [Q, k][, timing]); out=(ids, dist, groups):
+        buffers of the caller.  filter: a Filter of `store` (a group is then represented by its best allowed row)."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        if out is None:
+            out = (_empty_like_mem((Q, k), np.int64, x), _empty_like_mem((Q, k), np.float32, x), _empty_like_mem((Q, k), np.int64, x))
+        out_i, out_d, out_g = out
+        t = QkTiming()
+        check(self.lib.qk_search_grouped(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), int(k),
+                                         metric_code(metric), group_by.h if group_by is not None else None,
+                                         filter.h if filter is not None else None, _ptr(out_i), _ptr(out_d), _ptr(out_g), mem,
+                                         C.byref(t) if timing else None))
+        return (out_i, out_d, out_g, timing_dict(t)) if timing else (out_i, out_d, out_g)
+
+    def scan_grouped(self, store, x, pids, k, metric, group_by, filter=None, timing=False, out=None):
+        """qk_scan_grouped: search_grouped over the given lists -- pids [Q, P] (or [P] for every query); -1 / absent / empty lists
+        contribute nothing"""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        if pids.ndim == 1:
+            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
+                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        mem = _mem_of(x, pids)
+        if out is None:
+            out = (_empty_like_mem((Q, k), np.int64, x), _empty_like_mem((Q, k), np.float32, x), _empty_like_mem((Q, k), np.int64, x))
+        out_i, out_d, out_g = out
+        t = QkTiming()
+        check(self.lib.qk_scan_grouped(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), int(k),
+                                       metric_code(metric), group_by.h if group_by is not None else None,
+                                       filter.h if filter is not None else None, _ptr(out_i), _ptr(out_d), _ptr(out_g), mem,
+                                       C.byref(t) if timing else None))
+        return (out_i, out_d, out_g, timing_dict(t)) if timing else (out_i, out_d, out_g)
+
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):
         """recall-target search (adaptive partition scanning).  Returns (ids, dist, nscanned[, timing])."""
@@ -753,6 +790,13 @@ class Attr:
         lay = C.c_int()
         check(self.lib.qk_attr_info(self.h, C.byref(n), C.byref(ver), C.byref(lay), C.byref(db)))
         return {"n_ids": n.value, "version": ver.value, "layout": self.LAYOUTS[lay.value], "device_bytes": db.value}
+
+    def group_info(self):
+        """{builds, device_bytes} of the per-row values grouped search keeps for this column (qk_attr_group_info): builds counts
+        their derivations -- one per grouped call that found the store or the column changed"""
+        b, db = C.c_int64(), C.c_int64()
+        check(self.lib.qk_attr_group_info(self.h, C.byref(b), C.byref(db)))
+        return {"builds": b.value, "device_bytes": db.value}
 
 
 class Group:

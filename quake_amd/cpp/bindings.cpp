@@ -118,6 +118,8 @@ PYBIND11_MODULE(_bindings, m) {
         .def("attribute_names", &QuakeIndex::attribute_names)
         .def("range_search", &QuakeIndex::range_search, py::arg("x"), py::arg("radius"), py::arg("search_params"),
              "extension: every vector of the nprobe nearest partitions within `radius` of each query (lims, ids, distances)")
+        .def("grouped_search", &QuakeIndex::grouped_search, py::arg("x"), py::arg("group_by"), py::arg("search_params"),
+             "extension: the k best groups of attribute column `group_by` per query, every group by its best vector (ids, distances, groups)")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)
@@ -310,6 +312,13 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("ids", &RangeSearchResult::ids)
         .def_readwrite("distances", &RangeSearchResult::distances)
         .def_readwrite("timing_info", &RangeSearchResult::timing_info);
+
+    py::class_<GroupedSearchResult, std::shared_ptr<GroupedSearchResult>>(m, "GroupedSearchResult")
+        .def(py::init<>())
+        .def_readwrite("ids", &GroupedSearchResult::ids)
+        .def_readwrite("distances", &GroupedSearchResult::distances)
+        .def_readwrite("groups", &GroupedSearchResult::groups)
+        .def_readwrite("timing_info", &GroupedSearchResult::timing_info);
 
     py::class_<SearchResult, std::shared_ptr<SearchResult>>(m, "SearchResult")
         .def(py::init<>())

@@ -129,6 +129,15 @@ struct RangeSearchResult {
     shared_ptr<SearchTimingInfo> timing_info;
 };
 
+// extension (QuakeIndex::grouped_search): the k best groups of a column per query -- ids / distances [Q, k] of each group's best vector,
+// groups [Q, k] the group values (0 where ids is the padding id -1)
+struct GroupedSearchResult {
+    Tensor ids;
+    Tensor distances;
+    Tensor groups;
+    shared_ptr<SearchTimingInfo> timing_info;
+};
+
 struct Clustering {  // common.h:249-276
     Tensor centroids;
     Tensor partition_ids;

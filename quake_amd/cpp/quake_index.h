@@ -74,6 +74,9 @@ public:
     std::vector<std::string> attribute_names();
     // extension: every vector of the search_params->nprobe nearest partitions within `radius` of each query (qk_range_search)
     shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
+    // extension: the search_params->k best groups of attribute column `group_by` among the vectors of the nprobe nearest partitions,
+    // every group represented by its best (allowed) vector (qk_search_grouped)
+    shared_ptr<GroupedSearchResult> grouped_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> search_params);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

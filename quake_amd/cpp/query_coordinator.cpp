@@ -299,6 +299,72 @@ shared_ptr<RangeSearchResult> QueryCoordinator::range_search(Tensor x, float rad
     return res;
 }
 
+shared_ptr<GroupedSearchResult> QueryCoordinator::grouped_search(Tensor x, qk_attr *group_by, const std::string &name, shared_ptr<SearchParams> sp) {
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::grouped_search] partition_manager_ is null.");
+    if (!sp->filters.empty() || sp->query_filter.defined())
+        throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
+                                 "supported by grouped_search");
+    if (sp->recall_target > 0.0f) throw std::runtime_error("[QuakeIndex::grouped_search()] grouped_search is not supported with recall_target > 0");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group()) throw std::runtime_error("[QuakeIndex::grouped_search()] grouped_search is not supported with num_workers > 0");
+    if (!store) throw std::runtime_error("[QueryCoordinator::grouped_search] partitions are not initialized.");
+    if (!group_by) throw std::runtime_error("[QuakeIndex::grouped_search()] unknown attribute column '" + name + "'");
+    qk_filter *flt = nullptr;
+    if (sp->filter) {
+        if (!sp->filter->h) throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filter must come from make_filter()");
+        if (sp->filter->owner != store) throw std::runtime_error("[QuakeIndex::grouped_search()] the filter was made for another index");
+        flt = sp->filter->h;
+    }
+    const int k = sp->k > 0 ? sp->k : 1;
+    auto res = std::make_shared<GroupedSearchResult>();
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->search_params = sp;
+    ti->n_clusters = partition_manager_->nlist();
+    if (!x.defined() || x.size(0) == 0) {
+        res->ids = torch::empty({0, k}, torch::kInt64);
+        res->distances = torch::empty({0, k}, torch::kFloat32);
+        res->groups = torch::empty({0, k}, torch::kInt64);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x);
+    BoundToTorchStream bound(ctx, xq);
+    const int64_t Q = xq.size(0);
+    const int nprobe = std::max(sp->nprobe, 1);
+    const int mem = on_dev ? QK_MEM_DEVICE : QK_MEM_HOST;
+    ti->n_queries = Q;
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
+    auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(xq.device());
+    res->ids = torch::empty({Q, k}, i64);
+    res->distances = torch::empty({Q, k}, f32);
+    res->groups = torch::empty({Q, k}, i64);
+    qk_check(qk_search_grouped(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_, group_by, flt,
+                               res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), res->groups.data_ptr<int64_t>(), mem, &tm));
+    ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    if (parent_) {
+        ti->parent_info = std::make_shared<SearchTimingInfo>();
+        ti->parent_info->n_queries = Q;
+        ti->parent_info->n_clusters = 1;
+        ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
+    }
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
 shared_ptr<SearchResult> QueryCoordinator::scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> sp) {  // :659-673
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::scan_partitions] partition_manager_ is null.");
     if (!x.defined() || x.size(0) == 0) return empty_result(sp);

@@ -30,8 +30,86 @@ struct qk_attr_data {
     hipEvent_t upd_ev = nullptr;  // behind the last update, on upd_stream
     hipStream_t upd_stream = nullptr;
     bool updated = false;
+    // grouped search (qk_grouped.hip): the column's value of every arena row of the store -- rv_vals[row] and a has-value mask in
+    // the filter's layout, one 16-bit word per 16-row tile -- stamped with what they were derived from and re-derived in front of
+    // a grouped call when a stamp moved
+    int64_t *rv_vals = nullptr;
+    uint16_t *rv_has = nullptr;
+    int64_t rv_cap = 0;              // rows the arrays hold
+    bool rv_built = false;
+    uint64_t rv_store_version = 0, rv_col_version = 0;
+    int64_t rv_cap_rows = 0;
+    int64_t rv_builds = 0;           // derivations so far (qk_attr_group_info)
+    hipEvent_t rv_ev = nullptr;      // behind the last derivation, on the stream of rv_ctx
+    qk_ctx *rv_ctx = nullptr;
     ~qk_attr_data();
 };
+
+struct qk_attr {
+    std::shared_ptr<qk_attr_data> d;
+    qk_ctx *ctx = nullptr;  // the store's context: updates are enqueued on its stream
+};
+
+// ---- the lookup ---------------------------------------------------------------------------------------------------------------
+struct AttrCol {
+    const int64_t *vals;   // table: [n] by id; sorted: [n] next to ids
+    const uint32_t *bits;  // table: presence, bit (id & 31) of word id >> 5
+    const int64_t *ids;    // sorted: [n] ascending
+    int64_t n;             // table: ids covered (>= 32); sorted: pairs (>= 1)
+    int layout;
+};
+
+static inline AttrCol col_of(const qk_attr_data &d) {
+    AttrCol c;
+    if (d.layout == QK_ATTR_TABLE) c = AttrCol{d.t_vals, d.t_bits, nullptr, d.t_cap, QK_ATTR_TABLE};
+    else c = AttrCol{d.s_vals, nullptr, d.s_ids, d.n_ids, QK_ATTR_SORTED};
+    return c;
+}
+
+// (false after an update that failed half way, see "Errors" above: no kernel is given such a column)
+static inline bool col_usable(const AttrCol &c) { return c.vals && c.n >= 1 && (c.layout == QK_ATTR_TABLE ? c.bits != nullptr : c.ids != nullptr); }
+
+// U ids looked up at once: every load of a step is asked for before the first is used (a lookup is a chain of dependent loads and
+// a mask build has nothing else to hide them behind).  live[u] == false: the loads go to element 0 and the result is "no value".
+template <int U>
+__device__ __forceinline__ void attr_lookup(const AttrCol &c, const int64_t (&id)[U], const bool (&live)[U], int64_t (&v)[U], bool (&has)[U]) {
+    if (c.layout == QK_ATTR_TABLE) {
+        uint32_t w[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const bool in = live[u] && (uint64_t)id[u] < (uint64_t)c.n;  // (a negative id is a huge unsigned one)
+            const int64_t i = in ? id[u] : 0;
+            w[u] = c.bits[i >> 5];
+            v[u] = c.vals[i];
+            has[u] = in;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) has[u] = has[u] && ((w[u] >> (id[u] & 31)) & 1u);
+    } else {
+        // the last element <= id, all U searches in step: the answer stays in [base, base + len), every probe lies inside [0, n)
+        int64_t base[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) base[u] = 0;
+        for (int64_t len = c.n; len > 1;) {
+            const int64_t half = len >> 1;
+            int64_t k[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) k[u] = c.ids[base[u] + half];
+#pragma unroll
+            for (int u = 0; u < U; u++) base[u] += (live[u] && k[u] <= id[u]) ? half : 0;
+            len -= half;
+        }
+        int64_t k[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            k[u] = c.ids[base[u]];
+            v[u] = c.vals[base[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) has[u] = live[u] && k[u] == id[u];
+    }
+}
+
 
 enum { QK_FILTER_KIND_IDS = 0, QK_FILTER_KIND_WHERE = 1 };
 
@@ -71,3 +149,8 @@ int qk_filter_first_build(qk_store *s, qk_filter *f);
 int qk_launch_filter_build_where(qk_ctx *ctx, qk_store *s, qk_filter *f);
 // are the clauses' stamps those of their columns
 bool qk_filter_where_current(const qk_filter *f);
+
+// qk_grouped.hip: the k best groups of `col` per query over the probed lists (`a` as for qk_range_device, k and out_* set);
+// col's row values are up to date (the caller ensured them), mask: a filter's row mask or nullptr; out_groups [Q][k] or nullptr
+int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data &col, const uint16_t *mask, int64_t *out_groups,
+                      qk_timing *timing, int64_t *n_passes);

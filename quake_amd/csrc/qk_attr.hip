@@ -22,11 +22,6 @@
 #include <numeric>
 #include <vector>
 
-struct qk_attr {
-    std::shared_ptr<qk_attr_data> d;
-    qk_ctx *ctx = nullptr;  // the store's context: updates are enqueued on its stream
-};
-
 qk_attr_data::~qk_attr_data() {
     // (runs wherever the last owner goes -- qk_attr_destroy, qk_filter_destroy -- so the caller's current device is put back)
     int cur = -1;
@@ -42,71 +37,14 @@ qk_attr_data::~qk_attr_data() {
     if (s_ids) hipFree(s_ids);
     if (s_vals) hipFree(s_vals);
     if (stage) hipFree(stage);
+    if (rv_vals) hipFree(rv_vals);
+    if (rv_has) hipFree(rv_has);
+    if (rv_ev) hipEventDestroy(rv_ev);
     if (have_cur && cur != device) hipSetDevice(cur);
     (void)hipGetLastError();
 }
 
 namespace {
-
-// ---- the lookup ---------------------------------------------------------------------------------------------------------------
-struct AttrCol {
-    const int64_t *vals;   // table: [n] by id; sorted: [n] next to ids
-    const uint32_t *bits;  // table: presence, bit (id & 31) of word id >> 5
-    const int64_t *ids;    // sorted: [n] ascending
-    int64_t n;             // table: ids covered (>= 32); sorted: pairs (>= 1)
-    int layout;
-};
-
-AttrCol col_of(const qk_attr_data &d) {
-    AttrCol c;
-    if (d.layout == QK_ATTR_TABLE) c = AttrCol{d.t_vals, d.t_bits, nullptr, d.t_cap, QK_ATTR_TABLE};
-    else c = AttrCol{d.s_vals, nullptr, d.s_ids, d.n_ids, QK_ATTR_SORTED};
-    return c;
-}
-
-// (false after an update that failed half way, see "Errors" above: no kernel is given such a column)
-bool col_usable(const AttrCol &c) { return c.vals && c.n >= 1 && (c.layout == QK_ATTR_TABLE ? c.bits != nullptr : c.ids != nullptr); }
-
-// U ids looked up at once: every load of a step is asked for before the first is used (a lookup is a chain of dependent loads and
-// a mask build has nothing else to hide them behind).  live[u] == false: the loads go to element 0 and the result is "no value".
-template <int U>
-__device__ __forceinline__ void attr_lookup(const AttrCol &c, const int64_t (&id)[U], const bool (&live)[U], int64_t (&v)[U], bool (&has)[U]) {
-    if (c.layout == QK_ATTR_TABLE) {
-        uint32_t w[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const bool in = live[u] && (uint64_t)id[u] < (uint64_t)c.n;  // (a negative id is a huge unsigned one)
-            const int64_t i = in ? id[u] : 0;
-            w[u] = c.bits[i >> 5];
-            v[u] = c.vals[i];
-            has[u] = in;
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) has[u] = has[u] && ((w[u] >> (id[u] & 31)) & 1u);
-    } else {
-        // the last element <= id, all U searches in step: the answer stays in [base, base + len), every probe lies inside [0, n)
-        int64_t base[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) base[u] = 0;
-        for (int64_t len = c.n; len > 1;) {
-            const int64_t half = len >> 1;
-            int64_t k[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) k[u] = c.ids[base[u] + half];
-#pragma unroll
-            for (int u = 0; u < U; u++) base[u] += (live[u] && k[u] <= id[u]) ? half : 0;
-            len -= half;
-        }
-        int64_t k[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            k[u] = c.ids[base[u]];
-            v[u] = c.vals[base[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) has[u] = live[u] && k[u] == id[u];
-    }
-}
 
 __device__ __forceinline__ bool where_op(int op, int64_t a, int64_t b, int64_t v) {
     switch (op) {

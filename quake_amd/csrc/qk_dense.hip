@@ -1290,6 +1290,29 @@ void qk_launch_pair_offsets(qk_ctx *ctx, qk_store *s, const int64_t *pids, int64
     hipLaunchKernelGGL(k_exclusive_scan_i64, dim3(1), dim3(1024), 0, ctx->stream, sizes, pair_base, npairs + 1);
 }
 
+// k_select_pairs_large over the keys of one pass for a caller outside this file (qk_grouped.hip): nq queries, kp a power of two >= k
+int qk_launch_select_pairs(qk_ctx *ctx, qk_store *s, const uint32_t *keys, const int64_t *pair_base, const int64_t *pids, int64_t nq, int P,
+                           int k, int kp, int metric, bool sqrt_l2, int64_t *out_ids, float *out_dist) {
+    WideKParams w;
+    w.keys = keys;
+    w.pair_base = pair_base;
+    w.pids = pids;
+    w.pt_off = s->d_off;
+    w.ids = s->ids;
+    w.P = P;
+    w.k = k;
+    w.kp = kp;
+    w.metric = metric;
+    w.sqrt_l2 = sqrt_l2 ? 1 : 0;
+    w.out_ids = out_ids;
+    w.out_dist = out_dist;
+    const size_t lds = (size_t)kp * 12;
+    QK_HIP(hipFuncSetAttribute((const void *)k_select_pairs_large, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_select_pairs_large, dim3((unsigned)nq), dim3(256), lds, ctx->stream, w);
+    QK_HIP(hipGetLastError());
+    return QK_OK;
+}
+
 int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base) {
     const int64_t Q = a.Q;
     const int k = a.k;

@@ -1,0 +1,546 @@
+// qk_grouped.hip -- grouped search: the k best GROUPS of an attribute column, every group represented by its best row
+// (include/quake_hip.h, "grouped search").
+//
+// The expensive half is the key-emission scan of the wide-k path and of range search: keys[pair_base[pair] + row] holds the canonical
+// key of every (query, probed row), pairs in (query, rank) order.  Between emission and the exact selection that already exists
+// (k_select_pairs_large, qk_dense.hip) the keys of every row that is not the (min key, min id) of its group are overwritten with
+// 0xFFFFFFFF -- the key that is never a candidate -- so the selection sees one row per group.  New device work:
+//   k_grouped_rowvals   once per (store version, column version): the column's value of every arena row and a has-value mask in
+//                       the filter's layout (one 16-bit word per 16-row tile); a call that finds both stamps unchanged does nothing
+//   per pass of queries, an open-addressing table per query (value, min key, min id), cleared by one memset of 0xFF:
+//   k_grouped_claim     every candidate finds or claims the slot of its value (atomicCAS on the value word), remembers the slot
+//                       and folds its key into the slot's minimum (atomicMin)
+//   k_grouped_minid     every candidate whose key is its slot's minimum folds its id into the slot (64-bit atomicMin)
+//   k_grouped_rewrite   every emitted key that is not its slot's (min key, min id) becomes 0xFFFFFFFF
+//   k_grouped_values    groups[q][j] of the selected ids, through the column's lookup
+// No thread waits for another: a slot's key and id words hold "nothing yet" (all ones) from the memset on, so whoever finds a value
+// claimed proceeds at once, and the phases are separated by kernel boundaries.  Only commutative minima decide a slot, so the result
+// does not depend on who came first.  The value whose bits are all ones (-1) is the table's empty marker: it owns slot T of every query.
+#include "qk_attr.h"
+
+#include <cstring>
+
+namespace {
+
+constexpr unsigned long long GR_EMPTY = ~0ull;
+constexpr int GR_SLICE = 1024;  // keys per workgroup step: 256 threads x 4
+
+struct GroupedParams {
+    uint32_t *keys;
+    int32_t *slot;             // per emitted key: the slot of its value inside its query's table, -1 = no candidate
+    const int64_t *pair_base;  // [npairs + 1]
+    const int64_t *pids;       // [nq][P] or nullptr (pair r -> list r)
+    const int64_t *pt_off;
+    const int64_t *ids;        // arena ids
+    const uint16_t *mask;      // row mask of a filter, or nullptr
+    const uint16_t *has;       // has-value mask of the column
+    const int64_t *rowval;     // the column's value per arena row
+    unsigned long long *tvals; // [nq][T + 1]
+    unsigned long long *tids;  // [nq][T + 1]
+    uint32_t *tkeys;           // [nq][T + 1]
+    int P, Sg;
+    uint32_t tmask;            // T - 1
+};
+
+// arena row of the key at absolute position pos (pbase: the query's P + 1 pair offsets); empty pairs repeat an offset and are skipped
+__device__ __forceinline__ int64_t grouped_row(const GroupedParams &G, const int64_t *pbase, const int64_t *qpids, int64_t pos) {
+    int lo = 0, hi = G.P;  // pbase[lo] <= pos < pbase[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pbase[mid] <= pos) lo = mid; else hi = mid;
+    }
+    const int64_t pid = qpids ? qpids[lo] : lo;
+    return G.pt_off[pid] + (pos - pbase[lo]);
+}
+
+__device__ __forceinline__ uint32_t grouped_hash(unsigned long long v) {  // (the 64-bit finaliser of MurmurHash3)
+    v ^= v >> 33;
+    v *= 0xff51afd7ed558ccdull;
+    v ^= v >> 33;
+    v *= 0xc4ceb9fe1a85ec53ull;
+    v ^= v >> 33;
+    return (uint32_t)v;
+}
+
+// blockIdx.x = query * Sg + g: the workgroup takes slices g, g + Sg, ... of its query's segment (the decomposition of k_range_count)
+#define GROUPED_FOR_EACH_KEY(G)                                                                          \
+    const int64_t q = blockIdx.x / (G).Sg;                                                               \
+    const int64_t *pbase = (G).pair_base + q * (G).P;                                                    \
+    const int64_t *qpids = (G).pids ? (G).pids + q * (G).P : nullptr;                                    \
+    const int64_t beg = pbase[0], end = pbase[(G).P];                                                    \
+    const int64_t tbase = q * ((int64_t)(G).tmask + 2);                                                  \
+    for (int64_t s0 = beg + (int64_t)(blockIdx.x - q * (G).Sg) * GR_SLICE; s0 < end; s0 += (int64_t)(G).Sg * GR_SLICE) \
+        for (int64_t pos = s0 + threadIdx.x; pos < min(end, s0 + GR_SLICE); pos += 256)
+
+__global__ __launch_bounds__(256) void k_grouped_claim(GroupedParams G) {
+    GROUPED_FOR_EACH_KEY(G) {
+        const uint32_t key = G.keys[pos];
+        int32_t sl = -1;
+        if (key != 0xFFFFFFFFu) {
+            const int64_t row = grouped_row(G, pbase, qpids, pos);
+            bool ok = (G.has[row >> 4] >> (row & 15)) & 1;
+            if (ok && G.mask) ok = (G.mask[row >> 4] >> (row & 15)) & 1;
+            if (ok) {
+                const unsigned long long v = (unsigned long long)G.rowval[row];
+                if (v == GR_EMPTY) {
+                    sl = (int32_t)G.tmask + 1;  // the value that looks like an empty slot has a slot of its own
+                } else {
+                    // linear probing; the table holds at least twice the values a query can meet, so an empty slot ends every chain.
+                    // At most T probes whatever happens: this loop cannot spin.
+                    uint32_t h = grouped_hash(v) & G.tmask;
+                    for (uint32_t n = 0; n <= G.tmask; n++) {
+                        unsigned long long cur = __hip_atomic_load(&G.tvals[tbase + h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (cur == GR_EMPTY) {
+                            cur = atomicCAS(&G.tvals[tbase + h], GR_EMPTY, v);
+                            if (cur == GR_EMPTY) cur = v;
+                        }
+                        if (cur == v) {
+                            sl = (int32_t)h;
+                            break;
+                        }
+                        h = (h + 1) & G.tmask;
+                    }
+                }
+                if (sl >= 0) atomicMin(&G.tkeys[tbase + sl], key);
+            }
+        }
+        G.slot[pos] = sl;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_grouped_minid(GroupedParams G) {
+    GROUPED_FOR_EACH_KEY(G) {
+        const int32_t sl = G.slot[pos];
+        if (sl < 0) continue;
+        if (G.keys[pos] != G.tkeys[tbase + sl]) continue;
+        const int64_t row = grouped_row(G, pbase, qpids, pos);
+        atomicMin(&G.tids[tbase + sl], (unsigned long long)G.ids[row]);  // (attribute ids are non-negative)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_grouped_rewrite(GroupedParams G) {
+    GROUPED_FOR_EACH_KEY(G) {
+        const int32_t sl = G.slot[pos];
+        const uint32_t key = G.keys[pos];
+        bool win = false;
+        if (sl >= 0 && key == G.tkeys[tbase + sl]) {
+            const int64_t row = grouped_row(G, pbase, qpids, pos);
+            win = (unsigned long long)G.ids[row] == G.tids[tbase + sl];
+        }
+        if (!win && key != 0xFFFFFFFFu) G.keys[pos] = 0xFFFFFFFFu;
+    }
+}
+
+// the value of every selected id; the padding id (negative) and -- it cannot happen -- an id without a value give 0
+__global__ __launch_bounds__(256) void k_grouped_values(AttrCol c, const int64_t *out_ids, int64_t n, int64_t *groups) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t raw = i < n ? out_ids[i] : -1;
+    const bool live[1] = {raw >= 0};
+    const int64_t id[1] = {live[0] ? raw : 0};
+    int64_t v[1];
+    bool has[1];
+    attr_lookup<1>(c, id, live, v, has);
+    if (i < n) groups[i] = has[0] ? v[0] : 0;
+}
+
+// an all-padding result (no list to scan)
+__global__ __launch_bounds__(256) void k_grouped_pad(int64_t n, float worst, int64_t *out_ids, float *out_dist, int64_t *groups) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out_ids[i] = -1;
+    if (out_dist) out_dist[i] = worst;
+    if (groups) groups[i] = 0;
+}
+
+// ---- the column's value of every arena row ------------------------------------------------------------------------------------
+struct RowvalParams {
+    const int64_t *ids;      // arena ids
+    const int64_t *pt_off;   // [npids] first arena row of every list
+    const int32_t *pt_size;  // [npids] rows, -1 = absent
+    AttrCol col;
+    int64_t *vals;           // [cap_rows]
+    uint16_t *has;           // [has_words]
+    int64_t cap_rows, has_words;
+};
+
+constexpr int RV_U = 4;  // rows in flight per lane (k_filter_build_where's choice)
+
+// k_filter_build_where's grid and writer rule: blockIdx.x = list, blockIdx.y strides over its chunks of RV_U x 16 tiles; the word of
+// a tile is the ballot of the 16 lanes that looked at its rows, stored by the first of them; rows behind a list's size keep 0
+__global__ __launch_bounds__(256) void k_grouped_rowvals(RowvalParams R) {
+    const int p = blockIdx.x;
+    const int size = R.pt_size[p];
+    if (size <= 0) return;
+    const int64_t row_off = R.pt_off[p];
+    const int ntl = (size + 15) >> 4;
+    const int lane = threadIdx.x & 63, j = lane & 15;
+    const int sub = threadIdx.x >> 4;  // tile of a 16-tile chunk
+    for (int t0 = blockIdx.y * 16 * RV_U; t0 < ntl; t0 += gridDim.y * 16 * RV_U) {
+        int64_t id[RV_U], v[RV_U];
+        bool ok[RV_U], has[RV_U];
+#pragma unroll
+        for (int u = 0; u < RV_U; u++) {
+            const int tile = t0 + u * 16 + sub;
+            const int row = tile * 16 + j;
+            ok[u] = tile < ntl && row < size && row_off + row < R.cap_rows;
+            id[u] = R.ids[row_off + (ok[u] ? row : 0)];
+        }
+        attr_lookup<RV_U>(R.col, id, ok, v, has);
+#pragma unroll
+        for (int u = 0; u < RV_U; u++) {
+            const int tile = t0 + u * 16 + sub;
+            const int row = tile * 16 + j;
+            if (ok[u]) R.vals[row_off + row] = has[u] ? v[u] : 0;
+            const uint64_t b = __ballot(ok[u] && has[u]);
+            const uint32_t word = (uint32_t)((b >> (16 * (lane >> 4))) & 0xFFFFull);
+            const int64_t w = (row_off >> 4) + tile;
+            if (j == 0 && tile < ntl && w < R.has_words) R.has[w] = (uint16_t)word;
+        }
+    }
+}
+
+// rv_vals / rv_has of the column brought up to date for the store as it is (the table has been synced) on ctx's stream
+int rowvals_ensure(qk_ctx *ctx, qk_store *s, qk_attr_data &d) {
+    hipStream_t st = ctx->stream;
+    const bool current = d.rv_built && d.rv_store_version == s->version && d.rv_cap_rows == s->cap_rows && d.rv_col_version == d.version;
+    if (current) {
+        if (d.rv_ctx != ctx) QK_HIP(hipStreamWaitEvent(st, d.rv_ev, 0));  // derived on another context's stream
+        return QK_OK;
+    }
+    const AttrCol col = col_of(d);
+    if (!col_usable(col)) QK_FAIL(QK_ERR_HIP, "grouped search: the column lost its device data in a failed update");
+    if (!d.rv_ev) QK_HIP(hipEventCreateWithFlags(&d.rv_ev, hipEventDisableTiming));
+    const int64_t rows = std::max<int64_t>(16, qk_round_up64(s->cap_rows, 16));
+    if (rows > d.rv_cap || !d.rv_vals) {
+        // (hipFree waits for the device: nothing still reads the old arrays)
+        if (d.rv_vals) hipFree(d.rv_vals);
+        if (d.rv_has) hipFree(d.rv_has);
+        d.rv_vals = nullptr;
+        d.rv_has = nullptr;
+        d.rv_cap = 0;
+        d.rv_built = false;
+        if (hipMalloc((void **)&d.rv_vals, (size_t)rows * 8) != hipSuccess || hipMalloc((void **)&d.rv_has, (size_t)(rows / 16) * 2) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d.rv_vals) hipFree(d.rv_vals);
+            d.rv_vals = nullptr;
+            d.rv_has = nullptr;
+            QK_FAIL(QK_ERR_OOM, "grouped search: no device memory for the values of %lld rows", (long long)rows);
+        }
+        d.rv_cap = rows;
+    }
+    // behind the column's last update and behind the readers of the previous derivation
+    if (d.updated && d.upd_stream != st) QK_HIP(hipStreamWaitEvent(st, d.upd_ev, 0));
+    if (d.rv_built && d.rv_ctx != ctx) QK_HIP(hipStreamWaitEvent(st, d.rv_ev, 0));
+    const int64_t has_words = d.rv_cap / 16;
+    QK_HIP(hipMemsetAsync(d.rv_has, 0, (size_t)has_words * 2, st));
+    const int64_t npids = (int64_t)s->parts.size();
+    if (npids > 0 && s->ntotal > 0) {
+        RowvalParams R;
+        R.ids = s->ids;
+        R.pt_off = s->d_off;
+        R.pt_size = s->d_size;
+        R.col = col;
+        R.vals = d.rv_vals;
+        R.has = d.rv_has;
+        R.cap_rows = std::min(s->cap_rows, d.rv_cap);
+        R.has_words = has_words;
+        const int64_t max_tiles = (std::max<int64_t>(1, s->max_size) + 15) / 16;
+        const unsigned gy = (unsigned)std::min<int64_t>(65535, (max_tiles + 16 * RV_U - 1) / (16 * RV_U));
+        hipLaunchKernelGGL(k_grouped_rowvals, dim3((unsigned)npids, gy), dim3(256), 0, st, R);
+        QK_HIP(hipGetLastError());
+    }
+    QK_HIP(hipEventRecord(d.rv_ev, st));
+    d.rv_built = true;
+    d.rv_ctx = ctx;
+    d.rv_store_version = s->version;
+    d.rv_cap_rows = s->cap_rows;
+    d.rv_col_version = d.version;
+    d.rv_builds++;
+    return QK_OK;
+}
+
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// slots of a query's table: a power of two, at least twice the distinct values a query can meet -- no more than the keys it can
+// have, no more than the ids that have a value
+int64_t table_slots(int64_t per_query_ub, int64_t n_ids) {
+    const int64_t distinct = std::max<int64_t>(1, std::min(per_query_ub, n_ids));
+    int64_t T = 16;
+    while (T < 2 * distinct) T <<= 1;
+    return T;
+}
+
+}  // namespace
+
+// bytes of a pass that one query accounts for (include/quake_hip.h, QK_GROUPED_PASS_BYTES): 8 per key it has room for -- the key and
+// its slot number -- and 20 per table slot
+static inline int64_t grouped_query_bytes(int64_t per_query_ub, int64_t T) { return per_query_ub * 8 + (T + 1) * 20; }
+
+int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data &col, const uint16_t *mask, int64_t *out_groups,
+                      qk_timing *timing, int64_t *n_passes) {
+    const int64_t Q = a.Q;
+    const int k = a.k;
+    hipStream_t st = ctx->stream;
+    const int npids = (int)s->parts.size();
+    const int P = a.all_lists ? npids : a.P;
+    *n_passes = 0;
+    qk_phase_events pe;
+    pe.ctx = ctx;
+    pe.tm = ctx->timing && timing;
+    pe.dtm = false;
+    pe.ev_base = 4;
+    QK_TRY(pe.mark(0));
+    if (P <= 0 || npids <= 0) {  // no lists: padding
+        QK_TRY(qk_prep_flush(ctx));
+        hipLaunchKernelGGL(k_grouped_pad, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, Q * k,
+                           a.metric == QK_METRIC_IP ? -INFINITY : INFINITY, a.out_ids, a.out_dist, out_groups);
+        QK_HIP(hipGetLastError());
+        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
+        return QK_OK;
+    }
+    int64_t per_query_ub;
+    int64_t qc = qk_emit_pass_queries(Q, P, s->max_size, &per_query_ub);
+    if (per_query_ub > ((int64_t)1 << 30))
+        QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: %d lists per query of up to %lld rows is too large", P, (long long)s->max_size);
+    const int64_t T = table_slots(per_query_ub, col.n_ids);
+    const int64_t qbytes = grouped_query_bytes(per_query_ub, T);
+    if (qbytes > QK_GROUPED_PASS_BYTES)
+        QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: one query needs %lld bytes of workspace, more than QK_GROUPED_PASS_BYTES", (long long)qbytes);
+    qc = std::max<int64_t>(1, std::min<int64_t>(qc, QK_GROUPED_PASS_BYTES / qbytes));
+    const int64_t S = (per_query_ub + GR_SLICE - 1) / GR_SLICE;
+    if (qc * S > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: Q too large");
+    const int nblk = s->nblk;
+    int kp = 2;  // (k_select_pairs_large keeps kp keys and kp ids in LDS, the ids behind the keys: kp >= 2 keeps them 8-byte aligned)
+    while (kp < k) kp <<= 1;
+    // one buffer for the whole call (the scan recycles ctx->ws; this one survives it), sized for the largest pass:
+    // [sizes] [pair_base] [keys] [slots] [table values] [table ids] [table keys]
+    const int64_t npairs_max = qc * P, nslots = qc * (T + 1);
+    const size_t o_sizes = 0, o_base = al256((size_t)(npairs_max + 1) * 8);
+    const size_t o_keys = o_base + al256((size_t)(npairs_max + 1) * 8);
+    const size_t o_slot = o_keys + al256((size_t)qc * per_query_ub * 4 + 256);
+    const size_t o_tvals = o_slot + al256((size_t)qc * per_query_ub * 4 + 256);
+    const size_t o_tids = o_tvals + (size_t)nslots * 8;
+    const size_t o_tkeys = o_tids + (size_t)nslots * 8;
+    const size_t o_end = o_tkeys + (size_t)nslots * 4;
+    QK_TRY(qk_aps_reserve(ctx, o_end + 256));
+    char *B = ctx->aps;
+    int64_t *sizes = (int64_t *)(B + o_sizes), *pair_base = (int64_t *)(B + o_base);
+    uint32_t *keys = (uint32_t *)(B + o_keys);
+    for (int64_t q0 = 0; q0 < Q; q0 += qc) {
+        const int64_t nq = std::min(qc, Q - q0);
+        const int64_t npairs = nq * P;
+        const int64_t *pids = a.pids ? a.pids + q0 * P : nullptr;
+        qk_launch_pair_offsets(ctx, s, pids, npairs, P, sizes, pair_base);
+        // every slot of the pass: value = empty, min key = min id = "nothing yet" 
+        QK_HIP(hipMemsetAsync(B + o_tvals, 0xFF, (size_t)nq * (T + 1) * 8, st));
+        QK_HIP(hipMemsetAsync(B + o_tids, 0xFF, (size_t)nq * (T + 1) * 8, st));
+        QK_HIP(hipMemsetAsync(B + o_tkeys, 0xFF, (size_t)nq * (T + 1) * 4, st));
+        if (q0 == 0) QK_TRY(pe.mark(1));
+        qk_scan_args e = a;
+        e.x = a.x + q0 * s->d;
+        e.xq4 = a.xq4 + q0 * nblk * 4;
+        e.xn = a.xn + q0;
+        e.Q = nq;
+        e.pids = pids;
+        e.k = 1;
+        e.key_out = keys;
+        e.pair_base = pair_base;
+        e.out_ids = nullptr;
+        e.out_dist = nullptr;
+        e.record_events = false;
+        QK_TRY(qk_scan_device(ctx, s, e, nullptr, 4));
+        if (q0 + qc >= Q) QK_TRY(pe.mark(2));
+        GroupedParams G;
+        G.keys = keys;
+        G.slot = (int32_t *)(B + o_slot);
+        G.pair_base = pair_base;
+        G.pids = pids;
+        G.pt_off = s->d_off;
+        G.ids = s->ids;
+        G.mask = mask;
+        G.has = col.rv_has;
+        G.rowval = col.rv_vals;
+        G.tvals = (unsigned long long *)(B + o_tvals);
+        G.tids = (unsigned long long *)(B + o_tids);
+        G.tkeys = (uint32_t *)(B + o_tkeys);
+        G.P = P;
+        G.tmask = (uint32_t)(T - 1);
+        // about 16384 workgroups per pass, whatever S is
+        G.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / nq));
+        const unsigned grid = (unsigned)(nq * G.Sg);
+        hipLaunchKernelGGL(k_grouped_claim, dim3(grid), dim3(256), 0, st, G);
+        hipLaunchKernelGGL(k_grouped_minid, dim3(grid), dim3(256), 0, st, G);
+        hipLaunchKernelGGL(k_grouped_rewrite, dim3(grid), dim3(256), 0, st, G);
+        QK_HIP(hipGetLastError());
+        QK_TRY(qk_launch_select_pairs(ctx, s, keys, pair_base, pids, nq, P, k, kp, a.metric, a.sqrt_l2, a.out_ids + q0 * k,
+                                      a.out_dist ? a.out_dist + q0 * k : nullptr));
+        (*n_passes)++;
+    }
+    if (out_groups) {
+        hipLaunchKernelGGL(k_grouped_values, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, col_of(col), (const int64_t *)a.out_ids,
+                           Q * k, out_groups);
+        QK_HIP(hipGetLastError());
+    }
+    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
+    ctx->last_scan_kernel = wide ? "k_scan_wide (grouped)" : "k_scan (grouped)";
+    QK_TRY(pe.mark(3));
+    return QK_OK;
+}
+
+namespace {
+
+// the body of both entry points: parent == nullptr && pids == nullptr -> every list
+int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+                int k, int metric, qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
+                qk_timing *timing) {
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    if (!group_by) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column is null", who);
+    qk_attr_data &col = *group_by->d;
+    if (col.store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column belongs to another store", who);
+    if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
+    if (k > QK_MAX_WIDE_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds %d", who, k, QK_MAX_WIDE_K);
+    if (Q < 0 || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
+    QK_TRY(qk_check_overflow(ctx));
+    QK_HIP(hipSetDevice(ctx->device));
+    if (timing) memset(timing, 0, sizeof(*timing));
+    if (Q == 0) return QK_OK;
+    hipStream_t st = ctx->stream;
+    const int d = s->d;
+    const bool use_parent = parent != nullptr;
+    int kk = 0;
+    if (use_parent) {
+        if (parent->d != d) QK_FAIL(QK_ERR_INVALID, "parent store dimension %d != store dimension %d", parent->d, d);
+        kk = (int)std::min<int64_t>(nprobe, parent->ntotal);
+        if (kk > QK_MAX_NPROBE) QK_FAIL(QK_ERR_UNSUPPORTED, "nprobe=%d exceeds QK_MAX_NPROBE=%d", kk, QK_MAX_NPROBE);
+    }
+    const int Ps = use_parent ? std::max(kk, 1) : P;
+    const bool sqrt_l2 = !ctx->squared_l2;
+    // ---- stage caller buffers ------------------------------------------------------------------------------------------------
+    const size_t bx = al256((size_t)Q * d * 4), bp = al256((size_t)Q * std::max(Ps, 1) * 8);
+    const size_t bi = al256((size_t)Q * k * 8), bd = al256((size_t)Q * k * 4);
+    const float *dx = x;
+    const int64_t *dpids = pids;
+    int64_t *dids = out_ids, *dgroups = out_groups;
+    float *ddist = out_dist;
+    if (mem == QK_MEM_HOST) {
+        QK_TRY(qk_stage_reserve(ctx, bx + bp + 2 * bi + bd + 256));
+        char *b = ctx->stage;
+        QK_HIP(hipMemcpyAsync(b, x, (size_t)Q * d * 4, hipMemcpyHostToDevice, st));
+        dx = (const float *)b;
+        b += bx;
+        if (!use_parent && pids) QK_HIP(hipMemcpyAsync(b, pids, (size_t)Q * P * 8, hipMemcpyHostToDevice, st));
+        if (use_parent || pids) dpids = (const int64_t *)b;
+        b += bp;
+        dids = (int64_t *)b;
+        b += bi;
+        dgroups = out_groups ? (int64_t *)b : nullptr;
+        b += bi;
+        ddist = out_dist ? (float *)b : nullptr;
+    } else if (use_parent) {
+        QK_TRY(qk_stage_reserve(ctx, bp + 256));
+        dpids = (const int64_t *)ctx->stage;
+    }
+    const float4 *xq4 = nullptr;
+    const float *xn = nullptr;
+    QK_TRY(qk_prep_queries(ctx, dx, Q, d, &xq4, &xn, 0, use_parent && kk == 1));
+    // ---- coarse: the unfiltered qk_search's ----------------------------------------------------------------------------------
+    if (use_parent && kk > 0) {
+        qk_scan_args ca;
+        ca.x = dx;
+        ca.xq4 = xq4;
+        ca.xn = xn;
+        ca.Q = Q;
+        ca.all_lists = true;
+        ca.k = kk;
+        ca.metric = metric;
+        ca.out_ids = (int64_t *)dpids;
+        ca.out_dist = nullptr;
+        ca.record_events = timing != nullptr;
+        QK_TRY(qk_scan_device(ctx, parent, ca, nullptr, 0));
+    } else if (use_parent) {  // empty parent: nothing to probe
+        QK_HIP(hipMemsetAsync((void *)dpids, 0xFF, (size_t)Q * 8, st));
+    }
+    // ---- row values and mask, then emission + reduction + selection -----------------------------------------------------------------
+    qk_scan_args sa;
+    sa.x = dx;
+    sa.xq4 = xq4;
+    sa.xn = xn;
+    sa.Q = Q;
+    sa.k = k;
+    sa.metric = metric;
+    sa.sqrt_l2 = sqrt_l2;
+    sa.out_ids = dids;
+    sa.out_dist = ddist;
+    if (!use_parent && !pids) {
+        sa.all_lists = true;
+    } else {
+        sa.pids = dpids;
+        sa.P = Ps;
+    }
+    const uint16_t *mask = nullptr;
+    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
+    QK_TRY(qk_store_sync_table(s));
+    QK_TRY(rowvals_ensure(ctx, s, col));
+    int64_t n_passes = 0;
+    QK_TRY(qk_grouped_device(ctx, s, sa, col, mask, dgroups, timing, &n_passes));
+    // ---- results back ------------------------------------------------------------------------------------------------------------
+    if (mem == QK_MEM_HOST) {
+        QK_HIP(hipMemcpyAsync(out_ids, dids, (size_t)Q * k * 8, hipMemcpyDeviceToHost, st));
+        if (out_groups) QK_HIP(hipMemcpyAsync(out_groups, dgroups, (size_t)Q * k * 8, hipMemcpyDeviceToHost, st));
+        if (out_dist) QK_HIP(hipMemcpyAsync(out_dist, ddist, (size_t)Q * k * 4, hipMemcpyDeviceToHost, st));
+        QK_HIP(hipStreamSynchronize(st));
+    }
+    if (timing) {
+        // the scalars of the wide-k path: no list statistics; n_items = the query passes of the call
+        QK_HIP(hipStreamSynchronize(st));
+        timing->n_items = n_passes;
+        if (ctx->timing) {
+            float ms = 0.f;
+            const bool have_coarse = use_parent && kk > 0;
+            if (have_coarse) {
+                QK_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
+                timing->coarse_ms = ms;
+            }
+            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+            timing->group_ms = ms;
+            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
+            timing->scan_ms = ms;
+            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
+            timing->merge_ms = ms;
+            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[have_coarse ? 0 : 4], ctx->ev[7]));
+            timing->total_ms = ms;
+        }
+    }
+    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
+    return QK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qk_search_grouped(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric, qk_attr *group_by,
+                      qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_search_grouped: null argument");
+    if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_grouped: nprobe must be positive");
+    return grouped_run("qk_search_grouped", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, group_by, filter, out_ids, out_dist, out_groups,
+                       mem, timing);
+}
+
+int qk_scan_grouped(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric, qk_attr *group_by,
+                    qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: null argument");
+    if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: bad partition id list");
+    return grouped_run("qk_scan_grouped", ctx, nullptr, s, x, Q, pids, P, 0, k, metric, group_by, filter, out_ids, out_dist, out_groups, mem,
+                       timing);
+}
+
+int qk_attr_group_info(qk_attr *a, int64_t *builds, int64_t *device_bytes) {
+    if (!a) QK_FAIL(QK_ERR_INVALID, "qk_attr_group_info: null column");
+    const qk_attr_data &d = *a->d;
+    if (builds) *builds = d.rv_builds;
+    if (device_bytes) *device_bytes = d.rv_vals ? d.rv_cap * 8 + d.rv_cap / 16 * 2 : 0;
+    return QK_OK;
+}
+
+}  // extern "C"

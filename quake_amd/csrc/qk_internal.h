@@ -412,6 +412,9 @@ static inline int64_t qk_emit_pass_queries(int64_t Q, int P, int64_t max_size, i
 }
 // the pair offsets both pipelines start a pass with (qk_dense.hip: k_pair_sizes + k_exclusive_scan_i64)
 void qk_launch_pair_offsets(qk_ctx *ctx, qk_store *s, const int64_t *pids, int64_t npairs, int P, int64_t *sizes, int64_t *pair_base);
+// the exact selection of the wide-k path over keys some other pipeline emitted (and rewrote): k_select_pairs_large, qk_dense.hip
+int qk_launch_select_pairs(qk_ctx *ctx, qk_store *s, const uint32_t *keys, const int64_t *pair_base, const int64_t *pids, int64_t nq, int P,
+                           int k, int kp, int metric, bool sqrt_l2, int64_t *out_ids, float *out_dist);
 // range search (qk_range.hip): every row of the probed lists whose key lies in [key_lo, key_hi] (and is a candidate of `mask`),
 // in scan order; `a` as for qk_widek_device (k unused).  lims [Q + 1], out_ids / out_dist [cap] on the device.
 int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask,

@@ -247,6 +247,17 @@ class RangeSearchResult:
         self.timing_info = None
 
 
+class GroupedSearchResult:
+    """extension (QuakeIndex.grouped_search): the k best groups of a column per query -- ids / distances [Q, k] of each group's best
+    vector, groups [Q, k] the group values (0 where ids is the padding id -1)"""
+
+    def __init__(self):
+        self.ids = None
+        self.distances = None
+        self.groups = None
+        self.timing_info = None
+
+
 _CONTEXTS = {}
 
 
@@ -674,6 +685,68 @@ class QuakeIndex:
         res.lims = lims if on_dev else lims.cpu()
         res.ids = ids if on_dev else ids.cpu()
         res.distances = dist if on_dev else dist.cpu()
+        return res
+
+    def grouped_search(self, x, group_by, search_params):
+        """extension (no reference counterpart): the search_params.k best GROUPS of the attribute column `group_by` among the vectors
+        of the search_params.nprobe nearest partitions, every group represented by its best vector (restricted to
+        search_params.filter if one is set: then by its best allowed vector).  A vector without a value in the column is no
+        candidate.  Exact; the values are those of the moment of the call.  Returns a GroupedSearchResult on x's device."""
+        self._require_built("[QuakeIndex::grouped_search()] No query coordinator. Did you build the index?")
+        sp = search_params
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
+                               "supported by grouped_search")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError("[QuakeIndex::grouped_search()] grouped_search is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::grouped_search()] grouped_search is not supported with num_workers > 0")
+        cols = self._attributes()
+        if group_by not in cols:
+            raise RuntimeError("[QuakeIndex::grouped_search()] unknown attribute column '%s'" % group_by)
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError("[QuakeIndex::grouped_search()] the filter was made for another index")
+            flt = flt._h
+        k = max(int(sp.k), 1)
+        res = GroupedSearchResult()
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        nq = 0 if x is None else int(x.shape[0])
+        if nq == 0:
+            res.ids = torch.empty((0, k), dtype=torch.int64)
+            res.distances = torch.empty((0, k), dtype=torch.float32)
+            res.groups = torch.empty((0, k), dtype=torch.int64)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        self._ctx.set_timing(1)
+        try:
+            ids, dist, groups, tm = self._ctx.search_grouped(self.parent._store if self.parent is not None else None, self._store, xd,
+                                                             nprobe, k, self.metric_, cols[group_by], filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(0)
+        ti.n_queries = nq
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.ids = ids if on_dev else ids.cpu()
+        res.distances = dist if on_dev else dist.cpu()
+        res.groups = groups if on_dev else groups.cpu()
         return res
 
     def make_filter(self, ids=None, exclude=False, where=None):
