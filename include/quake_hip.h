@@ -284,6 +284,41 @@ QK_API int qk_scan_filtered_batch(qk_ctx *ctx, qk_store *s, const float *x, int6
                                   qk_filter *const *filters, int F, const int32_t *qfilter, int64_t *out_ids, float *out_dist,
                                   int mem, qk_timing *timing);
 
+/* Adaptive probing: probe until min_candidates candidates.  A filtered search probes exactly nprobe lists, whatever its filter
+ * leaves in them; under a selective filter that is a short or poor row, and raising nprobe for the whole batch makes the least
+ * selective query pay for the most selective one.  Here every query probes the shortest prefix of its ranked lists that holds
+ * enough candidates of ITS filter.  The definition, per query q under its filter:
+ *   M = min(max_nprobe, lists of the parent), n0 = min(nprobe, M);
+ *   r_1 .. r_M: the lists the unfiltered coarse step (qk_coarse) ranks for q at nprobe = M; a -1 padding entry (a NaN centroid,
+ *     fewer than M lists) is a list of 0 rows;
+ *   c(p): the rows of list p that are candidates of q's filter.  Only the mask counts -- a property of the store and the filter,
+ *     not of the query: a row whose distance to q is NaN still counts;
+ *   nprobed(q): the smallest t in [n0, M] with c(r_1) + .. + c(r_t) >= min_candidates; M if there is none;
+ *   the result row of q is, bit for bit, the row qk_scan_filtered returns for q alone with pids = r_1 .. r_nprobed(q): the same
+ *     ids and distance bits, padded if those lists still hold fewer than k candidates.
+ * With max_nprobe == nprobe the call equals qk_search_filtered / qk_search_filtered_batch, bit for bit.
+ *   filters [F], qfilter [Q]: as for qk_search_filtered_batch; F == 1 && qfilter == NULL: filters[0] for every query.  A DEVICE
+ *     qfilter value outside [0, F): nprobed = 0, an all -1 probed row, an all-padding result (range checked before any table is
+ *     indexed); a HOST one: QK_ERR_INVALID.
+ *   out_nprobed int32 [Q], may be NULL; out_probed int64 [Q][M], may be NULL: r_1 .. r_nprobed(q), then -1 (what the policy's hit
+ *     tracker takes, like qk_search_tracked's buffer).  Both in `mem`.
+ * QK_ERR_INVALID: min_candidates < 1, max_nprobe < nprobe, nprobe < 1, parent == NULL (a flat index has nothing to adapt), and
+ * what qk_search_filtered_batch refuses.  QK_ERR_UNSUPPORTED: k > QK_MAX_K, M > QK_MAX_NPROBE, F > QK_MAX_BATCH_FILTERS.
+ * timing is filled as for qk_search_filtered; partitions_scanned counts the pairs actually scanned (present, non-empty lists
+ * of the prefixes), not Q * M; the cut itself lies between coarse_ms and group_ms and is part of total_ms only.
+ * Inside, one enqueue, no host wait and no atomics between the coarse step and the scan: the coarse step at M; per filter an
+ * int32 count per list number (k_filter_list_counts: a wave per list, the popcount of the mask words of its extent), kept on
+ * the filter, dropped by every mask build and derived again by the next ADAPTIVE call -- the other filtered calls neither
+ * allocate nor launch anything for it, qk_filter_info's device_bytes includes it once it exists; k_probe_trim, a wave per query:
+ * a prefix sum of the counts along the ranked row, -1 written over the tail; then the filtered scan of the calls above at
+ * P = M, which skips -1.  The per-query form reads the count pointer of filters[qfilter[q]] from a device table kept next to
+ * the mask table under the same rule.
+ * Out of scope: range search, grouped search, the device group and the sharded index probe a fixed nprobe under a filter. */
+QK_API int qk_search_filtered_adaptive(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe,
+                                       int max_nprobe, int64_t min_candidates, int k, int metric, qk_filter *const *filters, int F,
+                                       const int32_t *qfilter, int64_t *out_ids, float *out_dist, int32_t *out_nprobed,
+                                       int64_t *out_probed, int mem, qk_timing *timing);
+
 /* ---- range search --------------------------------------------------------------------------------
  * No reference counterpart (every search of the reference is a top-k): all rows of the probed lists within a radius of each query.
  * Lists: qk_range_search probes what the unfiltered qk_search probes -- the same min(nprobe, parent lists) lists in the same rank

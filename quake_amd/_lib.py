@@ -97,6 +97,8 @@ SIGNATURES = {
                                          _int, C.POINTER(QkTiming)]),
     "qk_scan_filtered_batch": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, C.POINTER(_vp), _int, _vp, _vp, _vp, _int,
                                C.POINTER(QkTiming)]),
+    "qk_search_filtered_adaptive": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _i64, _int, _int, C.POINTER(_vp), _int, _vp, _vp, _vp,
+                                    _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_range_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, _vp, _i64, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_range_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _i64, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_attr_create": (_int, [_vp, C.POINTER(_vp)]),

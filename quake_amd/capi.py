@@ -284,6 +284,34 @@ class Context:
         out_p = out_p[:, :width]
         return (out_i, out_d, out_p, timing_dict(t)) if timing else (out_i, out_d, out_p)
 
+    def search_adaptive(self, parent, store, x, nprobe, max_nprobe, k, metric, min_candidates=None, filter=None, filters=None,
+                        query_filter=None, probed=True, nprobed=True):
+        """qk_search_filtered_adaptive: every query probes the shortest prefix of its max_nprobe ranked lists, at least nprobe of
+        them, that holds min_candidates (default k) candidates of its filter.  filter, or filters + query_filter as in search().
+        Returns (ids, dist, nprobed, probed, timing): nprobed int32 [Q] (None with nprobed=False), probed int64
+        [Q, min(max_nprobe, parent lists)] -- the prefix, then -1 -- or None with probed=False."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        fb = _filter_batch(filter, filters, query_filter, x)
+        if fb is None:
+            harr, F, qf = (C.c_void_p * 1)(filter.h if filter is not None else None), 1, None
+        else:
+            harr, F, qf = fb
+        width = max(min(int(max_nprobe), int(parent.ntotal())), 0) if parent is not None else 0
+        out_i = _empty_like_mem((Q, k), np.int64, x)
+        out_d = _empty_like_mem((Q, k), np.float32, x)
+        out_n = _empty_like_mem((Q,), np.int32, x) if nprobed else None
+        out_p = _empty_like_mem((Q, max(width, 1)), np.int64, x) if probed else None
+        t = QkTiming()
+        check(self.lib.qk_search_filtered_adaptive(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe),
+                                                   int(max_nprobe), int(k if min_candidates is None else min_candidates), int(k),
+                                                   metric_code(metric), harr, F, _ptr(qf), _ptr(out_i), _ptr(out_d), _ptr(out_n),
+                                                   _ptr(out_p), mem, C.byref(t)))
+        if probed:
+            out_p = out_p[:, :width]
+        return out_i, out_d, out_n, out_p, timing_dict(t)
+
     # ---- range search ---------------------------------------------------------------------------------
     def _range(self, call, x, cap, timing, out):
         """the capacity protocol of qk_range_search / qk_range_scan around `call(cap, lims, ids, dist, timing)`: with cap=None a

@@ -217,6 +217,8 @@ PYBIND11_MODULE(_bindings, m) {
                 return py::cast(p.query_filter);
             },
             [](SearchParams &p, py::object v) { p.query_filter = v.is_none() ? Tensor() : v.cast<Tensor>(); })
+        .def_readwrite("max_nprobe", &SearchParams::max_nprobe)  // extension: adaptive probing under a filter; not in the summary
+        .def_readwrite("filter_min_candidates", &SearchParams::filter_min_candidates)
         .def("__repr__", [](const SearchParams &p) {  // wrap.cpp:173-186
             return Repr().kv("k", p.k).kv("nprobe", p.nprobe).kv("recall_target", p.recall_target).kv("batched_scan", p.batched_scan)
                 .kv("use_precomputed", p.use_precomputed).kv("initial_search_fraction", p.initial_search_fraction)
@@ -324,5 +326,12 @@ PYBIND11_MODULE(_bindings, m) {
         .def(py::init<>())
         .def_readwrite("ids", &SearchResult::ids)
         .def_readwrite("distances", &SearchResult::distances)
-        .def_readwrite("timing_info", &SearchResult::timing_info);
+        .def_readwrite("timing_info", &SearchResult::timing_info)
+        .def_property(
+            "nprobed",  // extension: int32 [Q] under SearchParams.max_nprobe, else None
+            [](const SearchResult &r) -> py::object {
+                if (!r.nprobed.defined()) return py::none();
+                return py::cast(r.nprobed);
+            },
+            [](SearchResult &r, py::object v) { r.nprobed = v.is_none() ? Tensor() : v.cast<Tensor>(); });
 }

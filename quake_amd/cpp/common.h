@@ -88,6 +88,12 @@ struct SearchParams {  // common.h:171-184
     // filters[query_filter[i]] (query_filter: integer tensor [Q]).  Given together, exclusive with `filter`
     std::vector<shared_ptr<SearchFilter>> filters;
     Tensor query_filter;
+    // extension, not part of the summary: adaptive probing under a filter -- with max_nprobe > nprobe every query probes the
+    // shortest prefix of its max_nprobe nearest partitions, at least nprobe of them, that holds filter_min_candidates (0 = k)
+    // candidates of its filter; 0 = off, max_nprobe == nprobe is the fixed call, a value below nprobe is refused.
+    // SearchResult::nprobed says how many each query probed
+    int max_nprobe = 0;
+    int64_t filter_min_candidates = 0;
 };
 
 struct BuildTimingInfo {  // common.h:189-198
@@ -119,6 +125,7 @@ struct SearchResult {  // common.h:243-247
     Tensor ids;
     Tensor distances;
     shared_ptr<SearchTimingInfo> timing_info;
+    Tensor nprobed;  // extension: int32 [Q] partitions probed per query under SearchParams::max_nprobe, else undefined
 };
 
 // extension (QuakeIndex::range_search): query i's hits are ids / distances [lims[i], lims[i+1]), in scan order

@@ -153,7 +153,42 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
         qflt = qf.to(xq.device(), torch::kInt32).contiguous();
     }
     const int F = (int)flts.size();
-    if (sp->recall_target > 0.0f && parent_ && !sp->batched_scan) {
+    if (sp->max_nprobe > 0) {
+        // adaptive probing under a filter (extension): the same branch, the same refusals
+        if (!flt && !F)
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.max_nprobe needs a filter (filter, or filters and "
+                                     "query_filter): without one every probed row is a candidate");
+        if (sp->recall_target > 0.0f)
+            throw std::runtime_error("[QuakeIndex::search()] max_nprobe cannot be combined with recall_target > 0 "
+                                     "(the recall model counts volume, not allowed rows): not supported");
+        if (group) throw std::runtime_error("[QuakeIndex::search()] max_nprobe is not supported with num_workers > 0");
+        if (sp->max_nprobe < nprobe)
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.max_nprobe=" + std::to_string(sp->max_nprobe) +
+                                     " is below nprobe=" + std::to_string(nprobe) + " (0 turns adaptive probing off)");
+    }
+    const bool adaptive = sp->max_nprobe > nprobe && parent_;  // (a flat index scans everything: nothing to adapt)
+    if (adaptive) {
+        // one enqueue: coarse step at max_nprobe, the cut of every query's row on the device, the filtered scan
+        const int M = (int)std::min<int64_t>(sp->max_nprobe, parent_->ntotal());
+        const auto dev = torch::TensorOptions().device(xq.device());
+        res->nprobed = torch::empty({Q}, dev.dtype(torch::kInt32));
+        Tensor pids;
+        if (track) pids = torch::empty({Q, std::max(M, 1)}, dev.dtype(torch::kInt64));
+        qk_filter *one[1] = {flt};
+        qk_check(qk_search_filtered_adaptive(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, sp->max_nprobe,
+                                             sp->filter_min_candidates > 0 ? sp->filter_min_candidates : (int64_t)k, k, (int)metric_,
+                                             F ? flts.data() : one, F ? F : 1, F ? qflt.data_ptr<int32_t>() : nullptr,
+                                             res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(),
+                                             res->nprobed.data_ptr<int32_t>(), track ? pids.data_ptr<int64_t>() : nullptr, mem, tmp));
+        if (track) {  // (the rows end in -1: record_query_batch skips those)
+            if (M < 1) pids = pids.slice(1, 0, 0);
+            maintenance_policy_->record_query_batch_later(pids);
+        }
+        ti->partitions_scanned = (int)tm.partitions_scanned;
+        ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+        ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+        ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    } else if (sp->recall_target > 0.0f && parent_ && !sp->batched_scan) {
         // adaptive partition scanning (:502,637-641): candidates = nlist * initial_search_fraction; with workers the rounds run on
         // the group's lead and every member scans the pairs whose partitions it holds (the APS hook of worker_scan, :364-428)
         Tensor nscan = torch::empty({Q}, torch::TensorOptions().dtype(torch::kInt32).device(xq.device()));

@@ -62,7 +62,7 @@ int check_metric(int metric) {
 // `timing` are requested but read later, by qk_finish_timing, once every member of the group has been enqueued.
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
-                  bool defer_finish, int64_t *probed_out, qk_filter *filter, const qk_filter_batch *fbatch) {
+                  bool defer_finish, int64_t *probed_out, qk_filter *filter, const qk_filter_batch *fbatch, const qk_adaptive *adaptive) {
     QK_TRY(qk_check_overflow(ctx));  // a record-buffer overflow of an earlier launch is reported by the next call
     QK_HIP(hipSetDevice(ctx->device));
     if (timing) memset(timing, 0, sizeof(*timing));
@@ -81,6 +81,8 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
     // ---- stage caller buffers ------------------------------------------------------------------------
     size_t bx = al256((size_t)Q * d * 4), bp = al256((size_t)Q * std::max(Ps, 1) * 8);
     size_t bi = al256((size_t)Q * std::max(kout, 1) * 8), bd = al256((size_t)Q * std::max(kout, 1) * 4);
+    const size_t bn = adaptive && adaptive->out_nprobed ? al256((size_t)Q * 4) : 0;  // (adaptive probing: nprobed [Q] of a host caller)
+    int32_t *d_nprobed = adaptive ? adaptive->out_nprobed : nullptr;
     Staged sv;
     // host buffers through the context's pinned staging (qk_internal.h, pin_io) up to 64 MB per call; larger calls transfer directly
     char *pin = nullptr;
@@ -107,7 +109,7 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
         }
     }
     if (mem == QK_MEM_HOST) {
-        QK_TRY(qk_stage_reserve(ctx, bx + bp + bi + bd + 256));
+        QK_TRY(qk_stage_reserve(ctx, bx + bp + bi + bd + bn + 256));
         char *b = ctx->stage;
         const void *hx = x;
         if (pin) {
@@ -130,6 +132,7 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
         sv.out_ids = (int64_t *)b;
         b += bi;
         sv.out_dist = out_dist ? (float *)b : nullptr;  // (no distances asked for: none computed -- the kernels take NULL)
+        if (bn) d_nprobed = (int32_t *)(b + bd);
     } else {
         sv.x = x;
         sv.out_ids = out_ids;
@@ -205,7 +208,7 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
         ca.out_ids = coarse_only ? sv.out_ids : (int64_t *)sv.pids;
         ca.out_dist = coarse_only ? sv.out_dist : nullptr;
         ca.record_events = timing != nullptr;
-        if (!coarse_only && kk == 1 && k <= QK_MAX_K && !probed_out) ca.packed_out = &packed;  // nprobe = 1: see qk_scan_args::pids_packed
+        if (!coarse_only && kk == 1 && k <= QK_MAX_K && !probed_out && !adaptive) ca.packed_out = &packed;  // nprobe = 1: see qk_scan_args::pids_packed
         QK_TRY(qk_scan_device(ctx, parent, ca, coarse_only ? timing : nullptr, 0));
     }
     // ---- scan ------------------------------------------------------------------------------------------
@@ -251,6 +254,18 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
                 sa.qfilter = ctx->fb_qfilter;
             }
         }
+        // adaptive probing: the coarse step above ranked M = kk lists per query; k_probe_trim cuts every row to the shortest prefix
+        // that holds min_candidates candidates of its filter (-1 over the rest: the scan skips those), on the device, between the two
+        if (adaptive && kk > 0) {
+            const int32_t *counts = nullptr;
+            const int32_t *const *ctable = nullptr;
+            if (filter) QK_TRY(qk_filter_counts_ensure(ctx, s, filter, &counts));
+            else QK_TRY(qk_filter_batch_counts_ensure(ctx, s, fbatch->filters, fbatch->F, &ctable));
+            QK_TRY(qk_launch_probe_trim(ctx, s, (int64_t *)sv.pids, Q, kk, std::min(adaptive->nprobe, kk), adaptive->min_candidates, counts,
+                                        ctable, sa.qfilter, sa.F, d_nprobed));
+        } else if (adaptive && d_nprobed) {
+            QK_HIP(hipMemsetAsync(d_nprobed, 0, (size_t)Q * sizeof(int32_t), ctx->stream));
+        }
         if (use_parent && kk <= 0) {  // empty parent: nothing to probe -> padding only
             QK_HIP(hipMemsetAsync((void *)sv.pids, 0xFF, (size_t)Q * 8, ctx->stream));
             sa.P = 1;
@@ -263,6 +278,7 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
         if (out_ids) QK_HIP(hipMemcpyAsync(pin ? (void *)(pin + pin_i) : (void *)out_ids, sv.out_ids, (size_t)Q * kout * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (out_dist) QK_HIP(hipMemcpyAsync(pin ? (void *)(pin + pin_d) : (void *)out_dist, sv.out_dist, (size_t)Q * kout * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (pr) QK_HIP(hipMemcpyAsync(pin ? (void *)(pin + pin_pr) : (void *)probed_out, sv.pids, (size_t)Q * kk * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (bn) QK_HIP(hipMemcpyAsync(adaptive->out_nprobed, d_nprobed, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         QK_HIP(hipStreamSynchronize(ctx->stream));
         if (pin && out_ids) memcpy(out_ids, pin + pin_i, (size_t)Q * kout * 8);
         if (pin && out_dist) memcpy(out_dist, pin + pin_d, (size_t)Q * kout * 4);

@@ -138,6 +138,14 @@ struct qk_filter {
     unsigned long long *d_allowed = nullptr;  // [1] candidates of the last build
     hipEvent_t built_ev = nullptr;            // behind the last build, on the stream that ran it
     qk_ctx *built_ctx = nullptr;
+    // adaptive probing (qk_search_filtered_adaptive): candidates per LIST NUMBER of the store -- the popcount of the mask words of
+    // the list's extent -- derived from the mask by the first adaptive call behind a mask build (every build drops them), on that
+    // call's stream; nobody else allocates or reads them
+    int32_t *counts = nullptr;  // [counts_cap]
+    int64_t counts_cap = 0;
+    bool counts_built = false;
+    hipEvent_t counts_ev = nullptr;  // behind the last derivation, on the stream of counts_ctx
+    qk_ctx *counts_ctx = nullptr;
 };
 
 // qk_filter.hip

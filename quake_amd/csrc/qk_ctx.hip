@@ -68,6 +68,7 @@ int qk_ctx_destroy(qk_ctx *c) {
     if (c->aps_table) hipFree(c->aps_table);
     if (c->aps_rowof) hipFree(c->aps_rowof);
     if (c->fb_table) hipFree((void *)c->fb_table);
+    if (c->fb_ctable) hipFree((void *)c->fb_ctable);
     if (c->fb_union) hipFree(c->fb_union);
     if (c->fb_qfilter) hipFree(c->fb_qfilter);
     if (c->xcd_host) hipHostFree(c->xcd_host);

@@ -128,6 +128,7 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     QK_HIP(hipEventRecord(f->built_ev, st));
     if (f->built) f->rebuilds++;
     f->built = true;
+    f->counts_built = false;  // (adaptive probing: re-derived by the next call that needs them)
     f->built_ctx = ctx;
     f->version = s->version;
     f->cap_rows = s->cap_rows;
@@ -164,7 +165,148 @@ __global__ __launch_bounds__(256) void k_filter_union(const uint16_t *const *mas
     out[w] = (uint16_t)acc;
 }
 
+// ---- adaptive probing: candidates per list, and the cut of every query's ranked lists ---------------------------------------------
+// counts[p] = candidates of list number p: the popcount of the mask words of its extent (rows behind its size keep the 0 of the
+// build's memset; an absent or empty list has 0).  One wave per list, lanes on consecutive 16-bit words, a shuffle reduction:
+// every counts[p] has one writer.
+__global__ __launch_bounds__(256) void k_filter_list_counts(const uint16_t *mask, int64_t mask_words, const int64_t *pt_off,
+                                                            const int32_t *pt_size, int npids, int32_t *counts) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= npids) return;  // (the whole wave)
+    const int size = pt_size[p];
+    int n = 0;
+    if (size > 0) {
+        const int64_t w0 = pt_off[p] >> 4;
+        const int ntl = (size + 15) >> 4;
+        for (int t = lane; t < ntl; t += 64) {
+            const int64_t w = w0 + t;
+            if (w < mask_words) n += __popc((uint32_t)mask[w]);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off);
+    if (lane == 0) counts[p] = n;
+}
+
+// One wave per query over its row of M ranked list numbers: nprobed = the smallest t in [n0, M] whose first t lists hold
+// min_candidates candidates of the query's filter (M if none does), -1 over the rest of the row.  Chunks of 64 lists: a gather of
+// counts[pid] (-1 and numbers the store does not know: 0), an inclusive prefix sum over the wave carried from chunk to chunk, a
+// ballot for the first lane that is there.  A qfilter value outside [0, F) is checked before the table is indexed: nprobed = 0.
+__global__ __launch_bounds__(256) void k_probe_trim(int64_t *pids, int64_t Q, int M, int n0, long long minc, const int32_t *counts,
+                                                    const int32_t *const *ctable, const int32_t *qfilter, int F, int npids,
+                                                    int32_t *nprobed) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q) return;  // (the whole wave)
+    const int32_t *cnt = counts;
+    bool live = true;
+    if (ctable) {
+        const int f = qfilter[q];
+        live = (unsigned)f < (unsigned)F;
+        cnt = live ? ctable[f] : nullptr;
+    }
+    int64_t *row = pids + q * (int64_t)M;
+    int t = live ? M : 0;
+    if (live) {
+        long long carry = 0;
+        for (int c0 = 0; c0 < M; c0 += 64) {
+            const int i = c0 + lane;
+            long long v = 0;
+            if (i < M) {
+                const int64_t p = row[i];
+                if (p >= 0 && p < (int64_t)npids) v = cnt[p];
+            }
+            for (int off = 1; off < 64; off <<= 1) {
+                const long long u = __shfl_up(v, off);
+                if (lane >= off) v += u;
+            }
+            v += carry;
+            const uint64_t b = __ballot(i < M && i + 1 >= n0 && v >= minc);
+            if (b) {  // (the same for every lane)
+                t = c0 + __ffsll((unsigned long long)b);
+                break;
+            }
+            carry = __shfl(v, 63);
+        }
+    }
+    for (int i = t + lane; i < M; i += 64) row[i] = -1;
+    if (lane == 0 && nprobed) nprobed[q] = t;
+}
+
 }  // namespace
+
+int qk_filter_counts_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const int32_t **counts) {
+    hipStream_t st = ctx->stream;
+    const int64_t npids = (int64_t)s->parts.size();
+    if (!f->counts_ev) QK_HIP(hipEventCreateWithFlags(&f->counts_ev, hipEventDisableTiming));
+    if (npids > f->counts_cap || !f->counts) {
+        // (a trim in flight on some context may still read the old array: hipFree waits for the device)
+        if (f->counts) QK_HIP(hipFree(f->counts));
+        f->counts = nullptr;
+        f->counts_cap = 0;
+        f->counts_built = false;
+        const int64_t cap = std::max<int64_t>(npids + npids / 4, 64);
+        if (hipMalloc((void **)&f->counts, (size_t)cap * sizeof(int32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            QK_FAIL(QK_ERR_OOM, "qk_filter: no memory for the candidate counts of %lld lists", (long long)cap);
+        }
+        f->counts_cap = cap;
+    }
+    if (!f->counts_built) {
+        // behind the mask (built on this stream, or waited for by filter_current) and behind the last derivation on another
+        // context.  counts_ev covers derivations only, not the trims that read the array: like the mask's built_ev it relies on
+        // the rule of the header that nobody changes the store while searches are in flight
+        if (f->counts_ctx && f->counts_ctx != ctx) QK_HIP(hipStreamWaitEvent(st, f->counts_ev, 0));
+        if (npids > 0) {
+            hipLaunchKernelGGL(k_filter_list_counts, dim3((unsigned)((npids + 3) / 4)), dim3(256), 0, st, (const uint16_t *)f->mask,
+                               f->mask_words, (const int64_t *)s->d_off, (const int32_t *)s->d_size, (int)npids, f->counts);
+            QK_HIP(hipGetLastError());
+        }
+        QK_HIP(hipEventRecord(f->counts_ev, st));
+        f->counts_built = true;
+        f->counts_ctx = ctx;
+    } else if (f->counts_ctx != ctx) {
+        QK_HIP(hipStreamWaitEvent(st, f->counts_ev, 0));  // derived on another context's stream
+    }
+    *counts = f->counts;
+    return QK_OK;
+}
+
+int qk_filter_batch_counts_ensure(qk_ctx *ctx, qk_store *s, qk_filter *const *filters, int F, const int32_t *const **ctable) {
+    std::vector<const int32_t *> h((size_t)F);
+    for (int i = 0; i < F; i++) QK_TRY(qk_filter_counts_ensure(ctx, s, filters[i], &h[i]));
+    // the rule of the mask table: its key (the masks are current: qk_filter_batch_ensure ran), and every count pointer
+    std::vector<uint64_t> key = ctx->fb_key;
+    for (int i = 0; i < F; i++) key.push_back((uint64_t)(uintptr_t)h[i]);
+    if (key != ctx->fb_ckey || !ctx->fb_ctable) {
+        ctx->fb_ckey.clear();
+        if (F > ctx->fb_ctable_cap || !ctx->fb_ctable) {
+            if (ctx->fb_ctable) QK_HIP(hipFree((void *)ctx->fb_ctable));
+            ctx->fb_ctable = nullptr;
+            ctx->fb_ctable_cap = 0;
+            const int64_t cap = std::max<int64_t>(F, 64);
+            if (hipMalloc((void **)&ctx->fb_ctable, (size_t)cap * sizeof(int32_t *)) != hipSuccess) {
+                (void)hipGetLastError();
+                QK_FAIL(QK_ERR_OOM, "filtered search: no memory for a table of %lld count arrays", (long long)cap);
+            }
+            ctx->fb_ctable_cap = cap;
+        }
+        // (pageable source: copied out when the call returns)
+        QK_HIP(hipMemcpyAsync((void *)ctx->fb_ctable, h.data(), (size_t)F * sizeof(int32_t *), hipMemcpyHostToDevice, ctx->stream));
+        ctx->fb_ckey = std::move(key);
+    }
+    *ctable = (const int32_t *const *)ctx->fb_ctable;
+    return QK_OK;
+}
+
+int qk_launch_probe_trim(qk_ctx *ctx, qk_store *s, int64_t *pids, int64_t Q, int M, int n0, int64_t min_candidates, const int32_t *counts,
+                         const int32_t *const *ctable, const int32_t *qfilter, int F, int32_t *nprobed) {
+    if (Q <= 0 || M <= 0) return QK_OK;
+    hipLaunchKernelGGL(k_probe_trim, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, ctx->stream, pids, Q, M, n0, (long long)min_candidates,
+                       counts, ctable, qfilter, F, (int)s->parts.size(), nprobed);
+    QK_HIP(hipGetLastError());
+    return QK_OK;
+}
 
 int qk_filter_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const uint16_t **mask) {
     QK_TRY(filter_belongs(ctx, s, f));
@@ -295,7 +437,9 @@ int qk_filter_destroy(qk_filter *f) {
         hipEventSynchronize(f->built_ev);
         hipEventDestroy(f->built_ev);
     }
+    if (f->counts_ev) hipEventDestroy(f->counts_ev);
     if (f->mask) hipFree(f->mask);  // (hipFree waits for the device: no scan still reads the mask)
+    if (f->counts) hipFree(f->counts);
     if (f->d_ids) hipFree(f->d_ids);
     if (f->d_allowed) hipFree(f->d_allowed);
     (void)hipGetLastError();
@@ -318,6 +462,7 @@ int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t
     if (device_bytes) {
         if (f->kind == QK_FILTER_KIND_WHERE) *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t));  // (no ids: the mask only)
         else *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t) + std::max<int64_t>(f->n_ids, 1) * sizeof(int64_t) + 8);
+        *device_bytes += (int64_t)(f->counts_cap * sizeof(int32_t));  // (adaptive probing: once a call has derived them)
     }
     return QK_OK;
 }
@@ -415,6 +560,37 @@ int qk_scan_filtered_batch(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, 
     }
     const qk_filter_batch fb{filters, F, qfilter};
     return qk_run_search(ctx, nullptr, s, x, Q, pids, P, 0, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, nullptr, &fb);
+}
+
+// ---- adaptive probing ----------------------------------------------------------------------------------------------------------
+int qk_search_filtered_adaptive(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int max_nprobe,
+                                int64_t min_candidates, int k, int metric, qk_filter *const *filters, int F, const int32_t *qfilter,
+                                int64_t *out_ids, float *out_dist, int32_t *out_nprobed, int64_t *out_probed, int mem, qk_timing *timing) {
+    const char *who = "qk_search_filtered_adaptive";
+    if (!ctx || !s || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
+    if (!parent) QK_FAIL(QK_ERR_INVALID, "%s: parent is null (a flat index has nothing to adapt)", who);
+    const bool one = F == 1 && !qfilter;  // one filter for every query
+    if (one) {
+        if (!filters || !filters[0]) QK_FAIL(QK_ERR_INVALID, "%s: null filter", who);
+        if (k <= 0) QK_FAIL(QK_ERR_INVALID, "%s: k must be positive", who);
+        if (k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds QK_MAX_K=%d (filtered search has no wide-k path)", who, k, QK_MAX_K);
+    } else {
+        QK_TRY(check_filter_batch(who, filters, F, qfilter, Q, k, mem));
+    }
+    if (nprobe < 1) QK_FAIL(QK_ERR_INVALID, "%s: nprobe must be positive", who);
+    if (max_nprobe < nprobe) QK_FAIL(QK_ERR_INVALID, "%s: max_nprobe=%d < nprobe=%d", who, max_nprobe, nprobe);
+    if (min_candidates < 1) QK_FAIL(QK_ERR_INVALID, "%s: min_candidates must be positive", who);
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    qk_adaptive ad;
+    ad.nprobe = nprobe;
+    ad.min_candidates = min_candidates;
+    ad.out_nprobed = out_nprobed;
+    if (one)
+        return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, max_nprobe, k, metric, out_ids, out_dist, mem, timing, false, false, out_probed,
+                             filters[0], nullptr, &ad);
+    const qk_filter_batch fb{filters, F, qfilter};
+    return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, max_nprobe, k, metric, out_ids, out_dist, mem, timing, false, false, out_probed,
+                         nullptr, &fb, &ad);
 }
 
 }  // extern "C"

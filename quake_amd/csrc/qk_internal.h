@@ -184,6 +184,12 @@ struct qk_ctx {
     int64_t fb_union_words = 0;
     int32_t *fb_qfilter = nullptr;        // [fb_qfilter_cap] device copy of a host qfilter
     int64_t fb_qfilter_cap = 0;
+    // adaptive probing with one filter per query (qk_filter_batch_counts_ensure): the device table of the F per-list count arrays,
+    // next to fb_table and under the same rule -- valid while fb_ckey, the fb_key of the call that uploaded it plus every count
+    // pointer, is what the next adaptive call brings
+    std::vector<uint64_t> fb_ckey;
+    const int32_t **fb_ctable = nullptr;  // [fb_ctable_cap]
+    int64_t fb_ctable_cap = 0;
 };
 
 int qk_ws_reserve(qk_ctx *ctx, size_t bytes);          // make sure the workspace can hold `bytes` (may sync+realloc)
@@ -335,6 +341,21 @@ struct qk_filter_batch {
 // every one of the F masks brought up to date like qk_filter_ensure does (one table sync), then the device table of the F mask
 // pointers and the OR of the masks, both kept on the context and reused while the filters and the store are unchanged
 int qk_filter_batch_ensure(qk_ctx *ctx, qk_store *s, qk_filter *const *filters, int F, const uint16_t *const **table, const uint16_t **uni);
+// adaptive probing (qk_search_filtered_adaptive; the definition is in include/quake_hip.h): what the call adds to a filtered
+// search with nprobe = max_nprobe.  out_nprobed lives in the call's `mem` like the other buffers, or is nullptr.
+struct qk_adaptive {
+    int nprobe = 0;               // n0 before the clamp to M
+    int64_t min_candidates = 0;
+    int32_t *out_nprobed = nullptr;
+};
+// the per-list candidate counts of a filter whose mask the caller has just brought up to date on ctx's stream (qk_filter_ensure),
+// derived behind it if that mask is newer than they are
+int qk_filter_counts_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, const int32_t **counts);
+// the same for the F filters of a per-query call behind qk_filter_batch_ensure, and the device table of the F count pointers
+int qk_filter_batch_counts_ensure(qk_ctx *ctx, qk_store *s, qk_filter *const *filters, int F, const int32_t *const **ctable);
+// k_probe_trim on ctx's stream, in place on pids [Q][M] (device): one of counts / (ctable, qfilter, F) is given; nprobed [Q] or nullptr
+int qk_launch_probe_trim(qk_ctx *ctx, qk_store *s, int64_t *pids, int64_t Q, int M, int n0, int64_t min_candidates, const int32_t *counts,
+                         const int32_t *const *ctable, const int32_t *qfilter, int F, int32_t *nprobed);
 // x[Q][d] -> ctx->qprep (xq4 then xn); returns the two device pointers
 // zero_bytes > 0: the kernel also clears that many bytes for the scan of this batch (qk_scan_zero_bytes)
 int qk_prep_queries(qk_ctx *ctx, const float *x, int64_t Q, int d, const float4 **xq4, const float **xn, size_t zero_bytes = 0,
@@ -353,7 +374,8 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
 // the body of qk_coarse / qk_scan / qk_search (qk_api.hip) and the read-back of its scalars; see there
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
-                  bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr, const qk_filter_batch *fbatch = nullptr);
+                  bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr, const qk_filter_batch *fbatch = nullptr,
+                  const qk_adaptive *adaptive = nullptr);
 int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, int scan_ev_base);
 // adaptive (recall-target) search: the rounds run on `ctx`; a round's (query, list) pairs are scanned by `scan` (qk_aps.hip)
 struct qk_aps_round {

@@ -124,6 +124,12 @@ class SearchParams(_Summary):  # common.h:171-184, wrap.cpp:153-186
         # shape [Q]; query i sees the candidates of filters[query_filter[i]].  Given together, exclusive with `filter`
         self.filters = []
         self.query_filter = None
+        # extension (not part of the summary): adaptive probing under a filter -- with max_nprobe > nprobe every query probes the
+        # shortest prefix of its max_nprobe nearest partitions, at least nprobe of them, that holds filter_min_candidates
+        # (0 = k) candidates of its filter; 0 = off, max_nprobe == nprobe is the fixed call, a value below nprobe is refused.
+        # SearchResult.nprobed says how many each query probed
+        self.max_nprobe = 0
+        self.filter_min_candidates = 0
 
 
 class SearchFilter:
@@ -235,6 +241,7 @@ class SearchResult:  # common.h:243-247
         self.ids = None
         self.distances = None
         self.timing_info = None
+        self.nprobed = None  # extension: int32 [Q] partitions probed per query under SearchParams.max_nprobe, else None
 
 
 class RangeSearchResult:
@@ -565,6 +572,22 @@ class QuakeIndex:
             if not qflt.is_cuda and qflt.numel() > 0 and (int(qflt.min()) < 0 or int(qflt.max()) >= len(flts)):
                 raise RuntimeError("[QuakeIndex::search()] SearchParams.query_filter holds a value outside [0, %d)" % len(flts))
             fb = dict(filters=[f._h for f in flts], query_filter=qflt.to(device=xd.device, dtype=torch.int32))
+        nprobe = max(int(search_params.nprobe), 1)
+        max_nprobe = int(getattr(search_params, "max_nprobe", 0) or 0)
+        if max_nprobe > 0:
+            # adaptive probing under a filter (extension): the same branch, the same refusals
+            if flt is None and not fb:
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.max_nprobe needs a filter (filter, or filters and "
+                                   "query_filter): without one every probed row is a candidate")
+            if search_params.recall_target is not None and search_params.recall_target > 0.0:
+                raise RuntimeError("[QuakeIndex::search()] max_nprobe cannot be combined with recall_target > 0 "
+                                   "(the recall model counts volume, not allowed rows): not supported")
+            if grp is not None:
+                raise RuntimeError("[QuakeIndex::search()] max_nprobe is not supported with num_workers > 0")
+            if max_nprobe < nprobe:
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.max_nprobe=%d is below nprobe=%d (0 turns adaptive "
+                                   "probing off)" % (max_nprobe, nprobe))
+        adaptive = max_nprobe > nprobe and self.parent is not None  # (a flat index scans everything: nothing to adapt)
         if grp is not None:
             grp.set_stream(torch.cuda.current_stream(grp.device).cuda_stream)  # the lead's stream (see _context)
         if use_aps:
@@ -590,10 +613,21 @@ class QuakeIndex:
             res.ids = ids if on_dev else ids.cpu()
             res.distances = dist if on_dev else dist.cpu()
             return res
-        nprobe = max(int(search_params.nprobe), 1)
         self._ctx.set_timing(1)
         try:
-            if self.track_hits and self.parent is not None:
+            if adaptive:
+                # one enqueue: coarse step at max_nprobe, the cut of every query's row on the device, the filtered scan
+                mc = int(getattr(search_params, "filter_min_candidates", 0) or 0)
+                ids, dist, res.nprobed, pids, tm = self._ctx.search_adaptive(
+                    self.parent._store, self._store, xd, nprobe, max_nprobe, int(k), self.metric_,
+                    min_candidates=mc if mc > 0 else int(k), filter=flt, probed=bool(self.track_hits), **fb)
+                if not on_dev:
+                    res.nprobed = res.nprobed.cpu()
+                if self.track_hits:  # (the rows end in -1: record_query_hits skips those)
+                    self._pending_hits.append(pids)
+                    if len(self._pending_hits) >= 64:
+                        self._flush_hits()
+            elif self.track_hits and self.parent is not None:
                 # hit tracking for maintenance(): the probed partitions are needed by the policy (later, on the host)
                 if grp is not None:
                     pids, _ = self._ctx.coarse(self.parent._store, xd, nprobe, self.metric_, values=False)
@@ -612,7 +646,8 @@ class QuakeIndex:
         finally:
             self._ctx.set_timing(0)
         ti.n_queries = int(x.shape[0])
-        ti.partitions_scanned = int(tm["n_items"])
+        # (adaptive probing: the (query, partition) pairs actually scanned, as the compiled mirror reports them)
+        ti.partitions_scanned = int(tm["partitions_scanned"] if adaptive else tm["n_items"])
         ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
         ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
         ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)

@@ -40,6 +40,9 @@ def corpus(ctx, n, d, nlist, metric, seed):
     if metric == "ip":
         x /= x.norm(dim=1, keepdim=True)
     lists = x[torch.randperm(n, device="cuda", generator=g)[:nlist]].contiguous()
+    # the context runs on its own stream: everything torch has enqueued so far -- the rows it is about to read, and the randperm
+    # whose freed block `a` may be given -- must be done before the library call (it returns synchronised)
+    torch.cuda.synchronize()
     a = ctx.kmeans_assign_only(x, lists, metric)
     order = torch.argsort(a, stable=True)
     sizes = torch.bincount(a, minlength=nlist).cpu().numpy().astype(np.int64)
@@ -51,6 +54,7 @@ def corpus(ctx, n, d, nlist, metric, seed):
     vecs = x[order].contiguous()
     del x
     ids = torch.arange(n, device="cuda", dtype=torch.int64)
+    torch.cuda.synchronize()  # (as above: build_csr reads vecs and ids on the context's stream)
     s = Store(ctx, d)
     s.build_csr(offsets, ids, vecs)
     parent = Store(ctx, d)
