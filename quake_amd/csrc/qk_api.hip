@@ -18,8 +18,6 @@ struct Staged {  // device-side views of the caller's buffers for one call
     float *out_dist = nullptr;
 };
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // read back phase timings (events) and device scalars after the stream has drained
@@ -32,21 +30,24 @@ int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, i
     int64_t rows_unique;
     memcpy(&rows_unique, hs + 2, sizeof(int64_t));
     t->scan_bytes = rows_unique * (int64_t)s->d * 4;
-    if (ctx->timing) {
-        float ms = 0.f;
-        if (have_coarse) {
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
-            t->coarse_ms = ms;
-        }
-        QK_HIP(hipEventElapsedTime(&ms, ctx->ev[scan_ev_base + 0], ctx->ev[scan_ev_base + 1]));
-        t->group_ms = ms;
-        QK_HIP(hipEventElapsedTime(&ms, ctx->ev[scan_ev_base + 1], ctx->ev[scan_ev_base + 2]));
-        t->scan_ms = ms;
-        QK_HIP(hipEventElapsedTime(&ms, ctx->ev[scan_ev_base + 2], ctx->ev[scan_ev_base + 3]));
-        t->merge_ms = ms;
-        QK_HIP(hipEventElapsedTime(&ms, ctx->ev[have_coarse ? 0 : scan_ev_base], ctx->ev[scan_ev_base + 3]));
-        t->total_ms = ms;
+    return qk_read_phase_ms(ctx, t, have_coarse, scan_ev_base);
+}
+
+int qk_read_phase_ms(qk_ctx *ctx, qk_timing *t, bool have_coarse, int scan_ev_base) {
+    if (!ctx->timing) return QK_OK;
+    float ms = 0.f;
+    if (have_coarse) {
+        QK_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
+        t->coarse_ms = ms;
     }
+    QK_HIP(hipEventElapsedTime(&ms, ctx->ev[scan_ev_base + 0], ctx->ev[scan_ev_base + 1]));
+    t->group_ms = ms;
+    QK_HIP(hipEventElapsedTime(&ms, ctx->ev[scan_ev_base + 1], ctx->ev[scan_ev_base + 2]));
+    t->scan_ms = ms;
+    QK_HIP(hipEventElapsedTime(&ms, ctx->ev[scan_ev_base + 2], ctx->ev[scan_ev_base + 3]));
+    t->merge_ms = ms;
+    QK_HIP(hipEventElapsedTime(&ms, ctx->ev[have_coarse ? 0 : scan_ev_base], ctx->ev[scan_ev_base + 3]));
+    t->total_ms = ms;
     return QK_OK;
 }
 
@@ -79,9 +80,9 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
     const int Ps = coarse_only ? 0 : (use_parent ? kk : P);
     const int kout = coarse_only ? kk : k;
     // ---- stage caller buffers ------------------------------------------------------------------------
-    size_t bx = al256((size_t)Q * d * 4), bp = al256((size_t)Q * std::max(Ps, 1) * 8);
-    size_t bi = al256((size_t)Q * std::max(kout, 1) * 8), bd = al256((size_t)Q * std::max(kout, 1) * 4);
-    const size_t bn = adaptive && adaptive->out_nprobed ? al256((size_t)Q * 4) : 0;  // (adaptive probing: nprobed [Q] of a host caller)
+    size_t bx = qk_al256((size_t)Q * d * 4), bp = qk_al256((size_t)Q * std::max(Ps, 1) * 8);
+    size_t bi = qk_al256((size_t)Q * std::max(kout, 1) * 8), bd = qk_al256((size_t)Q * std::max(kout, 1) * 4);
+    const size_t bn = adaptive && adaptive->out_nprobed ? qk_al256((size_t)Q * 4) : 0;  // (adaptive probing: nprobed [Q] of a host caller)
     int32_t *d_nprobed = adaptive ? adaptive->out_nprobed : nullptr;
     Staged sv;
     // host buffers through the context's pinned staging (qk_internal.h, pin_io) up to 64 MB per call; larger calls transfer directly

@@ -512,8 +512,6 @@ __global__ void k_aps_init(int64_t Q, int M, int first, int metric, int32_t *run
     radius[q] = metric == QK_METRIC_L2 ? 1000000.0f : -1000000.0f;  // query_coordinator.cpp:523-527
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int qk_search_aps(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int k, int metric,
@@ -616,7 +614,7 @@ int qk_aps_run(qk_ctx *ctx, qk_store *parent, int64_t nlist, int d, const float 
     // ---- state ----------------------------------------------------------------------------------------------------------------
     const size_t QM = (size_t)Q * M, Qk = (size_t)Q * k, QCk = (size_t)Q * CH * k;
     size_t need = 0;
-    auto take = [&](size_t b) { size_t o = need; need += al256(b); return o; };
+    auto take = [&](size_t b) { size_t o = need; need += qk_al256(b); return o; };
     const size_t o_x = take((size_t)Q * d * 4), o_pids = take(QM * 8), o_bd = take(QM * 4), o_probs = take(QM * 4);
     const size_t o_rord = take(Qk * 4), o_rid = take(Qk * 8), o_q = take((size_t)Q * 4 * 7 + 64);
     const size_t o_rp = take((size_t)Q * CH * 8), o_pri = take(QCk * 8), o_prk = take(QCk * 4);

@@ -422,16 +422,7 @@ struct PairSrc {  // several lists: the query's keys are the concatenation of it
     const int64_t *ids;        // arena ids
     int P, n;
     __device__ __forceinline__ uint32_t key(int i) const { return row[i]; }
-    __device__ __forceinline__ int64_t id(int i) const {
-        const int64_t pos = pbase[0] + i;
-        int lo = 0, hi = P;  // pbase[lo] <= pos < pbase[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (pbase[mid] <= pos) lo = mid; else hi = mid;
-        }
-        const int64_t pid = pids ? pids[lo] : lo;
-        return ids[pt_off[pid] + (pos - pbase[lo])];
-    }
+    __device__ __forceinline__ int64_t id(int i) const { return ids[emit_key_row(pbase, pids, P, pt_off, pbase[0] + i)]; }
 };
 
 __device__ __forceinline__ int block_sum_256(int v, int *s_red) {
@@ -1284,13 +1275,12 @@ __global__ __launch_bounds__(1024) void k_exclusive_scan_i64(const int64_t *__re
 }
 
 // sizes[i] = rows of pair i's list (0: -1, absent, empty), pair_base = their exclusive prefix sums, [npairs + 1] entries each
-void qk_launch_pair_offsets(qk_ctx *ctx, qk_store *s, const int64_t *pids, int64_t npairs, int P, int64_t *sizes, int64_t *pair_base) {
+static void launch_pair_offsets(qk_ctx *ctx, qk_store *s, const int64_t *pids, int64_t npairs, int P, int64_t *sizes, int64_t *pair_base) {
     hipLaunchKernelGGL(k_pair_sizes, dim3((unsigned)((npairs + 256) / 256)), dim3(256), 0, ctx->stream, pids, npairs, P, s->d_size,
                        (int)s->parts.size(), sizes);
     hipLaunchKernelGGL(k_exclusive_scan_i64, dim3(1), dim3(1024), 0, ctx->stream, sizes, pair_base, npairs + 1);
 }
 
-// k_select_pairs_large over the keys of one pass for a caller outside this file (qk_grouped.hip): nq queries, kp a power of two >= k
 int qk_launch_select_pairs(qk_ctx *ctx, qk_store *s, const uint32_t *keys, const int64_t *pair_base, const int64_t *pids, int64_t nq, int P,
                            int k, int kp, int metric, bool sqrt_l2, int64_t *out_ids, float *out_dist) {
     WideKParams w;
@@ -1313,80 +1303,152 @@ int qk_launch_select_pairs(qk_ctx *ctx, qk_store *s, const uint32_t *keys, const
     return QK_OK;
 }
 
-int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base) {
+int qk_emit_passes(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, int P, const char *who, qk_phase_events &pe, const qk_emit_hooks &h,
+                   int64_t *n_passes) {
     const int64_t Q = a.Q;
+    QK_TRY(pe.mark(0));
+    int64_t per_query_ub;
+    int64_t qc = qk_emit_pass_queries(Q, P, s->max_size, &per_query_ub);
+    if (per_query_ub > ((int64_t)1 << 30))
+        QK_FAIL(QK_ERR_UNSUPPORTED, "%s: %d lists per query of up to %lld rows is too large", who, P, (long long)s->max_size);
+    size_t extra_bytes = 0;
+    if (h.plan) {
+        const int64_t qc_ub = qc;
+        QK_TRY(h.plan(per_query_ub, &qc, &extra_bytes));
+        qc = std::max<int64_t>(1, std::min(qc, qc_ub));
+    }
+    // one buffer for the whole call (the scan recycles ctx->ws; this one survives it), sized for the largest pass:
+    // [sizes] [pair_base] [keys] [the caller's bytes]
+    const size_t o_base = qk_al256((size_t)(qc * P + 1) * 8), o_keys = 2 * o_base;
+    const size_t o_extra = o_keys + qk_al256((size_t)qc * per_query_ub * 4 + 256);
+    QK_TRY(qk_aps_reserve(ctx, o_extra + extra_bytes + 256));
+    char *B = ctx->aps;
+    int64_t *sizes = (int64_t *)B, *pair_base = (int64_t *)(B + o_base);
+    const int nblk = s->nblk;
+    int64_t passes = 0;
+    for (int64_t q0 = 0; q0 < Q; q0 += qc, passes++) {
+        qk_emit_pass p;
+        p.q0 = q0;
+        p.nq = std::min(qc, Q - q0);
+        p.pids = a.pids ? a.pids + q0 * P : nullptr;
+        p.pair_base = pair_base;
+        p.keys = (uint32_t *)(B + o_keys);
+        p.extra = B + o_extra;
+        launch_pair_offsets(ctx, s, p.pids, p.nq * P, P, sizes, pair_base);
+        if (h.before_scan) QK_TRY(h.before_scan(p));
+        if (q0 == 0) QK_TRY(pe.mark(1));
+        qk_scan_args e = a;
+        e.x = a.x + q0 * s->d;
+        e.xq4 = a.xq4 + q0 * nblk * 4;
+        e.xn = a.xn + q0;
+        e.Q = p.nq;
+        e.pids = p.pids;
+        e.key_out = p.keys;
+        e.pair_base = pair_base;
+        e.out_ids = nullptr;
+        e.out_dist = nullptr;
+        e.record_events = false;
+        // (no qk_timing: the inner call records no per-call events; deferred modes are served by its own scan-kernel events)
+        QK_TRY(qk_scan_device(ctx, s, e, nullptr, pe.ev_base));
+        if (q0 + qc >= Q) QK_TRY(pe.mark(2));
+        QK_TRY(h.consume(p));
+    }
+    if (n_passes) *n_passes = passes;
+    return QK_OK;
+}
+
+int qk_emit_front_end(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+                      int metric, int mem, size_t out_bytes, bool record_events, qk_scan_args *sa, char **out, bool *have_coarse) {
+    hipStream_t st = ctx->stream;
+    const int d = s->d;
+    const bool use_parent = parent != nullptr;
+    int kk = 0;
+    if (use_parent) {
+        if (parent->d != d) QK_FAIL(QK_ERR_INVALID, "parent store dimension %d != store dimension %d", parent->d, d);
+        kk = (int)std::min<int64_t>(nprobe, parent->ntotal);
+        if (kk > QK_MAX_NPROBE) QK_FAIL(QK_ERR_UNSUPPORTED, "nprobe=%d exceeds QK_MAX_NPROBE=%d", kk, QK_MAX_NPROBE);
+    }
+    const int Ps = use_parent ? std::max(kk, 1) : P;
+    // ---- stage caller buffers: [x] [pids] [the caller's outputs] ----------------------------------------------------------------
+    const size_t bx = qk_al256((size_t)Q * d * 4), bp = qk_al256((size_t)Q * std::max(Ps, 1) * 8);
+    const float *dx = x;
+    const int64_t *dpids = pids;
+    *out = nullptr;
+    if (mem == QK_MEM_HOST) {
+        QK_TRY(qk_stage_reserve(ctx, bx + bp + out_bytes + 256));
+        char *b = ctx->stage;
+        QK_HIP(hipMemcpyAsync(b, x, (size_t)Q * d * 4, hipMemcpyHostToDevice, st));
+        dx = (const float *)b;
+        b += bx;
+        if (!use_parent && pids) QK_HIP(hipMemcpyAsync(b, pids, (size_t)Q * P * 8, hipMemcpyHostToDevice, st));
+        if (use_parent || pids) dpids = (const int64_t *)b;
+        *out = b + bp;
+    } else if (use_parent) {
+        QK_TRY(qk_stage_reserve(ctx, bp + 256));
+        dpids = (const int64_t *)ctx->stage;
+    }
+    const float4 *xq4 = nullptr;
+    const float *xn = nullptr;
+    QK_TRY(qk_prep_queries(ctx, dx, Q, d, &xq4, &xn, 0, use_parent && kk == 1));
+    // ---- coarse: the unfiltered qk_search's ------------------------------------------------------------------------------------
+    *have_coarse = use_parent && kk > 0;
+    if (*have_coarse) {
+        qk_scan_args ca;
+        ca.x = dx;
+        ca.xq4 = xq4;
+        ca.xn = xn;
+        ca.Q = Q;
+        ca.all_lists = true;
+        ca.k = kk;
+        ca.metric = metric;
+        ca.out_ids = (int64_t *)dpids;
+        ca.out_dist = nullptr;
+        ca.record_events = record_events;
+        QK_TRY(qk_scan_device(ctx, parent, ca, nullptr, 0));
+    } else if (use_parent) {  // empty parent: nothing to probe
+        QK_HIP(hipMemsetAsync((void *)dpids, 0xFF, (size_t)Q * 8, st));
+    }
+    sa->x = dx;
+    sa->xq4 = xq4;
+    sa->xn = xn;
+    sa->Q = Q;
+    sa->metric = metric;
+    sa->sqrt_l2 = !ctx->squared_l2;
+    if (!use_parent && !pids) {
+        sa->all_lists = true;
+    } else {
+        sa->pids = dpids;
+        sa->P = Ps;
+    }
+    return QK_OK;
+}
+
+int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base) {
     const int k = a.k;
     if (k > QK_MAX_WIDE_K) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: k=%d exceeds %d", k, QK_MAX_WIDE_K);
     QK_TRY(qk_store_sync_table(s));
     const int npids = (int)s->parts.size();
     const int P = a.all_lists ? npids : a.P;
     if (P <= 0 || npids <= 0) QK_FAIL(QK_ERR_INVALID, "qk_scan: no lists to scan");
-    hipStream_t st = ctx->stream;
     int kp = 1;
     while (kp < k) kp <<= 1;
-    // queries per pass: the keys of one pass stay under 2^29 (2 GiB)
-    int64_t per_query_ub;
-    const int64_t qc = qk_emit_pass_queries(Q, P, s->max_size, &per_query_ub);
-    if (per_query_ub > ((int64_t)1 << 30)) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: k=%d with %d lists per query is too large", k, P);
-    const int nblk = s->nblk;
-    // per-call phase events of THIS pipeline (the inner qk_scan_device runs without a qk_timing, so it records none):
-    // [0,1) pair sizes + offsets of the first pass, [1,2) key emission passes, [2,3) the last selection.  Deferred modes
-    // are served by the inner call's own scan-kernel events.
+    // per-call phase events of THIS pipeline: [0,1) pair sizes + offsets of the first pass, [1,2) key emission passes,
+    // [2,3) the last selection
     qk_phase_events pe;
     pe.ctx = ctx;
     pe.tm = ctx->timing && (timing || a.record_events);
     pe.dtm = false;
     pe.ev_base = ev_base;
-    QK_TRY(pe.mark(0));
-    for (int64_t q0 = 0; q0 < Q; q0 += qc) {
-        const int64_t nq = std::min(qc, Q - q0);
-        const int64_t npairs = nq * P;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_sizes = 0, o_base = al((size_t)(npairs + 1) * 8);
-        const size_t o_keys = o_base + al((size_t)(npairs + 1) * 8);
-        const size_t need = o_keys + (size_t)nq * per_query_ub * 4 + 256;
-        QK_TRY(qk_aps_reserve(ctx, need));  // (the scan below recycles ctx->ws; this buffer survives it)
-        char *B = ctx->aps;
-        int64_t *sizes = (int64_t *)(B + o_sizes), *pair_base = (int64_t *)(B + o_base);
-        uint32_t *keys = (uint32_t *)(B + o_keys);
-        const int64_t *pids = a.pids ? a.pids + q0 * P : nullptr;
-        qk_launch_pair_offsets(ctx, s, pids, npairs, P, sizes, pair_base);
-        if (q0 == 0) QK_TRY(pe.mark(1));
-        qk_scan_args e = a;
-        e.x = a.x + q0 * s->d;
-        e.xq4 = a.xq4 + q0 * nblk * 4;
-        e.xn = a.xn + q0;
-        e.Q = nq;
-        e.pids = pids;
-        e.key_out = keys;
-        e.pair_base = pair_base;
-        e.out_ids = nullptr;
-        e.out_dist = nullptr;
-        e.record_events = false;
-        QK_TRY(qk_scan_device(ctx, s, e, nullptr, ev_base));
-        if (q0 + qc >= Q) QK_TRY(pe.mark(2));
-        WideKParams w;
-        w.keys = keys;
-        w.pair_base = pair_base;
-        w.pids = pids;
-        w.pt_off = s->d_off;
-        w.ids = s->ids;
-        w.P = P;
-        w.k = k;
-        w.kp = kp;
-        w.metric = a.metric;
-        w.sqrt_l2 = a.sqrt_l2 ? 1 : 0;
-        w.out_ids = a.out_ids + q0 * k;
-        w.out_dist = a.out_dist ? a.out_dist + q0 * k : nullptr;
-        const size_t lds = (size_t)kp * 12;
-        QK_HIP(hipFuncSetAttribute((const void *)k_select_pairs_large, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_select_pairs_large, dim3((unsigned)nq), dim3(256), lds, st, w);
-        QK_HIP(hipGetLastError());
-    }
+    qk_emit_hooks h;
+    h.consume = [&](const qk_emit_pass &p) -> int {
+        return qk_launch_select_pairs(ctx, s, p.keys, p.pair_base, p.pids, p.nq, P, k, kp, a.metric, a.sqrt_l2, a.out_ids + p.q0 * k,
+                                      a.out_dist ? a.out_dist + p.q0 * k : nullptr);
+    };
+    QK_TRY(qk_emit_passes(ctx, s, a, P, "qk_scan", pe, h, nullptr));
     QK_TRY(pe.mark(3));
     if (timing) {
         QK_TRY(qk_pinned_reserve(ctx, 64));
-        QK_HIP(hipStreamSynchronize(st));
+        QK_HIP(hipStreamSynchronize(ctx->stream));
         memset(ctx->pinned, 0, 32);
     }
     return QK_OK;

@@ -39,6 +39,20 @@ __device__ __forceinline__ float l2_expanded(float xn, float yn, float ip) {
     return r < 0.0f ? 0.0f : r;
 }
 
+// ---- emitted keys: the arena row behind a key -----------------------------------------------------------
+// A key-emission pass (qk_emit_passes, qk_dense.hip) writes a query's keys list after list; pbase holds the query's P + 1 absolute
+// pair offsets, qpids its P lists (nullptr: pair r -> list r).  Arena row of the key at absolute position pos,
+// pbase[0] <= pos < pbase[P]; empty pairs repeat an offset and are skipped.
+__device__ __forceinline__ int64_t emit_key_row(const int64_t *pbase, const int64_t *qpids, int P, const int64_t *pt_off, int64_t pos) {
+    int lo = 0, hi = P;  // pbase[lo] <= pos < pbase[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pbase[mid] <= pos) lo = mid; else hi = mid;
+    }
+    const int64_t pid = qpids ? qpids[lo] : lo;
+    return pt_off[pid] + (pos - pbase[lo]);
+}
+
 // ---- LDS pool compaction (the TopkBuffer::flush of this design) ------------------------------------
 // Keeps the k best of n entries under the total order (ord, id, position) and leaves them sorted in [0,k).
 template <int MAXCH>

@@ -34,8 +34,6 @@ namespace {
 constexpr int QK_GROUP_MAX = 64;
 constexpr int64_t QK_GROUP_SPLIT_MIN_Q = 64;  // queries per member from which the coarse step is split by queries
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct Member {
     qk_ctx *ctx = nullptr;
     qk_store *store = nullptr;
@@ -334,10 +332,10 @@ int group_search(qk_group *g, qk_store *parent, const float *x, int64_t Q, const
     const bool no_lists = !use_parent && P_in == 0;  // zero partitions: padded output (query_coordinator.cpp:459-497)
     const int P = use_parent ? std::max(kk, 1) : (no_lists ? 1 : P_in);
     const bool split = use_parent && kk > 0 && G > 1 && Q >= QK_GROUP_SPLIT_MIN_Q * G;
-    const size_t bx = al256((size_t)Q * d * 4), bp = al256((size_t)Q * P * 8), bi = al256((size_t)Q * k * 8),
-                 bd = al256((size_t)Q * k * 4);
+    const size_t bx = qk_al256((size_t)Q * d * 4), bp = qk_al256((size_t)Q * P * 8), bi = qk_al256((size_t)Q * k * 8),
+                 bd = qk_al256((size_t)Q * k * 4);
     const size_t blk = qk_topk_block_bytes_(Q, k);
-    QK_TRY(reserve_call_buffers(g, bx + bp + bi + bd, al256((size_t)G * blk) + bi + bd));
+    QK_TRY(reserve_call_buffers(g, bx + bp + bi + bd, qk_al256((size_t)G * blk) + bi + bd));
     auto xb = [&](Member &mb) { return (float *)mb.buf; };
     auto pb = [&](Member &mb) { return (int64_t *)(mb.buf + bx); };
     auto ib = [&](Member &mb) { return (int64_t *)(mb.buf + bx + bp); };
@@ -418,8 +416,8 @@ int group_search(qk_group *g, qk_store *parent, const float *x, int64_t Q, const
     int64_t *o_ids = out_ids;
     float *o_dist = out_dist;
     if (mem == QK_MEM_HOST) {
-        o_ids = (int64_t *)(g->recv + al256((size_t)G * blk));
-        o_dist = out_dist ? (float *)(g->recv + al256((size_t)G * blk) + bi) : nullptr;
+        o_ids = (int64_t *)(g->recv + qk_al256((size_t)G * blk));
+        o_dist = out_dist ? (float *)(g->recv + qk_al256((size_t)G * blk) + bi) : nullptr;
     }
     QK_TRY(qk_merge_topk_packed_device(lead.ctx, g->recv, G, Q, k, metric, o_ids, o_dist, true));
     if (tm) QK_HIP(hipEventRecord(g->tev[3], ls));
@@ -790,7 +788,7 @@ int qk_group_add_batch(qk_group *g, int64_t n, const int64_t *ids, const float *
             QK_HIP(hipSetDevice(mb.ctx->device));
             hipStream_t st = mb.ctx->stream;
             char *tmp = nullptr;
-            const size_t bs = al256((size_t)nj * 8), bv = al256((size_t)nj * d * 4);
+            const size_t bs = qk_al256((size_t)nj * 8), bv = qk_al256((size_t)nj * d * 4);
             QK_HIP(hipMalloc((void **)&tmp, 3 * bs + bv));
             int64_t *dsel = (int64_t *)tmp, *did = (int64_t *)(tmp + bs), *das = (int64_t *)(tmp + 2 * bs);
             float *dv = (float *)(tmp + 3 * bs);
@@ -849,7 +847,7 @@ int qk_group_build_csr(qk_group *g, int64_t nlist, const int64_t *offsets, const
             const int64_t *di = ids + i0;
             if (mem == QK_MEM_HOST) {
                 const size_t vb = (size_t)n * d * 4;
-                char *si = lead.ctx->stage + al256(vb);
+                char *si = lead.ctx->stage + qk_al256(vb);
                 hipSetDevice(lead.ctx->device);
                 if (hipMemcpyAsync(lead.ctx->stage, dv, vb, hipMemcpyHostToDevice, lead.ctx->stream) != hipSuccess ||
                     hipMemcpyAsync(si, di, (size_t)n * 8, hipMemcpyHostToDevice, lead.ctx->stream) != hipSuccess ||
@@ -1019,11 +1017,11 @@ int qk_group_search_aps(qk_group *g, qk_store *parent, const float *x, int64_t Q
         const size_t npairs = (size_t)r.Q * r.CH;
         if (r.round == 0) {  // (sized for the longest round of the call)
             const size_t npairs_max = (size_t)r.Q * std::max(r.CH, r.CH_max);
-            bx = al256((size_t)r.Q * d * 4);
-            bp = al256(npairs_max * 8);
-            bt = al256((size_t)r.Q * 4);
-            bi = al256(npairs_max * r.k * 8);
-            QK_TRY(reserve_call_buffers(g, bx + bp + bt + bi + al256(npairs_max * r.k * 4), 0));
+            bx = qk_al256((size_t)r.Q * d * 4);
+            bp = qk_al256(npairs_max * 8);
+            bt = qk_al256((size_t)r.Q * 4);
+            bi = qk_al256(npairs_max * r.k * 8);
+            QK_TRY(reserve_call_buffers(g, bx + bp + bt + bi + qk_al256(npairs_max * r.k * 4), 0));
         }
         auto xb = [&](Member &mb) { return (float *)mb.buf; };
         auto pb = [&](Member &mb) { return (int64_t *)(mb.buf + bx); };

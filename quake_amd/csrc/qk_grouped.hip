@@ -1,10 +1,10 @@
 // qk_grouped.hip -- grouped search: the k best GROUPS of an attribute column, every group represented by its best row
 // (include/quake_hip.h, "grouped search").
 //
-// The expensive half is the key-emission scan of the wide-k path and of range search: keys[pair_base[pair] + row] holds the canonical
-// key of every (query, probed row), pairs in (query, rank) order.  Between emission and the exact selection that already exists
-// (k_select_pairs_large, qk_dense.hip) the keys of every row that is not the (min key, min id) of its group are overwritten with
-// 0xFFFFFFFF -- the key that is never a candidate -- so the selection sees one row per group.  New device work:
+// The expensive half is the key-emission scan, run pass by pass by qk_emit_passes (qk_dense.hip): keys[pair_base[pair] + row] holds
+// the canonical key of every (query, probed row), pairs in (query, rank) order.  Between emission and the exact selection of the
+// wide-k path (qk_launch_select_pairs, qk_dense.hip) the keys of every row that is not the (min key, min id) of its group are
+// overwritten with 0xFFFFFFFF -- the key that is never a candidate -- so the selection sees one row per group.  This file's device work:
 //   k_grouped_rowvals   once per (store version, column version): the column's value of every arena row and a has-value mask in
 //                       the filter's layout (one 16-bit word per 16-row tile); a call that finds both stamps unchanged does nothing
 //   per pass of queries, an open-addressing table per query (value, min key, min id), cleared by one memset of 0xFF:
@@ -19,6 +19,7 @@
 #include "qk_attr.h"
 
 #include <cstring>
+#include "qk_device.h"
 
 namespace {
 
@@ -41,17 +42,6 @@ struct GroupedParams {
     int P, Sg;
     uint32_t tmask;            // T - 1
 };
-
-// arena row of the key at absolute position pos (pbase: the query's P + 1 pair offsets); empty pairs repeat an offset and are skipped
-__device__ __forceinline__ int64_t grouped_row(const GroupedParams &G, const int64_t *pbase, const int64_t *qpids, int64_t pos) {
-    int lo = 0, hi = G.P;  // pbase[lo] <= pos < pbase[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pbase[mid] <= pos) lo = mid; else hi = mid;
-    }
-    const int64_t pid = qpids ? qpids[lo] : lo;
-    return G.pt_off[pid] + (pos - pbase[lo]);
-}
 
 __device__ __forceinline__ uint32_t grouped_hash(unsigned long long v) {  // (the 64-bit finaliser of MurmurHash3)
     v ^= v >> 33;
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(256) void k_grouped_claim(GroupedParams G) {
         const uint32_t key = G.keys[pos];
         int32_t sl = -1;
         if (key != 0xFFFFFFFFu) {
-            const int64_t row = grouped_row(G, pbase, qpids, pos);
+            const int64_t row = emit_key_row(pbase, qpids, G.P, G.pt_off, pos);
             bool ok = (G.has[row >> 4] >> (row & 15)) & 1;
             if (ok && G.mask) ok = (G.mask[row >> 4] >> (row & 15)) & 1;
             if (ok) {
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(256) void k_grouped_minid(GroupedParams G) {
         const int32_t sl = G.slot[pos];
         if (sl < 0) continue;
         if (G.keys[pos] != G.tkeys[tbase + sl]) continue;
-        const int64_t row = grouped_row(G, pbase, qpids, pos);
+        const int64_t row = emit_key_row(pbase, qpids, G.P, G.pt_off, pos);
         atomicMin(&G.tids[tbase + sl], (unsigned long long)G.ids[row]);  // (attribute ids are non-negative)
     }
 }
@@ -124,7 +114,7 @@ __global__ __launch_bounds__(256) void k_grouped_rewrite(GroupedParams G) {
         const uint32_t key = G.keys[pos];
         bool win = false;
         if (sl >= 0 && key == G.tkeys[tbase + sl]) {
-            const int64_t row = grouped_row(G, pbase, qpids, pos);
+            const int64_t row = emit_key_row(pbase, qpids, G.P, G.pt_off, pos);
             win = (unsigned long long)G.ids[row] == G.tids[tbase + sl];
         }
         if (!win && key != 0xFFFFFFFFu) G.keys[pos] = 0xFFFFFFFFu;
@@ -259,8 +249,6 @@ int rowvals_ensure(qk_ctx *ctx, qk_store *s, qk_attr_data &d) {
     return QK_OK;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // slots of a query's table: a power of two, at least twice the distinct values a query can meet -- no more than the keys it can
 // have, no more than the ids that have a value
 int64_t table_slots(int64_t per_query_ub, int64_t n_ids) {
@@ -289,8 +277,8 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
     pe.tm = ctx->timing && timing;
     pe.dtm = false;
     pe.ev_base = 4;
-    QK_TRY(pe.mark(0));
     if (P <= 0 || npids <= 0) {  // no lists: padding
+        QK_TRY(pe.mark(0));
         QK_TRY(qk_prep_flush(ctx));
         hipLaunchKernelGGL(k_grouped_pad, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, Q * k,
                            a.metric == QK_METRIC_IP ? -INFINITY : INFINITY, a.out_ids, a.out_dist, out_groups);
@@ -298,84 +286,61 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
         for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
         return QK_OK;
     }
-    int64_t per_query_ub;
-    int64_t qc = qk_emit_pass_queries(Q, P, s->max_size, &per_query_ub);
-    if (per_query_ub > ((int64_t)1 << 30))
-        QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: %d lists per query of up to %lld rows is too large", P, (long long)s->max_size);
-    const int64_t T = table_slots(per_query_ub, col.n_ids);
-    const int64_t qbytes = grouped_query_bytes(per_query_ub, T);
-    if (qbytes > QK_GROUPED_PASS_BYTES)
-        QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: one query needs %lld bytes of workspace, more than QK_GROUPED_PASS_BYTES", (long long)qbytes);
-    qc = std::max<int64_t>(1, std::min<int64_t>(qc, QK_GROUPED_PASS_BYTES / qbytes));
-    const int64_t S = (per_query_ub + GR_SLICE - 1) / GR_SLICE;
-    if (qc * S > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: Q too large");
-    const int nblk = s->nblk;
     int kp = 2;  // (k_select_pairs_large keeps kp keys and kp ids in LDS, the ids behind the keys: kp >= 2 keeps them 8-byte aligned)
     while (kp < k) kp <<= 1;
-    // one buffer for the whole call (the scan recycles ctx->ws; this one survives it), sized for the largest pass:
-    // [sizes] [pair_base] [keys] [slots] [table values] [table ids] [table keys]
-    const int64_t npairs_max = qc * P, nslots = qc * (T + 1);
-    const size_t o_sizes = 0, o_base = al256((size_t)(npairs_max + 1) * 8);
-    const size_t o_keys = o_base + al256((size_t)(npairs_max + 1) * 8);
-    const size_t o_slot = o_keys + al256((size_t)qc * per_query_ub * 4 + 256);
-    const size_t o_tvals = o_slot + al256((size_t)qc * per_query_ub * 4 + 256);
-    const size_t o_tids = o_tvals + (size_t)nslots * 8;
-    const size_t o_tkeys = o_tids + (size_t)nslots * 8;
-    const size_t o_end = o_tkeys + (size_t)nslots * 4;
-    QK_TRY(qk_aps_reserve(ctx, o_end + 256));
-    char *B = ctx->aps;
-    int64_t *sizes = (int64_t *)(B + o_sizes), *pair_base = (int64_t *)(B + o_base);
-    uint32_t *keys = (uint32_t *)(B + o_keys);
-    for (int64_t q0 = 0; q0 < Q; q0 += qc) {
-        const int64_t nq = std::min(qc, Q - q0);
-        const int64_t npairs = nq * P;
-        const int64_t *pids = a.pids ? a.pids + q0 * P : nullptr;
-        qk_launch_pair_offsets(ctx, s, pids, npairs, P, sizes, pair_base);
-        // every slot of the pass: value = empty, min key = min id = "nothing yet" 
-        QK_HIP(hipMemsetAsync(B + o_tvals, 0xFF, (size_t)nq * (T + 1) * 8, st));
-        QK_HIP(hipMemsetAsync(B + o_tids, 0xFF, (size_t)nq * (T + 1) * 8, st));
-        QK_HIP(hipMemsetAsync(B + o_tkeys, 0xFF, (size_t)nq * (T + 1) * 4, st));
-        if (q0 == 0) QK_TRY(pe.mark(1));
-        qk_scan_args e = a;
-        e.x = a.x + q0 * s->d;
-        e.xq4 = a.xq4 + q0 * nblk * 4;
-        e.xn = a.xn + q0;
-        e.Q = nq;
-        e.pids = pids;
-        e.k = 1;
-        e.key_out = keys;
-        e.pair_base = pair_base;
-        e.out_ids = nullptr;
-        e.out_dist = nullptr;
-        e.record_events = false;
-        QK_TRY(qk_scan_device(ctx, s, e, nullptr, 4));
-        if (q0 + qc >= Q) QK_TRY(pe.mark(2));
+    // this pipeline's bytes of the call's buffer, sized for the largest pass: [slots] [table values] [table ids] [table keys]
+    int64_t T = 0, S = 0;
+    size_t o_tvals = 0, o_tids = 0, o_tkeys = 0;
+    qk_emit_hooks h;
+    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+        T = table_slots(per_query_ub, col.n_ids);
+        const int64_t qbytes = grouped_query_bytes(per_query_ub, T);
+        if (qbytes > QK_GROUPED_PASS_BYTES)
+            QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: one query needs %lld bytes of workspace, more than QK_GROUPED_PASS_BYTES", (long long)qbytes);
+        *qc = std::max<int64_t>(1, std::min<int64_t>(*qc, QK_GROUPED_PASS_BYTES / qbytes));
+        S = (per_query_ub + GR_SLICE - 1) / GR_SLICE;
+        if (*qc * S > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: Q too large");
+        const int64_t nslots = *qc * (T + 1);
+        o_tvals = qk_al256((size_t)*qc * per_query_ub * 4 + 256);
+        o_tids = o_tvals + (size_t)nslots * 8;
+        o_tkeys = o_tids + (size_t)nslots * 8;
+        *extra_bytes = o_tkeys + (size_t)nslots * 4;
+        return QK_OK;
+    };
+    h.before_scan = [&](const qk_emit_pass &p) -> int {
+        // every slot of the pass: value = empty, min key = min id = "nothing yet"
+        QK_HIP(hipMemsetAsync(p.extra + o_tvals, 0xFF, (size_t)p.nq * (T + 1) * 8, st));
+        QK_HIP(hipMemsetAsync(p.extra + o_tids, 0xFF, (size_t)p.nq * (T + 1) * 8, st));
+        QK_HIP(hipMemsetAsync(p.extra + o_tkeys, 0xFF, (size_t)p.nq * (T + 1) * 4, st));
+        return QK_OK;
+    };
+    h.consume = [&](const qk_emit_pass &p) -> int {
         GroupedParams G;
-        G.keys = keys;
-        G.slot = (int32_t *)(B + o_slot);
-        G.pair_base = pair_base;
-        G.pids = pids;
+        G.keys = p.keys;
+        G.slot = (int32_t *)p.extra;
+        G.pair_base = p.pair_base;
+        G.pids = p.pids;
         G.pt_off = s->d_off;
         G.ids = s->ids;
         G.mask = mask;
         G.has = col.rv_has;
         G.rowval = col.rv_vals;
-        G.tvals = (unsigned long long *)(B + o_tvals);
-        G.tids = (unsigned long long *)(B + o_tids);
-        G.tkeys = (uint32_t *)(B + o_tkeys);
+        G.tvals = (unsigned long long *)(p.extra + o_tvals);
+        G.tids = (unsigned long long *)(p.extra + o_tids);
+        G.tkeys = (uint32_t *)(p.extra + o_tkeys);
         G.P = P;
         G.tmask = (uint32_t)(T - 1);
         // about 16384 workgroups per pass, whatever S is
-        G.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / nq));
-        const unsigned grid = (unsigned)(nq * G.Sg);
+        G.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));
+        const unsigned grid = (unsigned)(p.nq * G.Sg);
         hipLaunchKernelGGL(k_grouped_claim, dim3(grid), dim3(256), 0, st, G);
         hipLaunchKernelGGL(k_grouped_minid, dim3(grid), dim3(256), 0, st, G);
         hipLaunchKernelGGL(k_grouped_rewrite, dim3(grid), dim3(256), 0, st, G);
         QK_HIP(hipGetLastError());
-        QK_TRY(qk_launch_select_pairs(ctx, s, keys, pair_base, pids, nq, P, k, kp, a.metric, a.sqrt_l2, a.out_ids + q0 * k,
-                                      a.out_dist ? a.out_dist + q0 * k : nullptr));
-        (*n_passes)++;
-    }
+        return qk_launch_select_pairs(ctx, s, p.keys, p.pair_base, p.pids, p.nq, P, k, kp, a.metric, a.sqrt_l2, a.out_ids + p.q0 * k,
+                                      a.out_dist ? a.out_dist + p.q0 * k : nullptr);
+    };
+    QK_TRY(qk_emit_passes(ctx, s, a, P, "grouped search", pe, h, n_passes));
     if (out_groups) {
         hipLaunchKernelGGL(k_grouped_values, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, col_of(col), (const int64_t *)a.out_ids,
                            Q * k, out_groups);
@@ -405,78 +370,23 @@ int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, con
     if (timing) memset(timing, 0, sizeof(*timing));
     if (Q == 0) return QK_OK;
     hipStream_t st = ctx->stream;
-    const int d = s->d;
-    const bool use_parent = parent != nullptr;
-    int kk = 0;
-    if (use_parent) {
-        if (parent->d != d) QK_FAIL(QK_ERR_INVALID, "parent store dimension %d != store dimension %d", parent->d, d);
-        kk = (int)std::min<int64_t>(nprobe, parent->ntotal);
-        if (kk > QK_MAX_NPROBE) QK_FAIL(QK_ERR_UNSUPPORTED, "nprobe=%d exceeds QK_MAX_NPROBE=%d", kk, QK_MAX_NPROBE);
-    }
-    const int Ps = use_parent ? std::max(kk, 1) : P;
-    const bool sqrt_l2 = !ctx->squared_l2;
-    // ---- stage caller buffers ------------------------------------------------------------------------------------------------
-    const size_t bx = al256((size_t)Q * d * 4), bp = al256((size_t)Q * std::max(Ps, 1) * 8);
-    const size_t bi = al256((size_t)Q * k * 8), bd = al256((size_t)Q * k * 4);
-    const float *dx = x;
-    const int64_t *dpids = pids;
+    // ---- staging, query preparation, coarse; a host caller's outputs on the device: [ids] [groups] [distances] ---------------------
+    const size_t bi = qk_al256((size_t)Q * k * 8), bd = qk_al256((size_t)Q * k * 4);
+    qk_scan_args sa;
+    char *out = nullptr;
+    bool have_coarse = false;
+    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, 2 * bi + bd, timing != nullptr, &sa, &out, &have_coarse));
     int64_t *dids = out_ids, *dgroups = out_groups;
     float *ddist = out_dist;
     if (mem == QK_MEM_HOST) {
-        QK_TRY(qk_stage_reserve(ctx, bx + bp + 2 * bi + bd + 256));
-        char *b = ctx->stage;
-        QK_HIP(hipMemcpyAsync(b, x, (size_t)Q * d * 4, hipMemcpyHostToDevice, st));
-        dx = (const float *)b;
-        b += bx;
-        if (!use_parent && pids) QK_HIP(hipMemcpyAsync(b, pids, (size_t)Q * P * 8, hipMemcpyHostToDevice, st));
-        if (use_parent || pids) dpids = (const int64_t *)b;
-        b += bp;
-        dids = (int64_t *)b;
-        b += bi;
-        dgroups = out_groups ? (int64_t *)b : nullptr;
-        b += bi;
-        ddist = out_dist ? (float *)b : nullptr;
-    } else if (use_parent) {
-        QK_TRY(qk_stage_reserve(ctx, bp + 256));
-        dpids = (const int64_t *)ctx->stage;
+        dids = (int64_t *)out;
+        dgroups = out_groups ? (int64_t *)(out + bi) : nullptr;
+        ddist = out_dist ? (float *)(out + 2 * bi) : nullptr;
     }
-    const float4 *xq4 = nullptr;
-    const float *xn = nullptr;
-    QK_TRY(qk_prep_queries(ctx, dx, Q, d, &xq4, &xn, 0, use_parent && kk == 1));
-    // ---- coarse: the unfiltered qk_search's ----------------------------------------------------------------------------------
-    if (use_parent && kk > 0) {
-        qk_scan_args ca;
-        ca.x = dx;
-        ca.xq4 = xq4;
-        ca.xn = xn;
-        ca.Q = Q;
-        ca.all_lists = true;
-        ca.k = kk;
-        ca.metric = metric;
-        ca.out_ids = (int64_t *)dpids;
-        ca.out_dist = nullptr;
-        ca.record_events = timing != nullptr;
-        QK_TRY(qk_scan_device(ctx, parent, ca, nullptr, 0));
-    } else if (use_parent) {  // empty parent: nothing to probe
-        QK_HIP(hipMemsetAsync((void *)dpids, 0xFF, (size_t)Q * 8, st));
-    }
-    // ---- row values and mask, then emission + reduction + selection -----------------------------------------------------------------
-    qk_scan_args sa;
-    sa.x = dx;
-    sa.xq4 = xq4;
-    sa.xn = xn;
-    sa.Q = Q;
     sa.k = k;
-    sa.metric = metric;
-    sa.sqrt_l2 = sqrt_l2;
     sa.out_ids = dids;
     sa.out_dist = ddist;
-    if (!use_parent && !pids) {
-        sa.all_lists = true;
-    } else {
-        sa.pids = dpids;
-        sa.P = Ps;
-    }
+    // ---- row values and mask, then emission + reduction + selection -----------------------------------------------------------------
     const uint16_t *mask = nullptr;
     if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
     QK_TRY(qk_store_sync_table(s));
@@ -494,22 +404,7 @@ int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, con
         // the scalars of the wide-k path: no list statistics; n_items = the query passes of the call
         QK_HIP(hipStreamSynchronize(st));
         timing->n_items = n_passes;
-        if (ctx->timing) {
-            float ms = 0.f;
-            const bool have_coarse = use_parent && kk > 0;
-            if (have_coarse) {
-                QK_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
-                timing->coarse_ms = ms;
-            }
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
-            timing->group_ms = ms;
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
-            timing->scan_ms = ms;
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
-            timing->merge_ms = ms;
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[have_coarse ? 0 : 4], ctx->ev[7]));
-            timing->total_ms = ms;
-        }
+        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
     }
     if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
     return QK_OK;

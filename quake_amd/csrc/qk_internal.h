@@ -377,6 +377,8 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
                   bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr, const qk_filter_batch *fbatch = nullptr,
                   const qk_adaptive *adaptive = nullptr);
 int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, int scan_ev_base);
+// the event half of it: coarse_ms .. total_ms from ctx->ev of a drained stream (nothing unless the context records per-call events)
+int qk_read_phase_ms(qk_ctx *ctx, qk_timing *t, bool have_coarse, int scan_ev_base);
 // adaptive (recall-target) search: the rounds run on `ctx`; a round's (query, list) pairs are scanned by `scan` (qk_aps.hip)
 struct qk_aps_round {
     const float *x = nullptr;           // [Q][d] queries (device, on the context that runs the rounds)
@@ -425,18 +427,49 @@ int qk_launch_merge_slices(qk_ctx *ctx, const int64_t *sl_ids, const uint32_t *s
 // k > QK_MAX_K over several lists: emit every key (qk_scan_device in emission mode), then exact selection per query.  qk_dense.hip
 int qk_widek_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base);
 constexpr int QK_MAX_WIDE_K = 8192;  // = the reference's TOP_K_BUFFER_CAPACITY (list_scanning.h:39)
-// Pass size of a key-emission pipeline (qk_widek_device, qk_range_device): every query of a pass gets room for the keys of P
-// lists of the store's largest size, and the keys of one pass stay under 2^29 (2 GiB).  *per_query_ub: that room, in keys;
-// beyond 2^30 a single query no longer fits an int index and the callers refuse.
+// ---- key-emission pipelines (wide k, range search, grouped search): the shared half, qk_dense.hip ---------------------------------
+inline size_t qk_al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// Pass size of a key-emission pipeline (qk_emit_passes): every query of a pass gets room for the keys of P lists of the store's
+// largest size, and the keys of one pass stay under 2^29 (2 GiB).  *per_query_ub: that room, in keys; beyond 2^30 a single query
+// no longer fits an int index and qk_emit_passes refuses.
 static inline int64_t qk_emit_pass_queries(int64_t Q, int P, int64_t max_size, int64_t *per_query_ub) {
     *per_query_ub = std::max<int64_t>(1, (int64_t)P * std::max<int64_t>(1, max_size));
     return std::max<int64_t>(1, std::min<int64_t>(Q, ((int64_t)1 << 29) / *per_query_ub));
 }
-// the pair offsets both pipelines start a pass with (qk_dense.hip: k_pair_sizes + k_exclusive_scan_i64)
-void qk_launch_pair_offsets(qk_ctx *ctx, qk_store *s, const int64_t *pids, int64_t npairs, int P, int64_t *sizes, int64_t *pair_base);
-// the exact selection of the wide-k path over keys some other pipeline emitted (and rewrote): k_select_pairs_large, qk_dense.hip
+struct qk_phase_events;
+// one pass of qk_emit_passes as the caller's hooks see it (every pointer on the device, valid until the next pass)
+struct qk_emit_pass {
+    int64_t q0 = 0, nq = 0;              // the queries of the pass: q0 .. q0 + nq of the call
+    const int64_t *pids = nullptr;       // [nq][P] their lists, or nullptr (pair r -> list r)
+    const int64_t *pair_base = nullptr;  // [nq * P + 1] first key of every pair; the last entry is the pass's key count
+    uint32_t *keys = nullptr;            // keys[pair_base[pair] + row]
+    char *extra = nullptr;               // the bytes `plan` asked for (256-byte aligned, the same address in every pass)
+};
+struct qk_emit_hooks {
+    // once, before the buffer is reserved: a query has room for per_query_ub keys and a pass takes *qc queries.  May lower *qc
+    // (never raise it) and states the bytes the caller wants next to the keys, sized for a pass of *qc queries.  Optional.
+    std::function<int(int64_t per_query_ub, int64_t *qc, size_t *extra_bytes)> plan;
+    // per pass, behind the pair offsets and in front of the emission (the phase events count it as grouping).  Optional.
+    std::function<int(const qk_emit_pass &)> before_scan;
+    // per pass, behind the emission: whatever the caller does with the keys
+    std::function<int(const qk_emit_pass &)> consume;
+};
+// The emission passes of one call: `a` as for qk_scan_device (Q queries over P > 0 lists each, out_* and k unused), the store's
+// table synced.  Per pass: pair offsets, before_scan, qk_scan_device in emission mode, consume.  Records pe's events 0 (in front of
+// everything), 1 (behind the first pass's before_scan) and 2 (behind the last emission); 3 is the caller's, behind its own tail.
+// `who` names the caller in the refusal of a query that is too large; *n_passes (optional): the passes run.
+int qk_emit_passes(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, int P, const char *who, qk_phase_events &pe, const qk_emit_hooks &h,
+                   int64_t *n_passes);
+// the exact selection of the wide-k path over the keys of a pass (k_select_pairs_large): nq queries, kp a power of two >= k
 int qk_launch_select_pairs(qk_ctx *ctx, qk_store *s, const uint32_t *keys, const int64_t *pair_base, const int64_t *pids, int64_t nq, int P,
                            int k, int kp, int metric, bool sqrt_l2, int64_t *out_ids, float *out_dist);
+// The front end of an emission-based entry point (range, grouped) behind its own argument checks, Q > 0; every caller pointer in
+// `mem`; parent == nullptr && pids == nullptr -> every list.  Stages x and pids of a host caller plus out_bytes for the caller's
+// outputs (*out: that region, 256-byte aligned; nullptr for device memory, where only the coarse result is staged), prepares the
+// queries, runs the coarse scan (the unfiltered qk_search's) and fills sa's x, xq4, xn, Q, metric, sqrt_l2 and all_lists or pids / P.
+// *have_coarse: a coarse scan ran, its events are ctx->ev[0..3] when record_events.
+int qk_emit_front_end(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+                      int metric, int mem, size_t out_bytes, bool record_events, qk_scan_args *sa, char **out, bool *have_coarse);
 // range search (qk_range.hip): every row of the probed lists whose key lies in [key_lo, key_hi] (and is a candidate of `mask`),
 // in scan order; `a` as for qk_widek_device (k unused).  lims [Q + 1], out_ids / out_dist [cap] on the device.
 int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask,

@@ -1,10 +1,10 @@
 // qk_range.hip -- range search: every row of the probed lists within a radius of each query (include/quake_hip.h, "range search").
 //
-// The expensive half is the key-emission scan qk_widek_device runs for k > QK_MAX_K (qk_dense.hip): one pass over the vectors
+// The expensive half is the key-emission scan, run pass by pass by qk_emit_passes (qk_dense.hip): one pass over the vectors
 // writes the canonical key of every (query, probed row) to keys[pair_base[pair] + row] -- pairs in (query, rank) order, rows in
 // stored order, which is the order a range result wants.  The host turns the radius into ONE closed interval of keys
 // [key_lo, key_hi] (range_key_bounds below), so "inside the radius" is an integer comparison and inclusive means inclusive.
-// New device work, per pass of queries:
+// This file's device work, per pass of queries:
 //   k_range_count    a query's segment is cut into slices of QK_RANGE_SLICE keys; a workgroup takes one slice at a time, its four waves
 //                    count the hits of their quarter (ballot + popcount), the per-wave counts are kept for the writer
 //   k_range_qscan    one wave per query: exclusive scan of the counts of the query's slices, and the query's total
@@ -12,8 +12,9 @@
 //                    device (no host synchronisation between passes): lims[q0 .. q0 + nq]
 //   k_range_write    the same decomposition as the count: every wave starts at lims[q] + slice offset + the counts of the waves
 //                    before it and gives each hit its position with a ballot prefix -- a stable compaction, no atomics; positions
-//                    >= cap are skipped.  The hits of a wave are first listed in LDS, then written side by side.  List and row of key i: the search over the query's P + 1 pair offsets qk_widek_device's
-//                    PairSrc does; the id from the arena; the distance from the key, converted like every selection kernel does.
+//                    >= cap are skipped.  The hits of a wave are first listed in LDS, then written side by side.  List and row of
+//                    key i: emit_key_row (qk_device.h); the id from the arena; the distance from the key, converted like every
+//                    selection kernel does.
 // A filter is tested here, not in the scan (the emission kernels take no mask): the mask bit of arena row pt_off[list] + row.
 #include "qk_internal.h"
 
@@ -44,17 +45,6 @@ struct RangeParams {
     float *out_dist;
 };
 
-// arena row of key i of a query's segment (pbase: its P + 1 absolute pair offsets); empty pairs repeat an offset and are skipped
-__device__ __forceinline__ int64_t range_row(const RangeParams &R, const int64_t *pbase, const int64_t *qpids, int64_t pos) {
-    int lo = 0, hi = R.P;  // pbase[lo] <= pos < pbase[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pbase[mid] <= pos) lo = mid; else hi = mid;
-    }
-    const int64_t pid = qpids ? qpids[lo] : lo;
-    return R.pt_off[pid] + (pos - pbase[lo]);
-}
-
 // A wave's share of a slice: 16 steps of 64 consecutive keys from w0 on.  All 16 loads are issued before the first key is tested
 // (a wave that waits for one 256-byte load at a time leaves the memory system idle); keys behind `end` read as 0 and fail `in`.
 constexpr int QK_RANGE_STEPS = QK_RANGE_SLICE / 256;
@@ -72,7 +62,7 @@ __device__ __forceinline__ bool range_hit(const RangeParams &R, const int64_t *p
     *row = -1;
     if (!in || key < R.key_lo || key > R.key_hi) return false;
     if (!R.mask) return true;
-    const int64_t r = range_row(R, pbase, qpids, pos);
+    const int64_t r = emit_key_row(pbase, qpids, R.P, R.pt_off, pos);
     *row = r;
     return (R.mask[r >> 4] >> (r & 15)) & 1;
 }
@@ -201,7 +191,7 @@ __global__ __launch_bounds__(256) void k_range_write(RangeParams R, const int64_
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         for (int j = lane; j < n && at + j < R.cap; j += 64) {
             const int64_t pos = w0 + s_pos[wave][j];
-            const int64_t row = range_row(R, pbase, qpids, pos);
+            const int64_t row = emit_key_row(pbase, qpids, R.P, R.pt_off, pos);
             R.out_ids[at + j] = R.ids[row];
             if (R.out_dist) {
                 const uint32_t o = R.keys[pos];
@@ -249,8 +239,6 @@ __global__ __launch_bounds__(256) void k_range_rows(const unsigned char *flags, 
     }
     if (threadIdx.x == 0) *rows_out = s_r[0];
 }
-
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 inline uint32_t f2u(float f) {
     uint32_t u;
@@ -312,8 +300,8 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
     pe.tm = ctx->timing && timing;
     pe.dtm = false;
     pe.ev_base = 4;
-    QK_TRY(pe.mark(0));
     if (P <= 0 || npids <= 0) {  // no lists: no hits
+        QK_TRY(pe.mark(0));
         QK_TRY(qk_prep_flush(ctx));
         QK_HIP(hipMemsetAsync(lims, 0, (size_t)(Q + 1) * 8, st));
         for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
@@ -324,56 +312,40 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
         }
         return QK_OK;
     }
-    int64_t per_query_ub;
-    const int64_t qc = qk_emit_pass_queries(Q, P, s->max_size, &per_query_ub);
-    if (per_query_ub > ((int64_t)1 << 30)) QK_FAIL(QK_ERR_UNSUPPORTED, "range search: %d lists per query of up to %lld rows is too large", P, (long long)s->max_size);
-    const int S = (int)((per_query_ub + QK_RANGE_SLICE - 1) / QK_RANGE_SLICE);
-    if (qc * (int64_t)S > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "range search: Q too large");
-    const int nblk = s->nblk;
-    // one buffer for the whole call (the scan recycles ctx->ws; this one survives it), sized for the largest pass:
-    // [run: total hits, live pairs, rows of the lists reached, -] [list flags] [sizes] [pair_base] [cnt] [cnt4] [excl] [keys]
-    const int64_t npairs_max = qc * P, nsl_max = qc * S;
-    const size_t o_run = 0, o_flags = 256, o_sizes = o_flags + al256((size_t)npids);
-    const size_t o_base = o_sizes + al256((size_t)(npairs_max + 1) * 8);
-    const size_t o_cnt = o_base + al256((size_t)(npairs_max + 1) * 8);
-    const size_t o_cnt4 = o_cnt + al256((size_t)nsl_max * 4);
-    const size_t o_excl = o_cnt4 + al256((size_t)nsl_max * 16);
-    const size_t o_qtot = o_excl + al256((size_t)nsl_max * 4);
-    const size_t o_keys = o_qtot + al256((size_t)qc * 4);
-    QK_TRY(qk_aps_reserve(ctx, o_keys + (size_t)qc * per_query_ub * 4 + 256));
-    char *B = ctx->aps;
-    int64_t *run = (int64_t *)(B + o_run);
-    unsigned char *flags = (unsigned char *)(B + o_flags);
-    int64_t *sizes = (int64_t *)(B + o_sizes), *pair_base = (int64_t *)(B + o_base);
-    uint32_t *keys = (uint32_t *)(B + o_keys);
-    QK_HIP(hipMemsetAsync(B, 0, timing ? o_sizes : 256, st));
-    for (int64_t q0 = 0; q0 < Q; q0 += qc) {
-        const int64_t nq = std::min(qc, Q - q0);
-        const int64_t npairs = nq * P;
-        const int64_t *pids = a.pids ? a.pids + q0 * P : nullptr;
-        qk_launch_pair_offsets(ctx, s, pids, npairs, P, sizes, pair_base);
+    // this pipeline's bytes of the call's buffer, sized for the largest pass:
+    // [run: total hits, live pairs, rows of the lists reached, -] [list flags] [cnt] [cnt4] [excl] [qtot]
+    int S = 0;
+    const size_t o_flags = 256, o_cnt = o_flags + qk_al256((size_t)npids);
+    size_t o_cnt4 = 0, o_excl = 0, o_qtot = 0;
+    int64_t *run = nullptr;
+    unsigned char *flags = nullptr;
+    qk_emit_hooks h;
+    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+        S = (int)((per_query_ub + QK_RANGE_SLICE - 1) / QK_RANGE_SLICE);
+        if (*qc * (int64_t)S > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "range search: Q too large");
+        const int64_t nsl_max = *qc * S;
+        o_cnt4 = o_cnt + qk_al256((size_t)nsl_max * 4);
+        o_excl = o_cnt4 + qk_al256((size_t)nsl_max * 16);
+        o_qtot = o_excl + qk_al256((size_t)nsl_max * 4);
+        *extra_bytes = o_qtot + qk_al256((size_t)*qc * 4);
+        return QK_OK;
+    };
+    h.before_scan = [&](const qk_emit_pass &p) -> int {
+        if (p.q0 == 0) {
+            run = (int64_t *)p.extra;
+            flags = (unsigned char *)(p.extra + o_flags);
+            QK_HIP(hipMemsetAsync(p.extra, 0, timing ? o_cnt : 256, st));
+        }
         if (timing)
-            hipLaunchKernelGGL(k_range_mark, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, pids, npairs, P, s->d_size, npids, flags,
-                               (unsigned long long *)(run + 1));
-        if (q0 == 0) QK_TRY(pe.mark(1));
-        qk_scan_args e = a;
-        e.x = a.x + q0 * s->d;
-        e.xq4 = a.xq4 + q0 * nblk * 4;
-        e.xn = a.xn + q0;
-        e.Q = nq;
-        e.pids = pids;
-        e.k = 1;
-        e.key_out = keys;
-        e.pair_base = pair_base;
-        e.out_ids = nullptr;
-        e.out_dist = nullptr;
-        e.record_events = false;
-        QK_TRY(qk_scan_device(ctx, s, e, nullptr, 4));
-        if (q0 + qc >= Q) QK_TRY(pe.mark(2));
+            hipLaunchKernelGGL(k_range_mark, dim3((unsigned)((p.nq * P + 255) / 256)), dim3(256), 0, st, p.pids, p.nq * P, P, s->d_size, npids,
+                               flags, (unsigned long long *)(run + 1));
+        return QK_OK;
+    };
+    h.consume = [&](const qk_emit_pass &p) -> int {
         RangeParams R;
-        R.keys = keys;
-        R.pair_base = pair_base;
-        R.pids = pids;
+        R.keys = p.keys;
+        R.pair_base = p.pair_base;
+        R.pids = p.pids;
         R.pt_off = s->d_off;
         R.ids = s->ids;
         R.mask = mask;
@@ -383,23 +355,24 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
         R.key_hi = key_hi;
         R.metric = a.metric;
         R.sqrt_l2 = a.sqrt_l2 ? 1 : 0;
-        R.cnt = (int32_t *)(B + o_cnt);
-        R.cnt4 = (int4 *)(B + o_cnt4);
-        R.qexcl = (int32_t *)(B + o_excl);
-        R.qtot = (int32_t *)(B + o_qtot);
+        R.cnt = (int32_t *)(p.extra + o_cnt);
+        R.cnt4 = (int4 *)(p.extra + o_cnt4);
+        R.qexcl = (int32_t *)(p.extra + o_excl);
+        R.qtot = (int32_t *)(p.extra + o_qtot);
         R.cap = cap;
         R.out_ids = out_ids;
         R.out_dist = out_dist;
         // about 16384 workgroups per pass, whatever S is: few queries -> every slice its own workgroup, many -> a few per query
-        R.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / nq));
-        const unsigned grid = (unsigned)(nq * R.Sg);
+        R.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));
+        const unsigned grid = (unsigned)(p.nq * R.Sg);
         hipLaunchKernelGGL(k_range_count, dim3(grid), dim3(256), 0, st, R);
-        hipLaunchKernelGGL(k_range_qscan, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, R, nq);
-        hipLaunchKernelGGL(k_range_offsets, dim3(1), dim3(1024), 0, st, R.qtot, nq, run, lims + q0);
-        if (cap > 0) hipLaunchKernelGGL(k_range_write, dim3(grid), dim3(256), 0, st, R, (const int64_t *)(lims + q0));
+        hipLaunchKernelGGL(k_range_qscan, dim3((unsigned)((p.nq + 3) / 4)), dim3(256), 0, st, R, p.nq);
+        hipLaunchKernelGGL(k_range_offsets, dim3(1), dim3(1024), 0, st, R.qtot, p.nq, run, lims + p.q0);
+        if (cap > 0) hipLaunchKernelGGL(k_range_write, dim3(grid), dim3(256), 0, st, R, (const int64_t *)(lims + p.q0));
         QK_HIP(hipGetLastError());
-        (*n_passes)++;
-    }
+        return QK_OK;
+    };
+    QK_TRY(qk_emit_passes(ctx, s, a, P, "range search", pe, h, n_passes));
     const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
     ctx->last_scan_kernel = wide ? "k_scan_wide (range)" : "k_scan (range)";
     if (timing) hipLaunchKernelGGL(k_range_rows, dim3(1), dim3(256), 0, st, flags, s->d_size, npids, run + 2);
@@ -432,81 +405,25 @@ int range_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const
         else QK_HIP(hipMemsetAsync(out_lims, 0, 8, st));
         return QK_OK;
     }
-    const int d = s->d;
-    const bool use_parent = parent != nullptr;
-    int kk = 0;
-    if (use_parent) {
-        if (parent->d != d) QK_FAIL(QK_ERR_INVALID, "parent store dimension %d != store dimension %d", parent->d, d);
-        kk = (int)std::min<int64_t>(nprobe, parent->ntotal);
-        if (kk > QK_MAX_NPROBE) QK_FAIL(QK_ERR_UNSUPPORTED, "nprobe=%d exceeds QK_MAX_NPROBE=%d", kk, QK_MAX_NPROBE);
-    }
-    const int Ps = use_parent ? std::max(kk, 1) : P;
-    const bool sqrt_l2 = !ctx->squared_l2;
-    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
-    if (!range_key_bounds(metric, sqrt_l2, radius, &key_lo, &key_hi)) {
-        key_lo = 1;
-        key_hi = 0;
-    }
-    // ---- stage caller buffers ------------------------------------------------------------------------------------------------
-    const size_t bx = al256((size_t)Q * d * 4), bp = al256((size_t)Q * std::max(Ps, 1) * 8), bl = al256((size_t)(Q + 1) * 8);
-    const size_t bi = al256((size_t)cap * 8), bd = al256((size_t)cap * 4);
-    const float *dx = x;
-    const int64_t *dpids = pids;
+    // ---- staging, query preparation, coarse; a host caller's outputs on the device: [lims] [ids] [distances] -----------------------
+    const size_t bl = qk_al256((size_t)(Q + 1) * 8), bi = qk_al256((size_t)cap * 8), bd = qk_al256((size_t)cap * 4);
+    qk_scan_args sa;
+    char *out = nullptr;
+    bool have_coarse = false;
+    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, bl + bi + bd, timing != nullptr, &sa, &out, &have_coarse));
     int64_t *dlims = out_lims, *dids = out_ids;
     float *ddist = out_dist;
     if (mem == QK_MEM_HOST) {
-        QK_TRY(qk_stage_reserve(ctx, bx + bp + bl + bi + bd + 256));
-        char *b = ctx->stage;
-        QK_HIP(hipMemcpyAsync(b, x, (size_t)Q * d * 4, hipMemcpyHostToDevice, st));
-        dx = (const float *)b;
-        b += bx;
-        if (!use_parent && pids) QK_HIP(hipMemcpyAsync(b, pids, (size_t)Q * P * 8, hipMemcpyHostToDevice, st));
-        if (use_parent || pids) dpids = (const int64_t *)b;
-        b += bp;
-        dlims = (int64_t *)b;
-        b += bl;
-        dids = cap > 0 ? (int64_t *)b : nullptr;
-        b += bi;
-        ddist = cap > 0 && out_dist ? (float *)b : nullptr;
-    } else if (use_parent) {
-        QK_TRY(qk_stage_reserve(ctx, bp + 256));
-        dpids = (const int64_t *)ctx->stage;
+        dlims = (int64_t *)out;
+        dids = cap > 0 ? (int64_t *)(out + bl) : nullptr;
+        ddist = cap > 0 && out_dist ? (float *)(out + bl + bi) : nullptr;
     }
-    const float4 *xq4 = nullptr;
-    const float *xn = nullptr;
-    QK_TRY(qk_prep_queries(ctx, dx, Q, d, &xq4, &xn, 0, use_parent && kk == 1));
-    // ---- coarse: the unfiltered qk_search's ----------------------------------------------------------------------------------
-    if (use_parent && kk > 0) {
-        qk_scan_args ca;
-        ca.x = dx;
-        ca.xq4 = xq4;
-        ca.xn = xn;
-        ca.Q = Q;
-        ca.all_lists = true;
-        ca.k = kk;
-        ca.metric = metric;
-        ca.out_ids = (int64_t *)dpids;
-        ca.out_dist = nullptr;
-        ca.record_events = timing != nullptr;
-        QK_TRY(qk_scan_device(ctx, parent, ca, nullptr, 0));
-    } else if (use_parent) {  // empty parent: nothing to probe
-        QK_HIP(hipMemsetAsync((void *)dpids, 0xFF, (size_t)Q * 8, st));
+    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
+    if (!range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
+        key_lo = 1;
+        key_hi = 0;
     }
     // ---- emission scan + counting + compaction ----------------------------------------------------------------------------------
-    qk_scan_args sa;
-    sa.x = dx;
-    sa.xq4 = xq4;
-    sa.xn = xn;
-    sa.Q = Q;
-    sa.k = 1;
-    sa.metric = metric;
-    sa.sqrt_l2 = sqrt_l2;
-    if (!use_parent && !pids) {
-        sa.all_lists = true;
-    } else {
-        sa.pids = dpids;
-        sa.P = Ps;
-    }
     const uint16_t *mask = nullptr;
     if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
     int64_t n_passes = 0;
@@ -528,23 +445,8 @@ int range_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const
         memcpy(sc, ctx->pinned, 32);
         timing->n_items = n_passes;
         timing->partitions_scanned = sc[1];
-        timing->scan_bytes = sc[2] * (int64_t)d * 4;
-        if (ctx->timing) {
-            float ms = 0.f;
-            const bool have_coarse = use_parent && kk > 0;
-            if (have_coarse) {
-                QK_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
-                timing->coarse_ms = ms;
-            }
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
-            timing->group_ms = ms;
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]));
-            timing->scan_ms = ms;
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
-            timing->merge_ms = ms;
-            QK_HIP(hipEventElapsedTime(&ms, ctx->ev[have_coarse ? 0 : 4], ctx->ev[7]));
-            timing->total_ms = ms;
-        }
+        timing->scan_bytes = sc[2] * (int64_t)s->d * 4;
+        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
     }
     if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
     return QK_OK;

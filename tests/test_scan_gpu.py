@@ -306,6 +306,49 @@ def test_wide_k_with_timing_on_a_fresh_context():
     c.close()
 
 
+def test_wide_k_in_several_passes(ctx):
+    """k > QK_MAX_K across pass boundaries.  The pass size depends on the store's LARGEST list: one unprobed list of 300 000 rows
+    lets a pass of P = 32 take floor(2^29 / (32 * 300000)) = 55 queries, so 3 * 55 + 1 queries run in four passes, the last of one
+    query, while the probed work and the oracle stay tiny (the call reports no pass count: n_items is 0 on this path).  Every
+    query probes 756 .. 1159 rows: k = 449 is always filled, k = 1000 pads some rows -- the padding crosses a boundary too."""
+    import torch
+    from quake_amd.capi import Store
+    d, nsmall, big = 16, 48, 300000
+    rng = np.random.default_rng(41)
+    sizes = rng.integers(0, 60, size=nsmall)
+    sizes[[3, 17]] = 0
+    sizes = np.concatenate([sizes, [big]]).astype(np.int64)
+    offsets = np.zeros(nsmall + 2, np.int64)
+    offsets[1:] = np.cumsum(sizes)
+    n = int(offsets[-1])
+    vecs = rng.standard_normal((n, d)).astype(np.float32)
+    ids = rng.permutation(n).astype(np.int64)
+    P = 32
+    qc = (1 << 29) // (P * big)
+    Q = 3 * qc + 1
+    assert (qc, Q) == (55, 166)
+    q = rng.standard_normal((Q, d)).astype(np.float32)
+    pids = np.stack([rng.permutation(nsmall)[:P] for _ in range(Q)]).astype(np.int64)
+    pids[rng.random((Q, P)) < 0.05] = -1
+    probed = np.where(pids >= 0, sizes[np.maximum(pids, 0)], 0).sum(axis=1)
+    assert 449 <= probed.min() and probed.min() < 1000 < probed.max()
+    s = Store(ctx, d)
+    s.build_csr(offsets, ids, vecs)
+    try:
+        for k, metric in ((449, "l2"), (1000, "ip")):
+            gi, gd = ctx.scan(s, q, pids, k, metric)
+            oi, od = O.batched_serial_scan(q, vecs, ids, offsets, pids, k, metric)
+            np.testing.assert_array_equal(gi, oi)
+            np.testing.assert_array_equal(gd.view(np.uint32), od.view(np.uint32))
+        assert (oi[probed < 1000, -1] == -1).all() and (oi[:, 755] >= 0).all()  # (k = 1000: the padding is where it should be)
+        di, dd = ctx.scan(s, torch.from_numpy(q).cuda(), torch.from_numpy(pids).cuda(), 1000, "ip")
+        ctx.synchronize()
+        np.testing.assert_array_equal(di.cpu().numpy(), gi)
+        np.testing.assert_array_equal(dd.cpu().numpy().view(np.uint32), gd.view(np.uint32))
+    finally:
+        s.close()
+
+
 @pytest.mark.parametrize("d,metric", [(768, "ip"), (768, "l2"), (1024, "l2"), (512, "ip")])
 def test_wide_rows_shared_query_tile(ctx, d, metric):
     """d >= 512: several waves of a workgroup share one LDS query tile and split each segment (k_scan nw = 2/4), pools
