@@ -101,7 +101,7 @@ def lib():
         L.qo_search_aps.restype = C.c_int
         L.qo_search_aps.argtypes = [_f32p, C.c_int64, _f32p, _i64p, C.c_int64, _f32p, _i64p, _i64p, C.c_int64, C.c_int,
                                     C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, _i64p,
-                                    _f32p, C.POINTER(C.c_int32)]
+                                    _f32p, C.POINTER(C.c_int32), C.c_int64]
         _lib = L
     return _lib
 
@@ -415,8 +415,10 @@ def boundary_distances(q, centroids, euclidean=True):
 
 
 def search_aps(x, centroids, vecs, ids, offsets, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
-               initial_search_fraction=0.02, centroid_ids=None, expanded=True, num_threads=1):
-    """QuakeIndex::search with SearchParams.recall_target > 0 (serial_scan APS).  Returns (ids, dist, nscanned)."""
+               initial_search_fraction=0.02, centroid_ids=None, expanded=True, num_threads=1, nlist_present=None):
+    """QuakeIndex::search with SearchParams.recall_target > 0 (serial_scan APS).  Returns (ids, dist, nscanned).
+    nlist_present: the number of lists that exist when the CSR has holes (deleted lists kept as empty ones without a centroid);
+    only M = nlist * initial_search_fraction is taken from it.  None: the CSR length."""
     x = _f32(x)
     centroids = _f32(centroids)
     vecs = _f32(vecs)
@@ -432,7 +434,7 @@ def search_aps(x, centroids, vecs, ids, offsets, k, metric, recall_target, recom
     rc = lib().qo_search_aps(_pf(x), nq, _pf(centroids), _pi(cid), centroids.shape[0], _pf(vecs), _pi(ids), _pi(offsets), nlist, d,
                              k, metric_code(metric), float(recall_target), float(recompute_threshold), int(use_precomputed),
                              float(initial_search_fraction), int(expanded), int(num_threads), _pi(out_i), _pf(out_d),
-                             out_n.ctypes.data_as(C.POINTER(C.c_int32)))
+                             out_n.ctypes.data_as(C.POINTER(C.c_int32)), int(nlist_present) if nlist_present is not None else 0)
     if rc != 0:
         raise RuntimeError("Boundary distances must have at least 2 partitions to create an estimate.")
     return out_i, out_d, out_n

@@ -1203,13 +1203,15 @@ QO_API void qo_boundary_distances(const float *q, const float *const *cent, int 
  * expanded = 0: direct form, as scan_list.  centroid_row_of[pid] = row of that partition's centroid in `centroids`.
  * out_nscan[q] = partitions visited (p reached + 1, or M).  An empty profile (never computed because the radius test
  * produced NaN) contributes 0 to the estimate -- the reference indexes an empty vector there.
+ * nlist_present > 0: the number of lists that exist, where the CSR has holes (a deleted list stays in `offsets` as an empty list
+ * without a centroid): the index's nlist() of :638, used for M only.  <= 0: the CSR length.
  * returns 0, or -1 when M < 2 (compute_recall_profile throws). */
 QO_API int qo_search_aps(const float *x, int64_t nq, const float *centroids, const int64_t *centroid_ids, int64_t nlist_parent,
                          const float *vecs, const int64_t *ids, const int64_t *offsets, int64_t nlist, int d, int k, int metric,
                          float recall_target, float recompute_threshold, int use_precomputed, float initial_search_fraction,
-                         int expanded, int num_threads, int64_t *out_ids, float *out_dist, int32_t *out_nscan) {
+                         int expanded, int num_threads, int64_t *out_ids, float *out_dist, int32_t *out_nscan, int64_t nlist_present) {
     if (k <= 0) k = 1;
-    int M = (int)((float)nlist * initial_search_fraction);
+    int M = (int)((float)(nlist_present > 0 ? nlist_present : nlist) * initial_search_fraction);
     if (M < 1) M = 1;
     int kk = M < nlist_parent ? M : (int)nlist_parent;
     if (kk < 2) return -1;
