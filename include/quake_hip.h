@@ -441,6 +441,36 @@ QK_API int qk_search_grouped(qk_ctx *ctx, qk_store *parent, qk_store *s, const f
 QK_API int qk_scan_grouped(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric,
                            qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
                            qk_timing *timing);
+/* Grouped search with members: the group_size = m best rows of each of the k best groups, 1 <= m <= QK_MAX_GROUP_SIZE.  The
+ * argument lists of qk_search_grouped / qk_scan_grouped with group_size behind k; those two are these with m = 1, launch for launch.
+ * Candidates, the total order (key, id), the ranking of the groups by their best candidate and the choice of the k best groups are
+ * unchanged.  Of each chosen group the call returns its min(m, candidates of that group for this query) best candidates under
+ * (key, id), ascending: out_ids [Q][k][m], out_dist [Q][k][m] (may be NULL; the bits qk_search reports), out_groups [Q][k] (may be
+ * NULL).  Members a group does not have are padding (id -1, distance +inf / -inf), every member of a padded group slot is padding,
+ * out_groups is 0 where member 0 is.  Equal keys are ordered by id and both rows appear where there is room; ids are compared as
+ * 64-bit words, nothing is packed.  Member 0 of every group, and out_groups, are the one-row call's result bit for bit.
+ * m > 1: k_grouped_rewrite leaves the emitted keys alone and fills a second key array for the selection.  Behind the selection
+ * k_grouped_mark finds the slot of every selected row's value again (the hash and the bounded walk of k_grouped_claim, read only),
+ * records j there and places member 0; k_grouped_renumber turns every key's slot number into the j of its group or -1; then per
+ * member r = 1 .. m - 1 two sweeps over the pass's keys: k_grouped_next_key folds the keys of the group's candidates strictly above
+ * member r - 1 under (key, id) into a 32-bit word (atomicMin), k_grouped_next_id folds the ids of those that equal it into out_ids
+ * (64-bit atomicMin; the cleared word, all ones, is the padding id); k_grouped_member_dist converts the keys.  A key of a group that
+ * was not selected leaves a sweep after one load.  Hazards as above: no kernel waits, spins or locks, every loop is bounded, phases
+ * are kernel boundaries, only commutative minima decide a word.
+ * Workspace for m > 1, per query of a pass: 12 bytes per key it has room for (key, slot number, the selection's key), 24 per table
+ * slot (T + 1 slots, T as above), 12 per result of the one-row selection (k of them) and 4 per member word (k * m of them):
+ *   bytes = 12 * per_query_ub + 24 * (T + 1) + 12 * k + 4 * k * m
+ * Queries per pass = min(2^29 / per_query_ub, QK_GROUPED_PASS_BYTES / bytes), at least 1.  QK_ERR_INVALID: group_size < 1 (and
+ * the checks above); QK_ERR_UNSUPPORTED: group_size > QK_MAX_GROUP_SIZE, a single query whose bytes exceed QK_GROUPED_PASS_BYTES.
+ * The cap is a design choice: every member beyond the first costs two sweeps over the pass's keys.
+ * timing: the member rounds belong to merge_ms of their pass; n_items stays the number of query passes. */
+#define QK_MAX_GROUP_SIZE 16
+QK_API int qk_search_grouped_n(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int group_size,
+                               int metric, qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups,
+                               int mem, qk_timing *timing);
+QK_API int qk_scan_grouped_n(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int group_size,
+                             int metric, qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups,
+                             int mem, qk_timing *timing);
 /* builds: derivations of the column's row values so far (one per grouped call that found the store or the column changed);
  * device_bytes: HBM they hold (not part of qk_attr_info).  Either pointer may be NULL. */
 QK_API int qk_attr_group_info(qk_attr *a, int64_t *builds, int64_t *device_bytes);

@@ -109,6 +109,8 @@ SIGNATURES = {
     "qk_attr_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_uint64), C.POINTER(_int), C.POINTER(_i64)]),
     "qk_search_grouped": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_scan_grouped": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_search_grouped_n": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_scan_grouped_n": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
     "qk_search_aps": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, C.c_float, _int, C.c_float, _vp, _vp, _vp, _int,

@@ -381,40 +381,52 @@ class Context:
         return self._range(call, x, cap, timing, out)
 
     # ---- grouped search ---------------------------------------------------------------------------------
-    def search_grouped(self, parent, store, x, nprobe, k, metric, group_by, filter=None, timing=False, out=None):
+    @staticmethod
+    def _grouped_out(x, Q, k, group_size, out):
+        # group_size None: the one-row shapes [Q, k]; an int m: ids / dist [Q, k, m], groups [Q, k]
+        if out is not None:
+            return out
+        shp = (Q, k) if group_size is None else (Q, k, int(group_size))
+        return (_empty_like_mem(shp, np.int64, x), _empty_like_mem(shp, np.float32, x), _empty_like_mem((Q, k), np.int64, x))
+
+    def search_grouped(self, parent, store, x, nprobe, k, metric, group_by, filter=None, timing=False, out=None, group_size=None):
         """qk_search_grouped: the k best groups of the Attr `group_by` per query over the lists qk_search probes, every group
         represented by its best row.  Returns (ids [Q, k], dist [Q, k], groups [Q, k][, timing]); out=(ids, dist, groups):
-        buffers of the caller.  filter: a Filter of `store` (a group is then represented by its best allowed row)."""
+        buffers of the caller.  filter: a Filter of `store` (a group is then represented by its best allowed row).
+        group_size=m (an int, 1 <= m <= 16): qk_search_grouped_n, the m best rows of every group -- ids / dist [Q, k, m],
+        groups [Q, k]; `out` follows."""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
-        if out is None:
-            out = (_empty_like_mem((Q, k), np.int64, x), _empty_like_mem((Q, k), np.float32, x), _empty_like_mem((Q, k), np.int64, x))
-        out_i, out_d, out_g = out
+        out_i, out_d, out_g = self._grouped_out(x, Q, k, group_size, out)
         t = QkTiming()
-        check(self.lib.qk_search_grouped(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), int(k),
-                                         metric_code(metric), group_by.h if group_by is not None else None,
-                                         filter.h if filter is not None else None, _ptr(out_i), _ptr(out_d), _ptr(out_g), mem,
-                                         C.byref(t) if timing else None))
+        head = (self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), int(k))
+        tail = (metric_code(metric), group_by.h if group_by is not None else None, filter.h if filter is not None else None,
+                _ptr(out_i), _ptr(out_d), _ptr(out_g), mem, C.byref(t) if timing else None)
+        if group_size is None:
+            check(self.lib.qk_search_grouped(*head, *tail))
+        else:
+            check(self.lib.qk_search_grouped_n(*head, int(group_size), *tail))
         return (out_i, out_d, out_g, timing_dict(t)) if timing else (out_i, out_d, out_g)
 
-    def scan_grouped(self, store, x, pids, k, metric, group_by, filter=None, timing=False, out=None):
+    def scan_grouped(self, store, x, pids, k, metric, group_by, filter=None, timing=False, out=None, group_size=None):
         """qk_scan_grouped: search_grouped over the given lists -- pids [Q, P] (or [P] for every query); -1 / absent / empty lists
-        contribute nothing"""
+        contribute nothing.  group_size as for search_grouped (qk_scan_grouped_n)."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
         if pids.ndim == 1:
             pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
                     else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
         mem = _mem_of(x, pids)
-        if out is None:
-            out = (_empty_like_mem((Q, k), np.int64, x), _empty_like_mem((Q, k), np.float32, x), _empty_like_mem((Q, k), np.int64, x))
-        out_i, out_d, out_g = out
+        out_i, out_d, out_g = self._grouped_out(x, Q, k, group_size, out)
         t = QkTiming()
-        check(self.lib.qk_scan_grouped(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), int(k),
-                                       metric_code(metric), group_by.h if group_by is not None else None,
-                                       filter.h if filter is not None else None, _ptr(out_i), _ptr(out_d), _ptr(out_g), mem,
-                                       C.byref(t) if timing else None))
+        head = (self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), int(k))
+        tail = (metric_code(metric), group_by.h if group_by is not None else None, filter.h if filter is not None else None,
+                _ptr(out_i), _ptr(out_d), _ptr(out_g), mem, C.byref(t) if timing else None)
+        if group_size is None:
+            check(self.lib.qk_scan_grouped(*head, *tail))
+        else:
+            check(self.lib.qk_scan_grouped_n(*head, int(group_size), *tail))
         return (out_i, out_d, out_g, timing_dict(t)) if timing else (out_i, out_d, out_g)
 
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,

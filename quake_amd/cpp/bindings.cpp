@@ -119,7 +119,9 @@ PYBIND11_MODULE(_bindings, m) {
         .def("range_search", &QuakeIndex::range_search, py::arg("x"), py::arg("radius"), py::arg("search_params"),
              "extension: every vector of the nprobe nearest partitions within `radius` of each query (lims, ids, distances)")
         .def("grouped_search", &QuakeIndex::grouped_search, py::arg("x"), py::arg("group_by"), py::arg("search_params"),
-             "extension: the k best groups of attribute column `group_by` per query, every group by its best vector (ids, distances, groups)")
+             py::arg("group_size") = py::none(),
+             "extension: the k best groups of attribute column `group_by` per query, every group by its best vector (ids, distances, groups); "
+             "group_size = m: by its m best vectors, ids / distances [Q, k, m]")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)

@@ -5,6 +5,7 @@
 #include <torch/torch.h>
 
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -137,7 +138,7 @@ struct RangeSearchResult {
 };
 
 // extension (QuakeIndex::grouped_search): the k best groups of a column per query -- ids / distances [Q, k] of each group's best vector,
-// groups [Q, k] the group values (0 where ids is the padding id -1)
+// groups [Q, k] the group values (0 where ids is the padding id -1); with group_size = m, ids / distances [Q, k, m]
 struct GroupedSearchResult {
     Tensor ids;
     Tensor distances;

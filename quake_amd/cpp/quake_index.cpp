@@ -130,14 +130,15 @@ shared_ptr<RangeSearchResult> QuakeIndex::range_search(Tensor x, float radius, s
     return query_coordinator_->range_search(x, radius, sp);
 }
 
-shared_ptr<GroupedSearchResult> QuakeIndex::grouped_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> sp) {
+shared_ptr<GroupedSearchResult> QuakeIndex::grouped_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> sp,
+                                                           std::optional<int> group_size) {
     if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::grouped_search()] No query coordinator. Did you build the index?");
     qk_attr *col = nullptr;
     if (partition_manager_ && partition_manager_->has_lists() && partition_manager_->store() && partition_manager_->store() == attrs_store_) {
         auto it = attrs_.find(group_by);
         if (it != attrs_.end()) col = it->second;
     }
-    return query_coordinator_->grouped_search(x, col, group_by, sp);
+    return query_coordinator_->grouped_search(x, col, group_by, sp, group_size);
 }
 
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {

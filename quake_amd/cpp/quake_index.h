@@ -76,7 +76,9 @@ public:
     shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
     // extension: the search_params->k best groups of attribute column `group_by` among the vectors of the nprobe nearest partitions,
     // every group represented by its best (allowed) vector (qk_search_grouped)
-    shared_ptr<GroupedSearchResult> grouped_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> search_params);
+    // group_size = m, 1 <= m <= QK_MAX_GROUP_SIZE: the m best vectors of every group, ids / distances [Q, k, m] (qk_search_grouped_n)
+    shared_ptr<GroupedSearchResult> grouped_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> search_params,
+                                                   std::optional<int> group_size = std::nullopt);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

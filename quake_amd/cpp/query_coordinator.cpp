@@ -334,8 +334,11 @@ shared_ptr<RangeSearchResult> QueryCoordinator::range_search(Tensor x, float rad
     return res;
 }
 
-shared_ptr<GroupedSearchResult> QueryCoordinator::grouped_search(Tensor x, qk_attr *group_by, const std::string &name, shared_ptr<SearchParams> sp) {
+shared_ptr<GroupedSearchResult> QueryCoordinator::grouped_search(Tensor x, qk_attr *group_by, const std::string &name, shared_ptr<SearchParams> sp,
+                                                                 std::optional<int> group_size) {
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::grouped_search] partition_manager_ is null.");
+    if (group_size && (*group_size < 1 || *group_size > QK_MAX_GROUP_SIZE))
+        throw std::runtime_error("[QuakeIndex::grouped_search()] group_size must be between 1 and " + std::to_string(QK_MAX_GROUP_SIZE));
     if (!sp->filters.empty() || sp->query_filter.defined())
         throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                  "supported by grouped_search");
@@ -352,13 +355,15 @@ shared_ptr<GroupedSearchResult> QueryCoordinator::grouped_search(Tensor x, qk_at
         flt = sp->filter->h;
     }
     const int k = sp->k > 0 ? sp->k : 1;
+    // group_size unset: the one-row shapes [Q, k]; m: ids / distances [Q, k, m]
+    auto shape = [&](int64_t q) { return group_size ? std::vector<int64_t>{q, k, *group_size} : std::vector<int64_t>{q, k}; };
     auto res = std::make_shared<GroupedSearchResult>();
     auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
     ti->search_params = sp;
     ti->n_clusters = partition_manager_->nlist();
     if (!x.defined() || x.size(0) == 0) {
-        res->ids = torch::empty({0, k}, torch::kInt64);
-        res->distances = torch::empty({0, k}, torch::kFloat32);
+        res->ids = torch::empty(shape(0), torch::kInt64);
+        res->distances = torch::empty(shape(0), torch::kFloat32);
         res->groups = torch::empty({0, k}, torch::kInt64);
         return res;
     }
@@ -382,11 +387,16 @@ shared_ptr<GroupedSearchResult> QueryCoordinator::grouped_search(Tensor x, qk_at
     std::memset(&tm, 0, sizeof(tm));
     auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
     auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(xq.device());
-    res->ids = torch::empty({Q, k}, i64);
-    res->distances = torch::empty({Q, k}, f32);
+    res->ids = torch::empty(shape(Q), i64);
+    res->distances = torch::empty(shape(Q), f32);
     res->groups = torch::empty({Q, k}, i64);
-    qk_check(qk_search_grouped(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_, group_by, flt,
-                               res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), res->groups.data_ptr<int64_t>(), mem, &tm));
+    if (group_size)
+        qk_check(qk_search_grouped_n(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, *group_size, (int)metric_,
+                                     group_by, flt, res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), res->groups.data_ptr<int64_t>(),
+                                     mem, &tm));
+    else
+        qk_check(qk_search_grouped(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_, group_by, flt,
+                                   res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), res->groups.data_ptr<int64_t>(), mem, &tm));
     ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
     ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
     ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);

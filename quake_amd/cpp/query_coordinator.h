@@ -38,7 +38,9 @@ public:
     // extension (qk_range_search): all vectors of the nprobe nearest partitions within `radius`, restricted to sp->filter if set
     shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
     // extension (qk_search_grouped): the k best groups of `group_by` -- a column of this index's store, nullptr: unknown -- per query
-    shared_ptr<GroupedSearchResult> grouped_search(Tensor x, qk_attr *group_by, const std::string &name, shared_ptr<SearchParams> search_params);
+    // group_size = m (qk_search_grouped_n): ids / distances [Q, k, m], the m best vectors of every group; unset: the one-row result [Q, k]
+    shared_ptr<GroupedSearchResult> grouped_search(Tensor x, qk_attr *group_by, const std::string &name, shared_ptr<SearchParams> search_params,
+                                                   std::optional<int> group_size = std::nullopt);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

@@ -13,6 +13,15 @@
 //   k_grouped_minid     every candidate whose key is its slot's minimum folds its id into the slot (64-bit atomicMin)
 //   k_grouped_rewrite   every emitted key that is not its slot's (min key, min id) becomes 0xFFFFFFFF
 //   k_grouped_values    groups[q][j] of the selected ids, through the column's lookup
+// group_size = m > 1 (qk_*_grouped_n; DESIGN.md 5.10, "members"): the rewrite leaves the emitted keys alone and fills a second key
+// array for the selection; behind the selection
+//   k_grouped_mark      per (query, j): the value of the selected row finds its slot again, the slot learns j, member 0 goes to
+//                       [q][j][0] of the strided outputs
+//   k_grouped_renumber  every key's slot number becomes the j of its group, or -1 where the group was not selected
+//   per member r = 1 .. m - 1, the floor being member r - 1 of the key's group:
+//   k_grouped_next_key  the smallest key of the group's candidates above the floor (atomicMin)
+//   k_grouped_next_id   the smallest id among those with that key (64-bit atomicMin, straight into out_ids)
+//   k_grouped_member_dist  distances of members 1 .. m - 1 from their keys, by the selection's epilogue rule
 // No thread waits for another: a slot's key and id words hold "nothing yet" (all ones) from the memset on, so whoever finds a value
 // claimed proceeds at once, and the phases are separated by kernel boundaries.  Only commutative minima decide a slot, so the result
 // does not depend on who came first.  The value whose bits are all ones (-1) is the table's empty marker: it owns slot T of every query.
@@ -41,6 +50,12 @@ struct GroupedParams {
     uint32_t *tkeys;           // [nq][T + 1]
     int P, Sg;
     uint32_t tmask;            // T - 1
+    // group_size > 1 only
+    uint32_t *sel_keys;        // the keys the selection reads: keys with every non-representative set to 0xFFFFFFFF (nullptr: in place)
+    int32_t *tsel;             // [nq][T + 1] the j of a selected group, -1 elsewhere
+    uint32_t *mkeys;           // [nq][k][m] key of every member, 0xFFFFFFFF = none
+    int64_t *mids;             // [nq][k][m] out_ids of the pass
+    int k, m, r;               // r: the member a round decides
 };
 
 __device__ __forceinline__ uint32_t grouped_hash(unsigned long long v) {  // (the 64-bit finaliser of MurmurHash3)
@@ -117,8 +132,125 @@ __global__ __launch_bounds__(256) void k_grouped_rewrite(GroupedParams G) {
             const int64_t row = emit_key_row(pbase, qpids, G.P, G.pt_off, pos);
             win = (unsigned long long)G.ids[row] == G.tids[tbase + sl];
         }
-        if (!win && key != 0xFFFFFFFFu) G.keys[pos] = 0xFFFFFFFFu;
+        if (G.sel_keys) G.sel_keys[pos] = win ? key : 0xFFFFFFFFu;
+        else if (!win && key != 0xFFFFFFFFu) G.keys[pos] = 0xFFFFFFFFu;
     }
+}
+
+// ---- group_size > 1: members 1 .. m - 1 of the k selected groups ------------------------------------------------------------------
+struct MarkParams {
+    AttrCol col;
+    const int64_t *sel_ids;             // [nq][k] the selection's result
+    const float *sel_dist;              // [nq][k] or nullptr
+    const unsigned long long *tvals;    // [nq][T + 1]
+    const uint32_t *tkeys;              // [nq][T + 1]
+    int32_t *tsel;                      // [nq][T + 1], cleared to -1
+    uint32_t *mkeys;                    // [nq][k][m], cleared to 0xFFFFFFFF
+    int64_t *out_ids;                   // [nq][k][m], cleared to -1
+    float *out_dist;                    // [nq][k][m] or nullptr
+    int64_t *out_groups;                // [nq][k] or nullptr
+    int64_t n;                          // nq * k
+    int k, m;
+    uint32_t tmask;
+};
+
+// one thread per (query, j).  The slot of the selected row's value is found the way k_grouped_claim found it -- same hash, same
+// bounded walk, read only: the value is in the table because its row claimed it.
+__global__ __launch_bounds__(256) void k_grouped_mark(MarkParams M) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t raw = i < M.n ? M.sel_ids[i] : -1;
+    const bool live[1] = {raw >= 0};
+    const int64_t id[1] = {live[0] ? raw : 0};
+    int64_t v[1];
+    bool has[1];
+    attr_lookup<1>(M.col, id, live, v, has);
+    if (i >= M.n) return;
+    const int64_t q = i / M.k;
+    const int j = (int)(i - q * M.k);
+    const int64_t tbase = q * ((int64_t)M.tmask + 2);
+    if (M.out_groups) M.out_groups[i] = has[0] ? v[0] : 0;
+    if (M.out_dist) M.out_dist[i * M.m] = M.sel_dist[i];
+    if (!has[0]) return;  // padding: every member keeps the cleared words
+    const unsigned long long val = (unsigned long long)v[0];
+    int32_t sl = -1;
+    if (val == GR_EMPTY) {
+        sl = (int32_t)M.tmask + 1;
+    } else {
+        uint32_t h = grouped_hash(val) & M.tmask;
+        for (uint32_t n = 0; n <= M.tmask; n++) {
+            const unsigned long long cur = M.tvals[tbase + h];
+            if (cur == val) {
+                sl = (int32_t)h;
+                break;
+            }
+            if (cur == GR_EMPTY) break;
+            h = (h + 1) & M.tmask;
+        }
+    }
+    M.out_ids[i * M.m] = raw;
+    if (sl >= 0) {
+        M.tsel[tbase + sl] = j;
+        M.mkeys[i * M.m] = M.tkeys[tbase + sl];
+    }
+}
+
+// slot[pos]: the slot of the key's value -> the j of its group among the k selected, -1 for every other key.  The rounds below then
+// drop a key of a group that was not selected after one load.
+__global__ __launch_bounds__(256) void k_grouped_renumber(GroupedParams G) {
+    GROUPED_FOR_EACH_KEY(G) {
+        const int32_t sl = G.slot[pos];
+        if (sl >= 0) G.slot[pos] = G.tsel[tbase + sl];
+    }
+}
+
+// a key of group j qualifies for member r when its (key, id) lies strictly above member r - 1's: the smallest such key
+__global__ __launch_bounds__(256) void k_grouped_next_key(GroupedParams G) {
+    GROUPED_FOR_EACH_KEY(G) {
+        const int32_t j = G.slot[pos];
+        if (j < 0) continue;
+        const int64_t w = ((q * G.k + j) * G.m) + G.r;
+        const uint32_t fkey = G.mkeys[w - 1];
+        if (fkey == 0xFFFFFFFFu) continue;  // the group ran out of rows in an earlier round
+        const uint32_t key = G.keys[pos];
+        if (key < fkey) continue;
+        if (key == fkey) {
+            const int64_t row = emit_key_row(pbase, qpids, G.P, G.pt_off, pos);
+            if ((unsigned long long)G.ids[row] <= (unsigned long long)G.mids[w - 1]) continue;
+        }
+        atomicMin(&G.mkeys[w], key);
+    }
+}
+
+// ... and the smallest id among the qualifying keys that equal it
+__global__ __launch_bounds__(256) void k_grouped_next_id(GroupedParams G) {
+    GROUPED_FOR_EACH_KEY(G) {
+        const int32_t j = G.slot[pos];
+        if (j < 0) continue;
+        const int64_t w = ((q * G.k + j) * G.m) + G.r;
+        const uint32_t key = G.keys[pos];
+        if (key != G.mkeys[w]) continue;
+        const int64_t row = emit_key_row(pbase, qpids, G.P, G.pt_off, pos);
+        const unsigned long long id = (unsigned long long)G.ids[row];
+        if (key == G.mkeys[w - 1] && id <= (unsigned long long)G.mids[w - 1]) continue;
+        atomicMin((unsigned long long *)&G.mids[w], id);
+    }
+}
+
+// distances of members 1 .. m - 1 (the epilogue rule of k_select_pairs_large); member 0 carries the selection's own bits
+__global__ __launch_bounds__(256) void k_grouped_member_dist(const uint32_t *mkeys, int64_t n, int m, int metric, int sqrt_l2, float *out_dist) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || i % m == 0) return;
+    const uint32_t o = mkeys[i];
+    float od = metric == QK_METRIC_IP ? -INFINITY : INFINITY;
+    if (o != 0xFFFFFFFFu) {
+        if (metric == QK_METRIC_L2) {
+            const float d2 = __uint_as_float(o);
+            od = sqrt_l2 ? sqrtf(d2) : d2;
+        } else {
+            od = ip_from_ord(o);
+        }
+    }
+    out_dist[i] = od;
 }
 
 // the value of every selected id; the padding id (negative) and -- it cannot happen -- an id without a value give 0
@@ -261,10 +393,14 @@ int64_t table_slots(int64_t per_query_ub, int64_t n_ids) {
 }  // namespace
 
 // bytes of a pass that one query accounts for (include/quake_hip.h, QK_GROUPED_PASS_BYTES): 8 per key it has room for -- the key and
-// its slot number -- and 20 per table slot
-static inline int64_t grouped_query_bytes(int64_t per_query_ub, int64_t T) { return per_query_ub * 8 + (T + 1) * 20; }
+// its slot number -- and 20 per table slot; with group_size = m > 1, 12 per key (the selection's copy), 24 per slot (the j of a
+// selected group), 12 per result of the one-row selection and 4 per member word
+static inline int64_t grouped_query_bytes(int64_t per_query_ub, int64_t T, int k, int m) {
+    if (m == 1) return per_query_ub * 8 + (T + 1) * 20;
+    return per_query_ub * 12 + (T + 1) * 24 + (int64_t)k * 12 + (int64_t)k * m * 4;
+}
 
-int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data &col, const uint16_t *mask, int64_t *out_groups,
+int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data &col, const uint16_t *mask, int m, int64_t *out_groups,
                       qk_timing *timing, int64_t *n_passes) {
     const int64_t Q = a.Q;
     const int k = a.k;
@@ -280,21 +416,24 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
     if (P <= 0 || npids <= 0) {  // no lists: padding
         QK_TRY(pe.mark(0));
         QK_TRY(qk_prep_flush(ctx));
-        hipLaunchKernelGGL(k_grouped_pad, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, Q * k,
-                           a.metric == QK_METRIC_IP ? -INFINITY : INFINITY, a.out_ids, a.out_dist, out_groups);
+        const int64_t nw = Q * k * m;  // (m > 1: the groups, [Q][k], are cleared apart)
+        hipLaunchKernelGGL(k_grouped_pad, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, nw,
+                           a.metric == QK_METRIC_IP ? -INFINITY : INFINITY, a.out_ids, a.out_dist, m == 1 ? out_groups : nullptr);
         QK_HIP(hipGetLastError());
+        if (m > 1 && out_groups) QK_HIP(hipMemsetAsync(out_groups, 0, (size_t)Q * k * 8, st));
         for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
         return QK_OK;
     }
     int kp = 2;  // (k_select_pairs_large keeps kp keys and kp ids in LDS, the ids behind the keys: kp >= 2 keeps them 8-byte aligned)
     while (kp < k) kp <<= 1;
-    // this pipeline's bytes of the call's buffer, sized for the largest pass: [slots] [table values] [table ids] [table keys]
+    // this pipeline's bytes of the call's buffer, sized for the largest pass: [slots] [table values] [table ids] [table keys], and
+    // for m > 1 [selected j per slot] [the selection's keys] [the selection's ids] [its distances] [member keys]
     int64_t T = 0, S = 0;
-    size_t o_tvals = 0, o_tids = 0, o_tkeys = 0;
+    size_t o_tvals = 0, o_tids = 0, o_tkeys = 0, o_tsel = 0, o_skeys = 0, o_sids = 0, o_sdist = 0, o_mkeys = 0;
     qk_emit_hooks h;
     h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
         T = table_slots(per_query_ub, col.n_ids);
-        const int64_t qbytes = grouped_query_bytes(per_query_ub, T);
+        const int64_t qbytes = grouped_query_bytes(per_query_ub, T, k, m);
         if (qbytes > QK_GROUPED_PASS_BYTES)
             QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: one query needs %lld bytes of workspace, more than QK_GROUPED_PASS_BYTES", (long long)qbytes);
         *qc = std::max<int64_t>(1, std::min<int64_t>(*qc, QK_GROUPED_PASS_BYTES / qbytes));
@@ -305,6 +444,14 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
         o_tids = o_tvals + (size_t)nslots * 8;
         o_tkeys = o_tids + (size_t)nslots * 8;
         *extra_bytes = o_tkeys + (size_t)nslots * 4;
+        if (m > 1) {
+            o_tsel = qk_al256(*extra_bytes);
+            o_skeys = qk_al256(o_tsel + (size_t)nslots * 4);
+            o_sids = qk_al256(o_skeys + (size_t)*qc * per_query_ub * 4 + 256);
+            o_sdist = qk_al256(o_sids + (size_t)*qc * k * 8);
+            o_mkeys = qk_al256(o_sdist + (size_t)*qc * k * 4);
+            *extra_bytes = o_mkeys + (size_t)*qc * k * m * 4;
+        }
         return QK_OK;
     };
     h.before_scan = [&](const qk_emit_pass &p) -> int {
@@ -330,6 +477,13 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
         G.tkeys = (uint32_t *)(p.extra + o_tkeys);
         G.P = P;
         G.tmask = (uint32_t)(T - 1);
+        G.sel_keys = m > 1 ? (uint32_t *)(p.extra + o_skeys) : nullptr;
+        G.tsel = (int32_t *)(p.extra + o_tsel);
+        G.mkeys = (uint32_t *)(p.extra + o_mkeys);
+        G.mids = a.out_ids + p.q0 * k * m;
+        G.k = k;
+        G.m = m;
+        G.r = 0;
         // about 16384 workgroups per pass, whatever S is
         G.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));
         const unsigned grid = (unsigned)(p.nq * G.Sg);
@@ -337,11 +491,47 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
         hipLaunchKernelGGL(k_grouped_minid, dim3(grid), dim3(256), 0, st, G);
         hipLaunchKernelGGL(k_grouped_rewrite, dim3(grid), dim3(256), 0, st, G);
         QK_HIP(hipGetLastError());
-        return qk_launch_select_pairs(ctx, s, p.keys, p.pair_base, p.pids, p.nq, P, k, kp, a.metric, a.sqrt_l2, a.out_ids + p.q0 * k,
-                                      a.out_dist ? a.out_dist + p.q0 * k : nullptr);
+        if (m == 1)
+            return qk_launch_select_pairs(ctx, s, p.keys, p.pair_base, p.pids, p.nq, P, k, kp, a.metric, a.sqrt_l2, a.out_ids + p.q0 * k,
+                                          a.out_dist ? a.out_dist + p.q0 * k : nullptr);
+        // ---- members: the one-row selection into the workspace, then member 0 into place and a round per further member ----------
+        int64_t *sids = (int64_t *)(p.extra + o_sids);
+        float *sdist = a.out_dist ? (float *)(p.extra + o_sdist) : nullptr;
+        QK_TRY(qk_launch_select_pairs(ctx, s, G.sel_keys, p.pair_base, p.pids, p.nq, P, k, kp, a.metric, a.sqrt_l2, sids, sdist));
+        const int64_t nw = p.nq * k * m;  // member words of the pass
+        float *mdist = a.out_dist ? a.out_dist + p.q0 * k * m : nullptr;
+        QK_HIP(hipMemsetAsync(G.tsel, 0xFF, (size_t)p.nq * (T + 1) * 4, st));
+        QK_HIP(hipMemsetAsync(G.mkeys, 0xFF, (size_t)nw * 4, st));
+        QK_HIP(hipMemsetAsync(G.mids, 0xFF, (size_t)nw * 8, st));
+        MarkParams M;
+        M.col = col_of(col);
+        M.sel_ids = sids;
+        M.sel_dist = sdist;
+        M.tvals = G.tvals;
+        M.tkeys = G.tkeys;
+        M.tsel = G.tsel;
+        M.mkeys = G.mkeys;
+        M.out_ids = G.mids;
+        M.out_dist = mdist;
+        M.out_groups = out_groups ? out_groups + p.q0 * k : nullptr;
+        M.n = p.nq * k;
+        M.k = k;
+        M.m = m;
+        M.tmask = G.tmask;
+        hipLaunchKernelGGL(k_grouped_mark, dim3((unsigned)((M.n + 255) / 256)), dim3(256), 0, st, M);
+        hipLaunchKernelGGL(k_grouped_renumber, dim3(grid), dim3(256), 0, st, G);
+        for (G.r = 1; G.r < m; G.r++) {
+            hipLaunchKernelGGL(k_grouped_next_key, dim3(grid), dim3(256), 0, st, G);
+            hipLaunchKernelGGL(k_grouped_next_id, dim3(grid), dim3(256), 0, st, G);
+        }
+        if (mdist)
+            hipLaunchKernelGGL(k_grouped_member_dist, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, (const uint32_t *)G.mkeys, nw, m,
+                               a.metric, a.sqrt_l2 ? 1 : 0, mdist);
+        QK_HIP(hipGetLastError());
+        return QK_OK;
     };
     QK_TRY(qk_emit_passes(ctx, s, a, P, "grouped search", pe, h, n_passes));
-    if (out_groups) {
+    if (out_groups && m == 1) {
         hipLaunchKernelGGL(k_grouped_values, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, col_of(col), (const int64_t *)a.out_ids,
                            Q * k, out_groups);
         QK_HIP(hipGetLastError());
@@ -356,7 +546,7 @@ namespace {
 
 // the body of both entry points: parent == nullptr && pids == nullptr -> every list
 int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
-                int k, int metric, qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
+                int k, int m, int metric, qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
                 qk_timing *timing) {
     if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
     if (!group_by) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column is null", who);
@@ -364,6 +554,8 @@ int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, con
     if (col.store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column belongs to another store", who);
     if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
     if (k > QK_MAX_WIDE_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds %d", who, k, QK_MAX_WIDE_K);
+    if (m < 1) QK_FAIL(QK_ERR_INVALID, "%s: group_size=%d must be at least 1", who, m);
+    if (m > QK_MAX_GROUP_SIZE) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: group_size=%d exceeds QK_MAX_GROUP_SIZE=%d", who, m, QK_MAX_GROUP_SIZE);
     if (Q < 0 || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
     QK_TRY(qk_check_overflow(ctx));
     QK_HIP(hipSetDevice(ctx->device));
@@ -371,17 +563,17 @@ int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, con
     if (Q == 0) return QK_OK;
     hipStream_t st = ctx->stream;
     // ---- staging, query preparation, coarse; a host caller's outputs on the device: [ids] [groups] [distances] ---------------------
-    const size_t bi = qk_al256((size_t)Q * k * 8), bd = qk_al256((size_t)Q * k * 4);
+    const size_t bi = qk_al256((size_t)Q * k * m * 8), bg = qk_al256((size_t)Q * k * 8), bd = qk_al256((size_t)Q * k * m * 4);
     qk_scan_args sa;
     char *out = nullptr;
     bool have_coarse = false;
-    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, 2 * bi + bd, timing != nullptr, &sa, &out, &have_coarse));
+    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, bi + bg + bd, timing != nullptr, &sa, &out, &have_coarse));
     int64_t *dids = out_ids, *dgroups = out_groups;
     float *ddist = out_dist;
     if (mem == QK_MEM_HOST) {
         dids = (int64_t *)out;
         dgroups = out_groups ? (int64_t *)(out + bi) : nullptr;
-        ddist = out_dist ? (float *)(out + 2 * bi) : nullptr;
+        ddist = out_dist ? (float *)(out + bi + bg) : nullptr;
     }
     sa.k = k;
     sa.out_ids = dids;
@@ -392,12 +584,12 @@ int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, con
     QK_TRY(qk_store_sync_table(s));
     QK_TRY(rowvals_ensure(ctx, s, col));
     int64_t n_passes = 0;
-    QK_TRY(qk_grouped_device(ctx, s, sa, col, mask, dgroups, timing, &n_passes));
+    QK_TRY(qk_grouped_device(ctx, s, sa, col, mask, m, dgroups, timing, &n_passes));
     // ---- results back ------------------------------------------------------------------------------------------------------------
     if (mem == QK_MEM_HOST) {
-        QK_HIP(hipMemcpyAsync(out_ids, dids, (size_t)Q * k * 8, hipMemcpyDeviceToHost, st));
+        QK_HIP(hipMemcpyAsync(out_ids, dids, (size_t)Q * k * m * 8, hipMemcpyDeviceToHost, st));
         if (out_groups) QK_HIP(hipMemcpyAsync(out_groups, dgroups, (size_t)Q * k * 8, hipMemcpyDeviceToHost, st));
-        if (out_dist) QK_HIP(hipMemcpyAsync(out_dist, ddist, (size_t)Q * k * 4, hipMemcpyDeviceToHost, st));
+        if (out_dist) QK_HIP(hipMemcpyAsync(out_dist, ddist, (size_t)Q * k * m * 4, hipMemcpyDeviceToHost, st));
         QK_HIP(hipStreamSynchronize(st));
     }
     if (timing) {
@@ -414,20 +606,30 @@ int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, con
 
 extern "C" {
 
-int qk_search_grouped(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric, qk_attr *group_by,
-                      qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
+int qk_search_grouped_n(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int group_size, int metric,
+                        qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_search_grouped: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_grouped: nprobe must be positive");
-    return grouped_run("qk_search_grouped", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, group_by, filter, out_ids, out_dist, out_groups,
-                       mem, timing);
+    return grouped_run("qk_search_grouped", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, group_size, metric, group_by, filter, out_ids, out_dist,
+                       out_groups, mem, timing);
+}
+
+int qk_scan_grouped_n(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int group_size, int metric,
+                      qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: null argument");
+    if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: bad partition id list");
+    return grouped_run("qk_scan_grouped", ctx, nullptr, s, x, Q, pids, P, 0, k, group_size, metric, group_by, filter, out_ids, out_dist,
+                       out_groups, mem, timing);
+}
+
+int qk_search_grouped(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric, qk_attr *group_by,
+                      qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
+    return qk_search_grouped_n(ctx, parent, s, x, Q, nprobe, k, 1, metric, group_by, filter, out_ids, out_dist, out_groups, mem, timing);
 }
 
 int qk_scan_grouped(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric, qk_attr *group_by,
                     qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
-    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: null argument");
-    if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: bad partition id list");
-    return grouped_run("qk_scan_grouped", ctx, nullptr, s, x, Q, pids, P, 0, k, metric, group_by, filter, out_ids, out_dist, out_groups, mem,
-                       timing);
+    return qk_scan_grouped_n(ctx, s, x, Q, pids, P, k, 1, metric, group_by, filter, out_ids, out_dist, out_groups, mem, timing);
 }
 
 int qk_attr_group_info(qk_attr *a, int64_t *builds, int64_t *device_bytes) {

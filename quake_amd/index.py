@@ -254,9 +254,13 @@ class RangeSearchResult:
         self.timing_info = None
 
 
+MAX_GROUP_SIZE = 16  # QK_MAX_GROUP_SIZE (include/quake_hip.h)
+
+
 class GroupedSearchResult:
     """extension (QuakeIndex.grouped_search): the k best groups of a column per query -- ids / distances [Q, k] of each group's best
-    vector, groups [Q, k] the group values (0 where ids is the padding id -1)"""
+    vector, groups [Q, k] the group values (0 where ids is the padding id -1).  With group_size = m: ids / distances [Q, k, m],
+    the m best vectors of every group"""
 
     def __init__(self):
         self.ids = None
@@ -722,13 +726,18 @@ class QuakeIndex:
         res.distances = dist if on_dev else dist.cpu()
         return res
 
-    def grouped_search(self, x, group_by, search_params):
+    def grouped_search(self, x, group_by, search_params, group_size=None):
         """extension (no reference counterpart): the search_params.k best GROUPS of the attribute column `group_by` among the vectors
         of the search_params.nprobe nearest partitions, every group represented by its best vector (restricted to
         search_params.filter if one is set: then by its best allowed vector).  A vector without a value in the column is no
-        candidate.  Exact; the values are those of the moment of the call.  Returns a GroupedSearchResult on x's device."""
+        candidate.  Exact; the values are those of the moment of the call.  Returns a GroupedSearchResult on x's device.
+        group_size = m (1 <= m <= 16): ids / distances are [Q, k, m], the m best vectors of every group under (distance, id),
+        padded with -1 / the worst distance where a group has fewer."""
         self._require_built("[QuakeIndex::grouped_search()] No query coordinator. Did you build the index?")
         sp = search_params
+        if group_size is not None and not 1 <= int(group_size) <= MAX_GROUP_SIZE:
+            raise RuntimeError("[QuakeIndex::grouped_search()] group_size must be between 1 and %d" % MAX_GROUP_SIZE)
+        shape = (lambda q: (q, k)) if group_size is None else (lambda q: (q, k, int(group_size)))
         if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
             raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                "supported by grouped_search")
@@ -755,8 +764,8 @@ class QuakeIndex:
         t0 = time.perf_counter()
         nq = 0 if x is None else int(x.shape[0])
         if nq == 0:
-            res.ids = torch.empty((0, k), dtype=torch.int64)
-            res.distances = torch.empty((0, k), dtype=torch.float32)
+            res.ids = torch.empty(shape(0), dtype=torch.int64)
+            res.distances = torch.empty(shape(0), dtype=torch.float32)
             res.groups = torch.empty((0, k), dtype=torch.int64)
             return res
         on_dev = x.is_cuda
@@ -765,7 +774,8 @@ class QuakeIndex:
         self._ctx.set_timing(1)
         try:
             ids, dist, groups, tm = self._ctx.search_grouped(self.parent._store if self.parent is not None else None, self._store, xd,
-                                                             nprobe, k, self.metric_, cols[group_by], filter=flt, timing=True)
+                                                             nprobe, k, self.metric_, cols[group_by], filter=flt, timing=True,
+                                                             group_size=group_size)
         finally:
             self._ctx.set_timing(0)
         ti.n_queries = nq
