@@ -475,6 +475,40 @@ QK_API int qk_scan_grouped_n(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q
  * device_bytes: HBM they hold (not part of qk_attr_info).  Either pointer may be NULL. */
 QK_API int qk_attr_group_info(qk_attr *a, int64_t *builds, int64_t *device_bytes);
 
+/* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
+ * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
+ * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.
+ *   Candidates of query i with cursor (ck, cid): the rows of the probed lists whose key is not 0xFFFFFFFF and whose (key, id) >
+ *     (ck, cid) lexicographically -- unsigned key, signed id -- and which `filter` (may be NULL) allows.
+ *   Probed lists: the unfiltered qk_search's (the same min(nprobe, parent lists) in the same rank order; every list when parent ==
+ *     NULL); qk_scan_after: the pids row, as qk_scan.
+ *   The page: the k smallest candidates in (key, id) order, padded with id -1 and distance +inf (L2) / -inf (IP) as qk_search pads.
+ *   Start cursor: (0, -1) lies below every row.  after_key == after_id == NULL means that cursor for every query; the page then
+ *     equals qk_search's (qk_search_filtered's) bit for bit, ids and distances.
+ *   Next cursor: a row that holds k results -> the (key, id) of its k-th, the key being the integer the merge compared (not
+ *     re-derived from the reported distance: sqrt is not injective in fp32); fewer, or none -> the exhausted cursor
+ *     (0xFFFFFFFF, INT64_MAX), behind which every page is padding.
+ * So pages of any sizes chained from the start cursor concatenate to a prefix of the full ordering; after qk_store_add_* /
+ * remove between two pages the later page holds the then-current rows behind the cursor and no row is returned twice for one
+ * query; the queries of a batch may sit at different depths.  A page costs one filtered-form search whatever its depth: it works
+ * under a filter, where k > QK_MAX_K has no other route, and it has no depth limit.
+ * after_key / next_key: uint32 [Q], after_id / next_id: int64 [Q], all in `mem`; next_* may alias after_* and may both be NULL.
+ * 1 <= k <= QK_MAX_K (QK_ERR_UNSUPPORTED beyond).  QK_ERR_INVALID: exactly one of after_key / after_id (of next_key / next_id) is
+ * NULL; the filter belongs to another store.  There is no paged form of the per-query filter tables, of adaptive probing, of
+ * qk_search_aps or of the device group.
+ * The scan is the filtered call's: k_scan_after / k_scan_wide_after -- the filtered tile form with the cursor test in its
+ * epilogue, qk_ctx_last_scan_kernel names "k_scan (after)" / "k_scan_wide (after)" -- without bound seeding: the k nearest rows
+ * of a later page all lie before the cursor and must not set a bound.  Without a filter the same kernels run under a deny-nothing
+ * filter the store keeps (made by the first such call: a few allocations once per store; counted by neither
+ * qk_store_device_bytes nor any qk_filter_info).  k_next_cursor writes the next cursors behind the merge.  One enqueue: with
+ * device memory nothing waits for the stream unless `timing` is given. */
+QK_API int qk_search_after(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,
+                           const uint32_t *after_key, const int64_t *after_id, qk_filter *filter, int64_t *out_ids, float *out_dist,
+                           uint32_t *next_key, int64_t *next_id, int mem, qk_timing *timing);
+QK_API int qk_scan_after(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int metric,
+                         const uint32_t *after_key, const int64_t *after_id, qk_filter *filter, int64_t *out_ids, float *out_dist,
+                         uint32_t *next_key, int64_t *next_id, int mem, qk_timing *timing);
+
 /* QueryCoordinator::search with SearchParams::recall_target > 0 and batched_scan == false: adaptive partition
  * scanning (query_coordinator.cpp:612-657 picks M = max((int)(nlist * initial_search_fraction), 1) candidate partitions
  * from the parent; the use_aps branch of serial_scan, :471-611, scans them in rank order and stops a query once the

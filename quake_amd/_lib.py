@@ -91,6 +91,9 @@ SIGNATURES = {
     "qk_search_filtered_tracked": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _int,
                                    C.POINTER(QkTiming)]),
     "qk_scan_filtered": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    # paged search: (.., metric, after_key, after_id, filter, out_ids, out_dist, next_key, next_id, mem, timing)
+    "qk_search_after": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_scan_after": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search_filtered_batch": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, C.POINTER(_vp), _int, _vp, _vp, _vp, _int,
                                  C.POINTER(QkTiming)]),
     "qk_search_filtered_batch_tracked": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, C.POINTER(_vp), _int, _vp, _vp, _vp, _vp,
@@ -164,6 +167,17 @@ SIGNATURES = {
 }
 
 _lib = None
+
+
+def header_constant(name):
+    """the value of an integer `#define name value` of include/quake_hip.h: limits the mirrors check before they call are read
+    from the header the library was built from, not repeated by hand"""
+    import re
+    txt = open(os.path.join(os.path.dirname(HERE), "include", "quake_hip.h")).read()
+    m = re.search(r"^#define\s+%s\s+(\d+)\b" % re.escape(name), txt, re.M)
+    if not m:
+        raise KeyError(name + " is not an integer constant of include/quake_hip.h")
+    return int(m.group(1))
 
 
 def load():

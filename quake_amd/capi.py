@@ -312,6 +312,68 @@ class Context:
             out_p = out_p[:, :width]
         return out_i, out_d, out_n, out_p, timing_dict(t)
 
+    # ---- paged search ---------------------------------------------------------------------------------
+    def _after(self, after, x):
+        """the (keys, ids) of a cursor in x's memory space -- keys int32 holding the uint32 bit pattern, ids int64, one entry per
+        query; either may be None (the C ABI then says what it thinks of one without the other)"""
+        if after is None:
+            return None, None
+        keys, ids = after
+        Q = x.shape[0]
+        if keys is not None:
+            if not _is_torch(keys):
+                keys = np.ascontiguousarray(keys)
+                if keys.dtype == np.uint32:
+                    keys = keys.view(np.int32)
+            keys = _i32_with(keys, x)
+        if ids is not None:
+            if _is_torch(x) and x.is_cuda:
+                import torch
+                ids = ids if _is_torch(ids) else torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64))
+                ids = ids.reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
+            else:
+                ids = _i64(ids.detach().cpu().numpy() if _is_torch(ids) else ids).reshape(-1)
+        for a in (keys, ids):
+            if a is not None and a.shape[0] != Q:
+                raise ValueError("a cursor has one entry per query: %d != %d" % (a.shape[0], Q))
+        return keys, ids
+
+    def search_after(self, parent, store, x, nprobe, k, metric, after=None, filter=None, timing=False):
+        """qk_search_after: the page of k results behind every query's cursor, in (key, id) order over the lists search() probes.
+        after: (keys, ids) as a call returned them, or None = from the start (the page is then search()'s, bit for bit).
+        filter: a Filter of `store`.  Returns (ids, dist, (next_keys, next_ids)[, timing]); keys are int32 arrays / tensors that
+        hold the uint32 bit pattern, a row with fewer than k results leaves the exhausted cursor (0xFFFFFFFF, INT64_MAX)."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        ak, ai = self._after(after, x)
+        out_i = _empty_like_mem((Q, k), np.int64, x)
+        out_d = _empty_like_mem((Q, k), np.float32, x)
+        nk, ni = _empty_like_mem((Q,), np.int32, x), _empty_like_mem((Q,), np.int64, x)
+        t = QkTiming()
+        check(self.lib.qk_search_after(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), int(k),
+                                       metric_code(metric), _ptr(ak), _ptr(ai), filter.h if filter is not None else None, _ptr(out_i),
+                                       _ptr(out_d), _ptr(nk), _ptr(ni), mem, C.byref(t) if timing else None))
+        return (out_i, out_d, (nk, ni), timing_dict(t)) if timing else (out_i, out_d, (nk, ni))
+
+    def scan_after(self, store, x, pids, k, metric, after=None, filter=None, timing=False):
+        """qk_scan_after: search_after over the given lists (pids as in scan())"""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        if pids.ndim == 1:
+            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
+                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        mem = _mem_of(x, pids)
+        ak, ai = self._after(after, x)
+        out_i = _empty_like_mem((Q, k), np.int64, x)
+        out_d = _empty_like_mem((Q, k), np.float32, x)
+        nk, ni = _empty_like_mem((Q,), np.int32, x), _empty_like_mem((Q,), np.int64, x)
+        t = QkTiming()
+        check(self.lib.qk_scan_after(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), int(k),
+                                     metric_code(metric), _ptr(ak), _ptr(ai), filter.h if filter is not None else None, _ptr(out_i),
+                                     _ptr(out_d), _ptr(nk), _ptr(ni), mem, C.byref(t) if timing else None))
+        return (out_i, out_d, (nk, ni), timing_dict(t)) if timing else (out_i, out_d, (nk, ni))
+
     # ---- range search ---------------------------------------------------------------------------------
     def _range(self, call, x, cap, timing, out):
         """the capacity protocol of qk_range_search / qk_range_scan around `call(cap, lims, ids, dist, timing)`: with cap=None a

@@ -116,6 +116,9 @@ PYBIND11_MODULE(_bindings, m) {
         .def("unset_attribute", &QuakeIndex::unset_attribute, py::arg("name"), py::arg("ids"))
         .def("get_attribute", &QuakeIndex::get_attribute, py::arg("name"), py::arg("ids"), "(values int64 [n], found bool [n])")
         .def("attribute_names", &QuakeIndex::attribute_names)
+        .def("search_after", &QuakeIndex::search_after, py::arg("x"), py::arg("search_params"), py::arg("cursor") = nullptr,
+             "extension: the page of search_params.k results behind `cursor` (a SearchResult.cursor of the same queries; None: from the "
+             "start); the result's .cursor continues behind it.  Records no hits for maintenance")
         .def("range_search", &QuakeIndex::range_search, py::arg("x"), py::arg("radius"), py::arg("search_params"),
              "extension: every vector of the nprobe nearest partitions within `radius` of each query (lims, ids, distances)")
         .def("grouped_search", &QuakeIndex::grouped_search, py::arg("x"), py::arg("group_by"), py::arg("search_params"),
@@ -324,6 +327,19 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("groups", &GroupedSearchResult::groups)
         .def_readwrite("timing_info", &GroupedSearchResult::timing_info);
 
+    py::class_<SearchCursor, std::shared_ptr<SearchCursor>>(m, "SearchCursor")
+        .def(py::init([](py::object keys, py::object ids) {  // (None: left undefined -- search_after refuses such a cursor)
+                 auto c = std::make_shared<SearchCursor>();
+                 if (!keys.is_none()) c->keys = keys.cast<Tensor>();
+                 if (!ids.is_none()) c->ids = ids.cast<Tensor>();
+                 return c;
+             }), py::arg("keys"), py::arg("ids"))
+        .def_property("keys", [](const SearchCursor &c) -> py::object { return c.keys.defined() ? py::cast(c.keys) : py::none(); },
+                      [](SearchCursor &c, py::object v) { c.keys = v.is_none() ? Tensor() : v.cast<Tensor>(); })
+        .def_property("ids", [](const SearchCursor &c) -> py::object { return c.ids.defined() ? py::cast(c.ids) : py::none(); },
+                      [](SearchCursor &c, py::object v) { c.ids = v.is_none() ? Tensor() : v.cast<Tensor>(); })
+        .def("__len__", [](const SearchCursor &c) { return c.ids.defined() ? c.ids.numel() : (int64_t)0; });
+
     py::class_<SearchResult, std::shared_ptr<SearchResult>>(m, "SearchResult")
         .def(py::init<>())
         .def_readwrite("ids", &SearchResult::ids)
@@ -335,5 +351,6 @@ PYBIND11_MODULE(_bindings, m) {
                 if (!r.nprobed.defined()) return py::none();
                 return py::cast(r.nprobed);
             },
-            [](SearchResult &r, py::object v) { r.nprobed = v.is_none() ? Tensor() : v.cast<Tensor>(); });
+            [](SearchResult &r, py::object v) { r.nprobed = v.is_none() ? Tensor() : v.cast<Tensor>(); })
+        .def_readwrite("cursor", &SearchResult::cursor);  // extension: the SearchCursor behind a search_after page, else None
 }

@@ -122,11 +122,20 @@ struct MaintenanceTimingInfo {  // common.h:233-241
             split_refine_time_us = 0, total_time_us = 0;
 };
 
+// extension (QuakeIndex::search_after): one position per query in the total order (key, id) of its results -- keys int32 [Q] holding
+// the uint32 bit pattern of the integer key the top-k compares, ids int64 [Q].  A position, not a snapshot: it stays valid across
+// add / remove / maintenance.  (0, -1) is the start, (0xFFFFFFFF, INT64_MAX) an exhausted query
+struct SearchCursor {
+    Tensor keys;
+    Tensor ids;
+};
+
 struct SearchResult {  // common.h:243-247
     Tensor ids;
     Tensor distances;
     shared_ptr<SearchTimingInfo> timing_info;
     Tensor nprobed;  // extension: int32 [Q] partitions probed per query under SearchParams::max_nprobe, else undefined
+    shared_ptr<SearchCursor> cursor = nullptr;  // extension: the cursor behind this page (QuakeIndex::search_after), else null
 };
 
 // extension (QuakeIndex::range_search): query i's hits are ids / distances [lims[i], lims[i+1]), in scan order

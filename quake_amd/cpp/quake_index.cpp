@@ -125,6 +125,11 @@ shared_ptr<SearchResult> QuakeIndex::search(Tensor x, shared_ptr<SearchParams> s
     return query_coordinator_->search(x, sp);
 }
 
+shared_ptr<SearchResult> QuakeIndex::search_after(Tensor x, shared_ptr<SearchParams> sp, shared_ptr<SearchCursor> cursor) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::search_after()] No query coordinator. Did you build the index?");
+    return query_coordinator_->search_after(x, sp, cursor);
+}
+
 shared_ptr<RangeSearchResult> QuakeIndex::range_search(Tensor x, float radius, shared_ptr<SearchParams> sp) {
     if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::range_search()] No query coordinator. Did you build the index?");
     return query_coordinator_->range_search(x, radius, sp);

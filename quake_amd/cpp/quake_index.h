@@ -72,6 +72,9 @@ public:
     void unset_attribute(const std::string &name, Tensor ids);
     std::pair<Tensor, Tensor> get_attribute(const std::string &name, Tensor ids);  // (values int64 [n], found bool [n])
     std::vector<std::string> attribute_names();
+    // extension: the page of search_params->k results behind `cursor` (null: from the start); pages chained from the start concatenate
+    // to what search() with a larger k returns (qk_search_after).  Records no hits for maintenance
+    shared_ptr<SearchResult> search_after(Tensor x, shared_ptr<SearchParams> search_params, shared_ptr<SearchCursor> cursor = nullptr);
     // extension: every vector of the search_params->nprobe nearest partitions within `radius` of each query (qk_range_search)
     shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
     // extension: the search_params->k best groups of attribute column `group_by` among the vectors of the nprobe nearest partitions,

@@ -260,6 +260,94 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
     return res;
 }
 
+shared_ptr<SearchResult> QueryCoordinator::search_after(Tensor x, shared_ptr<SearchParams> sp, shared_ptr<SearchCursor> cursor) {
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::search_after] partition_manager_ is null.");
+    if (!sp->filters.empty() || sp->query_filter.defined())
+        throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.filters / query_filter (one filter per query) are not "
+                                 "supported by search_after");
+    if (sp->max_nprobe > 0)
+        throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.max_nprobe (adaptive probing) is not supported by "
+                                 "search_after: a page is defined over a fixed set of probed partitions");
+    if (sp->recall_target > 0.0f) throw std::runtime_error("[QuakeIndex::search_after()] search_after is not supported with recall_target > 0");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group()) throw std::runtime_error("[QuakeIndex::search_after()] search_after is not supported with num_workers > 0");
+    if (!store) throw std::runtime_error("[QueryCoordinator::search_after] partitions are not initialized.");
+    qk_filter *flt = nullptr;
+    if (sp->filter) {
+        if (!sp->filter->h) throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.filter must come from make_filter()");
+        if (sp->filter->owner != store) throw std::runtime_error("[QuakeIndex::search_after()] the filter was made for another index");
+        flt = sp->filter->h;
+    }
+    const int k = sp->k > 0 ? sp->k : 1;
+    if (k > QK_MAX_K)
+        throw std::runtime_error("[QuakeIndex::search_after()] k=" + std::to_string(k) + " exceeds the page limit of " + std::to_string(QK_MAX_K) +
+                                 ": ask for the rest with the next cursor");
+    const int64_t Q = x.defined() ? x.size(0) : 0;
+    if (cursor) {
+        if (!cursor->keys.defined() || !cursor->ids.defined())
+            throw std::runtime_error("[QuakeIndex::search_after()] cursor must be the SearchCursor of an earlier page (keys and ids)");
+        if (cursor->keys.numel() != Q || cursor->ids.numel() != Q)
+            throw std::runtime_error("[QuakeIndex::search_after()] the cursor has " + std::to_string(cursor->keys.numel()) + " / " +
+                                     std::to_string(cursor->ids.numel()) + " entries for " + std::to_string(Q) + " queries");
+    }
+    auto res = std::make_shared<SearchResult>();
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->search_params = sp;
+    ti->n_clusters = partition_manager_->nlist();
+    res->cursor = std::make_shared<SearchCursor>();
+    if (Q == 0) {
+        res->ids = torch::empty({0}, torch::kInt64);
+        res->distances = torch::empty({0}, torch::kFloat32);
+        res->cursor->keys = torch::empty({0}, torch::kInt32);
+        res->cursor->ids = torch::empty({0}, torch::kInt64);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x);
+    BoundToTorchStream bound(ctx, xq);
+    const int nprobe = std::max(sp->nprobe, 1);
+    const int mem = on_dev ? QK_MEM_DEVICE : QK_MEM_HOST;
+    ti->n_queries = Q;
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto opt = [&](torch::ScalarType t) { return torch::TensorOptions().dtype(t).device(xq.device()); };
+    res->ids = torch::empty({Q, (int64_t)k}, opt(torch::kInt64));
+    res->distances = torch::empty({Q, (int64_t)k}, opt(torch::kFloat32));
+    res->cursor->keys = torch::empty({Q}, opt(torch::kInt32));
+    res->cursor->ids = torch::empty({Q}, opt(torch::kInt64));
+    Tensor ak, ai;  // the caller's cursor in the queries' memory space
+    if (cursor) {
+        ak = cursor->keys.reshape({Q}).to(opt(torch::kInt32)).contiguous();
+        ai = cursor->ids.reshape({Q}).to(opt(torch::kInt64)).contiguous();
+    }
+    qk_check(qk_search_after(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, k, (int)metric_,
+                             cursor ? (const uint32_t *)ak.data_ptr<int32_t>() : nullptr, cursor ? ai.data_ptr<int64_t>() : nullptr, flt,
+                             res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), (uint32_t *)res->cursor->keys.data_ptr<int32_t>(),
+                             res->cursor->ids.data_ptr<int64_t>(), mem, &tm));
+    ti->partitions_scanned = (int)tm.partitions_scanned;
+    ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    if (parent_) {
+        ti->parent_info = std::make_shared<SearchTimingInfo>();
+        ti->parent_info->n_queries = Q;
+        ti->parent_info->n_clusters = 1;
+        ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
+    }
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
 shared_ptr<RangeSearchResult> QueryCoordinator::range_search(Tensor x, float radius, shared_ptr<SearchParams> sp) {
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::range_search] partition_manager_ is null.");
     if (!sp->filters.empty() || sp->query_filter.defined())

@@ -35,6 +35,9 @@ public:
     ~QueryCoordinator();
 
     shared_ptr<SearchResult> search(Tensor x, shared_ptr<SearchParams> search_params);
+    // extension (qk_search_after): the page of sp->k results behind `cursor` (null: from the start) among the nprobe nearest partitions,
+    // restricted to sp->filter if set; the result's cursor continues behind it.  Records no hits for maintenance
+    shared_ptr<SearchResult> search_after(Tensor x, shared_ptr<SearchParams> search_params, shared_ptr<SearchCursor> cursor);
     // extension (qk_range_search): all vectors of the nprobe nearest partitions within `radius`, restricted to sp->filter if set
     shared_ptr<RangeSearchResult> range_search(Tensor x, float radius, shared_ptr<SearchParams> search_params);
     // extension (qk_search_grouped): the k best groups of `group_by` -- a column of this index's store, nullptr: unknown -- per query

@@ -63,7 +63,8 @@ int check_metric(int metric) {
 // `timing` are requested but read later, by qk_finish_timing, once every member of the group has been enqueued.
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
-                  bool defer_finish, int64_t *probed_out, qk_filter *filter, const qk_filter_batch *fbatch, const qk_adaptive *adaptive) {
+                  bool defer_finish, int64_t *probed_out, qk_filter *filter, const qk_filter_batch *fbatch, const qk_adaptive *adaptive,
+                  const qk_cursors *cursors) {
     QK_TRY(qk_check_overflow(ctx));  // a record-buffer overflow of an earlier launch is reported by the next call
     QK_HIP(hipSetDevice(ctx->device));
     if (timing) memset(timing, 0, sizeof(*timing));
@@ -236,6 +237,12 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
         sa.sqrt_l2 = !ctx->squared_l2;
         // filtered search: the row mask, re-derived here (on this stream, in front of the scan) if the store changed
         if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &sa.mask));
+        if (cursors) {  // paged search
+            sa.after_key = cursors->after_key;
+            sa.after_id = cursors->after_id;
+            sa.next_key = cursors->next_key;
+            sa.next_id = cursors->next_id;
+        }
         if (fbatch) {
             // one filter per query: every mask brought up to date, then the table of their pointers and their union (kept on the
             // context while nothing changes); a host qfilter -- range-checked by the entry point -- goes to the device behind them

@@ -33,6 +33,13 @@ __device__ __forceinline__ float ip_from_ord(uint32_t o) {
     uint32_t b = (asc & 0x80000000u) ? (asc ^ 0x80000000u) : ~asc;
     return __uint_as_float(b);
 }
+// paged search (qk_after.hip): does (key, id) lie behind the cursor (ck, cid) -- key > ck, or key == ck and id > cid?  Written as
+// one comparison without a branch: the key against ck, or against ck + 1 where the id does not pass (in 64 bits: ck + 1 may be
+// 2^32, which no key reaches -- nothing lies behind the exhausted cursor 0xFFFFFFFF, INT64_MAX)
+__device__ __forceinline__ bool qk_behind_cursor(uint32_t key, int64_t id, uint32_t ck, int64_t cid) {
+    const uint64_t first = (uint64_t)ck + (id > cid ? 0u : 1u);
+    return (uint64_t)key >= first;
+}
 // faiss::knn_L2sqr expansion, clamped at 0 (oracle: l2sqr_expanded)
 __device__ __forceinline__ float l2_expanded(float xn, float yn, float ip) {
     float r = __fmaf_rn(-2.0f, ip, xn + yn);

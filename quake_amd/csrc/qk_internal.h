@@ -190,6 +190,10 @@ struct qk_ctx {
     std::vector<uint64_t> fb_ckey;
     const int32_t **fb_ctable = nullptr;  // [fb_ctable_cap]
     int64_t fb_ctable_cap = 0;
+    // paged search (qk_after.hip): device copies of a call's cursors -- a host caller's arrays, or the start cursor of a call
+    // that names none -- and the next cursors on their way back to a host caller
+    char *after_buf = nullptr;
+    size_t after_cap = 0;
 };
 
 int qk_ws_reserve(qk_ctx *ctx, size_t bytes);          // make sure the workspace can hold `bytes` (may sync+realloc)
@@ -254,6 +258,9 @@ struct qk_store {
     QkIdMap id_to_list;
     std::vector<uint64_t> kill_bits;  // scratch of remove_ids: one bit per id of [min_id_seen, max_id_seen], zero between calls
     bool index_valid = false;
+    // paged search without a filter (qk_after.hip): a deny-nothing filter of this store, made by the first such call and kept; like
+    // every filter it follows add / remove / maintenance through qk_filter_ensure
+    qk_filter *allow_all = nullptr;
 };
 void qk_store_ensure_index(qk_store *s);
 int qk_store_add_batch_host_assign(qk_store *s, int64_t n, const int64_t *ids_dev, const float *vecs_dev, const std::vector<int64_t> &h_assign,
@@ -327,6 +334,13 @@ struct qk_scan_args {
     const uint16_t *const *qmasks = nullptr;
     const int32_t *qfilter = nullptr;
     int F = 0;
+    // paged search (qk_after.hip): [Q] cursors on the device; a row is a candidate of query i only if its (key, id) lies behind
+    // (after_key[i], after_id[i]).  Needs `mask` (the cursor test lives in the filtered kernels).  next_key / next_id [Q] (may
+    // alias after_*; nullptr: not wanted): the cursor behind this page, written behind the merge
+    const uint32_t *after_key = nullptr;
+    const int64_t *after_id = nullptr;
+    uint32_t *next_key = nullptr;
+    int64_t *next_id = nullptr;
 };
 // filters (qk_filter.hip)
 struct qk_filter;
@@ -371,11 +385,19 @@ int qk_pack_topk_device(qk_ctx *ctx, const int64_t *ids, const float *key, int G
 int qk_merge_topk_packed_device(qk_ctx *ctx, const void *packed, int G, int64_t per, int k, int metric, int64_t *out_ids,
                                 float *out_dist, bool sqrt_l2);
 int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *timing, int ev_base);
+// paged search (qk_after.hip): the cursors of a call as qk_run_search hands them to the scan -- on the DEVICE whatever the call's
+// `mem` is (the entry point stages a host caller's), see qk_scan_args::after_key
+struct qk_cursors {
+    const uint32_t *after_key = nullptr;
+    const int64_t *after_id = nullptr;
+    uint32_t *next_key = nullptr;
+    int64_t *next_id = nullptr;
+};
 // the body of qk_coarse / qk_scan / qk_search (qk_api.hip) and the read-back of its scalars; see there
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
                   bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr, const qk_filter_batch *fbatch = nullptr,
-                  const qk_adaptive *adaptive = nullptr);
+                  const qk_adaptive *adaptive = nullptr, const qk_cursors *cursors = nullptr);
 int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, int scan_ev_base);
 // the event half of it: coarse_ms .. total_ms from ctx->ev of a drained stream (nothing unless the context records per-call events)
 int qk_read_phase_ms(qk_ctx *ctx, qk_timing *t, bool have_coarse, int scan_ev_base);

@@ -30,6 +30,7 @@
 #include <climits>
 #include "qk_device.h"
 #include "qk_scan_types.h"
+#include "qk_scan_opts.h"
 
 #include <algorithm>
 #include <climits>
@@ -748,17 +749,7 @@ __global__ __launch_bounds__(64 * W) void k_seed_tau_wg(SeedParams S) {
 #endif
 
 // ---- the scan kernel ---------------------------------------------------------------------------------
-// Compile-time experiment switches (scripts/scan_ab.sh builds one library per combination)
-#ifndef QK_OPT_EARLY_LOAD
-#define QK_OPT_EARLY_LOAD 1   // first tile's loads before the query staging
-#endif
-#ifndef QK_OPT_EARLY_REC
-#define QK_OPT_EARLY_REC 0    // reserve record slots at segment start + deferred rec_next store
-#endif
-#ifndef QK_OPT_ONE_BALLOT
-#define QK_OPT_ONE_BALLOT 1   // one ballot per tile in the steady state
-#endif
-
+// (the compile-time experiment switches of the kernel body and its streaming load: qk_scan_opts.h)
 #ifndef QK_DYN_PCT_DEFAULT
 // Dynamic tail.  Measured on the bench configuration (QK_SCAN_DYN_PCT / QK_SCAN_DYN_CHUNK sweeps): 20 % in 16-tile chunks
 // takes 5-12 % off k_scan at 6 or 8 waves per CU, but every chunk is a segment and leaves a record per live query, and
@@ -774,25 +765,6 @@ __global__ __launch_bounds__(64 * W) void k_seed_tau_wg(SeedParams S) {
 #ifndef QK_DYN_CHUNK_DEFAULT
 #define QK_DYN_CHUNK_DEFAULT 16  // tiles per dynamic chunk
 #endif
-
-#ifndef QK_OPT_SELECT1
-#define QK_OPT_SELECT1 1      // in-loop compaction of one-wave pools (k <= 36) by bisection select instead of the rank sort
-#endif
-#ifndef QK_OPT_NT
-#define QK_OPT_NT 1           // non-temporal loads for the streamed partition rows (measured: loads-only 5.74 -> 6.44 TB/s)
-#endif
-#ifndef QK_OPT_STEP_DRAIN
-#define QK_OPT_STEP_DRAIN 0   // s_waitcnt vmcnt(0) after every step (limits the bytes in flight per wave)
-#endif
-
-__device__ __forceinline__ float4 qk_ld_stream(const float4 *p) {
-#if QK_OPT_NT
-    const f32x4 t = __builtin_nontemporal_load((const f32x4 *)p);
-    return make_float4(t[0], t[1], t[2], t[3]);
-#else
-    return *p;
-#endif
-}
 
 // MODE 0 = product; 1 = skip the top-k epilogue; 2 = loads only (probe variants for bandwidth attribution, QK_SCAN_MODE);
 // 3 = product with query-sharing workgroups (ScanParams::qshare) -- a compile-time variant: the extra branches cost the
@@ -882,6 +854,7 @@ static int launch_scan_filt(dim3 grid, dim3 block, size_t lds, hipStream_t st, c
 static int launch_scan(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp) {
     if (sp.mask) {  // filtered call: the tile form's geometry, the filtered instantiations
         if (sp.key_out || sp.qshare) QK_FAIL(QK_ERR_UNSUPPORTED, "no filtered scan kernel for key emission / query sharing");
+        if (sp.after_key) return qk_launch_scan_after(db, maxch, grid, block, lds, st, sp);  // paged search: k_scan_after (qk_after.hip)
 #define QK_CASEF(D, M) \
     if (db == D && maxch == M) return launch_scan_filt<D, M>(grid, block, lds, st, sp);
         QK_CASEF(1, 1) QK_CASEF(1, 2) QK_CASEF(1, 4) QK_CASEF(1, 8) QK_CASEF(2, 1) QK_CASEF(2, 2) QK_CASEF(2, 4) QK_CASEF(2, 8)
@@ -932,6 +905,10 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     const bool filtered = a.mask != nullptr;  // (qk_filter.hip: the mask is current for this store -- qk_filter_ensure ran)
     if (filtered && (k > QK_MAX_K || emit || a.per_pair))
         QK_FAIL(QK_ERR_UNSUPPORTED, "filtered scan: k=%d beyond QK_MAX_K=%d (and per-pair / key-emission calls) is not supported", k, QK_MAX_K);
+    // paged search (qk_after.hip): the cursor test lives in the filtered kernels only -- a call without a filter brings the store's
+    // all-allowed mask
+    const bool paged = a.after_key != nullptr;
+    if (paged && (!filtered || a.qmasks || !a.after_id)) QK_FAIL(QK_ERR_UNSUPPORTED, "paged scan: needs one row mask and both cursor arrays");
     // (a flat index with a filter takes the grouped scan below: the dense forms know nothing of masks)
     const bool one_list = a.all_lists && s->nlist == 1 && !emit && !filtered;
     if (k > QK_MAX_K && !one_list) {
@@ -1287,6 +1264,8 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         sp.qmasks = a.qmasks;
         sp.qfilter = a.qfilter;
         sp.F = a.F;
+        sp.after_key = a.after_key;
+        sp.after_id = a.after_id;
         sp.pair_slots = pair_slots;
         sp.rec_counter = rec_counter;
         sp.max_recs = (int32_t)max_recs;
@@ -1393,7 +1372,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             QK_HIP(hipMemsetAsync(d_clock, 0, (size_t)grid * wpw * 64 * 2, st));
             sp.wave_clock = d_clock;
         }
-        ctx->last_scan_kernel = a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
+        ctx->last_scan_kernel = paged ? (wide ? "k_scan_wide (after)" : "k_scan (after)") : a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
         if (wide)
             QK_TRY(qk_launch_scan_wide(maxch, (unsigned)grid, lds_launch, st, sp));
         else if (use_rl)
@@ -1546,6 +1525,8 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     mp.sqrt_l2 = a.sqrt_l2 ? 1 : 0;
     const dim3 mgrid((unsigned)(a.per_pair ? Q * P : Q));
     QK_TRY(qk_launch_merge(ctx, mp, mgrid));
+    // paged search: every query's next cursor, from the keys the merge has just compared
+    if (paged && a.next_key) QK_TRY(qk_launch_next_cursor(ctx, mp, Q, a.out_ids, a.next_key, a.next_id));
     if (fmeasure && hipEventRecord(fmeasure->e1, ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
         fmeasure->pending = -1;

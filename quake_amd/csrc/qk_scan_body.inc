@@ -8,6 +8,9 @@
 // (which tiles are read); the word that reaches the epilogue is the lane's own, qmasks[qfilter[myq]][tile] -- lane (j, g) holds
 // rows 4g..4g+3 of the tile for query j, so the 16 queries of a tile are answered under 16 different filters in one pass.  The
 // four g groups of a query read the same word: at most 16 distinct 2-byte addresses per tile.
+// QK_SCAN_AFTER (with QK_SCAN_FILT 1) = k_scan_after, paged search: the filtered body plus one more test in the epilogue -- the
+// row's (key, id) must lie behind the lane's own query's cursor (ScanParams::after_key / after_id).  Everything it adds sits
+// behind #ifdef QK_SCAN_AFTER: the preprocessed text of the three kernels above does not change.
 // Expects: template parameters DB, MAXCH, MODE, L2 and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     // nw waves per workgroup (1, 2 or 4) share ONE LDS query tile and split every segment's tiles between them; each
@@ -188,6 +191,16 @@
 #else
 #define QK_MASK_WORD(T) (uint32_t)mrow[T]
 #endif
+#ifdef QK_SCAN_AFTER
+            // this lane's own query's cursor, resolved once per segment like qm_keep above.  A lane without a query keeps the
+            // exhausted cursor: nothing lies behind it
+            uint32_t cur_key = 0xFFFFFFFFu;
+            int64_t cur_id = INT64_MAX;
+            if (myq >= 0) {
+                cur_key = P.after_key[myq];
+                cur_id = P.after_id[myq];
+            }
+#endif
             int fl_base = tl, lt = min(tl, tend_wg - 1), lt_issued = lt;
             uint64_t fl_bits = 0;
             uint32_t y0_m = 0, y1_m = 0;  // the tile's word, double-buffered with its norms (y0 / y1) and ids
@@ -346,8 +359,15 @@
 #endif
                     const float v = acc[reg];
                     const uint32_t o = l2 ? ord_from_l2(l2_expanded(xnj, yv[reg], v)) : ord_from_ip(v);
+#ifdef QK_SCAN_AFTER
+                    // a row at or before the cursor is no candidate: it never reaches a pool, so it never sets a bound either
+                    const bool cand = valid && qk_behind_cursor(o, idv[reg], cur_key, cur_id);
+                    ordv[reg] = cand ? o : 0xFFFFFFFFu;
+                    anyp |= cand && o <= tau;
+#else
                     ordv[reg] = valid ? o : 0xFFFFFFFFu;  // an invalid row can never pass (tau < 0xFFFFFFFF once set; see below)
                     anyp |= valid && o <= tau;
+#endif
                 }
                 // steady state: nothing beats the running k-th best -> one ballot, one branch per tile
                 if (!QK_OPT_ONE_BALLOT || __ballot(anyp)) {

@@ -148,6 +148,10 @@ struct ScanParams {
     const uint16_t *const *qmasks;  // [F] device table of mask pointers
     const int32_t *qfilter;         // [Q]
     int F;
+    // paged search (k_scan_after, k_scan_wide_after; qk_after.hip): query i's candidates are the rows whose (key, id) lies behind
+    // its cursor (after_key[i], after_id[i]) -- unsigned key, signed id, lexicographic.  nullptr = no cursor
+    const uint32_t *after_key;      // [Q]
+    const int64_t *after_id;        // [Q]
 };
 
 // ---- merge stage (qk_merge.hip) ------------------------------------------------------------------------------------------
@@ -219,3 +223,7 @@ struct ScanPlan {
 int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int k, int P, int64_t npairs, ScanPlan *pl);
 // wide-row scan (qk_scan_wide.hip): one wave per workgroup, lds = its 16 pools of sp.C entries
 int qk_launch_scan_wide(int maxch, unsigned grid, size_t lds, hipStream_t st, const ScanParams &sp);
+// paged search (qk_after.hip): k_scan_after, launched like k_scan_filt; and the kernel behind the merge that writes every query's
+// next cursor -- the (key, id) of its k-th result, the exhausted cursor where the row holds fewer than k
+int qk_launch_scan_after(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
+int qk_launch_next_cursor(qk_ctx *ctx, const MergeParams &mp, int64_t Q, const int64_t *out_ids, uint32_t *next_key, int64_t *next_id);

@@ -103,6 +103,24 @@ __global__ __launch_bounds__(64) void k_scan_wide_filtq(ScanParams P) {
 #undef QK_SCAN_FILT
 }
 
+// paged search (qk_after.hip): the filtered body plus the cursor test in the epilogue (see qk_scan_wide_body.inc)
+template <bool L2, int MAXCH>
+__global__ __launch_bounds__(64) void k_scan_wide_after(ScanParams P) {
+    constexpr bool EMIT = false;
+#define QK_SCAN_FILT 1
+#define QK_SCAN_AFTER
+#include "qk_scan_wide_body.inc"
+#undef QK_SCAN_AFTER
+#undef QK_SCAN_FILT
+}
+
+template <bool L2, int MAXCH>
+static int launch_scan_wide_a(unsigned grid, size_t lds, hipStream_t st, const ScanParams &sp) {
+    QK_HIP(hipFuncSetAttribute((const void *)k_scan_wide_after<L2, MAXCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_scan_wide_after<L2, MAXCH>), dim3(grid), dim3(64), lds, st, sp);
+    return QK_OK;
+}
+
 template <bool L2, int MAXCH>
 static int launch_scan_wide_fq(unsigned grid, size_t lds, hipStream_t st, const ScanParams &sp) {
     QK_HIP(hipFuncSetAttribute((const void *)k_scan_wide_filtq<L2, MAXCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -132,6 +150,12 @@ static int launch_scan_wide_m(int maxch, unsigned grid, size_t lds, hipStream_t 
             if (maxch == 2) return launch_scan_wide_fq<L2, 2>(grid, lds, st, sp);
             if (maxch == 4) return launch_scan_wide_fq<L2, 4>(grid, lds, st, sp);
             return launch_scan_wide_fq<L2, 8>(grid, lds, st, sp);
+        }
+        if (sp.after_key) {  // paged search
+            if (maxch == 1) return launch_scan_wide_a<L2, 1>(grid, lds, st, sp);
+            if (maxch == 2) return launch_scan_wide_a<L2, 2>(grid, lds, st, sp);
+            if (maxch == 4) return launch_scan_wide_a<L2, 4>(grid, lds, st, sp);
+            return launch_scan_wide_a<L2, 8>(grid, lds, st, sp);
         }
         if (maxch == 1) return launch_scan_wide_f<L2, 1>(grid, lds, st, sp);
         if (maxch == 2) return launch_scan_wide_f<L2, 2>(grid, lds, st, sp);

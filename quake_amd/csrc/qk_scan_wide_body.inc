@@ -3,7 +3,8 @@
 // (one 16-bit word per arena tile, qk_filter.hip): a row passes the epilogue only with its bit set, and the walk jumps over tiles
 // whose word is 0 (a tile of a wide row is 16 x d x 4 bytes: 192 KB at d = 3072).  QK_SCAN_FILT 2 = k_scan_wide_filtq, one filter
 // per query: the walk jumps by ScanParams::mask, the OR of the call's masks; the epilogue's word is the lane's own query's
-// (qmasks[qfilter[myq]], see qk_scan_body.inc).
+// (qmasks[qfilter[myq]], see qk_scan_body.inc).  QK_SCAN_AFTER (with QK_SCAN_FILT 1) = k_scan_wide_after: the filtered body plus
+// the cursor test of paged search in the epilogue (see qk_scan_body.inc); its lines sit behind #ifdef QK_SCAN_AFTER.
 // Expects: template parameters L2, MAXCH, EMIT and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int R = QK_WIDE_R;
@@ -78,6 +79,15 @@
             }
         }
 #endif
+#ifdef QK_SCAN_AFTER
+        // this lane's own query's cursor, resolved once per segment; no query: the exhausted cursor, nothing lies behind it
+        uint32_t cur_key = 0xFFFFFFFFu;
+        int64_t cur_id = INT64_MAX;
+        if (myq >= 0) {
+            cur_key = P.after_key[myq];
+            cur_id = P.after_id[myq];
+        }
+#endif
         const float4 *qsrc = P.xq4 + (int64_t)qsafe * nblk * 4 + g;
         auto bload = [&](int c) { return qsrc[c * 4]; };
 
@@ -116,8 +126,14 @@
                 const bool valid = (myq >= 0) && (row0 + 4 * g + reg < size_p);
 #endif
                 const uint32_t o = l2 ? ord_from_l2(l2_expanded(xnj, yv[reg], acc[reg])) : ord_from_ip(acc[reg]);
+#ifdef QK_SCAN_AFTER
+                const bool cand = valid && qk_behind_cursor(o, idv[reg], cur_key, cur_id);
+                ordv[reg] = cand ? o : 0xFFFFFFFFu;
+                anyp |= cand && o <= tau;
+#else
                 ordv[reg] = valid ? o : 0xFFFFFFFFu;
                 anyp |= valid && o <= tau;
+#endif
             }
             if (!__ballot(anyp)) return;
 #pragma unroll

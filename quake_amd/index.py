@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import capi
-from ._lib import QuakeHipError
+from ._lib import QuakeHipError, header_constant
 from .where import lower_where
 
 # defaults: src/cpp/include/common.h:66-99
@@ -242,6 +242,20 @@ class SearchResult:  # common.h:243-247
         self.distances = None
         self.timing_info = None
         self.nprobed = None  # extension: int32 [Q] partitions probed per query under SearchParams.max_nprobe, else None
+        self.cursor = None   # extension: the SearchCursor behind this page (QuakeIndex.search_after), else None
+
+
+class SearchCursor:
+    """extension (QuakeIndex.search_after): one position per query in the total order (key, id) of its results -- keys int32 [Q]
+    holding the uint32 bit pattern of the integer key the top-k compares, ids int64 [Q].  A position, not a snapshot: it stays
+    valid across add / remove / maintenance.  (0, -1) is the start, (0xFFFFFFFF, INT64_MAX) an exhausted query."""
+
+    def __init__(self, keys, ids):
+        self.keys = keys
+        self.ids = ids
+
+    def __len__(self):
+        return int(self.ids.shape[0])
 
 
 class RangeSearchResult:
@@ -255,6 +269,7 @@ class RangeSearchResult:
 
 
 MAX_GROUP_SIZE = 16  # QK_MAX_GROUP_SIZE (include/quake_hip.h)
+MAX_K = header_constant("QK_MAX_K")  # the largest page of search_after, as include/quake_hip.h states it
 
 
 class GroupedSearchResult:
@@ -664,6 +679,84 @@ class QuakeIndex:
         ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
         res.ids = ids if on_dev else ids.cpu()
         res.distances = dist if on_dev else dist.cpu()
+        return res
+
+    def search_after(self, x, search_params, cursor=None):
+        """extension (no reference counterpart): the page of search_params.k results behind `cursor` -- a SearchCursor an earlier
+        search_after of the SAME queries returned (any page size), None = from the start -- among the vectors of the
+        search_params.nprobe nearest partitions, restricted to search_params.filter if one is set.  Pages chained from None
+        concatenate to what search() with a larger k returns, without its limits on k (448 under a filter) and at the cost of one
+        filtered search per page whatever the depth; vectors added or removed between two pages appear / vanish behind the cursor
+        and nothing is returned twice.  Returns a SearchResult whose .cursor continues behind it; a query with fewer than k
+        results left is padded like search() and its cursor is exhausted.  Records no hits for maintenance(): turning the pages
+        of one search is not new evidence of which partitions are hot."""
+        self._require_built("[QuakeIndex::search_after()] No query coordinator. Did you build the index?")
+        sp = search_params
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError("[QuakeIndex::search_after()] SearchParams.filters / query_filter (one filter per query) are not "
+                               "supported by search_after")
+        if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
+            raise RuntimeError("[QuakeIndex::search_after()] SearchParams.max_nprobe (adaptive probing) is not supported by "
+                               "search_after: a page is defined over a fixed set of probed partitions")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError("[QuakeIndex::search_after()] search_after is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::search_after()] search_after is not supported with num_workers > 0")
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError("[QuakeIndex::search_after()] SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError("[QuakeIndex::search_after()] the filter was made for another index")
+            flt = flt._h
+        k = sp.k if sp.k and sp.k > 0 else 1
+        if k > MAX_K:
+            raise RuntimeError("[QuakeIndex::search_after()] k=%d exceeds the page limit of %d: ask for the rest with the next "
+                               "cursor" % (k, MAX_K))
+        nq = 0 if x is None else int(x.shape[0])
+        if cursor is not None:
+            if not isinstance(cursor, SearchCursor) or cursor.keys is None or cursor.ids is None:
+                raise RuntimeError("[QuakeIndex::search_after()] cursor must be the SearchCursor of an earlier page (keys and ids)")
+            if int(cursor.keys.shape[0]) != nq or int(cursor.ids.shape[0]) != nq:
+                raise RuntimeError("[QuakeIndex::search_after()] the cursor has %d / %d entries for %d queries"
+                                   % (int(cursor.keys.shape[0]), int(cursor.ids.shape[0]), nq))
+        res = SearchResult()
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        if nq == 0:
+            res.ids = torch.empty((0,), dtype=torch.int64)
+            res.distances = torch.empty((0,), dtype=torch.float32)
+            res.cursor = SearchCursor(torch.empty((0,), dtype=torch.int32), torch.empty((0,), dtype=torch.int64))
+            return res
+        t0 = time.perf_counter()
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        after = None if cursor is None else (cursor.keys, cursor.ids)
+        was = self._ctx.get_timing()  # (restored: a caller's deferred timing survives the call, as in the compiled mirror)
+        self._ctx.set_timing(1)
+        try:
+            ids, dist, (nk, ni), tm = self._ctx.search_after(self.parent._store if self.parent is not None else None, self._store, xd,
+                                                             nprobe, int(k), self.metric_, after=after, filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(was)
+        ti.n_queries = nq
+        ti.partitions_scanned = int(tm["partitions_scanned"])
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.ids = ids if on_dev else ids.cpu()
+        res.distances = dist if on_dev else dist.cpu()
+        res.cursor = SearchCursor(nk if on_dev else nk.cpu(), ni if on_dev else ni.cpu())
         return res
 
     def range_search(self, x, radius, search_params):
