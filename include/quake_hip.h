@@ -319,6 +319,43 @@ QK_API int qk_search_filtered_adaptive(qk_ctx *ctx, qk_store *parent, qk_store *
                                        const int32_t *qfilter, int64_t *out_ids, float *out_dist, int32_t *out_nprobed,
                                        int64_t *out_probed, int mem, qk_timing *timing);
 
+/* Exact filtered search: compact the filter's candidates, search them flat.  A probed filtered search returns the best candidates
+ * OF THE PROBED LISTS; under a selective filter those hold almost none of the filter's rows.  The right answer for such a filter
+ * is the exact top-k of its candidates, and it is cheap: the candidates are gathered once into a private one-list store kept on
+ * the filter, and every call is the flat search of that store -- no parent, no nprobe, cost by candidates, not by lists.
+ *   Result: row q is bit for bit -- ids and distance bits, padding included -- what qk_search(ctx, NULL, c, ..) returns over a
+ *     one-list store c that holds exactly the candidate rows; that is qk_search_filtered with every list probed.  (A row's key
+ *     does not depend on its neighbours and results are ordered by (key, id): where the rows sit cannot show.)
+ *   1 <= k <= 8192, whatever the flat search accepts (QK_ERR_UNSUPPORTED beyond): the filtered route beyond QK_MAX_K.
+ *   qk_ctx_set_squared_l2 is honoured as in qk_search; NaN / Inf / overflow follow the flat search's contract (see the top).
+ *   No candidates, fewer than k, an empty store: padded rows (-1, +inf / -inf).
+ *   max_rows > 0: a filter with more candidates is refused with QK_ERR_UNSUPPORTED before anything is allocated or enqueued for
+ *     the candidate store -- the caller bounds its memory, rows x (dpad * 4 + 12) bytes (never less than the 1024 rows every
+ *     arena starts with; the prefiltered dense forms keep a row-major copy of a list of up to 128 MiB next to it, as they do
+ *     for every flat index: qk_filter_exact_info counts it); max_rows == 0: no bound.
+ *   QK_ERR_INVALID: another store's filter, a filter on another device, max_rows < 0.
+ *   timing is filled as the flat search fills it: scan_bytes = the candidate rows' bytes, coarse_ms = 0; a mask build and the
+ *     gather lie in front of the scan's events and are part of total_ms only, like the cut of an adaptive call.  qk_ctx_last_scan_kernel names the
+ *     dense kernel that ran.
+ * The candidate store follows the life cycle of the adaptive counts: derived from the row mask by the first EXACT call behind a
+ * mask build, on that call's stream behind the mask; a call on another context waits for it by event; every mask build drops it
+ * (the memory is kept, and grown geometrically); qk_filter_destroy frees it; the other filtered calls neither allocate nor launch
+ * anything for it; qk_filter_info's device_bytes includes it once it exists.  It reads only the mask, so id sets, deny sets and
+ * predicates are served alike.  Inside: k_filter_block_counts (candidates per 64 mask words), k_filter_block_scan (their
+ * exclusive prefix sum, int64, one workgroup) and k_filter_gather (a wave per destination tile: destination row j is the j-th
+ * candidate in ascending arena-row order; vectors, norm bits and ids are copied, the tail of the last tile is written with what a
+ * fresh arena holds) -- no atomics, no device library, and no row or id travels to the host: the only host read is the candidate
+ * count, 8 bytes per mask build.
+ * qk_filter_candidate_rows: the candidates of f in s NOW -- brings the mask up to date on ctx's stream and waits for it only if
+ * the count of this build has not been read yet.  qk_filter_exact_info (any pointer may be NULL): rows = rows of the candidate
+ * store as of its last derivation, builds = derivations so far -- one per exact call that found the mask newer than the store,
+ * none otherwise --, device_bytes = what the candidate store holds (0 before the first exact call).
+ * Out of scope: per-query filters, range / grouped / paged search over the candidate store, the device group. */
+QK_API int qk_filter_candidate_rows(qk_ctx *ctx, qk_store *s, qk_filter *f, int64_t *rows);
+QK_API int qk_search_filtered_exact(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, int k, int metric, qk_filter *f,
+                                    int64_t max_rows, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_filter_exact_info(qk_filter *f, int64_t *rows, int64_t *builds, int64_t *device_bytes);
+
 /* ---- range search --------------------------------------------------------------------------------
  * No reference counterpart (every search of the reference is a top-k): all rows of the probed lists within a radius of each query.
  * Lists: qk_range_search probes what the unfiltered qk_search probes -- the same min(nprobe, parent lists) lists in the same rank

@@ -87,6 +87,9 @@ SIGNATURES = {
     "qk_filter_create": (_int, [_vp, _vp, _i64, _int, _int, C.POINTER(_vp)]),
     "qk_filter_destroy": (_int, [_vp]),
     "qk_filter_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_uint64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "qk_filter_candidate_rows": (_int, [_vp, _vp, _vp, C.POINTER(_i64)]),
+    "qk_search_filtered_exact": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _i64, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_filter_exact_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_search_filtered": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search_filtered_tracked": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _int,
                                    C.POINTER(QkTiming)]),

@@ -257,6 +257,22 @@ class Context:
                                  metric_code(metric), _ptr(out_i), _ptr(out_d), mem, C.byref(t) if timing else None))
         return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
 
+    def search_exact(self, store, x, k, metric, filter, max_rows=0, timing=False, out=None):
+        """qk_search_filtered_exact: the k best candidates of `filter` over the WHOLE store -- no parent, no nprobe; the flat
+        search of the filter's candidate rows, k up to 8192.  max_rows > 0: a filter with more candidates is refused."""
+        x = _f32(x)
+        Q = x.shape[0]
+        if out is None:
+            out_i = _empty_like_mem((Q, k), np.int64, x)
+            out_d = _empty_like_mem((Q, k), np.float32, x)
+        else:
+            out_i, out_d = out
+        t = QkTiming()
+        check(self.lib.qk_search_filtered_exact(self.h, store.h, _ptr(x), Q, int(k), metric_code(metric),
+                                                filter.h if filter is not None else None, int(max_rows), _ptr(out_i), _ptr(out_d),
+                                                _mem_of(x), C.byref(t) if timing else None))
+        return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
+
     def search_tracked(self, parent, store, x, nprobe, k, metric, timing=False, filter=None, filters=None, query_filter=None):
         """qk_search_tracked: search + the [Q, min(nprobe, parent lists)] list numbers every query scanned, one enqueue.
         Returns (ids, dist, probed[, timing]).  filter: a Filter of `store` (qk_search_filtered_tracked; the probed lists are
@@ -836,6 +852,18 @@ class Filter:
         check(self.lib.qk_filter_info(self.h, C.byref(n), C.byref(ra), C.byref(ver), C.byref(rb), C.byref(db)))
         return {"n_ids": n.value, "rows_allowed": ra.value, "store_version": ver.value, "rebuilds": rb.value,
                 "device_bytes": db.value}
+
+    def candidate_rows(self, ctx):
+        """the candidate rows of the store NOW (qk_filter_candidate_rows): brings the mask up to date on ctx's stream"""
+        n = C.c_int64()
+        check(self.lib.qk_filter_candidate_rows(ctx.h, self.store.h, self.h, C.byref(n)))
+        return n.value
+
+    def exact_info(self):
+        """{rows, builds, device_bytes} of the candidate store of exact search (qk_filter_exact_info)"""
+        r, b, db = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.lib.qk_filter_exact_info(self.h, C.byref(r), C.byref(b), C.byref(db)))
+        return {"rows": r.value, "builds": b.value, "device_bytes": db.value}
 
 
 class Attr:

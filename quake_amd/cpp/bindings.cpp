@@ -224,6 +224,7 @@ PYBIND11_MODULE(_bindings, m) {
             [](SearchParams &p, py::object v) { p.query_filter = v.is_none() ? Tensor() : v.cast<Tensor>(); })
         .def_readwrite("max_nprobe", &SearchParams::max_nprobe)  // extension: adaptive probing under a filter; not in the summary
         .def_readwrite("filter_min_candidates", &SearchParams::filter_min_candidates)
+        .def_readwrite("filter_exact_rows", &SearchParams::filter_exact_rows)  // extension: exact search under a selective filter
         .def("__repr__", [](const SearchParams &p) {  // wrap.cpp:173-186
             return Repr().kv("k", p.k).kv("nprobe", p.nprobe).kv("recall_target", p.recall_target).kv("batched_scan", p.batched_scan)
                 .kv("use_precomputed", p.use_precomputed).kv("initial_search_fraction", p.initial_search_fraction)
@@ -352,5 +353,12 @@ PYBIND11_MODULE(_bindings, m) {
                 return py::cast(r.nprobed);
             },
             [](SearchResult &r, py::object v) { r.nprobed = v.is_none() ? Tensor() : v.cast<Tensor>(); })
+        .def_property(
+            "exact",  // extension: True / False on a search that consulted SearchParams.filter_exact_rows, else None
+            [](const SearchResult &r) -> py::object {
+                if (r.exact < 0) return py::none();
+                return py::bool_(r.exact == 1);
+            },
+            [](SearchResult &r, py::object v) { r.exact = v.is_none() ? -1 : (v.cast<bool>() ? 1 : 0); })
         .def_readwrite("cursor", &SearchResult::cursor);  // extension: the SearchCursor behind a search_after page, else None
 }

@@ -95,6 +95,12 @@ struct SearchParams {  // common.h:171-184
     // SearchResult::nprobed says how many each query probed
     int max_nprobe = 0;
     int64_t filter_min_candidates = 0;
+    // extension, not part of the summary: exact search under a selective filter -- with filter_exact_rows > 0 and `filter` set, a
+    // filter that has at most that many candidate vectors in the index NOW is answered exactly: the k best of ALL its candidates,
+    // no partition probed, k up to 8192 (SearchResult::exact = 1); a filter with more takes the path it takes today, fixed nprobe
+    // or adaptive under max_nprobe (exact = 0).  0 = off.  An exact call probes no partition, so it records no hits for the
+    // maintenance policy
+    int64_t filter_exact_rows = 0;
 };
 
 struct BuildTimingInfo {  // common.h:189-198
@@ -135,6 +141,7 @@ struct SearchResult {  // common.h:243-247
     Tensor distances;
     shared_ptr<SearchTimingInfo> timing_info;
     Tensor nprobed;  // extension: int32 [Q] partitions probed per query under SearchParams::max_nprobe, else undefined
+    int exact = -1;  // extension: 1 / 0 on a search that consulted SearchParams::filter_exact_rows, else -1 (None in Python)
     shared_ptr<SearchCursor> cursor = nullptr;  // extension: the cursor behind this page (QuakeIndex::search_after), else null
 };
 

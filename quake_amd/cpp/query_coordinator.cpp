@@ -116,6 +116,22 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
         }
     } timing_mode(ctx, !on_dev || device_timing_);
     qk_timing *tmp = (!on_dev || device_timing_) ? &tm : nullptr;  // device tensors: asynchronous unless the caller opted in
+    if (sp->filter_exact_rows < 0)
+        throw std::runtime_error("[QuakeIndex::search()] SearchParams.filter_exact_rows must not be negative (0 turns exact "
+                                 "filtered search off)");
+    if (sp->filter_exact_rows > 0) {
+        // exact filtered search (extension): one filter, one device, no recall target; the rest is refused, not approximated
+        if (!sp->filters.empty() || sp->query_filter.defined())
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.filter_exact_rows is not supported with filters / "
+                                     "query_filter (one filter per query)");
+        if (!sp->filter)
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.filter_exact_rows needs a filter: without one every "
+                                     "vector is a candidate");
+        if (sp->recall_target > 0.0f)
+            throw std::runtime_error("[QuakeIndex::search()] filter_exact_rows cannot be combined with recall_target > 0: "
+                                     "not supported");
+        if (group) throw std::runtime_error("[QuakeIndex::search()] filter_exact_rows is not supported with num_workers > 0");
+    }
     qk_filter *flt = nullptr;
     if (sp->filter) {
         // filtered search (extension): the fixed-nprobe branch of one device; the rest is refused, not approximated
@@ -167,6 +183,23 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
                                      " is below nprobe=" + std::to_string(nprobe) + " (0 turns adaptive probing off)");
     }
     const bool adaptive = sp->max_nprobe > nprobe && parent_;  // (a flat index scans everything: nothing to adapt)
+    if (sp->filter_exact_rows > 0) {
+        if (sp->filter->owner != store) throw std::runtime_error("[QuakeIndex::search()] the filter was made for another index");
+        int64_t rows = 0;
+        qk_check(qk_filter_candidate_rows(ctx, store, flt, &rows));
+        res->exact = rows <= sp->filter_exact_rows ? 1 : 0;
+    }
+    if (res->exact == 1) {
+        // the flat search of the filter's candidate rows: no parent, no nprobe, no hits for the policy
+        qk_check(qk_search_filtered_exact(ctx, store, xq.data_ptr<float>(), Q, k, (int)metric_, flt, sp->filter_exact_rows,
+                                          res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, tmp));
+        ti->partitions_scanned = (int)tm.partitions_scanned;  // (as this mirror's search of a flat index reports it: one per query)
+        ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+        ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+        ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+        ti->total_time_ns = ns_since(t0);
+        return res;
+    }
     if (adaptive) {
         // one enqueue: coarse step at max_nprobe, the cut of every query's row on the device, the filtered scan
         const int M = (int)std::min<int64_t>(sp->max_nprobe, parent_->ntotal());
@@ -268,6 +301,9 @@ shared_ptr<SearchResult> QueryCoordinator::search_after(Tensor x, shared_ptr<Sea
     if (sp->max_nprobe > 0)
         throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.max_nprobe (adaptive probing) is not supported by "
                                  "search_after: a page is defined over a fixed set of probed partitions");
+    if (sp->filter_exact_rows > 0)
+        throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                                 "search_after");
     if (sp->recall_target > 0.0f) throw std::runtime_error("[QuakeIndex::search_after()] search_after is not supported with recall_target > 0");
     qk_ctx *ctx = partition_manager_->ctx();
     qk_store *store = partition_manager_->store();
@@ -353,6 +389,9 @@ shared_ptr<RangeSearchResult> QueryCoordinator::range_search(Tensor x, float rad
     if (!sp->filters.empty() || sp->query_filter.defined())
         throw std::runtime_error("[QuakeIndex::range_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                  "supported by range_search");
+    if (sp->filter_exact_rows > 0)
+        throw std::runtime_error("[QuakeIndex::range_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                                 "range_search");
     if (sp->recall_target > 0.0f) throw std::runtime_error("[QuakeIndex::range_search()] range_search is not supported with recall_target > 0");
     qk_ctx *ctx = partition_manager_->ctx();
     qk_store *store = partition_manager_->store();
@@ -430,6 +469,9 @@ shared_ptr<GroupedSearchResult> QueryCoordinator::grouped_search(Tensor x, qk_at
     if (!sp->filters.empty() || sp->query_filter.defined())
         throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                  "supported by grouped_search");
+    if (sp->filter_exact_rows > 0)
+        throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                                 "grouped_search");
     if (sp->recall_target > 0.0f) throw std::runtime_error("[QuakeIndex::grouped_search()] grouped_search is not supported with recall_target > 0");
     qk_ctx *ctx = partition_manager_->ctx();
     qk_store *store = partition_manager_->store();

@@ -146,6 +146,17 @@ struct qk_filter {
     bool counts_built = false;
     hipEvent_t counts_ev = nullptr;  // behind the last derivation, on the stream of counts_ctx
     qk_ctx *counts_ctx = nullptr;
+    // exact search (qk_search_filtered_exact): the candidate rows gathered into a private store of ONE list -- rows 0 .. n - 1 of its
+    // arena in ascending arena-row order of the source, norms and ids copied bit for bit -- which the flat search then takes like
+    // any one-list store.  The life cycle of `counts`: derived from the mask by the first exact call behind a mask build (every
+    // build drops it: cand_built; the arena is kept and grown geometrically), on that call's stream; nobody else allocates or
+    // reads it.  Its id mirror on the host stays empty: no id travels to the host
+    qk_store *cand = nullptr;
+    bool cand_built = false;
+    int64_t cand_builds = 0;        // derivations so far (qk_filter_exact_info)
+    int64_t cand_rows = -1;         // candidates of the last mask build, read from d_allowed once per build (-1: not read yet)
+    hipEvent_t cand_ev = nullptr;   // behind the last derivation, on the stream of cand_ctx
+    qk_ctx *cand_ctx = nullptr;
 };
 
 // qk_filter.hip

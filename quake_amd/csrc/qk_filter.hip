@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -129,6 +130,8 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     if (f->built) f->rebuilds++;
     f->built = true;
     f->counts_built = false;  // (adaptive probing: re-derived by the next call that needs them)
+    f->cand_built = false;    // (exact search: the candidate store too, and the count is read again)
+    f->cand_rows = -1;
     f->built_ctx = ctx;
     f->version = s->version;
     f->cap_rows = s->cap_rows;
@@ -231,6 +234,233 @@ __global__ __launch_bounds__(256) void k_probe_trim(int64_t *pids, int64_t Q, in
     }
     for (int i = t + lane; i < M; i += 64) row[i] = -1;
     if (lane == 0 && nprobed) nprobed[q] = t;
+}
+
+// ---- exact search: the candidate rows of a filter, compacted into a one-list store ------------------------------------------------
+// The mask is a bitmap of arena rows: bit r of word w is row 16 w + r, and four consecutive words read as one little-endian
+// 64-bit CHUNK are rows 64 c .. 64 c + 63.  A scan BLOCK is QK_CAND_BLOCK = 64 words = 16 chunks = 1024 rows.  Three launches, no
+// atomics, no device library, int64 offsets: the candidates of every block (k_filter_block_counts), their exclusive prefix sum
+// (k_filter_block_scan, one workgroup), and the gather, which finds its source rows from the block offsets and the block's own
+// 128 bytes of mask (k_filter_gather).
+constexpr int QK_CAND_BLOCK = 64;
+
+// chunk c of a mask of nwords words (8-byte aligned: the mask is a hipMalloc of its own); words behind the end read as 0
+__device__ __forceinline__ uint64_t mask_chunk(const uint16_t *mask, int64_t c, int64_t nwords) {
+    const int64_t w = c * 4;
+    if (w + 4 <= nwords) return *(const uint64_t *)(mask + w);
+    uint64_t v = 0;
+    for (int i = 0; i < 4; i++)
+        if (w + i < nwords) v |= (uint64_t)mask[w + i] << (16 * i);
+    return v;
+}
+
+// one lane per chunk, 16 lanes per block: a wave reads 512 consecutive bytes; every cnt[b] has one writer
+__global__ __launch_bounds__(256) void k_filter_block_counts(const uint16_t *mask, int64_t nwords, int64_t nb, int64_t *cnt) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane;
+    int n = __popcll(mask_chunk(mask, c, nwords));
+    for (int off = 1; off < 16; off <<= 1) n += __shfl_xor(n, off);
+    const int64_t b = c >> 4;
+    if ((lane & 15) == 0 && b < nb) cnt[b] = n;
+}
+
+// off[i] = cnt[0] + .. + cnt[i - 1] for i in [0, nb]; one workgroup: thread t owns a contiguous slice, the 1024 slice sums are
+// scanned through LDS (nb is cap_rows / 1024: 9766 at 10M rows)
+__global__ __launch_bounds__(1024) void k_filter_block_scan(const int64_t *__restrict__ cnt, int64_t *__restrict__ off, int64_t nb) {
+    __shared__ int64_t part[1024];
+    const int t = threadIdx.x;
+    const int64_t per = (nb + 1023) / 1024;
+    const int64_t b = min(nb, (int64_t)t * per), e = min(nb, b + per);
+    int64_t s = 0;
+    for (int64_t i = b; i < e; i++) s += cnt[i];
+    part[t] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int64_t v = t >= o ? part[t - o] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int64_t run = part[t] - s;
+    for (int64_t i = b; i < e; i++) {
+        off[i] = run;
+        run += cnt[i];
+    }
+    if (t == 1023) off[nb] = part[1023];
+}
+
+struct GatherParams {
+    const uint16_t *mask;
+    int64_t nwords;      // live words of the mask (the source arena's tiles)
+    const int64_t *boff;  // [nb + 1]
+    int64_t nb;
+    int64_t n;           // candidates = boff[nb]
+    int64_t ntiles;      // destination tiles: ceil(n / 16)
+    int nblk;
+    const float4 *sv;    // source arena
+    const uint32_t *sn;
+    const int64_t *si;
+    int64_t src_rows;    // its capacity
+    float4 *dv;          // destination arena (>= ntiles tiles)
+    uint32_t *dn;
+    int64_t *di;
+};
+
+// The stable compaction, destination-driven: destination row j is the j-th candidate in ascending arena-row order.  One wave per
+// destination tile, lane g * 16 + dr: the lane finds the source of row dr -- a binary search of the block offsets, a walk over
+// the block's 16 chunks, the (j - offset)-th set bit of the chunk it lands in -- and then copies, per 16-column block, the float4
+// of (row, g): 16-byte gathers, one coalesced 1 KiB store per wave.  The rows behind the last candidate in the last tile get
+// what a fresh arena holds (zeros, norm 0, id -1) on every build.  The four lanes of a row do the search redundantly.
+__global__ __launch_bounds__(256) void k_filter_gather(GatherParams G) {
+    const int lane = threadIdx.x & 63, dr = lane & 15, g = lane >> 4;
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= G.ntiles) return;  // (the whole wave)
+    const int64_t j = tile * 16 + dr;
+    int64_t src = -1;
+    if (j < G.n) {
+        int64_t lo = 0, hi = G.nb;  // boff[lo] <= j < boff[hi]: the last block that starts at or below j holds row j
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (G.boff[mid] <= j) lo = mid;
+            else hi = mid;
+        }
+        int64_t rem = j - G.boff[lo];
+        const int64_t c0 = lo * (QK_CAND_BLOCK / 4);
+        for (int c = 0; c < QK_CAND_BLOCK / 4; c++) {
+            uint64_t v = mask_chunk(G.mask, c0 + c, G.nwords);
+            const int pc = __popcll(v);
+            if (rem < pc) {
+                for (int i = 0; i < (int)rem; i++) v &= v - 1;  // drop the `rem` lowest set bits
+                src = (c0 + c) * 64 + (__ffsll((unsigned long long)v) - 1);
+                break;
+            }
+            rem -= pc;
+        }
+        if (src >= G.src_rows) src = -1;  // (cannot happen with offsets derived from this mask: never read outside the arena)
+    }
+    const bool live = src >= 0;
+    const float4 *sp = G.sv + ((live ? src >> 4 : 0) * G.nblk) * 64 + g * 16 + (live ? (int)(src & 15) : 0);
+    float4 *dp = G.dv + (tile * G.nblk) * 64 + lane;
+#pragma unroll 4
+    for (int c = 0; c < G.nblk; c++) dp[(int64_t)c * 64] = live ? sp[(int64_t)c * 64] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g == 0) {
+        G.dn[j] = live ? G.sn[src] : 0u;  // (the norm's bits, not a recomputation)
+        G.di[j] = live ? G.si[src] : -1;
+    }
+}
+
+void cand_free_arena(qk_store *c) {
+    if (c->vecs) hipFree(c->vecs);  // (hipFree waits for the device: no scan still reads the rows)
+    if (c->norms) hipFree(c->norms);
+    if (c->ids) hipFree(c->ids);
+    c->vecs = nullptr;
+    c->norms = nullptr;
+    c->ids = nullptr;
+    c->cap_rows = 0;
+    (void)hipGetLastError();
+}
+
+int64_t cand_device_bytes(const qk_filter *f) {
+    const qk_store *c = f->cand;
+    if (!c) return 0;
+    return c->cap_rows * ((int64_t)c->dpad * 4 + 12) + c->table_cap * 12 + c->rowmajor_cap * 4;
+}
+
+// the candidates of a filter whose mask is current on ctx's stream (filter_current ran): 8 bytes of d_allowed, once per mask build
+int cand_count(qk_filter *f, int64_t *rows) {
+    if (f->cand_rows < 0) {
+        unsigned long long v = 0;
+        QK_HIP(hipEventSynchronize(f->built_ev));
+        QK_HIP(hipMemcpy(&v, f->d_allowed, sizeof(v), hipMemcpyDeviceToHost));
+        f->cand_rows = (int64_t)v;
+    }
+    *rows = f->cand_rows;
+    return QK_OK;
+}
+
+// the candidate store of a filter whose mask the caller has just brought up to date on ctx's stream and whose n candidates it has
+// counted: derived behind the mask if the mask is newer than it is.  max_rows > 0 bounds the capacity a growth may ask for
+int cand_ensure(qk_ctx *ctx, qk_store *s, qk_filter *f, int64_t n, int64_t max_rows) {
+    hipStream_t st = ctx->stream;
+    if (f->cand_built) {
+        f->cand->ctx = ctx;  // (a row-major copy the dense forms may ask for is made on the calling context, complete on return)
+        if (f->cand_ctx != ctx) QK_HIP(hipStreamWaitEvent(st, f->cand_ev, 0));  // derived on another context's stream
+        return QK_OK;
+    }
+    if (n > (int64_t)INT32_MAX - 16) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_search_filtered_exact: %lld candidates exceed a list's 2^31 rows", (long long)n);
+    if (!f->cand_ev) QK_HIP(hipEventCreateWithFlags(&f->cand_ev, hipEventDisableTiming));
+    if (!f->cand) {
+        QK_TRY(qk_store_create(ctx, s->d, &f->cand));
+        QK_TRY(qk_store_add_list(f->cand, 0));
+    }
+    qk_store *c = f->cand;
+    // behind the last derivation on another context (its gather wrote the arena this one rewrites).  cand_ev covers derivations
+    // only, not the searches that read the rows: like the mask's built_ev it relies on the rule of the header that nobody changes
+    // the store while searches are in flight
+    if (f->cand_ctx && f->cand_ctx != ctx) QK_HIP(hipStreamWaitEvent(st, f->cand_ev, 0));
+    const int64_t need = std::max<int64_t>(qk_round_up64(n, 16), 1024);  // (at least 1024 rows, like every arena)
+    if (need > c->cap_rows || !c->vecs) {
+        cand_free_arena(c);
+        int64_t cap = need + need / 4;
+        if (max_rows > 0) cap = std::min(cap, max_rows);
+        cap = qk_round_up64(std::max(cap, need), 16);
+        if (hipMalloc((void **)&c->vecs, (size_t)cap * c->dpad * sizeof(float)) != hipSuccess ||
+            hipMalloc((void **)&c->norms, (size_t)cap * sizeof(float)) != hipSuccess ||
+            hipMalloc((void **)&c->ids, (size_t)cap * sizeof(int64_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            cand_free_arena(c);
+            QK_FAIL(QK_ERR_OOM, "qk_search_filtered_exact: no memory for %lld candidate rows x %d dims", (long long)cap, c->dpad);
+        }
+        c->cap_rows = cap;
+        // what a fresh arena holds: rows behind the data are only ever read masked, but finite and deterministic
+        QK_HIP(hipMemsetAsync(c->vecs, 0, (size_t)cap * c->dpad * sizeof(float), st));
+        QK_HIP(hipMemsetAsync(c->norms, 0, (size_t)cap * sizeof(float), st));
+        QK_HIP(hipMemsetAsync(c->ids, 0xFF, (size_t)cap * sizeof(int64_t), st));
+    }
+    if (n > 0) {
+        const int64_t nwords = f->cap_rows / 16;  // (the mask was built for this capacity: filter_current)
+        const int64_t nb = (nwords + QK_CAND_BLOCK - 1) / QK_CAND_BLOCK;
+        QK_TRY(qk_ws_reserve(ctx, (size_t)(2 * nb + 1) * sizeof(int64_t) + 1024));
+        int64_t *cnt = (int64_t *)qk_ws_alloc(ctx, (size_t)nb * sizeof(int64_t));
+        int64_t *boff = (int64_t *)qk_ws_alloc(ctx, (size_t)(nb + 1) * sizeof(int64_t));
+        if (!cnt || !boff) QK_FAIL(QK_ERR_OOM, "qk_search_filtered_exact: workspace exhausted");
+        hipLaunchKernelGGL(k_filter_block_counts, dim3((unsigned)((nb + 15) / 16)), dim3(256), 0, st, (const uint16_t *)f->mask, nwords, nb, cnt);
+        hipLaunchKernelGGL(k_filter_block_scan, dim3(1), dim3(1024), 0, st, (const int64_t *)cnt, boff, nb);
+        GatherParams G;
+        G.mask = f->mask;
+        G.nwords = nwords;
+        G.boff = boff;
+        G.nb = nb;
+        G.n = n;
+        G.ntiles = (n + 15) / 16;
+        G.nblk = s->nblk;
+        G.sv = (const float4 *)s->vecs;
+        G.sn = (const uint32_t *)s->norms;
+        G.si = s->ids;
+        G.src_rows = s->cap_rows;
+        G.dv = (float4 *)c->vecs;
+        G.dn = (uint32_t *)c->norms;
+        G.di = c->ids;
+        hipLaunchKernelGGL(k_filter_gather, dim3((unsigned)((G.ntiles + 3) / 4)), dim3(256), 0, st, G);
+        QK_HIP(hipGetLastError());
+    }
+    QK_HIP(hipEventRecord(f->cand_ev, st));
+    // the one list: rows 0 .. n - 1.  The id bounds are the source's (bounds of a subset); the host id mirror stays empty
+    c->ctx = ctx;  // (its table upload and row-major copy run on the stream that ran the gather)
+    qk_part &pt = c->parts[0];
+    pt.row_off = 0;
+    pt.size = n;
+    pt.cap = c->cap_rows;
+    c->ntotal = n;
+    c->used_rows = qk_round_up64(n, 16);
+    c->min_id_seen = s->min_id_seen;
+    c->max_id_seen = s->max_id_seen;
+    c->table_dirty = true;
+    QK_TRY(qk_store_sync_table(c));
+    f->cand_built = true;
+    f->cand_builds++;
+    f->cand_ctx = ctx;
+    return QK_OK;
 }
 
 }  // namespace
@@ -440,6 +670,15 @@ int qk_filter_destroy(qk_filter *f) {
     if (f->counts_ev) hipEventDestroy(f->counts_ev);
     if (f->mask) hipFree(f->mask);  // (hipFree waits for the device: no scan still reads the mask)
     if (f->counts) hipFree(f->counts);
+    if (f->cand_ev) hipEventDestroy(f->cand_ev);
+    if (f->cand) {  // (not qk_store_destroy: its context may be gone; every hipFree waits for the device)
+        qk_store *c = f->cand;
+        cand_free_arena(c);
+        if (c->d_off) hipFree(c->d_off);
+        if (c->d_size) hipFree(c->d_size);
+        if (c->rowmajor) hipFree(c->rowmajor);
+        delete c;
+    }
     if (f->d_ids) hipFree(f->d_ids);
     if (f->d_allowed) hipFree(f->d_allowed);
     (void)hipGetLastError();
@@ -463,6 +702,7 @@ int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t
         if (f->kind == QK_FILTER_KIND_WHERE) *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t));  // (no ids: the mask only)
         else *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t) + std::max<int64_t>(f->n_ids, 1) * sizeof(int64_t) + 8);
         *device_bytes += (int64_t)(f->counts_cap * sizeof(int32_t));  // (adaptive probing: once a call has derived them)
+        *device_bytes += cand_device_bytes(f);                        // (exact search: once a call has derived the store)
     }
     return QK_OK;
 }
@@ -503,6 +743,53 @@ int qk_scan_filtered(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const 
         }
     }
     return qk_run_search(ctx, nullptr, s, x, Q, pids, P, 0, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, f);
+}
+
+// ---- exact search --------------------------------------------------------------------------------------------------------------
+int qk_filter_candidate_rows(qk_ctx *ctx, qk_store *s, qk_filter *f, int64_t *rows) {
+    if (!ctx || !s || !f || !rows) QK_FAIL(QK_ERR_INVALID, "qk_filter_candidate_rows: null argument");
+    QK_HIP(hipSetDevice(ctx->device));
+    const uint16_t *mask = nullptr;
+    QK_TRY(qk_filter_ensure(ctx, s, f, &mask));
+    return cand_count(f, rows);
+}
+
+int qk_search_filtered_exact(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, int k, int metric, qk_filter *f, int64_t max_rows,
+                             int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+    if (!ctx || !s || !f || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_exact: null argument");
+    if (k <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_exact: k must be positive");
+    if (k > QK_MAX_WIDE_K) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_search_filtered_exact: k=%d exceeds %d", k, QK_MAX_WIDE_K);
+    if (max_rows < 0) QK_FAIL(QK_ERR_INVALID, "qk_search_filtered_exact: max_rows must not be negative");
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    QK_TRY(qk_check_overflow(ctx));
+    QK_HIP(hipSetDevice(ctx->device));
+    if (timing) memset(timing, 0, sizeof(*timing));
+    // (a mask build and the gather lie in front of the scan's events: part of total_ms only, like the cut of an adaptive call)
+    const bool tm = ctx->timing && timing && Q > 0;
+    if (tm) QK_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+    const uint16_t *mask = nullptr;
+    QK_TRY(qk_filter_ensure(ctx, s, f, &mask));
+    int64_t n = 0;
+    QK_TRY(cand_count(f, &n));
+    if (max_rows > 0 && n > max_rows)
+        QK_FAIL(QK_ERR_UNSUPPORTED, "qk_search_filtered_exact: the filter has %lld candidates, max_rows=%lld", (long long)n, (long long)max_rows);
+    if (Q <= 0) return QK_OK;
+    QK_TRY(cand_ensure(ctx, s, f, n, max_rows));
+    QK_TRY(qk_run_search(ctx, nullptr, f->cand, x, Q, nullptr, 0, 0, k, metric, out_ids, out_dist, mem, timing, false, false));
+    if (tm) {
+        float ms = 0.f;
+        QK_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[7]));
+        timing->total_ms = ms;
+    }
+    return QK_OK;
+}
+
+int qk_filter_exact_info(qk_filter *f, int64_t *rows, int64_t *builds, int64_t *device_bytes) {
+    if (!f) QK_FAIL(QK_ERR_INVALID, "qk_filter_exact_info: null filter");
+    if (rows) *rows = f->cand ? f->cand->ntotal : 0;
+    if (builds) *builds = f->cand_builds;
+    if (device_bytes) *device_bytes = cand_device_bytes(f);
+    return QK_OK;
 }
 
 // ---- one filter per query ------------------------------------------------------------------------------------------------------

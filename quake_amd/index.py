@@ -130,6 +130,12 @@ class SearchParams(_Summary):  # common.h:171-184, wrap.cpp:153-186
         # SearchResult.nprobed says how many each query probed
         self.max_nprobe = 0
         self.filter_min_candidates = 0
+        # extension (not part of the summary): exact search under a selective filter -- with filter_exact_rows > 0 and `filter`
+        # set, a filter that has at most that many candidate vectors in the index NOW is answered exactly: the k best of ALL its
+        # candidates, no partition probed, k up to 8192 (SearchResult.exact is True); a filter with more takes the path it takes
+        # today, fixed nprobe or adaptive under max_nprobe (exact is False).  0 = off.  An exact call probes no partition, so it
+        # records no hits for the maintenance policy
+        self.filter_exact_rows = 0
 
 
 class SearchFilter:
@@ -242,6 +248,7 @@ class SearchResult:  # common.h:243-247
         self.distances = None
         self.timing_info = None
         self.nprobed = None  # extension: int32 [Q] partitions probed per query under SearchParams.max_nprobe, else None
+        self.exact = None    # extension: True / False on a search that consulted SearchParams.filter_exact_rows, else None
         self.cursor = None   # extension: the SearchCursor behind this page (QuakeIndex.search_after), else None
 
 
@@ -552,6 +559,23 @@ class QuakeIndex:
         use_aps = (search_params.recall_target is not None and search_params.recall_target > 0.0 and self.parent is not None
                    and not search_params.batched_scan)  # query_coordinator.cpp:502,637-641,659-673
         grp = self._store if isinstance(self._store, capi.Group) else None
+        exact_rows = int(getattr(search_params, "filter_exact_rows", 0) or 0)
+        if exact_rows < 0:
+            raise RuntimeError("[QuakeIndex::search()] SearchParams.filter_exact_rows must not be negative (0 turns exact "
+                               "filtered search off)")
+        if exact_rows > 0:
+            # exact filtered search (extension): one filter, one device, no recall target; the rest is refused, not approximated
+            if (getattr(search_params, "filters", None) or []) or getattr(search_params, "query_filter", None) is not None:
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.filter_exact_rows is not supported with filters / "
+                                   "query_filter (one filter per query)")
+            if getattr(search_params, "filter", None) is None:
+                raise RuntimeError("[QuakeIndex::search()] SearchParams.filter_exact_rows needs a filter: without one every "
+                                   "vector is a candidate")
+            if search_params.recall_target is not None and search_params.recall_target > 0.0:
+                raise RuntimeError("[QuakeIndex::search()] filter_exact_rows cannot be combined with recall_target > 0: "
+                                   "not supported")
+            if grp is not None:
+                raise RuntimeError("[QuakeIndex::search()] filter_exact_rows is not supported with num_workers > 0")
         flt = getattr(search_params, "filter", None)
         if flt is not None:
             # filtered search (extension): the fixed-nprobe branch of one device; the rest is refused, not approximated
@@ -607,6 +631,24 @@ class QuakeIndex:
                 raise RuntimeError("[QuakeIndex::search()] SearchParams.max_nprobe=%d is below nprobe=%d (0 turns adaptive "
                                    "probing off)" % (max_nprobe, nprobe))
         adaptive = max_nprobe > nprobe and self.parent is not None  # (a flat index scans everything: nothing to adapt)
+        if exact_rows > 0:
+            res.exact = flt.candidate_rows(self._ctx) <= exact_rows
+        if res.exact:
+            # the flat search of the filter's candidate rows: no parent, no nprobe, no hits for the policy
+            self._ctx.set_timing(1)
+            try:
+                ids, dist, tm = self._ctx.search_exact(self._store, xd, int(k), self.metric_, flt, max_rows=exact_rows, timing=True)
+            finally:
+                self._ctx.set_timing(0)
+            ti.n_queries = int(x.shape[0])
+            ti.partitions_scanned = int(tm["n_items"])  # (as this mirror's search of a flat index reports it: the one list)
+            ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+            ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+            ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+            ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+            res.ids = ids if on_dev else ids.cpu()
+            res.distances = dist if on_dev else dist.cpu()
+            return res
         if grp is not None:
             grp.set_stream(torch.cuda.current_stream(grp.device).cuda_stream)  # the lead's stream (see _context)
         if use_aps:
@@ -698,6 +740,9 @@ class QuakeIndex:
         if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
             raise RuntimeError("[QuakeIndex::search_after()] SearchParams.max_nprobe (adaptive probing) is not supported by "
                                "search_after: a page is defined over a fixed set of probed partitions")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) > 0:
+            raise RuntimeError("[QuakeIndex::search_after()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                               "search_after")
         if sp.recall_target is not None and sp.recall_target > 0.0:
             raise RuntimeError("[QuakeIndex::search_after()] search_after is not supported with recall_target > 0")
         if isinstance(self._store, capi.Group):
@@ -770,6 +815,9 @@ class QuakeIndex:
         if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
             raise RuntimeError("[QuakeIndex::range_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                "supported by range_search")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) > 0:
+            raise RuntimeError("[QuakeIndex::range_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                               "range_search")
         if sp.recall_target is not None and sp.recall_target > 0.0:
             raise RuntimeError("[QuakeIndex::range_search()] range_search is not supported with recall_target > 0")
         if isinstance(self._store, capi.Group):
@@ -834,6 +882,9 @@ class QuakeIndex:
         if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
             raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                "supported by grouped_search")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) > 0:
+            raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                               "grouped_search")
         if sp.recall_target is not None and sp.recall_target > 0.0:
             raise RuntimeError("[QuakeIndex::grouped_search()] grouped_search is not supported with recall_target > 0")
         if isinstance(self._store, capi.Group):
