@@ -356,6 +356,52 @@ QK_API int qk_search_filtered_exact(qk_ctx *ctx, qk_store *s, const float *x, in
                                     int64_t max_rows, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
 QK_API int qk_filter_exact_info(qk_filter *f, int64_t *rows, int64_t *builds, int64_t *device_bytes);
 
+/* Exact filtered search, one filter per query: a candidate pool, one list per filter.  A batch that mixes tenants is answered
+ * exactly in one enqueue: query i gets the exact top-k of the candidates of filters[qfilter[i]].
+ *   Result: row i is bit for bit -- ids, distance bits, padding -- row 0 of qk_search_filtered_exact(query i alone,
+ *     filters[qfilter[i]]).  1 <= k <= 8192, d up to QK_MAX_D, qk_ctx_set_squared_l2 and the NaN / Inf / overflow / signed zero
+ *     contract as there.
+ *   filters [F], qfilter [Q]: as in qk_search_filtered_batch -- a host array of 1 .. QK_MAX_BATCH_FILTERS handles of s (the same
+ *     handle may appear twice: one slot); qfilter in `mem`; a host value outside [0, F) is QK_ERR_INVALID, a device value outside
+ *     gives that query an all-padding row (checked on the device before any table is indexed).
+ *   The POOL is a private store owned by s: made by the first call, freed by qk_store_exact_pool_drop and qk_store_destroy.  A
+ *     filter that was ADMITTED holds a slot = a list of the pool with exactly its candidate rows (vectors, norm bits, ids) in
+ *     ascending arena-row order: the rows and the order of the private candidate store of qk_search_filtered_exact, which stays as
+ *     it is -- a filter used by both calls holds two copies.  A slot is valid while the filter's mask is current: every mask
+ *     build gives it back, the next call that names the filter gathers it again, qk_filter_destroy frees it, a call on another
+ *     context waits for an admission by event, and no other call allocates or launches anything for the pool.  Slots persist
+ *     across calls with different filter lists: after [A, B], a call with [B, C] gathers C only.  Every filter of `filters` is
+ *     admitted, whether a query names it or not (also with Q == 0).
+ *   Admission of the M filters of a call without a valid slot is one launch series (per 64 MiB of block offsets: 400 filters at
+ *     10M rows): k_pool_block_counts, k_pool_block_scan, k_pool_gather -- the three kernels of the single-filter call indexed by
+ *     a device table of (mask, candidates, destination extent, first destination tile); the gather finds its filter from its
+ *     destination tile.  No atomics, no device library, int64 offsets; no row or id travels to the host.  The candidate counts
+ *     nobody has read since the mask build come back in ONE copy behind ONE wait; the pool's list table is written in stream
+ *     order from host memory without a wait.  A call whose filters are all resident waits for nothing and uploads no table.
+ *   max_rows > 0: if a filter of the call has more candidates the call fails with QK_ERR_UNSUPPORTED, naming the first such index,
+ *     before anything is allocated or enqueued for the pool.
+ *   pool_rows > 0 bounds the rows the pool holds after the call, counted as the sum over resident slots of the candidates rounded
+ *     up to 16: slots of filters NOT named by this call are evicted, least recently named first (ties: lowest slot number); if the
+ *     filters of the call alone need more: QK_ERR_UNSUPPORTED, the pool unchanged.  The pool arena then never exceeds
+ *     max(2 pool_rows, 1024) rows; pool_rows == 0: no bound.  Extents of evicted, rebuilt and destroyed filters are handed out
+ *     again (first fit); when nothing fits, the live extents are packed into a fresh arena (both exist during the copy).
+ *   QK_ERR_INVALID: a null handle, another store's or device's filter, max_rows < 0, pool_rows < 0, k < 1.
+ *   Inside: k_pool_pids turns a device qfilter into pids [Q][1] of pool list numbers (-1 out of range; a host qfilter is mapped
+ *     on the host), then the unfiltered partition scan of the pool runs with P = 1 (the wide-k pipeline beyond QK_MAX_K):
+ *     qk_ctx_last_scan_kernel names an unfiltered form.  timing as qk_scan fills it; mask builds and the admission lie in front
+ *     of the scan's events and are part of total_ms only.
+ * qk_store_exact_pool_info (any pointer may be NULL; all 0 before the first call and after a drop): slots = resident slots,
+ * rows = the measure pool_rows bounds, cap_rows = the pool arena's capacity, builds = slots gathered so far (one per filter
+ * admitted, not per admission), evictions = slots evicted by a budget, device_bytes = arena + list table.
+ * qk_store_exact_pool_drop frees the pool; filters stay valid and are admitted again on demand.
+ * Out of scope: the device group, range / grouped / paged search over the pool, the recall-target walk. */
+QK_API int qk_search_filtered_exact_batch(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, int k, int metric,
+                                          qk_filter *const *filters, int F, const int32_t *qfilter, int64_t max_rows,
+                                          int64_t pool_rows, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_store_exact_pool_info(qk_store *s, int64_t *slots, int64_t *rows, int64_t *cap_rows, int64_t *builds,
+                                    int64_t *evictions, int64_t *device_bytes);
+QK_API int qk_store_exact_pool_drop(qk_store *s);
+
 /* ---- range search --------------------------------------------------------------------------------
  * No reference counterpart (every search of the reference is a top-k): all rows of the probed lists within a radius of each query.
  * Lists: qk_range_search probes what the unfiltered qk_search probes -- the same min(nprobe, parent lists) lists in the same rank

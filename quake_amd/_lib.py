@@ -90,6 +90,11 @@ SIGNATURES = {
     "qk_filter_candidate_rows": (_int, [_vp, _vp, _vp, C.POINTER(_i64)]),
     "qk_search_filtered_exact": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _i64, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_filter_exact_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    # exact search per query: (ctx, s, x, Q, k, metric, filters, F, qfilter, max_rows, pool_rows, out_ids, out_dist, mem, timing)
+    "qk_search_filtered_exact_batch": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _int, _vp, _i64, _i64, _vp, _vp, _int,
+                                       C.POINTER(QkTiming)]),
+    "qk_store_exact_pool_info": (_int, [_vp] + [C.POINTER(_i64)] * 6),
+    "qk_store_exact_pool_drop": (_int, [_vp]),
     "qk_search_filtered": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search_filtered_tracked": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _int,
                                    C.POINTER(QkTiming)]),

@@ -273,6 +273,25 @@ class Context:
                                                 _mem_of(x), C.byref(t) if timing else None))
         return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
 
+    def search_exact_batch(self, store, x, k, metric, filters, query_filter, max_rows=0, pool_rows=0, timing=False, out=None):
+        """qk_search_filtered_exact_batch: query i gets the k best candidates of filters[query_filter[i]] over the WHOLE store,
+        exactly, in one enqueue -- every filter's candidates are a list of the store's candidate pool (Store.exact_pool_info).
+        query_filter: int32 [Q], on the host or on the device with x.  max_rows > 0: a filter with more candidates is refused;
+        pool_rows > 0: the rows the pool may hold after the call."""
+        x = _f32(x)
+        Q = x.shape[0]
+        if out is None:
+            out_i = _empty_like_mem((Q, k), np.int64, x)
+            out_d = _empty_like_mem((Q, k), np.float32, x)
+        else:
+            out_i, out_d = out
+        t = QkTiming()
+        harr, F, qf = _filter_batch(None, filters, query_filter, x)
+        check(self.lib.qk_search_filtered_exact_batch(self.h, store.h, _ptr(x), Q, int(k), metric_code(metric), harr, F, _ptr(qf),
+                                                      int(max_rows), int(pool_rows), _ptr(out_i), _ptr(out_d), _mem_of(x),
+                                                      C.byref(t) if timing else None))
+        return (out_i, out_d, timing_dict(t)) if timing else (out_i, out_d)
+
     def search_tracked(self, parent, store, x, nprobe, k, metric, timing=False, filter=None, filters=None, query_filter=None):
         """qk_search_tracked: search + the [Q, min(nprobe, parent lists)] list numbers every query scanned, one enqueue.
         Returns (ids, dist, probed[, timing]).  filter: a Filter of `store` (qk_search_filtered_tracked; the probed lists are
@@ -778,6 +797,17 @@ class Store:
 
     def device_bytes(self):
         return self.lib.qk_store_device_bytes(self.h)
+
+    def exact_pool_info(self):
+        """{slots, rows, cap_rows, builds, evictions, device_bytes} of the candidate pool of exact per-query search
+        (qk_store_exact_pool_info); all 0 before the first Context.search_exact_batch and after exact_pool_drop"""
+        v = [C.c_int64() for _ in range(6)]
+        check(self.lib.qk_store_exact_pool_info(self.h, *[C.byref(a) for a in v]))
+        return dict(zip(("slots", "rows", "cap_rows", "builds", "evictions", "device_bytes"), (a.value for a in v)))
+
+    def exact_pool_drop(self):
+        """free the candidate pool (qk_store_exact_pool_drop); filters stay valid and are admitted again on demand"""
+        check(self.lib.qk_store_exact_pool_drop(self.h))
 
     COUNTER_NAMES = ("arena_reallocations", "arena_compactions", "list_relocations", "rows_copied", "rowmajor_rebuilds",
                      "table_uploads", "id_index_rebuilds", "context_scratch_reallocations")

@@ -225,6 +225,8 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("max_nprobe", &SearchParams::max_nprobe)  // extension: adaptive probing under a filter; not in the summary
         .def_readwrite("filter_min_candidates", &SearchParams::filter_min_candidates)
         .def_readwrite("filter_exact_rows", &SearchParams::filter_exact_rows)  // extension: exact search under a selective filter
+        .def_readwrite("filters_exact_rows", &SearchParams::filters_exact_rows)  // extension: the same, one filter per query
+        .def_readwrite("filters_exact_pool_rows", &SearchParams::filters_exact_pool_rows)
         .def("__repr__", [](const SearchParams &p) {  // wrap.cpp:173-186
             return Repr().kv("k", p.k).kv("nprobe", p.nprobe).kv("recall_target", p.recall_target).kv("batched_scan", p.batched_scan)
                 .kv("use_precomputed", p.use_precomputed).kv("initial_search_fraction", p.initial_search_fraction)
@@ -360,5 +362,9 @@ PYBIND11_MODULE(_bindings, m) {
                 return py::bool_(r.exact == 1);
             },
             [](SearchResult &r, py::object v) { r.exact = v.is_none() ? -1 : (v.cast<bool>() ? 1 : 0); })
+        .def_property(
+            "exact_mask",  // extension: bool [Q], the queries answered exactly under SearchParams.filters_exact_rows, else None
+            [](const SearchResult &r) -> py::object { return r.exact_mask.defined() ? py::cast(r.exact_mask) : py::none(); },
+            [](SearchResult &r, py::object v) { r.exact_mask = v.is_none() ? Tensor() : v.cast<Tensor>(); })
         .def_readwrite("cursor", &SearchResult::cursor);  // extension: the SearchCursor behind a search_after page, else None
 }

@@ -101,6 +101,12 @@ struct SearchParams {  // common.h:171-184
     // or adaptive under max_nprobe (exact = 0).  0 = off.  An exact call probes no partition, so it records no hits for the
     // maintenance policy
     int64_t filter_exact_rows = 0;
+    // extension, not part of the summary: the same with one filter per query -- with filters_exact_rows > 0 and `filters` /
+    // `query_filter` set, the queries whose filter has at most that many candidates NOW are answered exactly in one call over the
+    // index's candidate pool (SearchResult::exact_mask says which), the others take the path they take today.
+    // filters_exact_pool_rows > 0 bounds the rows that pool holds (0 = no bound)
+    int64_t filters_exact_rows = 0;
+    int64_t filters_exact_pool_rows = 0;
 };
 
 struct BuildTimingInfo {  // common.h:189-198
@@ -143,6 +149,7 @@ struct SearchResult {  // common.h:243-247
     Tensor nprobed;  // extension: int32 [Q] partitions probed per query under SearchParams::max_nprobe, else undefined
     int exact = -1;  // extension: 1 / 0 on a search that consulted SearchParams::filter_exact_rows, else -1 (None in Python)
     shared_ptr<SearchCursor> cursor = nullptr;  // extension: the cursor behind this page (QuakeIndex::search_after), else null
+    Tensor exact_mask;  // extension: bool [Q], the queries answered exactly under SearchParams::filters_exact_rows, else undefined
 };
 
 // extension (QuakeIndex::range_search): query i's hits are ids / distances [lims[i], lims[i+1]), in scan order

@@ -116,6 +116,82 @@ shared_ptr<SearchResult> QueryCoordinator::search(Tensor x, shared_ptr<SearchPar
         }
     } timing_mode(ctx, !on_dev || device_timing_);
     qk_timing *tmp = (!on_dev || device_timing_) ? &tm : nullptr;  // device tensors: asynchronous unless the caller opted in
+    if (sp->filters_exact_rows < 0 || sp->filters_exact_pool_rows < 0)
+        throw std::runtime_error("[QuakeIndex::search()] SearchParams.filters_exact_rows / filters_exact_pool_rows must not be "
+                                 "negative (0 turns exact per-query filtered search off / leaves the pool unbounded)");
+    if (sp->filters_exact_rows > 0) {
+        // exact search with one filter per query (extension): the queries whose filter has at most filters_exact_rows candidates go
+        // to qk_search_filtered_exact_batch with only those filters -- the others never enter the pool --, the rest go through
+        // search() as they do today, and the two answers are scattered into one result
+        if (sp->filter)
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.filters_exact_rows is not supported with filter (one filter "
+                                     "for every query: that is filter_exact_rows)");
+        if (sp->filters.empty() || !sp->query_filter.defined())
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.filters_exact_rows needs filters and query_filter: without "
+                                     "them every vector is a candidate");
+        if (sp->recall_target > 0.0f)
+            throw std::runtime_error("[QuakeIndex::search()] filters_exact_rows cannot be combined with recall_target > 0: "
+                                     "not supported");
+        if (group) throw std::runtime_error("[QuakeIndex::search()] filters_exact_rows is not supported with num_workers > 0");
+        for (const auto &f : sp->filters)
+            if (!f || !f->h) throw std::runtime_error("[QuakeIndex::search()] SearchParams.filters must come from make_filter()");
+        for (const auto &f : sp->filters)
+            if (f->owner != store) throw std::runtime_error("[QuakeIndex::search()] the filter was made for another index");
+        const Tensor &qf = sp->query_filter;
+        const int64_t F = (int64_t)sp->filters.size();
+        if (qf.dim() != 1 || qf.size(0) != Q)
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.query_filter must have one entry per query (" +
+                                     std::to_string(qf.dim() >= 1 ? qf.size(0) : 0) + " != " + std::to_string(Q) + ")");
+        if (!qf.is_cuda() && qf.numel() > 0 && (qf.min().item<int64_t>() < 0 || qf.max().item<int64_t>() >= F))
+            throw std::runtime_error("[QuakeIndex::search()] SearchParams.query_filter holds a value outside [0, " + std::to_string(F) + ")");
+        std::vector<qk_filter *> small;
+        Tensor remap = torch::full({F}, -1, torch::kInt64);
+        for (int64_t i = 0; i < F; i++) {
+            int64_t rows = 0;  // (the count is cached per mask build)
+            qk_check(qk_filter_candidate_rows(ctx, store, sp->filters[i]->h, &rows));
+            if (rows <= sp->filters_exact_rows) {
+                remap[i] = (int64_t)small.size();
+                small.push_back(sp->filters[i]->h);
+            }
+        }
+        // split where query_filter lives: a host tensor on the host, a device tensor with torch ops on the device (a device value
+        // outside [0, F) stays with the probed call, which pads that row)
+        Tensor ql = qf.to(torch::kInt64);
+        Tensor slot = torch::where((ql >= 0) & (ql < F), remap.to(ql.device()).index_select(0, ql.clamp(0, F - 1)), torch::full_like(ql, -1));
+        Tensor mask = slot >= 0;
+        Tensor ie = torch::nonzero(mask).reshape({-1}), ip = torch::nonzero(~mask).reshape({-1});
+        const auto xdev = xq.device();
+        if (ie.numel() > 0) {
+            // one enqueue, no partition probed: no hits for the policy
+            Tensor xe = xq.index_select(0, ie.to(xdev)).contiguous();
+            Tensor qe = slot.index_select(0, ie).to(xdev, torch::kInt32).contiguous();
+            const int64_t Qe = xe.size(0);
+            Tensor gi = torch::empty({Qe, k}, res->ids.options()), gd = torch::empty({Qe, k}, res->distances.options());
+            qk_check(qk_search_filtered_exact_batch(ctx, store, xe.data_ptr<float>(), Qe, k, (int)metric_, small.data(), (int)small.size(),
+                                                    qe.data_ptr<int32_t>(), sp->filters_exact_rows, sp->filters_exact_pool_rows,
+                                                    gi.data_ptr<int64_t>(), gd.data_ptr<float>(), mem, nullptr));
+            res->ids.index_copy_(0, ie.to(xdev), gi);
+            res->distances.index_copy_(0, ie.to(xdev), gd);
+        }
+        if (ip.numel() > 0) {
+            auto sp2 = std::make_shared<SearchParams>(*sp);
+            sp2->filters_exact_rows = 0;
+            sp2->query_filter = qf.index_select(0, ip);
+            auto r2 = search(xq.index_select(0, ip.to(xdev)).contiguous(), sp2);
+            res->ids.index_copy_(0, ip.to(xdev), r2->ids);
+            res->distances.index_copy_(0, ip.to(xdev), r2->distances);
+            ti->partitions_scanned = r2->timing_info->partitions_scanned;
+            ti->parent_info = r2->timing_info->parent_info;
+            if (r2->nprobed.defined()) {  // (adaptive probing: an exact query probed no partition)
+                res->nprobed = torch::zeros({Q}, r2->nprobed.options());
+                res->nprobed.index_copy_(0, ip.to(r2->nprobed.device()), r2->nprobed);
+            }
+        }
+        res->exact = 0;  // (its meaning is the single-filter call's: this was not one)
+        res->exact_mask = mask.to(xdev);
+        ti->total_time_ns = ns_since(t0);
+        return res;
+    }
     if (sp->filter_exact_rows < 0)
         throw std::runtime_error("[QuakeIndex::search()] SearchParams.filter_exact_rows must not be negative (0 turns exact "
                                  "filtered search off)");
@@ -301,6 +377,9 @@ shared_ptr<SearchResult> QueryCoordinator::search_after(Tensor x, shared_ptr<Sea
     if (sp->max_nprobe > 0)
         throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.max_nprobe (adaptive probing) is not supported by "
                                  "search_after: a page is defined over a fixed set of probed partitions");
+    if (sp->filters_exact_rows != 0)
+        throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
+                                 "supported by search_after");
     if (sp->filter_exact_rows > 0)
         throw std::runtime_error("[QuakeIndex::search_after()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
                                  "search_after");
@@ -389,6 +468,9 @@ shared_ptr<RangeSearchResult> QueryCoordinator::range_search(Tensor x, float rad
     if (!sp->filters.empty() || sp->query_filter.defined())
         throw std::runtime_error("[QuakeIndex::range_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                  "supported by range_search");
+    if (sp->filters_exact_rows != 0)
+        throw std::runtime_error("[QuakeIndex::range_search()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
+                                 "supported by range_search");
     if (sp->filter_exact_rows > 0)
         throw std::runtime_error("[QuakeIndex::range_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
                                  "range_search");
@@ -468,6 +550,9 @@ shared_ptr<GroupedSearchResult> QueryCoordinator::grouped_search(Tensor x, qk_at
         throw std::runtime_error("[QuakeIndex::grouped_search()] group_size must be between 1 and " + std::to_string(QK_MAX_GROUP_SIZE));
     if (!sp->filters.empty() || sp->query_filter.defined())
         throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
+                                 "supported by grouped_search");
+    if (sp->filters_exact_rows != 0)
+        throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
                                  "supported by grouped_search");
     if (sp->filter_exact_rows > 0)
         throw std::runtime_error("[QuakeIndex::grouped_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "

@@ -157,6 +157,10 @@ struct qk_filter {
     int64_t cand_rows = -1;         // candidates of the last mask build, read from d_allowed once per build (-1: not read yet)
     hipEvent_t cand_ev = nullptr;   // behind the last derivation, on the stream of cand_ctx
     qk_ctx *cand_ctx = nullptr;
+    // exact search per query (qk_search_filtered_exact_batch): the list of the store's candidate pool that holds a copy of the same
+    // rows, -1 = none.  The pool is found through store_uid and knows the slot's owner by serial; every mask build and
+    // qk_filter_destroy give the slot back
+    int64_t pool_slot = -1;
 };
 
 // qk_filter.hip

@@ -194,6 +194,11 @@ struct qk_ctx {
     // that names none -- and the next cursors on their way back to a host caller
     char *after_buf = nullptr;
     size_t after_cap = 0;
+    // exact search per query with device buffers (qk_filter.hip): the pool list number of every filter of the call ([0, 32 KiB):
+    // QK_MAX_BATCH_FILTERS int64, uploaded when pool_key -- those numbers -- changes) and the pids [Q] derived from them
+    char *pool_buf = nullptr;
+    size_t pool_buf_cap = 0;
+    std::vector<int64_t> pool_key;
 };
 
 int qk_ws_reserve(qk_ctx *ctx, size_t bytes);          // make sure the workspace can hold `bytes` (may sync+realloc)
@@ -261,7 +266,11 @@ struct qk_store {
     // paged search without a filter (qk_after.hip): a deny-nothing filter of this store, made by the first such call and kept; like
     // every filter it follows add / remove / maintenance through qk_filter_ensure
     qk_filter *allow_all = nullptr;
+    // exact search per query (qk_filter.hip, "the candidate pool"): made by the first qk_search_filtered_exact_batch, freed by
+    // qk_store_exact_pool_drop and qk_store_destroy
+    struct qk_pool *pool = nullptr;
 };
+void qk_pool_destroy(qk_store *s);
 void qk_store_ensure_index(qk_store *s);
 int qk_store_add_batch_host_assign(qk_store *s, int64_t n, const int64_t *ids_dev, const float *vecs_dev, const std::vector<int64_t> &h_assign,
                                    bool ids_indexed = false);

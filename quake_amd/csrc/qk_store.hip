@@ -671,6 +671,7 @@ int qk_store_destroy(qk_store *s) {
     if (s->bounce_n) hipFree(s->bounce_n);
     if (s->bounce_i) hipFree(s->bounce_i);
     if (s->allow_all) qk_filter_destroy(s->allow_all);
+    qk_pool_destroy(s);
     delete s;
     return QK_OK;
 }

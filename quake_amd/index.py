@@ -9,6 +9,7 @@ the bookkeeping the reference keeps in PartitionManager (resident-id set, next p
 Tensors: torch tensors in, torch tensors out.  CPU tensors behave like the reference (results are CPU tensors);
 CUDA tensors stay on the device.
 """
+import copy
 import os
 import struct
 import time
@@ -136,6 +137,12 @@ class SearchParams(_Summary):  # common.h:171-184, wrap.cpp:153-186
         # today, fixed nprobe or adaptive under max_nprobe (exact is False).  0 = off.  An exact call probes no partition, so it
         # records no hits for the maintenance policy
         self.filter_exact_rows = 0
+        # extension (not part of the summary): the same with one filter per query -- with filters_exact_rows > 0 and `filters` /
+        # `query_filter` set, the queries whose filter has at most that many candidates NOW are answered exactly in one call over
+        # the index's candidate pool (SearchResult.exact_mask says which), the others take the path they take today.
+        # filters_exact_pool_rows > 0 bounds the rows that pool holds (0 = no bound)
+        self.filters_exact_rows = 0
+        self.filters_exact_pool_rows = 0
 
 
 class SearchFilter:
@@ -250,6 +257,7 @@ class SearchResult:  # common.h:243-247
         self.nprobed = None  # extension: int32 [Q] partitions probed per query under SearchParams.max_nprobe, else None
         self.exact = None    # extension: True / False on a search that consulted SearchParams.filter_exact_rows, else None
         self.cursor = None   # extension: the SearchCursor behind this page (QuakeIndex.search_after), else None
+        self.exact_mask = None  # extension: bool [Q], the queries answered exactly under SearchParams.filters_exact_rows, else None
 
 
 class SearchCursor:
@@ -559,6 +567,13 @@ class QuakeIndex:
         use_aps = (search_params.recall_target is not None and search_params.recall_target > 0.0 and self.parent is not None
                    and not search_params.batched_scan)  # query_coordinator.cpp:502,637-641,659-673
         grp = self._store if isinstance(self._store, capi.Group) else None
+        fx_rows = int(getattr(search_params, "filters_exact_rows", 0) or 0)
+        fx_pool = int(getattr(search_params, "filters_exact_pool_rows", 0) or 0)
+        if fx_rows < 0 or fx_pool < 0:
+            raise RuntimeError("[QuakeIndex::search()] SearchParams.filters_exact_rows / filters_exact_pool_rows must not be "
+                               "negative (0 turns exact per-query filtered search off / leaves the pool unbounded)")
+        if fx_rows > 0:
+            return self._search_filters_exact(x, xd, search_params, res, int(k), fx_rows, fx_pool, grp, t0)
         exact_rows = int(getattr(search_params, "filter_exact_rows", 0) or 0)
         if exact_rows < 0:
             raise RuntimeError("[QuakeIndex::search()] SearchParams.filter_exact_rows must not be negative (0 turns exact "
@@ -723,6 +738,77 @@ class QuakeIndex:
         res.distances = dist if on_dev else dist.cpu()
         return res
 
+    def _search_filters_exact(self, x, xd, sp, res, k, fx_rows, fx_pool, grp, t0):
+        """search() under SearchParams.filters_exact_rows: the queries whose filter has at most fx_rows candidates go to the exact
+        per-query call (qk_search_filtered_exact_batch) with only those filters -- the others never enter the pool --, the rest
+        go through search() as they do today, and the two answers are scattered into one result"""
+        flts = list(getattr(sp, "filters", None) or [])
+        qflt = getattr(sp, "query_filter", None)
+        if getattr(sp, "filter", None) is not None:
+            raise RuntimeError("[QuakeIndex::search()] SearchParams.filters_exact_rows is not supported with filter (one filter "
+                               "for every query: that is filter_exact_rows)")
+        if not flts or qflt is None:
+            raise RuntimeError("[QuakeIndex::search()] SearchParams.filters_exact_rows needs filters and query_filter: without "
+                               "them every vector is a candidate")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError("[QuakeIndex::search()] filters_exact_rows cannot be combined with recall_target > 0: "
+                               "not supported")
+        if grp is not None:
+            raise RuntimeError("[QuakeIndex::search()] filters_exact_rows is not supported with num_workers > 0")
+        if any(not isinstance(f, SearchFilter) for f in flts):
+            raise RuntimeError("[QuakeIndex::search()] SearchParams.filters must come from make_filter()")
+        if any(f._store is not self._store for f in flts):
+            raise RuntimeError("[QuakeIndex::search()] the filter was made for another index")
+        qflt = qflt if torch.is_tensor(qflt) else torch.as_tensor(np.asarray(qflt))
+        Q, F = int(x.shape[0]), len(flts)
+        if qflt.dim() != 1 or qflt.shape[0] != Q:
+            raise RuntimeError("[QuakeIndex::search()] SearchParams.query_filter must have one entry per query "
+                               "(%d != %d)" % (qflt.shape[0] if qflt.dim() >= 1 else 0, Q))
+        if not qflt.is_cuda and qflt.numel() > 0 and (int(qflt.min()) < 0 or int(qflt.max()) >= F):
+            raise RuntimeError("[QuakeIndex::search()] SearchParams.query_filter holds a value outside [0, %d)" % F)
+        small = [f._h.candidate_rows(self._ctx) <= fx_rows for f in flts]  # (the count is cached per mask build)
+        remap = torch.tensor(np.cumsum(small) - 1, dtype=torch.int64).masked_fill(~torch.tensor(small), -1).to(qflt.device)
+        # split where query_filter lives: a host tensor on the host, a device tensor with torch ops on the device (a device value
+        # outside [0, F) stays with the probed call, which pads that row)
+        ql = qflt.to(torch.int64)
+        slot = torch.where((ql >= 0) & (ql < F), remap[ql.clamp(0, F - 1)], torch.full_like(ql, -1))
+        mask = slot >= 0
+        dev = xd.device
+        ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
+        dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
+        ti = res.timing_info
+        ti.n_queries = Q
+        ie = torch.nonzero(mask).reshape(-1)
+        ip = torch.nonzero(~mask).reshape(-1)
+        if ie.numel() > 0:
+            # one enqueue, no partition probed: no hits for the policy
+            gi, gd = self._ctx.search_exact_batch(self._store, xd[ie.to(dev)].contiguous(), k, self.metric_,
+                                                  [f._h for f, sm in zip(flts, small) if sm],
+                                                  slot[ie].to(device=dev, dtype=torch.int32), max_rows=fx_rows, pool_rows=fx_pool)
+            ids[ie.to(dev)] = gi
+            dist[ie.to(dev)] = gd
+        if ip.numel() > 0:
+            sp2 = copy.copy(sp)
+            sp2.filters_exact_rows = 0
+            sp2.query_filter = qflt[ip]
+            r2 = self.search(xd[ip.to(dev)].contiguous(), sp2)
+            ids[ip.to(dev)] = r2.ids
+            dist[ip.to(dev)] = r2.distances
+            ti.partitions_scanned = r2.timing_info.partitions_scanned
+            ti.parent_info = r2.timing_info.parent_info
+            if r2.nprobed is not None:  # (adaptive probing: an exact query probed no partition)
+                res.nprobed = torch.zeros(Q, dtype=torch.int32, device=dev)
+                res.nprobed[ip.to(dev)] = r2.nprobed.to(dev)
+        on_dev = x.is_cuda
+        if res.nprobed is not None and not on_dev:
+            res.nprobed = res.nprobed.cpu()
+        res.exact = False  # (its meaning is the single-filter call's: this was not one)
+        res.exact_mask = mask.to(dev) if on_dev else mask.cpu()
+        res.ids = ids if on_dev else ids.cpu()
+        res.distances = dist if on_dev else dist.cpu()
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        return res
+
     def search_after(self, x, search_params, cursor=None):
         """extension (no reference counterpart): the page of search_params.k results behind `cursor` -- a SearchCursor an earlier
         search_after of the SAME queries returned (any page size), None = from the start -- among the vectors of the
@@ -740,6 +826,9 @@ class QuakeIndex:
         if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
             raise RuntimeError("[QuakeIndex::search_after()] SearchParams.max_nprobe (adaptive probing) is not supported by "
                                "search_after: a page is defined over a fixed set of probed partitions")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::search_after()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
+                               "supported by search_after")
         if int(getattr(sp, "filter_exact_rows", 0) or 0) > 0:
             raise RuntimeError("[QuakeIndex::search_after()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
                                "search_after")
@@ -815,6 +904,9 @@ class QuakeIndex:
         if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
             raise RuntimeError("[QuakeIndex::range_search()] SearchParams.filters / query_filter (one filter per query) are not "
                                "supported by range_search")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::range_search()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
+                               "supported by range_search")
         if int(getattr(sp, "filter_exact_rows", 0) or 0) > 0:
             raise RuntimeError("[QuakeIndex::range_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
                                "range_search")
@@ -881,6 +973,9 @@ class QuakeIndex:
         shape = (lambda q: (q, k)) if group_size is None else (lambda q: (q, k, int(group_size)))
         if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
             raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filters / query_filter (one filter per query) are not "
+                               "supported by grouped_search")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
                                "supported by grouped_search")
         if int(getattr(sp, "filter_exact_rows", 0) or 0) > 0:
             raise RuntimeError("[QuakeIndex::grouped_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
