@@ -485,6 +485,39 @@ QK_API int qk_attr_info(qk_attr *a, int64_t *n_ids, uint64_t *version, int *layo
 /* QK_ERR_INVALID: n_clauses < 1, a null column, a column of another store, an unknown op; QK_ERR_UNSUPPORTED: n_clauses >
  * QK_MAX_CLAUSES.  qk_filter_info of the result: n_ids = -1, device_bytes = the mask only. */
 QK_API int qk_filter_create_where(qk_store *s, const qk_clause *clauses, int n_clauses, qk_filter **out);
+/* An EXPRESSION filter: an OR of 1 .. QK_MAX_TERMS conjunctions (terms) over the five ops above and two value-set ops
+ *   QK_OP_IN_SET      the id has a value and it is one of the set's
+ *   QK_OP_NOT_IN_SET  the id has a value and it is none of the set's
+ * `clauses` holds the terms one after the other, term t has term_sizes[t] >= 1 clauses.  A stored row is a candidate iff, for SOME
+ * term, EVERY clause of that term holds for its id; an id without a value in a clause's column fails that clause, NOT_IN_SET
+ * included.  set / n_set: a HOST array read by the two set ops only -- any order, duplicates allowed; the empty set is legal
+ * (IN_SET of it matches nothing, NOT_IN_SET of it every id that has a value); a / b are read by the other five.  At creation the
+ * sets are sorted, de-duplicated and uploaded once into one buffer the filter owns.  Neither term order nor clause order matters.
+ * Otherwise a predicate filter in every respect: it answers like the QK_FILTER_ALLOW filter over {id : some term holds}, is passed
+ * to every entry point that takes a filter, is stamped with the store's (uid, version, cap_rows) and the (serial, version) of the
+ * column of every clause of every term and re-derived by the next filtered call when a stamp moved (k_filter_build_expr: the
+ * sibling of k_filter_build_where -- per row `accepted by an earlier term` and `alive in this term`, a term skipped by a wave none
+ * of whose rows is undecided, set membership by the sorted layout's branch-free binary search), shares ownership of its columns.
+ * QK_ERR_INVALID: n_terms < 1, a term_sizes[t] < 1, a null column, a column of another store, an op outside 0 .. 6, n_set < 0,
+ * n_set > 0 with a null set; QK_ERR_UNSUPPORTED: n_terms > QK_MAX_TERMS, more than QK_MAX_EXPR_CLAUSES clauses in total, n_set >
+ * QK_MAX_SET_VALUES.  qk_filter_info of the result: n_ids = -1, device_bytes = the mask + the set buffer (the clause table travels
+ * in the kernel arguments).  Footprint: every set clause keeps its own sorted copy -- a set named by several clauses is held once
+ * per clause -- so the worst case, 32 set clauses of 2^20 values, is 256 MB of host temporaries during the call and 256 MB of
+ * device buffer for the filter's life; QK_ERR_OOM when either is not to be had.  qk_filter_create_where is unchanged: its own
+ * kernel, QK_MAX_CLAUSES, ops 0 .. 4. */
+#define QK_OP_IN_SET 5
+#define QK_OP_NOT_IN_SET 6
+#define QK_MAX_TERMS 8
+#define QK_MAX_EXPR_CLAUSES 32      /* over all terms */
+#define QK_MAX_SET_VALUES (1 << 20) /* per clause, as given */
+typedef struct {
+    qk_attr *attr;
+    int op;
+    int64_t a, b;
+    const int64_t *set; /* HOST array, read by the two set ops only; any order, duplicates allowed */
+    int64_t n_set;
+} qk_expr_clause;
+QK_API int qk_filter_create_expr(qk_store *s, const qk_expr_clause *clauses, const int *term_sizes, int n_terms, qk_filter **out);
 
 /* ---- grouped search -------------------------------------------------------------------------------
  * No reference counterpart.  The k best GROUPS of a column per query, every group represented by its best row: results that are

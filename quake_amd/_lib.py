@@ -14,7 +14,9 @@ QK_MEM_DEVICE = 1
 QK_MAX_K = 448
 QK_MAX_NPROBE = 8192
 QK_OP_RANGE, QK_OP_NOT_RANGE, QK_OP_ANY_BITS, QK_OP_ALL_BITS, QK_OP_NO_BITS = 0, 1, 2, 3, 4
+QK_OP_IN_SET, QK_OP_NOT_IN_SET = 5, 6
 QK_MAX_CLAUSES = 8
+QK_MAX_TERMS, QK_MAX_EXPR_CLAUSES, QK_MAX_SET_VALUES = 8, 32, 1 << 20
 QK_ATTR_TABLE, QK_ATTR_SORTED = 0, 1
 
 STATUS_NAMES = {1: "QK_ERR_INVALID", 2: "QK_ERR_NOT_FOUND", 3: "QK_ERR_HIP", 4: "QK_ERR_UNSUPPORTED", 5: "QK_ERR_OOM"}
@@ -28,6 +30,11 @@ class QkTiming(C.Structure):
 
 class QkClause(C.Structure):  # qk_clause: one clause of a predicate filter
     _fields_ = [("attr", C.c_void_p), ("op", C.c_int), ("a", C.c_int64), ("b", C.c_int64)]
+
+
+class QkExprClause(C.Structure):  # qk_expr_clause: a clause of an expression filter; set / n_set: a HOST array, the set ops only
+    _fields_ = [("attr", C.c_void_p), ("op", C.c_int), ("a", C.c_int64), ("b", C.c_int64), ("set", C.POINTER(C.c_int64)),
+                ("n_set", C.c_int64)]
 
 
 class QuakeHipError(RuntimeError):
@@ -124,6 +131,7 @@ SIGNATURES = {
     "qk_scan_grouped_n": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
+    "qk_filter_create_expr": (_int, [_vp, C.POINTER(QkExprClause), C.POINTER(_int), _int, C.POINTER(_vp)]),
     "qk_search_aps": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, C.c_float, _int, C.c_float, _vp, _vp, _vp, _int,
                       C.POINTER(QkTiming)]),
     "qk_merge_topk": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp]),

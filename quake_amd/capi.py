@@ -864,6 +864,39 @@ class Filter:
         check(self.lib.qk_filter_create_where(store.h, arr, len(clauses), C.byref(self.h)))
         return self
 
+    EXPR_OPS = dict(OPS, **{"in": _lib.QK_OP_IN_SET, "not_in": _lib.QK_OP_NOT_IN_SET})
+
+    @classmethod
+    def expr(cls, store, terms):
+        """An expression filter (qk_filter_create_expr): `terms` is a sequence of sequences of (attr, op, a[, b]) as for where(),
+        or (attr, "in" | "not_in", values) with values a host sequence / array of int64 (any order, duplicates allowed).  A
+        stored row is a candidate iff for SOME term EVERY clause of it holds for the row's id.  Holds no ids; follows later
+        Attr.set / unset and store changes like where()."""
+        terms = [list(t) for t in terms]
+        flat = [cl for t in terms for cl in t]
+        arr = (_lib.QkExprClause * max(len(flat), 1))()
+        sizes = (C.c_int * max(len(terms), 1))(*[len(t) for t in terms])
+        keep = []  # the value arrays, alive until the call returns
+        for i, cl in enumerate(flat):
+            attr, op = cl[0], cl[1]
+            code = cls.EXPR_OPS[op] if isinstance(op, str) else int(op)
+            arr[i].attr = attr.h if attr is not None else None
+            arr[i].op = code
+            if code in (_lib.QK_OP_IN_SET, _lib.QK_OP_NOT_IN_SET):
+                vals = np.ascontiguousarray(cl[2], dtype=np.int64).reshape(-1)
+                keep.append(vals)
+                arr[i].set = vals.ctypes.data_as(C.POINTER(C.c_int64)) if vals.shape[0] else None
+                arr[i].n_set = vals.shape[0]
+            else:
+                arr[i].a, arr[i].b = int(cl[2]), int(cl[3]) if len(cl) > 3 else 0
+        self = cls.__new__(cls)
+        self.lib = store.lib
+        self.store = store
+        self.mode = "expr"
+        self.h = C.c_void_p()
+        check(self.lib.qk_filter_create_expr(store.h, arr, sizes, len(terms), C.byref(self.h)))
+        return self
+
     def close(self):
         if getattr(self, "h", None) and self.h:
             self.lib.qk_filter_destroy(self.h)

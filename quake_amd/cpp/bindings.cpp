@@ -77,6 +77,17 @@ std::vector<WhereTerm> parse_where(const py::object &where) {
         WhereTerm t;
         t.name = cl[0].cast<std::string>();
         t.op = cl[1].cast<std::string>();
+        if (t.op == "in" || t.op == "not_in") {  // a value set (lower_expr)
+            if (cl.size() != 3) throw std::runtime_error("[QuakeIndex::make_filter()] where op '" + t.op + "' takes 1 operand");
+            py::object v = cl[2];
+            if (py::isinstance<py::str>(v) || py::isinstance<py::bytes>(v) || py::isinstance<py::dict>(v) || !PySequence_Check(v.ptr()))
+                throw std::runtime_error("[QuakeIndex::make_filter()] the operand of '" + t.op + "' must be a sequence of integers, got " +
+                                         std::string(py::repr(v)));
+            t.has_values = true;
+            for (py::handle e : py::reinterpret_borrow<py::sequence>(v)) t.values.push_back(parse_operand(e, false));
+            out.push_back(t);
+            continue;
+        }
         const bool mask = t.op == "any_bits" || t.op == "all_bits" || t.op == "no_bits";
         t.n_operands = (int)cl.size() - 2;
         t.a = parse_operand(cl[2], mask);
@@ -102,15 +113,29 @@ PYBIND11_MODULE(_bindings, m) {
         .def("maintenance", &QuakeIndex::maintenance)
         .def("initialize_maintenance_policy", &QuakeIndex::initialize_maintenance_policy)
         .def("refine_partitions", &QuakeIndex::refine_partitions, py::arg("partition_ids"), py::arg("iterations") = 0)
-        .def("make_filter", [](QuakeIndex &q, py::object ids, bool exclude, py::object where) {
-                 if (ids.is_none() == where.is_none())
-                     throw std::runtime_error("[QuakeIndex::make_filter()] exactly one of ids and where must be given");
-                 if (where.is_none()) return q.make_filter(ids.cast<Tensor>(), exclude);
+        .def("make_filter", [](QuakeIndex &q, py::object ids, bool exclude, py::object where, py::object any_of) {
+                 if ((int)!ids.is_none() + (int)!where.is_none() + (int)!any_of.is_none() != 1)
+                     throw std::runtime_error("[QuakeIndex::make_filter()] exactly one of ids, where and any_of must be given");
+                 if (!ids.is_none()) return q.make_filter(ids.cast<Tensor>(), exclude);
                  if (exclude) throw std::runtime_error("[QuakeIndex::make_filter()] exclude applies to ids, not to where (negate the clauses)");
-                 return q.make_filter_where(parse_where(where));
-             }, py::arg("ids") = py::none(), py::arg("exclude") = false, py::arg("where") = py::none(),
+                 if (!where.is_none()) return q.make_filter_where(parse_where(where));
+                 std::vector<std::vector<WhereTerm>> terms;
+                 if (PyObject *it = PyObject_GetIter(any_of.ptr())) {
+                     Py_DECREF(it);
+                 } else {
+                     PyErr_Clear();
+                     throw std::runtime_error("[QuakeIndex::make_filter()] any_of is a list of where lists, got " + std::string(py::repr(any_of)));
+                 }
+                 for (py::handle t : any_of) {
+                     if (!py::isinstance<py::tuple>(t) && !py::isinstance<py::list>(t))
+                         throw std::runtime_error("[QuakeIndex::make_filter()] a term is a list of where clauses, got " + std::string(py::repr(t)));
+                     terms.push_back(parse_where(py::reinterpret_borrow<py::object>(t)));
+                 }
+                 return q.make_filter_expr(terms);
+             }, py::arg("ids") = py::none(), py::arg("exclude") = false, py::arg("where") = py::none(), py::arg("any_of") = py::none(),
              "extension: a SearchFilter for SearchParams.filter -- over vector ids (ids, exclude) or a predicate over the attribute "
-             "columns: where = [(name, op, a[, b]), ...], all of which must hold")
+             "columns: where = [(name, op, a[, b]) | (name, 'in' | 'not_in', [v, ...]), ...], all of which must hold; any_of = a list of "
+             "such lists, one of which must hold")
         .def("set_attribute", &QuakeIndex::set_attribute, py::arg("name"), py::arg("ids"), py::arg("values"),
              "extension: int64 values keyed by vector id in column `name` (created on first use)")
         .def("unset_attribute", &QuakeIndex::unset_attribute, py::arg("name"), py::arg("ids"))

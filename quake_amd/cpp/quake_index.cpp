@@ -225,6 +225,47 @@ std::vector<LoweredClause> lower_where(const std::vector<WhereTerm> &where) {
     return out;
 }
 
+std::vector<std::vector<LoweredClause>> lower_expr(const std::vector<std::vector<WhereTerm>> &any_of) {
+    const std::string who = "[QuakeIndex::make_filter()]";
+    if (any_of.empty()) throw std::runtime_error(who + " any_of needs at least one term");
+    if (any_of.size() > QK_MAX_TERMS)
+        throw std::runtime_error(who + " any_of has " + std::to_string(any_of.size()) + " terms, at most " + std::to_string(QK_MAX_TERMS) +
+                                 " are supported");
+    std::vector<std::vector<LoweredClause>> out;
+    size_t total = 0;
+    for (const std::vector<WhereTerm> &term : any_of) {
+        if (term.empty()) throw std::runtime_error(who + " where needs at least one clause");
+        if (term.size() > QK_MAX_CLAUSES)
+            throw std::runtime_error(who + " where has " + std::to_string(term.size()) + " clauses, at most " + std::to_string(QK_MAX_CLAUSES) +
+                                     " are supported");
+        std::vector<LoweredClause> lt;
+        for (const WhereTerm &t : term) {
+            if (t.op != "in" && t.op != "not_in") {
+                lt.push_back(lower_where({t})[0]);
+                continue;
+            }
+            if (!t.has_values) throw std::runtime_error(who + " the operand of '" + t.op + "' must be a sequence of integers");
+            if (t.values.size() > (size_t)QK_MAX_SET_VALUES)
+                throw std::runtime_error(who + " the set of '" + t.op + "' has " + std::to_string(t.values.size()) + " values, at most " +
+                                         std::to_string(QK_MAX_SET_VALUES) + " are supported");
+            LoweredClause c;
+            c.name = t.name;
+            c.op = t.op == "in" ? QK_OP_IN_SET : QK_OP_NOT_IN_SET;
+            for (const WhereOperand &o : t.values)
+                if (!o.over) c.values.push_back(o.v);  // (a value outside int64 equals no stored value)
+            std::sort(c.values.begin(), c.values.end());
+            c.values.erase(std::unique(c.values.begin(), c.values.end()), c.values.end());
+            lt.push_back(std::move(c));
+        }
+        total += lt.size();
+        out.push_back(std::move(lt));
+    }
+    if (total > QK_MAX_EXPR_CLAUSES)
+        throw std::runtime_error(who + " any_of has " + std::to_string(total) + " clauses in total, at most " +
+                                 std::to_string(QK_MAX_EXPR_CLAUSES) + " are supported");
+    return out;
+}
+
 void QuakeIndex::drop_attributes() {
     for (auto &kv : attrs_) (void)qk_attr_destroy(kv.second);  // (filters that name a column keep its values)
     attrs_.clear();
@@ -297,7 +338,29 @@ std::vector<std::string> QuakeIndex::attribute_names() {
     return names;
 }
 
+shared_ptr<SearchFilter> QuakeIndex::make_filter_expr(const std::vector<std::vector<WhereTerm>> &any_of) {
+    auto &cols = attributes("make_filter");
+    const std::vector<std::vector<LoweredClause>> terms = lower_expr(any_of);
+    std::vector<qk_expr_clause> cl;
+    std::vector<int> sizes;
+    for (const std::vector<LoweredClause> &term : terms) {
+        for (const LoweredClause &c : term) {
+            auto it = cols.find(c.name);
+            if (it == cols.end()) throw std::runtime_error("[QuakeIndex::make_filter()] unknown attribute column '" + c.name + "'");
+            cl.push_back(qk_expr_clause{it->second, c.op, c.a, c.b, c.values.empty() ? nullptr : c.values.data(), (int64_t)c.values.size()});
+        }
+        sizes.push_back((int)term.size());
+    }
+    auto f = std::make_shared<SearchFilter>();
+    f->owner = attrs_store_;
+    qk_check(qk_filter_create_expr(attrs_store_, cl.data(), sizes.data(), (int)sizes.size(), &f->h));
+    return f;
+}
+
 shared_ptr<SearchFilter> QuakeIndex::make_filter_where(const std::vector<WhereTerm> &where) {
+    // (a conjunction without sets keeps its own entry point and kernel)
+    for (const WhereTerm &t : where)
+        if (t.op == "in" || t.op == "not_in") return make_filter_expr({where});
     auto &cols = attributes("make_filter");
     std::vector<qk_clause> cl;
     for (const LoweredClause &c : lower_where(where)) {

@@ -25,14 +25,21 @@ struct WhereTerm {
     std::string name, op;
     WhereOperand a, b;
     int n_operands = 1;
+    // the set ops "in" / "not_in" (lower_expr only): the operand is a value list
+    std::vector<WhereOperand> values;
+    bool has_values = false;
 };
 struct LoweredClause {
     std::string name;
     int op = QK_OP_RANGE;
     int64_t a = 0, b = 0;
+    std::vector<int64_t> values;  // QK_OP_IN_SET / QK_OP_NOT_IN_SET: ascending, distinct
 };
 // the C clauses of a predicate (the Python mirror's quake_amd/where.py: same rules, same errors as std::runtime_error)
 std::vector<LoweredClause> lower_where(const std::vector<WhereTerm> &where);
+// an OR of conjunctions with the set ops (where.py's lower_expr): every term is lowered like a `where`, ("in" | "not_in", values)
+// becomes a set clause, a value outside int64 is dropped
+std::vector<std::vector<LoweredClause>> lower_expr(const std::vector<std::vector<WhereTerm>> &any_of);
 
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
@@ -66,6 +73,9 @@ public:
     // extension: a predicate filter over the attribute columns below -- every clause must hold; it holds no ids and follows
     // later set_attribute / add calls (qk_filter_create_where)
     shared_ptr<SearchFilter> make_filter_where(const std::vector<WhereTerm> &where);
+    // extension: an OR of up to QK_MAX_TERMS such conjunctions, with the value sets "in" / "not_in" (qk_filter_create_expr);
+    // make_filter_where hands a `where` that names a set op to it
+    shared_ptr<SearchFilter> make_filter_expr(const std::vector<std::vector<WhereTerm>> &any_of);
     // extension: attribute columns -- int64 values keyed by vector id, on the device (qk_attr_*); a column is created by its
     // first set_attribute; ids need not be stored, remove / modify keep the values; not persisted by save()
     void set_attribute(const std::string &name, Tensor ids, Tensor values);

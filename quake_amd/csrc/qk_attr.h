@@ -111,13 +111,14 @@ __device__ __forceinline__ void attr_lookup(const AttrCol &c, const int64_t (&id
 }
 
 
-enum { QK_FILTER_KIND_IDS = 0, QK_FILTER_KIND_WHERE = 1 };
+enum { QK_FILTER_KIND_IDS = 0, QK_FILTER_KIND_WHERE = 1, QK_FILTER_KIND_EXPR = 2 };
 
 struct qk_filter_clause {
     std::shared_ptr<qk_attr_data> col;
     int op = QK_OP_RANGE;
     int64_t a = 0, b = 0;
     uint64_t col_version = 0;  // stamp: the column's version the mask was derived for
+    int64_t set_off = 0, set_n = 0;  // (expression, the set ops) the clause's slice of qk_filter::d_sets
 };
 
 struct qk_filter {
@@ -128,7 +129,10 @@ struct qk_filter {
     int mode = QK_FILTER_ALLOW;
     int64_t n_ids = 0;
     int64_t *d_ids = nullptr;  // [n_ids] ascending, no duplicates (id set)
-    std::vector<qk_filter_clause> clauses;  // (predicate)
+    std::vector<qk_filter_clause> clauses;  // (predicate; expression: the terms one after the other)
+    std::vector<int> term_end;              // (expression) term t is the clauses [term_end[t - 1], term_end[t])
+    int64_t *d_sets = nullptr;              // (expression) [max(sets_len, 1)] the clauses' value sets, each ascending and distinct
+    int64_t sets_len = 0;
     uint16_t *mask = nullptr;  // [mask_words] one word per arena tile
     int64_t mask_words = 0;    // capacity
     bool built = false;
@@ -170,7 +174,9 @@ int qk_filter_first_build(qk_store *s, qk_filter *f);
 // qk_attr.hip: the predicate sibling of k_filter_build on ctx's stream (mask and counter already cleared), behind the columns' last
 // updates; stamps the clauses with their columns' versions
 int qk_launch_filter_build_where(qk_ctx *ctx, qk_store *s, qk_filter *f);
-// are the clauses' stamps those of their columns
+// the same for an expression filter (k_filter_build_expr)
+int qk_launch_filter_build_expr(qk_ctx *ctx, qk_store *s, qk_filter *f);
+// are the clauses' stamps those of their columns (both predicate kinds)
 bool qk_filter_where_current(const qk_filter *f);
 
 // qk_grouped.hip: the k best groups of `col` per query over the probed lists (`a` as for qk_range_device, k and out_* set);

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <new>
 #include <numeric>
 #include <vector>
 
@@ -121,6 +122,136 @@ __global__ __launch_bounds__(256) void k_filter_build_where(WhereBuildParams F) 
         for (int u = 0; u < WB_U; u++) {
             const int tile = t0 + u * 16 + sub;
             const uint64_t b = __ballot(ok[u]);
+            const uint32_t word = (uint32_t)((b >> (16 * (lane >> 4))) & 0xFFFFull);
+            const int64_t w = (row_off >> 4) + tile;
+            if (j == 0 && tile < ntl && w < F.mask_words) {
+                F.mask[w] = (uint16_t)word;
+                mine += __popc(word);
+            }
+        }
+    }
+    // one atomic per wave
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
+    if (lane == 0 && mine) atomicAdd(F.allowed, mine);
+}
+
+// ---- the mask of an expression: an OR of conjunctions, with value sets ---------------------------------------------------------
+struct ExprClause {
+    AttrCol col;
+    int op;
+    int64_t a, b;        // the five ops of where_op
+    const int64_t *set;  // IN_SET / NOT_IN_SET: the clause's slice of the filter's set buffer, ascending and distinct
+    int64_t n_set;       //                      its length, 0 = the empty set (set is not read)
+};
+
+// (the clause table travels in the kernel arguments: 32 x 80 bytes + the rest < 4 KB; term and clause numbers are wave-uniform, so a
+// clause's parameters are scalar loads from there, as in k_filter_build_where)
+struct ExprBuildParams {
+    const int64_t *ids;
+    const int64_t *pt_off;
+    const int32_t *pt_size;
+    uint16_t *mask;
+    int64_t mask_words;
+    unsigned long long *allowed;
+    int nt;
+    int term_end[QK_MAX_TERMS];  // term t is the clauses [term_end[t - 1], term_end[t])
+    ExprClause c[QK_MAX_EXPR_CLAUSES];
+};
+
+// is v[u] an element of set[0 .. n), n >= 1: the sorted layout's search of attr_lookup -- the last element <= v, all U searches in
+// step, every probe inside [0, n) -- and one comparison.  live[u] == false: the probes go to element 0 and the answer is "no".
+template <int U>
+__device__ __forceinline__ void set_member(const int64_t *set, int64_t n, const int64_t (&v)[U], const bool (&live)[U], bool (&in)[U]) {
+    int64_t base[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) base[u] = 0;
+    for (int64_t len = n; len > 1;) {
+        const int64_t half = len >> 1;
+        int64_t k[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) k[u] = set[base[u] + half];
+#pragma unroll
+        for (int u = 0; u < U; u++) base[u] += (live[u] && k[u] <= v[u]) ? half : 0;
+        len -= half;
+    }
+    int64_t k[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) k[u] = set[base[u]];
+#pragma unroll
+    for (int u = 0; u < U; u++) in[u] = live[u] && k[u] == v[u];
+}
+
+// k_filter_build_where's sibling for qk_filter_create_expr: the same grid, the same writer rule, the same WB_U ids in flight.  Per
+// lane and row two flags: acc -- an earlier term held -- and ok -- alive in the current term.  A term starts with the valid rows
+// no earlier term accepted and ANDs its clauses like k_filter_build_where; the wave skips a term when none of its rows is left
+// undecided and a clause when none is alive in the term.  OR and AND commute: neither order can change a bit of the mask.
+__global__ __launch_bounds__(256) void k_filter_build_expr(ExprBuildParams F) {
+    const int p = blockIdx.x;
+    const int size = F.pt_size[p];
+    if (size <= 0) return;
+    const int64_t row_off = F.pt_off[p];
+    const int ntl = (size + 15) >> 4;
+    const int lane = threadIdx.x & 63, j = lane & 15;
+    const int sub = threadIdx.x >> 4;  // tile of a 16-tile chunk
+    unsigned long long mine = 0;
+    for (int t0 = blockIdx.y * 16 * WB_U; t0 < ntl; t0 += gridDim.y * 16 * WB_U) {
+        int64_t id[WB_U];
+        bool valid[WB_U], acc[WB_U];
+#pragma unroll
+        for (int u = 0; u < WB_U; u++) {
+            const int tile = t0 + u * 16 + sub;
+            const int row = tile * 16 + j;
+            valid[u] = tile < ntl && row < size;
+            acc[u] = false;
+            id[u] = F.ids[row_off + (valid[u] ? row : 0)];  // (unconditional: the loads leave together; row 0 exists)
+        }
+        // (neither loop unrolled: see k_filter_build_where)
+        int ci = 0;
+#pragma unroll 1
+        for (int t = 0; t < F.nt; t++) {
+            const int end = F.term_end[t];
+            bool ok[WB_U], open = false;
+#pragma unroll
+            for (int u = 0; u < WB_U; u++) {
+                ok[u] = valid[u] && !acc[u];
+                open = open || ok[u];
+            }
+            if (!__any(open)) break;  // (every valid row of the wave is accepted: no later term can change one)
+#pragma unroll 1
+            for (; ci < end; ci++) {
+                bool any = false;
+#pragma unroll
+                for (int u = 0; u < WB_U; u++) any = any || ok[u];
+                if (!__any(any)) break;
+                int64_t v[WB_U];
+                bool has[WB_U];
+                attr_lookup<WB_U>(F.c[ci].col, id, ok, v, has);
+                const int op = F.c[ci].op;
+                if (op < QK_OP_IN_SET) {
+#pragma unroll
+                    for (int u = 0; u < WB_U; u++) ok[u] = ok[u] && has[u] && where_op(op, F.c[ci].a, F.c[ci].b, v[u]);
+                } else {
+                    bool in[WB_U];
+#pragma unroll
+                    for (int u = 0; u < WB_U; u++) {
+                        ok[u] = ok[u] && has[u];  // (an id without a value fails NOT_IN_SET too)
+                        in[u] = false;
+                    }
+                    const int64_t n_set = F.c[ci].n_set;
+                    if (n_set > 0) set_member<WB_U>(F.c[ci].set, n_set, v, ok, in);  // (the empty set: no load)
+                    const bool want = op == QK_OP_IN_SET;
+#pragma unroll
+                    for (int u = 0; u < WB_U; u++) ok[u] = ok[u] && in[u] == want;
+                }
+            }
+            ci = end;
+#pragma unroll
+            for (int u = 0; u < WB_U; u++) acc[u] = acc[u] || ok[u];
+        }
+#pragma unroll
+        for (int u = 0; u < WB_U; u++) {
+            const int tile = t0 + u * 16 + sub;
+            const uint64_t b = __ballot(acc[u]);
             const uint32_t word = (uint32_t)((b >> (16 * (lane >> 4))) & 0xFFFFull);
             const int64_t w = (row_off >> 4) + tile;
             if (j == 0 && tile < ntl && w < F.mask_words) {
@@ -439,6 +570,42 @@ int qk_launch_filter_build_where(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     return QK_OK;
 }
 
+int qk_launch_filter_build_expr(qk_ctx *ctx, qk_store *s, qk_filter *f) {
+    hipStream_t st = ctx->stream;
+    ExprBuildParams F;
+    const int nc = (int)f->clauses.size();
+    F.nt = (int)f->term_end.size();
+    for (int t = 0; t < QK_MAX_TERMS; t++) F.term_end[t] = t < F.nt ? f->term_end[(size_t)t] : nc;
+    for (int i = 0; i < nc; i++) {
+        qk_filter_clause &c = f->clauses[(size_t)i];
+        // a column updated on another stream: behind its last update
+        if (c.col->updated && c.col->upd_stream != st) QK_HIP(hipStreamWaitEvent(st, c.col->upd_ev, 0));
+        F.c[i].col = col_of(*c.col);
+        if (!col_usable(F.c[i].col)) QK_FAIL(QK_ERR_HIP, "filtered search: the column of clause %d lost its device data in a failed update", i);
+        F.c[i].op = c.op;
+        F.c[i].a = c.a;
+        F.c[i].b = c.b;
+        F.c[i].set = f->d_sets + c.set_off;
+        F.c[i].n_set = c.set_n;
+        c.col_version = c.col->version;
+    }
+    for (int i = nc; i < QK_MAX_EXPR_CLAUSES; i++) F.c[i] = F.c[0];
+    const int64_t npids = (int64_t)s->parts.size();
+    if (npids > 0 && s->ntotal > 0) {
+        F.ids = s->ids;
+        F.pt_off = s->d_off;
+        F.pt_size = s->d_size;
+        F.mask = f->mask;
+        F.mask_words = f->mask_words;
+        F.allowed = f->d_allowed;
+        const int64_t max_tiles = (std::max<int64_t>(1, s->max_size) + 15) / 16;
+        const unsigned gy = (unsigned)std::min<int64_t>(65535, (max_tiles + 16 * WB_U - 1) / (16 * WB_U));
+        hipLaunchKernelGGL(k_filter_build_expr, dim3((unsigned)npids, gy), dim3(256), 0, st, F);
+        QK_HIP(hipGetLastError());
+    }
+    return QK_OK;
+}
+
 extern "C" {
 
 int qk_attr_create(qk_store *s, qk_attr **out) {
@@ -669,6 +836,85 @@ int qk_filter_create_where(qk_store *s, const qk_clause *clauses, int n_clauses,
         (void)hipGetLastError();
         qk_filter_destroy(f);
         QK_FAIL(QK_ERR_OOM, "qk_filter_create_where: no device memory");
+    }
+    // the first mask now, on the store's context: the first filtered search does not pay for it
+    const int rc = qk_filter_first_build(s, f);
+    if (rc != QK_OK) {
+        qk_filter_destroy(f);
+        return rc;
+    }
+    *out = f;
+    return QK_OK;
+}
+
+int qk_filter_create_expr(qk_store *s, const qk_expr_clause *clauses, const int *term_sizes, int n_terms, qk_filter **out) {
+    if (!s || !out) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: null argument");
+    if (n_terms < 1 || !clauses || !term_sizes) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: at least one term is required (n_terms=%d)", n_terms);
+    if (n_terms > QK_MAX_TERMS) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_filter_create_expr: n_terms=%d exceeds QK_MAX_TERMS=%d", n_terms, QK_MAX_TERMS);
+    int64_t nc = 0;
+    for (int t = 0; t < n_terms; t++) {
+        if (term_sizes[t] < 1) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: term %d needs at least one clause (term_sizes[%d]=%d)", t, t, term_sizes[t]);
+        nc += term_sizes[t];
+    }
+    if (nc > QK_MAX_EXPR_CLAUSES)
+        QK_FAIL(QK_ERR_UNSUPPORTED, "qk_filter_create_expr: %lld clauses in total exceed QK_MAX_EXPR_CLAUSES=%d", (long long)nc, QK_MAX_EXPR_CLAUSES);
+    for (int i = 0; i < (int)nc; i++) {
+        const qk_expr_clause &c = clauses[i];
+        if (!c.attr) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: clause %d names a null column", i);
+        if (c.attr->d->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: the column of clause %d belongs to another store", i);
+        if (c.op < QK_OP_RANGE || c.op > QK_OP_NOT_IN_SET) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: clause %d has the unknown op %d", i, c.op);
+        if (c.op < QK_OP_IN_SET) continue;  // (set / n_set are read by the two set ops only)
+        if (c.n_set < 0) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: clause %d has a negative n_set (%lld)", i, (long long)c.n_set);
+        if (c.n_set > 0 && !c.set) QK_FAIL(QK_ERR_INVALID, "qk_filter_create_expr: clause %d has n_set=%lld and a null set", i, (long long)c.n_set);
+        if (c.n_set > QK_MAX_SET_VALUES)
+            QK_FAIL(QK_ERR_UNSUPPORTED, "qk_filter_create_expr: n_set=%lld of clause %d exceeds QK_MAX_SET_VALUES=%d", (long long)c.n_set, i,
+                    QK_MAX_SET_VALUES);
+    }
+    qk_ctx *ctx = s->ctx;
+    QK_HIP(hipSetDevice(ctx->device));
+    qk_filter *f = new qk_filter();
+    f->serial = qk_filter_next_serial();
+    f->store_uid = s->uid;
+    f->device = ctx->device;
+    f->kind = QK_FILTER_KIND_EXPR;
+    f->n_ids = 0;
+    // the sets sorted and de-duplicated on the host, one after the other in one buffer: every set clause has its own slice, a set
+    // given to several clauses is held once per clause (at worst 32 x 2^20 values = 256 MB, on the host here and on the device)
+    std::vector<int64_t> sets;
+    try {
+        int i = 0;
+        for (int t = 0; t < n_terms; t++) {
+            for (int e = i + term_sizes[t]; i < e; i++) {
+                qk_filter_clause c;
+                c.col = clauses[i].attr->d;
+                c.op = clauses[i].op;
+                c.a = clauses[i].a;
+                c.b = clauses[i].b;
+                if (c.op >= QK_OP_IN_SET && clauses[i].n_set > 0) {
+                    std::vector<int64_t> h(clauses[i].set, clauses[i].set + clauses[i].n_set);
+                    std::sort(h.begin(), h.end());
+                    h.erase(std::unique(h.begin(), h.end()), h.end());
+                    c.set_off = (int64_t)sets.size();
+                    c.set_n = (int64_t)h.size();
+                    sets.insert(sets.end(), h.begin(), h.end());
+                }
+                f->clauses.push_back(std::move(c));
+            }
+            f->term_end.push_back(i);
+        }
+    } catch (const std::bad_alloc &) {  // (no exception crosses the C ABI)
+        qk_filter_destroy(f);
+        QK_FAIL(QK_ERR_OOM, "qk_filter_create_expr: no host memory for the value sets");
+    }
+    f->sets_len = (int64_t)sets.size();
+    bool ok = hipMalloc((void **)&f->d_sets, std::max<size_t>(sets.size(), 1) * sizeof(int64_t)) == hipSuccess &&
+              hipMalloc((void **)&f->d_allowed, sizeof(unsigned long long)) == hipSuccess &&
+              hipEventCreateWithFlags(&f->built_ev, hipEventDisableTiming) == hipSuccess;
+    if (ok && !sets.empty()) ok = hipMemcpy(f->d_sets, sets.data(), sets.size() * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        qk_filter_destroy(f);
+        QK_FAIL(QK_ERR_OOM, "qk_filter_create_expr: no device memory");
     }
     // the first mask now, on the store's context: the first filtered search does not pay for it
     const int rc = qk_filter_first_build(s, f);

@@ -13,9 +13,10 @@
 // new version.  qk_filter_ensure compares the stamp after that sync and re-derives the mask from the ids when it differs: a filter
 // is defined by ids and stays correct whatever moves rows.
 //
-// A filter is of one of two kinds (qk_attr.h): an id set, as above, or a PREDICATE over attribute columns (qk_attr.hip), whose
-// mask k_filter_build_where derives and whose stamp also holds the version of every column it names.  Everything behind the mask
-// -- the scans, the per-query table, the union -- is the same for both.
+// A filter is of one of three kinds (qk_attr.h): an id set, as above, or a PREDICATE over attribute columns (qk_attr.hip) -- a
+// conjunction, whose mask k_filter_build_where derives, or an EXPRESSION (an OR of conjunctions with value sets,
+// k_filter_build_expr) -- whose stamp also holds the version of every column it names.  Everything behind the mask -- the scans,
+// the per-query table, the union -- is the same for all.
 #include "qk_attr.h"
 
 #include <algorithm>
@@ -128,6 +129,7 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     QK_TRY(filter_build_prepare(ctx, s, f));
     // (a predicate's clauses are stamped with their columns' versions even when there is no row to look at)
     if (f->kind == QK_FILTER_KIND_WHERE) QK_TRY(qk_launch_filter_build_where(ctx, s, f));
+    else if (f->kind == QK_FILTER_KIND_EXPR) QK_TRY(qk_launch_filter_build_expr(ctx, s, f));
     else QK_TRY(filter_build_ids(ctx, s, f));
     hipStream_t st = ctx->stream;
     QK_HIP(hipEventRecord(f->built_ev, st));
@@ -146,7 +148,7 @@ int filter_build(qk_ctx *ctx, qk_store *s, qk_filter *f) {
 // the mask of a filter of this store and device, current for the store's table (the caller has synced it)
 int filter_current(qk_ctx *ctx, qk_store *s, qk_filter *f) {
     if (!f->built || f->version != s->version || f->cap_rows != s->cap_rows ||
-        (f->kind == QK_FILTER_KIND_WHERE && !qk_filter_where_current(f))) {
+        (f->kind != QK_FILTER_KIND_IDS && !qk_filter_where_current(f))) {
         QK_TRY(filter_build(ctx, s, f));
     } else if (f->built_ctx != ctx) {
         QK_HIP(hipStreamWaitEvent(ctx->stream, f->built_ev, 0));  // the build ran on another context's stream
@@ -1175,6 +1177,7 @@ int qk_filter_destroy(qk_filter *f) {
         delete c;
     }
     if (f->d_ids) hipFree(f->d_ids);
+    if (f->d_sets) hipFree(f->d_sets);
     if (f->d_allowed) hipFree(f->d_allowed);
     (void)hipGetLastError();
     delete f;
@@ -1184,7 +1187,7 @@ int qk_filter_destroy(qk_filter *f) {
 int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t *store_version, int64_t *rebuilds, int64_t *device_bytes) {
     if (!f) QK_FAIL(QK_ERR_INVALID, "qk_filter_info: null filter");
     QK_HIP(hipSetDevice(f->device));
-    if (n_ids) *n_ids = f->kind == QK_FILTER_KIND_WHERE ? -1 : f->n_ids;
+    if (n_ids) *n_ids = f->kind != QK_FILTER_KIND_IDS ? -1 : f->n_ids;
     if (rows_allowed) {
         unsigned long long v = 0;
         QK_HIP(hipEventSynchronize(f->built_ev));
@@ -1195,6 +1198,8 @@ int qk_filter_info(qk_filter *f, int64_t *n_ids, int64_t *rows_allowed, uint64_t
     if (rebuilds) *rebuilds = f->rebuilds;
     if (device_bytes) {
         if (f->kind == QK_FILTER_KIND_WHERE) *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t));  // (no ids: the mask only)
+        else if (f->kind == QK_FILTER_KIND_EXPR)  // (the mask and the set buffer; the clause table travels in the kernel arguments)
+            *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t) + std::max<int64_t>(f->sets_len, 1) * sizeof(int64_t));
         else *device_bytes = (int64_t)(f->mask_words * sizeof(uint16_t) + std::max<int64_t>(f->n_ids, 1) * sizeof(int64_t) + 8);
         *device_bytes += (int64_t)(f->counts_cap * sizeof(int32_t));  // (adaptive probing: once a call has derived them)
         *device_bytes += cand_device_bytes(f);                        // (exact search: once a call has derived the store)

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_where
+from .where import lower_expr
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -150,25 +150,30 @@ class SearchFilter:
     iff its id is in the set, with exclude=True iff it is not.  Defined by ids, so it stays valid across add / remove / modify /
     maintenance; it is not persisted by save().  info(): {n_ids, rows_allowed, store_version, rebuilds, device_bytes}."""
 
-    def __init__(self, index, ids=None, exclude=False, where=None):
+    def __init__(self, index, ids=None, exclude=False, where=None, any_of=None):
         if isinstance(index._store, capi.Group):
             raise RuntimeError("[QuakeIndex::make_filter()] filtered search is not supported with num_workers > 0")
-        if (ids is None) == (where is None):
-            raise RuntimeError("[QuakeIndex::make_filter()] exactly one of ids and where must be given")
+        if (ids is not None) + (where is not None) + (any_of is not None) != 1:
+            raise RuntimeError("[QuakeIndex::make_filter()] exactly one of ids, where and any_of must be given")
         self.exclude = bool(exclude)
         self._store = index._store
-        if where is not None:
+        if ids is None:
             # a predicate over the index's attribute columns (set_attribute): no ids are held, later set_attribute / add calls
             # are seen by the next search
             if exclude:
                 raise RuntimeError("[QuakeIndex::make_filter()] exclude applies to ids, not to where (negate the clauses)")
             cols = index._attributes()
-            clauses = []
-            for name, op, a, b in lower_where(where):
-                if name not in cols:
-                    raise RuntimeError("[QuakeIndex::make_filter()] unknown attribute column '%s'" % name)
-                clauses.append((cols[name], op, a, b))
-            self._h = capi.Filter.where(index._store, clauses)
+            terms = lower_expr(where=where, any_of=any_of)
+            for term in terms:
+                for cl in term:
+                    if cl[0] not in cols:
+                        raise RuntimeError("[QuakeIndex::make_filter()] unknown attribute column '%s'" % cl[0])
+            if where is not None and all(values is None for _, _, _, _, values in terms[0]):
+                # a conjunction without sets keeps its own entry point and kernel (qk_filter_create_where)
+                self._h = capi.Filter.where(index._store, [(cols[name], op, a, b) for name, op, a, b, _ in terms[0]])
+            else:
+                self._h = capi.Filter.expr(index._store, [[(cols[name], op, a, b) if values is None else (cols[name], op, values)
+                                                          for name, op, a, b, values in term] for term in terms])
             return
         ids = ids if torch.is_tensor(ids) else torch.as_tensor(np.asarray(ids))
         ids = ids.reshape(-1).to(torch.int64)
@@ -1033,13 +1038,14 @@ class QuakeIndex:
         res.groups = groups if on_dev else groups.cpu()
         return res
 
-    def make_filter(self, ids=None, exclude=False, where=None):
+    def make_filter(self, ids=None, exclude=False, where=None, any_of=None):
         """extension: a SearchFilter for SearchParams.filter -- over this index's vector ids (`ids`, `exclude`), or a predicate
         over its attribute columns: `where` is a list of (name, op, a[, b]), all of which must hold (quake_amd/where.py: "=="
-        "!=" "<" "<=" ">" ">=" "between" "any_bits" "all_bits" "no_bits"); a vector without a value in a named column is no
-        candidate.  Exactly one of ids / where."""
+        "!=" "<" "<=" ">" ">=" "between" "any_bits" "all_bits" "no_bits", and the value sets (name, "in" | "not_in", [v, ...]));
+        `any_of` is a list of up to 8 such lists, one of which must hold.  A vector without a value in a named column fails the
+        clause.  Exactly one of ids / where / any_of."""
         self._require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?")
-        return SearchFilter(self, ids, exclude, where)
+        return SearchFilter(self, ids, exclude, where, any_of)
 
     # -- attribute columns (extension): int64 values keyed by vector id, on the device; not persisted by save() ---------------
     def _attributes(self):

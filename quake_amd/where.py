@@ -3,16 +3,24 @@
 `where` is a list of (name, op, a[, b]); the ops are "==" "!=" "<" "<=" ">" ">=" "between" "any_bits" "all_bits" "no_bits".  The C
 ABI knows five ops over int64: RANGE / NOT_RANGE over a closed interval [a, b] (a > b: empty) and three bit tests.  Operands are
 Python integers of any size and are saturated, not wrapped: a comparison with a number outside int64 means what it means over the
-integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  Pure Python: importable without the library or a GPU."""
+integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
+the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
+Pure Python: importable without the library or a GPU."""
 
 INT64_MIN = -(1 << 63)
 INT64_MAX = (1 << 63) - 1
 
 QK_OP_RANGE, QK_OP_NOT_RANGE, QK_OP_ANY_BITS, QK_OP_ALL_BITS, QK_OP_NO_BITS = 0, 1, 2, 3, 4
+QK_OP_IN_SET, QK_OP_NOT_IN_SET = 5, 6
 QK_MAX_CLAUSES = 8
+QK_MAX_TERMS = 8
+QK_MAX_EXPR_CLAUSES = 32
+QK_MAX_SET_VALUES = 1 << 20
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
+SET_OPS = ("in", "not_in")  # lower_expr only
 _BIT_OPS = {"any_bits": QK_OP_ANY_BITS, "all_bits": QK_OP_ALL_BITS, "no_bits": QK_OP_NO_BITS}
+_SET_OPS = {"in": QK_OP_IN_SET, "not_in": QK_OP_NOT_IN_SET}
 EMPTY = (1, 0)  # the canonical empty interval
 
 
@@ -67,3 +75,63 @@ def lower_where(where, who="[QuakeIndex::make_filter()]"):
             code, (lo, hi) = QK_OP_RANGE, _interval(a, _int(cl[3], who))
         out.append((name, code, lo, hi))
     return out
+
+
+def _values(v, op, who):
+    """the operand of a set op: ascending distinct int64 values; a value outside int64 equals no stored value and is dropped"""
+    # (a sequence: indexable and sized -- a list, a tuple, a range, an array; not a set, whose order nobody should rely on)
+    if isinstance(v, (str, bytes, dict)) or not (hasattr(v, "__getitem__") and hasattr(v, "__len__")):
+        raise RuntimeError("%s the operand of %r must be a sequence of integers, got %r" % (who, op, v))
+    if len(v) > QK_MAX_SET_VALUES:
+        raise RuntimeError("%s the set of %r has %d values, at most %d are supported" % (who, op, len(v), QK_MAX_SET_VALUES))
+    return tuple(sorted({x for x in (_int(x, who) for x in v) if INT64_MIN <= x <= INT64_MAX}))
+
+
+def _lower_term(term, who):
+    """one conjunction with the set ops: lower_where's clauses as (name, code, a, b, None), a set clause as (name, code, 0, 0, values)"""
+    try:
+        term = list(term)
+    except TypeError:
+        raise RuntimeError("%s a term is a list of where clauses, got %r" % (who, term))
+    if len(term) < 1:
+        raise RuntimeError("%s where needs at least one clause" % who)
+    if len(term) > QK_MAX_CLAUSES:
+        raise RuntimeError("%s where has %d clauses, at most %d are supported" % (who, len(term), QK_MAX_CLAUSES))
+    out = []
+    for cl in term:
+        if isinstance(cl, (tuple, list)) and len(cl) >= 2 and isinstance(cl[0], str) and isinstance(cl[1], str) and cl[1] in _SET_OPS:
+            if len(cl) != 3:
+                raise RuntimeError("%s where op %r takes 1 operand(s), got %r" % (who, cl[1], cl))
+            out.append((cl[0], _SET_OPS[cl[1]], 0, 0, _values(cl[2], cl[1], who)))
+        else:
+            try:
+                out.append(lower_where([cl], who)[0] + (None,))
+            except RuntimeError as e:  # (the op list of the message: the set ops belong to it here)
+                if "unknown where op" in str(e):
+                    raise RuntimeError("%s unknown where op %r (one of %s)" % (who, cl[1], " ".join(OPS + SET_OPS)))
+                raise
+    return out
+
+
+def lower_expr(where=None, any_of=None, who="[QuakeIndex::make_filter()]"):
+    """An OR of conjunctions -> [[(name, QK_OP_*, a, b, values), ...], ...]: `where` is one term, `any_of` a list of terms; a clause
+    is lower_where's or (name, "in" | "not_in", [v, ...]).  values: None, or the ascending distinct int64 values of a set op.
+    RuntimeError: what lower_where refuses per term, no term or more than QK_MAX_TERMS, more than QK_MAX_EXPR_CLAUSES clauses in
+    total, a set operand that is no sequence or holds more than QK_MAX_SET_VALUES values."""
+    if (where is None) == (any_of is None):
+        raise RuntimeError("%s exactly one of where and any_of must be given" % who)
+    if where is not None:
+        return [_lower_term(where, who)]
+    try:
+        any_of = list(any_of)
+    except TypeError:
+        raise RuntimeError("%s any_of is a list of where lists, got %r" % (who, any_of))
+    if len(any_of) < 1:
+        raise RuntimeError("%s any_of needs at least one term" % who)
+    if len(any_of) > QK_MAX_TERMS:
+        raise RuntimeError("%s any_of has %d terms, at most %d are supported" % (who, len(any_of), QK_MAX_TERMS))
+    terms = [_lower_term(t, who) for t in any_of]
+    total = sum(len(t) for t in terms)
+    if total > QK_MAX_EXPR_CLAUSES:
+        raise RuntimeError("%s any_of has %d clauses in total, at most %d are supported" % (who, total, QK_MAX_EXPR_CLAUSES))
+    return terms
