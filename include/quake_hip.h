@@ -748,7 +748,9 @@ QK_API int qk_kmeans_accumulate_blocked(qk_ctx *ctx, const float *x, int64_t n, 
  * PartitionManager::refine_partitions (partition_manager.cpp:446-487), applied to the device store: the vectors of the m
  * lists `list_nos` (host array) are re-assigned to the nearest of the m centroids [m][d] (in `mem`; row c = centroid of
  * list_nos[c]) for max(refinement_iterations, 1) passes, centroids recomputed between passes; on return list_nos[c] holds
- * the vectors assigned to centroid c (append order of the reference) and `centroids` the ones used for the last pass. */
+ * the vectors assigned to centroid c (append order of the reference) and `centroids` the ones used for the last pass.
+ * A cluster that holds no row when its centroid is recomputed (possible from the second pass on) would get the centroid 0 / 0:
+ * the call then fails with QK_ERR_INVALID and leaves the store and `centroids` as they were. */
 QK_API int qk_store_refine_lists(qk_store *s, const int64_t *list_nos, int64_t m, float *centroids, int metric,
                                  int refinement_iterations, int mem);
 /* kmeans() (clustering.cpp:13-97): Lloyd iterations on the GPU.  x [n][d] (IP: normalised IN PLACE, as the

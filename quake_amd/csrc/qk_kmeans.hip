@@ -627,6 +627,12 @@ __global__ void k_finalize_centroids(const float *__restrict__ sums, const int64
     c[idx] = sums[idx] / (float)cnt;
 }
 
+// clusters without a row (qk_store_refine_lists: their next centroid would be 0 / 0)
+__global__ void k_count_emptied(const int64_t *__restrict__ counts, int64_t m, int32_t *__restrict__ nempty) {
+    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m && counts[j] == 0) atomicAdd(nempty, 1);
+}
+
 __global__ void k_normalize_rows(float *x, int64_t n, int d) {
     // vectors / vectors.norm(2,1) (clustering.cpp:25-26): canonical norm = sqrt of the fmaf chain
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -991,7 +997,8 @@ int qk_kmeans_assign(qk_ctx *ctx, const float *x, int64_t n, const float *c, int
 
 static int kmeans_accumulate_api(qk_ctx *ctx, const float *x, int64_t n, int d, const int64_t *assign, int64_t m, float *sums,
                                  int64_t *counts, int mem, bool blocked) {
-    if (!ctx || !x || !assign || !sums || !counts) QK_FAIL(QK_ERR_INVALID, "qk_kmeans_accumulate: null argument");
+    // (no rows: nothing is read from x / assign, which may then be null -- an empty device tensor has no address)
+    if (!ctx || !sums || !counts || (n > 0 && (!x || !assign))) QK_FAIL(QK_ERR_INVALID, "qk_kmeans_accumulate: null argument");
     if (n < 0 || m <= 0 || d <= 0) QK_FAIL(QK_ERR_INVALID, "qk_kmeans_accumulate: bad sizes");
     QK_HIP(hipSetDevice(ctx->device));
     KmScratch ks(ctx);
@@ -1085,9 +1092,17 @@ int qk_store_refine_lists(qk_store *s, const int64_t *list_nos, int64_t m, float
     AccumScratch as;
     QK_TRY(accum_prepare(st, ks, as, std::max<int64_t>(total, 1), m, d));
     std::vector<int64_t> hcounts((size_t)m, 0);
+    // a cluster that is empty when its centroid is recomputed: the mean is 0 / 0 (the reference divides and goes on, :122-124, and
+    // no vector can be assigned to a NaN centroid: it loses every comparison).  The store refuses such a call after the loop, before
+    // anything is replaced; the clusters are counted on the device, the passes themselves run on as the reference's do.
+    int32_t *dnempty;
+    QK_TRY(ks.alloc(&dnempty, 1));
+    QK_HIP(hipMemsetAsync(dnempty, 0, sizeof(int32_t), st));
     for (int iter = 0; iter < iterations; iter++) {
-        if (iter > 0)  // centroids = sums / counts; a count of 0 gives NaN exactly like the reference (:122-124)
+        if (iter > 0) {  // centroids = sums / counts; a count of 0 gives NaN exactly like the reference (:122-124)
+            hipLaunchKernelGGL(k_count_emptied, dim3(km_grid(m, 256)), dim3(256), 0, st, dcounts, m, dnempty);
             hipLaunchKernelGGL(k_finalize_centroids, dim3(km_grid(m * d, 256)), dim3(256), 0, st, dsums, dcounts, m, d, 0, dc);
+        }
         QK_TRY(assign_device(ctx, xa, total, dc, m, d, metric, dassign, nullptr, ctile, cnorm));
         // (a row without an assignment -- NaN centroid -- is dropped by the bucketing: the tail of the row list it leaves must not
         //  hold garbage for the gathers below; the call fails after the loop in that case)
@@ -1102,14 +1117,23 @@ int qk_store_refine_lists(qk_store *s, const int64_t *list_nos, int64_t m, float
         std::swap(xa, xb);
         std::swap(ia, ib);
     }
+    int32_t hnempty = 0;
     QK_HIP(hipMemcpyAsync(hcounts.data(), dcounts, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-    QK_HIP(hipMemcpyAsync(centroids, dc, (size_t)m * d * 4, mem == QK_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    QK_HIP(hipMemcpyAsync(&hnempty, dnempty, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     QK_HIP(hipStreamSynchronize(st));
     int64_t assigned = 0;
     for (int64_t c = 0; c < m; c++) assigned += hcounts[c];
+    // (refused before `centroids` is written: the caller's centroids and the store are as they were)
+    if (hnempty > 0)
+        QK_FAIL(QK_ERR_INVALID,
+                "qk_store_refine_lists: NaN centroid from an emptied cluster (%d cluster-passes without a row): the %lld vectors could not be "
+                "assigned to it",
+                (int)hnempty, (long long)total);
     if (assigned != total)
         QK_FAIL(QK_ERR_INVALID, "qk_store_refine_lists: %lld of %lld vectors could not be assigned (NaN centroid from an emptied cluster)",
                 (long long)(total - assigned), (long long)total);
+    QK_HIP(hipMemcpyAsync(centroids, dc, (size_t)m * d * 4, mem == QK_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    QK_HIP(hipStreamSynchronize(st));
     // replace the partitions (partition_manager.cpp:481-483)
     // (the rows lie grouped by list in list_nos order: ONE ingest for all of them -- an add_entries per list was a launch, a copy of
     //  the ids and a synchronisation each, 0.26 s for the ~3000 lists a maintenance call of a 50M index refines)

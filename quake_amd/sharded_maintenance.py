@@ -419,6 +419,11 @@ class ShardedPartitions:
         sums = counts = a = None
         for it in range(max(int(iterations), 1)):  # clustering.cpp:110
             if it > 0:
+                # a cluster without a row: its mean is 0 / 0 and no vector can be assigned to a NaN centroid -- refused before
+                # anything is replaced, as qk_store_refine_lists does (the counts are global: every rank raises)
+                if (counts == 0).any():
+                    raise RuntimeError("refine_partitions: NaN centroid from an emptied cluster (%d without a row): the %d vectors "
+                                       "could not be assigned to it" % (int((counts == 0).sum()), total))
                 # centroids = sums / counts, a count of 0 gives NaN exactly like the reference (:122-124)
                 with np.errstate(invalid="ignore", divide="ignore"):
                     c = (sums / counts.astype(np.float32)[:, None]).astype(np.float32)
