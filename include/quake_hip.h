@@ -591,6 +591,59 @@ QK_API int qk_scan_grouped_n(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q
  * device_bytes: HBM they hold (not part of qk_attr_info).  Either pointer may be NULL. */
 QK_API int qk_attr_group_info(qk_attr *a, int64_t *builds, int64_t *device_bytes);
 
+/* ---- facet counts -----------------------------------------------------------------------------------
+ * No reference counterpart.  Per query, how many of its range hits carry each value of up to QK_MAX_FACET_COLS columns, and the
+ * n_values most frequent values of every column: the aggregation a caller would otherwise compute on the host from every hit's id.
+ * Hits: the hit multiset H(q) is BY DEFINITION that of qk_range_search / qk_range_scan for the same (parent, nprobe | pids, metric,
+ * radius, filter): the same probed lists (qk_facet_scan: -1, absent and empty lists contribute nothing), the same inclusive
+ * float32 radius test (L2 dist <= r, IP dist >= r; qk_ctx_set_squared_l2 is honoured), a NaN distance is never a hit, radius =
+ * +inf (L2) / -inf (IP) takes every probed candidate row whose distance is not NaN, a NaN radius is QK_ERR_INVALID, a filter of
+ * another store is QK_ERR_INVALID, a row stored twice counts twice.
+ * Per column c of facet_by [n_cols] (the same column twice is allowed), val_c(row) being the column's value for the row's id:
+ *   total[q]        = |H(q)| = lims[q + 1] - lims[q] of the range call                        out_total [Q] (may be NULL)
+ *   missing[c][q]   = hits whose id has no value in c                                         out_missing [n_cols][Q] (may be NULL)
+ *   count(c, q, v)  = hits with val_c = v;  sum over v of count + missing = total
+ *   distinct[c][q]  = number of v with count > 0                                              out_distinct [n_cols][Q] (may be NULL)
+ * Returned: the n_values entries with the largest count, ties broken by the smaller value (signed int64), in that order:
+ * out_values / out_counts [n_cols][Q][n_values]; entries behind `distinct` are padding, value = 0 and count = 0 (a returned value
+ * always has count >= 1, so count 0 marks padding).  Every int64 is a legal value, -1, INT64_MIN and INT64_MAX included.  The
+ * result is a pure function of the store, the columns and the call: counters are integer sums, the selection is exact on distinct
+ * keys, and which thread claimed which table slot is not visible.
+ * Liveness: values are looked up when the call runs, through the per-row values grouped search keeps (k_grouped_rowvals, re-derived
+ * once per column when the store or the column changed).
+ * Limits: 1 <= n_cols <= QK_MAX_FACET_COLS and 1 <= n_values <= QK_MAX_FACET_VALUES -- below: QK_ERR_INVALID, above:
+ * QK_ERR_UNSUPPORTED; a NULL column or one of another store: QK_ERR_INVALID.  Q == 0: QK_OK.  No lists probed: all zeros.
+ * Inside: the key-emission scan of range search (the same launches, the same pass size), then per pass of queries k_facet_hits --
+ * the hit test of k_range_count, the hits of every query -- and, per group of queries whose tables fit the workspace,
+ * k_facet_clear, k_facet_count -- one sweep over the group's keys for all columns: per column an atomic add to the query's missing
+ * counter or to the 32-bit counter of the value's slot in an open-addressing table per (column, query) (64-bit atomicCAS claims,
+ * linear probing, at most as many probes as slots; the value -1, the empty marker, owns the slot behind the others) -- and
+ * k_facet_select, one workgroup per (column, query): compaction of the occupied slots, an exact most-significant-byte-first
+ * selection on the 96-bit key (~count, value ^ sign bit) when more than 256 values are present, a bitonic sort in LDS.  No kernel
+ * waits or spins (qk_facet.hip).
+ * Workspace: keys as for range search (queries per pass = 2^29 / per_query_ub, per_query_ub = P lists of the store's largest
+ * size; a query whose keys exceed 2^30 is QK_ERR_UNSUPPORTED).  Tables are RESERVED by the grouped rule: T + 1 slots of 12 bytes
+ * per (column, query), T = the power of two >= max(16, 2 * min(per_query_ub, the largest number of ids with a value among the
+ * call's columns)), for min(queries per pass, QK_GROUPED_PASS_BYTES / (12 * n_cols * (T + 1))) queries at a time, at least 1 -- a
+ * pass's queries go through the tables group after group; a single query whose tables exceed QK_GROUPED_PASS_BYTES is
+ * QK_ERR_UNSUPPORTED.  Tables are USED by a tighter rule, known on the device once the hits are counted: a query's tables have
+ * T_q = the power of two >= max(16, 2 * min(its hits, that number of ids)) slots (a query has no more distinct values than hits);
+ * only those are cleared, probed and selected from, so a call costs what its hits cost.  Counters are 32-bit inside a pass (a
+ * query has fewer than 2^30 keys), outputs int64.  Nothing synchronises between passes or groups.
+ * timing: coarse_ms and scan_ms as for range search, merge_ms = counting + selection (of the last pass), n_items = the number of
+ * query passes; no list statistics.  qk_ctx_last_scan_kernel names "k_scan (facet)" / "k_scan_wide (facet)".  There is no facet
+ * form of qk_search_aps, of the device group, of per-query filter tables or of adaptive probing. */
+#define QK_MAX_FACET_COLS 4
+#define QK_MAX_FACET_VALUES 256
+QK_API int qk_facet_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int metric, float radius,
+                           qk_filter *filter, qk_attr *const *facet_by, int n_cols, int n_values, int64_t *out_values,
+                           int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem,
+                           qk_timing *timing);
+QK_API int qk_facet_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric, float radius,
+                         qk_filter *filter, qk_attr *const *facet_by, int n_cols, int n_values, int64_t *out_values,
+                         int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem,
+                         qk_timing *timing);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

@@ -526,6 +526,50 @@ class Context:
             check(self.lib.qk_scan_grouped_n(*head, int(group_size), *tail))
         return (out_i, out_d, out_g, timing_dict(t)) if timing else (out_i, out_d, out_g)
 
+    # ---- facet counts -----------------------------------------------------------------------------------
+    @staticmethod
+    def _facet_args(x, Q, facet_by, n_values, out):
+        cols = list(facet_by) if isinstance(facet_by, (list, tuple)) else [facet_by]
+        C_, n = len(cols), int(n_values)
+        harr = (C.c_void_p * max(C_, 1))(*[a.h if a is not None else None for a in cols])
+        if out is None:
+            # (the library refuses a count outside its limits before it writes: the buffers only have to exist)
+            shp = (max(C_, 0), Q, max(n, 0))
+            out = (_empty_like_mem(shp, np.int64, x), _empty_like_mem(shp, np.int64, x), _empty_like_mem(shp[:2], np.int64, x),
+                   _empty_like_mem(shp[:2], np.int64, x), _empty_like_mem((Q,), np.int64, x))
+        return harr, C_, n, out
+
+    def facet_search(self, parent, store, x, nprobe, radius, metric, facet_by, n_values=10, filter=None, timing=False, out=None):
+        """qk_facet_search: per query, the value counts of the Attr columns `facet_by` (one Attr or a list of up to 4) over the
+        hits of range_search with the same arguments.  Returns (values [C, Q, n], counts [C, Q, n], distinct [C, Q],
+        missing [C, Q], total [Q][, timing]): per column the n_values most frequent values, count descending then value
+        ascending, padded with value 0 / count 0; out=(values, counts, distinct, missing, total): buffers of the caller."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        harr, C_, n, out = self._facet_args(x, Q, facet_by, n_values, out)
+        t = QkTiming()
+        check(self.lib.qk_facet_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe),
+                                       metric_code(metric), float(radius), filter.h if filter is not None else None, harr, C_, n,
+                                       *[_ptr(o) for o in out], mem, C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
+    def facet_scan(self, store, x, pids, radius, metric, facet_by, n_values=10, filter=None, timing=False, out=None):
+        """qk_facet_scan: facet_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / absent / empty lists
+        contribute nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        if pids.ndim == 1:
+            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
+                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        mem = _mem_of(x, pids)
+        harr, C_, n, out = self._facet_args(x, Q, facet_by, n_values, out)
+        t = QkTiming()
+        check(self.lib.qk_facet_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]),
+                                     metric_code(metric), float(radius), filter.h if filter is not None else None, harr, C_, n,
+                                     *[_ptr(o) for o in out], mem, C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):
         """recall-target search (adaptive partition scanning).  Returns (ids, dist, nscanned[, timing])."""

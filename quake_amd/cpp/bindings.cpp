@@ -150,6 +150,19 @@ PYBIND11_MODULE(_bindings, m) {
              py::arg("group_size") = py::none(),
              "extension: the k best groups of attribute column `group_by` per query, every group by its best vector (ids, distances, groups); "
              "group_size = m: by its m best vectors, ids / distances [Q, k, m]")
+        .def("facet_counts",
+             [](QuakeIndex &self, Tensor x, py::object facet_by, shared_ptr<SearchParams> sp, py::object radius, int n_values) {
+                 std::vector<std::string> names;
+                 if (py::isinstance<py::str>(facet_by)) names.push_back(facet_by.cast<std::string>());
+                 else names = facet_by.cast<std::vector<std::string>>();
+                 std::optional<float> r;
+                 if (!radius.is_none()) r = radius.cast<float>();
+                 return self.facet_counts(x, names, sp, r, n_values);
+             },
+             py::arg("x"), py::arg("facet_by"), py::arg("search_params"), py::arg("radius") = py::none(), py::arg("n_values") = 10,
+             "extension: per query, the value counts of the attribute columns `facet_by` (a name or a list of names) over the vectors "
+             "range_search returns for the same arguments (radius None: every vector of the probed partitions): values, counts, "
+             "distinct, missing, totals")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)
@@ -354,6 +367,16 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("distances", &GroupedSearchResult::distances)
         .def_readwrite("groups", &GroupedSearchResult::groups)
         .def_readwrite("timing_info", &GroupedSearchResult::timing_info);
+
+    py::class_<FacetResult, std::shared_ptr<FacetResult>>(m, "FacetResult")
+        .def(py::init<>())
+        .def_readwrite("values", &FacetResult::values)
+        .def_readwrite("counts", &FacetResult::counts)
+        .def_readwrite("distinct", &FacetResult::distinct)
+        .def_readwrite("missing", &FacetResult::missing)
+        .def_readwrite("totals", &FacetResult::totals)
+        .def_readwrite("columns", &FacetResult::columns)
+        .def_readwrite("timing_info", &FacetResult::timing_info);
 
     py::class_<SearchCursor, std::shared_ptr<SearchCursor>>(m, "SearchCursor")
         .def(py::init([](py::object keys, py::object ids) {  // (None: left undefined -- search_after refuses such a cursor)

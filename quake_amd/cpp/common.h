@@ -169,6 +169,19 @@ struct GroupedSearchResult {
     shared_ptr<SearchTimingInfo> timing_info;
 };
 
+// extension (QuakeIndex::facet_counts): per column and query the n_values most frequent values among the query's range hits --
+// values / counts [C, Q, n] (count descending, then value ascending; padding is value 0, count 0), distinct / missing [C, Q],
+// totals [Q] the hits of every query, columns the C column names
+struct FacetResult {
+    Tensor values;
+    Tensor counts;
+    Tensor distinct;
+    Tensor missing;
+    Tensor totals;
+    std::vector<std::string> columns;
+    shared_ptr<SearchTimingInfo> timing_info;
+};
+
 struct Clustering {  // common.h:249-276
     Tensor centroids;
     Tensor partition_ids;

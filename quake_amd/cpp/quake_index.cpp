@@ -146,6 +146,18 @@ shared_ptr<GroupedSearchResult> QuakeIndex::grouped_search(Tensor x, const std::
     return query_coordinator_->grouped_search(x, col, group_by, sp, group_size);
 }
 
+shared_ptr<FacetResult> QuakeIndex::facet_counts(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> sp,
+                                                 std::optional<float> radius, int n_values) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::facet_counts()] No query coordinator. Did you build the index?");
+    std::vector<qk_attr *> cols(facet_by.size(), nullptr);
+    if (partition_manager_ && partition_manager_->has_lists() && partition_manager_->store() && partition_manager_->store() == attrs_store_)
+        for (size_t c = 0; c < facet_by.size(); c++) {
+            auto it = attrs_.find(facet_by[c]);
+            if (it != attrs_.end()) cols[c] = it->second;
+        }
+    return query_coordinator_->facet_counts(x, cols, facet_by, sp, radius, n_values);
+}
+
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?");
     qk_store *s = partition_manager_->store();

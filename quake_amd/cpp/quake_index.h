@@ -92,6 +92,10 @@ public:
     // group_size = m, 1 <= m <= QK_MAX_GROUP_SIZE: the m best vectors of every group, ids / distances [Q, k, m] (qk_search_grouped_n)
     shared_ptr<GroupedSearchResult> grouped_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> search_params,
                                                    std::optional<int> group_size = std::nullopt);
+    // extension: per query, the value counts of up to QK_MAX_FACET_COLS attribute columns over the hits of range_search with the
+    // same arguments (radius unset: every vector of the probed partitions), the n_values most frequent per column (qk_facet_search)
+    shared_ptr<FacetResult> facet_counts(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> search_params,
+                                         std::optional<float> radius = std::nullopt, int n_values = 10);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

@@ -44,6 +44,9 @@ public:
     // group_size = m (qk_search_grouped_n): ids / distances [Q, k, m], the m best vectors of every group; unset: the one-row result [Q, k]
     shared_ptr<GroupedSearchResult> grouped_search(Tensor x, qk_attr *group_by, const std::string &name, shared_ptr<SearchParams> search_params,
                                                    std::optional<int> group_size = std::nullopt);
+    // extension (qk_facet_search): value counts of `cols` -- columns of this index's store, nullptr: unknown -- over the range hits
+    shared_ptr<FacetResult> facet_counts(Tensor x, const std::vector<qk_attr *> &cols, const std::vector<std::string> &names,
+                                         shared_ptr<SearchParams> search_params, std::optional<float> radius, int n_values);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

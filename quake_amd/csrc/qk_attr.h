@@ -184,3 +184,7 @@ bool qk_filter_where_current(const qk_filter *f);
 // m = group_size: out_ids / out_dist are [Q][k][m], the m best rows of every group; m == 1 is the one-row call, launch for launch
 int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data &col, const uint16_t *mask, int m, int64_t *out_groups,
                       qk_timing *timing, int64_t *n_passes);
+// qk_grouped.hip: rv_vals / rv_has of the column brought up to date for the store as it is (the table has been synced) on ctx's
+// stream, and the slots of a query's open-addressing table: the power of two >= max(16, 2 * min(per_query_ub, n_ids))
+int qk_rowvals_ensure(qk_ctx *ctx, qk_store *s, qk_attr_data &d);
+int64_t qk_grouped_table_slots(int64_t per_query_ub, int64_t n_ids);

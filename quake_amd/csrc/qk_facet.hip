@@ -1,0 +1,571 @@
+// qk_facet.hip -- facet counts: per query, how many hits of a range call carry each value of up to QK_MAX_FACET_COLS attribute
+// columns, and the n_values most frequent values of every column (include/quake_hip.h, "facet counts").
+//
+// The expensive half is the key-emission scan, run pass by pass by qk_emit_passes (qk_dense.hip) exactly as for range search; the
+// hit test is k_range_count's: the key inside the closed interval the host derived from the radius (qk_range_key_bounds) and the
+// filter's mask bit of the arena row.  This file's device work, per pass of queries, over one open-addressing table per
+// (column, query).  The tables are RESERVED by the grouped rule (T + 1 slots each, T from the largest list of the store) for as
+// many queries as fit QK_GROUPED_PASS_BYTES -- a pass's queries go through them group after group, so the emission keeps range
+// search's pass size -- but a query USES only the power of two >= max(16, 2 * min(its hits, ids that have a value)) of its slots
+// (facet_used_mask).  Per pass k_facet_hits, then per group k_facet_clear, k_facet_count, k_facet_select:
+//   k_facet_hits    the hits of every query (ballot + popcount per wave, one atomic add per wave): total
+//   k_facet_clear   the used slots of every table: value words all ones, 32-bit counters 0
+//   k_facet_count   one sweep over the pass's keys serves every column of the call: per column a hit goes to the query's missing
+//                   counter or to the counter of its value's slot (found or claimed like k_grouped_claim: atomicCAS on the value
+//                   word, linear probing, at most as many probes as slots) with an atomic add per hit; QK_FACET_WAVE_AGG=1 adds
+//                   equal values of a wave up in registers first (measured, not shipped)
+//   k_facet_select  one workgroup per (column, query): the occupied slots are compacted to the front of the table, then the n_values
+//                   smallest under the 96-bit key (~count, value ^ sign bit) -- count descending, value ascending signed -- are
+//                   selected exactly (most significant byte first) and sorted in LDS.  Values are distinct, so keys are: the result
+//                   does not depend on which slot a value landed in
+// No thread waits for another and every loop is bounded.  Only integer additions decide a counter, so the result is a pure function
+// of the store, the columns and the call.  The value whose bits are all ones (-1) is the table's empty marker: it owns the slot
+// behind the used ones.
+#include "qk_attr.h"
+
+#include <cstring>
+#include "qk_device.h"
+
+// 0 (shipped): every hit adds 1 to its slot with its own atomic; 1: equal values of a wave are first counted in registers and added
+// by one lane.  Measured with scripts/facet_probe.py: at a radius that keeps 1-2 % of the probed rows a wave step
+// of 64 keys holds about one hit, there is nothing to add up, and the per-lane form is 1-2 % faster in every case of the probe
+#ifndef QK_FACET_WAVE_AGG
+#define QK_FACET_WAVE_AGG 0
+#endif
+
+namespace {
+
+constexpr unsigned long long FC_EMPTY = ~0ull;
+constexpr int FC_SLICE = 1024;      // keys per workgroup step: 256 threads x 4 (the decomposition of GROUPED_FOR_EACH_KEY)
+constexpr int FC_AGG_ROUNDS = 4;    // leaders a wave elects per column and step before the lanes that are left add for themselves
+constexpr int FC_SEL = QK_MAX_FACET_VALUES;  // entries the selection sorts in LDS
+
+struct FacetParams {
+    const uint32_t *keys;
+    const int64_t *pair_base;  // [npairs + 1]
+    const int64_t *pids;       // [nq][P] or nullptr (pair r -> list r)
+    const int64_t *pt_off;
+    const uint16_t *mask;      // row mask of a filter, or nullptr
+    const uint16_t *has[QK_MAX_FACET_COLS];   // has-value mask of every column
+    const int64_t *rowval[QK_MAX_FACET_COLS]; // its value per arena row
+    unsigned long long *tvals; // [C][ng][T + 1]: the tables of the query group g0 .. g0 + ng of the pass
+    uint32_t *tcnt;            // [C][ng][T + 1]
+    uint32_t *total;           // [nq]
+    uint32_t *missing;         // [C][nq]
+    int64_t nq, g0, ng;
+    int P, Sg, C;
+    uint32_t tmask;            // T - 1 of the reserved tables: the stride of a table is T + 1 slots
+    uint32_t key_lo, key_hi;
+    int64_t max_ids;           // the largest number of ids with a value among the call's columns
+};
+
+// The slots a query's tables USE of the T + 1 reserved ones: the power of two >= max(16, 2 * min(hits of the query, max_ids)),
+// known once the hits are counted (k_facet_hits) and never more than T -- a query has no more distinct values than hits.  Clearing,
+// counting and selecting touch these slots only, so a call costs what its hits cost, not what the largest list of the store would.
+__device__ __forceinline__ uint32_t facet_used_mask(uint32_t hits, int64_t max_ids, uint32_t tmask) {
+    const uint64_t distinct = min((uint64_t)hits, (uint64_t)max(max_ids, (int64_t)1));
+    uint64_t T = 16;
+    while (T < 2 * distinct) T <<= 1;
+    return (uint32_t)min(T - 1, (uint64_t)tmask);
+}
+
+__device__ __forceinline__ uint32_t facet_hash(unsigned long long v) {  // (the 64-bit finaliser of MurmurHash3, as grouped_hash)
+    v ^= v >> 33;
+    v *= 0xff51afd7ed558ccdull;
+    v ^= v >> 33;
+    v *= 0xc4ceb9fe1a85ec53ull;
+    v ^= v >> 33;
+    return (uint32_t)v;
+}
+
+// `add` hits of value v go to v's slot of the table at tv / tc.  Linear probing; the table holds at least twice the values a query
+// can meet, so an empty slot ends every chain -- and at most T probes whatever happens: this loop cannot spin.
+__device__ __forceinline__ void facet_add(unsigned long long *tv, uint32_t *tc, uint32_t tmask, unsigned long long v, uint32_t add) {
+    if (v == FC_EMPTY) {  // the value that looks like an empty slot has a slot of its own
+        atomicAdd(&tc[(int64_t)tmask + 1], add);
+        return;
+    }
+    uint32_t h = facet_hash(v) & tmask;
+    for (uint32_t n = 0; n <= tmask; n++) {
+        unsigned long long cur = __hip_atomic_load(&tv[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == FC_EMPTY) {
+            cur = atomicCAS(&tv[h], FC_EMPTY, v);
+            if (cur == FC_EMPTY) cur = v;
+        }
+        if (cur == v) {
+            atomicAdd(&tc[h], add);
+            return;
+        }
+        h = (h + 1) & tmask;
+    }
+}
+
+// is the key at absolute position pos a hit (k_range_count's test); *row: its arena row when it passed the key interval
+__device__ __forceinline__ bool facet_hit(const FacetParams &F, const int64_t *pbase, const int64_t *qpids, int64_t pos, int64_t lim, int64_t *row) {
+    const uint32_t key = pos < lim ? F.keys[pos] : 0xFFFFFFFFu;
+    bool hit = pos < lim && key >= F.key_lo && key <= F.key_hi;  // (0xFFFFFFFF lies outside every interval)
+    *row = 0;
+    if (hit) {
+        *row = emit_key_row(pbase, qpids, F.P, F.pt_off, pos);
+        if (F.mask) hit = (F.mask[*row >> 4] >> (*row & 15)) & 1;
+    }
+    return hit;
+}
+
+// blockIdx.x = query * Sg + g: the workgroup takes slices g, g + Sg, ... of its query's segment; every wave runs the same number
+// of steps (the ballots below want whole waves), a position behind the segment is no hit.  total[q] = the hits of the query
+__global__ __launch_bounds__(256) void k_facet_hits(FacetParams F) {
+    const int64_t q = blockIdx.x / F.Sg;
+    const int lane = threadIdx.x & 63;
+    const int64_t *pbase = F.pair_base + q * F.P;
+    const int64_t *qpids = F.pids ? F.pids + q * F.P : nullptr;
+    const int64_t beg = pbase[0], end = pbase[F.P];
+    uint32_t n_total = 0;  // (wave-uniform)
+    for (int64_t s0 = beg + (int64_t)(blockIdx.x - q * F.Sg) * FC_SLICE; s0 < end; s0 += (int64_t)F.Sg * FC_SLICE) {
+        const int64_t lim = min(end, s0 + FC_SLICE);
+        for (int64_t w0 = s0 + (threadIdx.x & ~63); w0 < lim; w0 += 256) {
+            int64_t row;
+            n_total += __popcll(__ballot(facet_hit(F, pbase, qpids, w0 + lane, lim, &row)));
+        }
+    }
+    if (lane == 0 && n_total) atomicAdd(&F.total[q], n_total);
+}
+
+// blockIdx.x = column * ng + query of the group: the slots the query's table uses become empty (value all ones, counter 0)
+__global__ __launch_bounds__(256) void k_facet_clear(FacetParams F) {
+    const int64_t q = F.g0 + blockIdx.x % F.ng;
+    const int64_t tb = (int64_t)blockIdx.x * ((int64_t)F.tmask + 2);
+    const int64_t used = (int64_t)facet_used_mask(F.total[q], F.max_ids, F.tmask) + 2;
+    for (int64_t i = threadIdx.x; i < used; i += 256) {
+        F.tvals[tb + i] = FC_EMPTY;
+        F.tcnt[tb + i] = 0u;
+    }
+}
+
+// the decomposition of k_facet_hits over the queries of the group; a query without hits is left at once
+__global__ __launch_bounds__(256) void k_facet_count(FacetParams F) {
+    const int64_t ql = blockIdx.x / F.Sg, q = F.g0 + ql;
+    const uint32_t hits = F.total[q];
+    if (hits == 0) return;
+    const uint32_t umask = facet_used_mask(hits, F.max_ids, F.tmask);
+    const int lane = threadIdx.x & 63;
+    const int64_t *pbase = F.pair_base + q * F.P;
+    const int64_t *qpids = F.pids ? F.pids + q * F.P : nullptr;
+    const int64_t beg = pbase[0], end = pbase[F.P];
+    const int64_t tstride = (int64_t)F.tmask + 2;
+    uint32_t n_missing[QK_MAX_FACET_COLS] = {0, 0, 0, 0};  // (wave-uniform)
+    for (int64_t s0 = beg + (int64_t)(blockIdx.x - ql * F.Sg) * FC_SLICE; s0 < end; s0 += (int64_t)F.Sg * FC_SLICE) {
+        const int64_t lim = min(end, s0 + FC_SLICE);
+        for (int64_t w0 = s0 + (threadIdx.x & ~63); w0 < lim; w0 += 256) {
+            int64_t row;
+            const bool hit = facet_hit(F, pbase, qpids, w0 + lane, lim, &row);
+            const uint64_t hm = __ballot(hit);
+            if (hm == 0) continue;
+#pragma unroll
+            for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+                if (c >= F.C) break;
+                const bool has = hit && ((F.has[c][row >> 4] >> (row & 15)) & 1);
+                n_missing[c] += __popcll(hm) - __popcll(__ballot(has));
+                const unsigned long long v = has ? (unsigned long long)F.rowval[c][row] : 0ull;
+                uint32_t add = has ? 1u : 0u;
+#if QK_FACET_WAVE_AGG
+                bool open = has;  // not yet counted by a leader
+                for (int r = 0; r < FC_AGG_ROUNDS; r++) {
+                    const uint64_t om = __ballot(open);
+                    if (om == 0) break;
+                    const int leader = __ffsll((unsigned long long)om) - 1;
+                    const unsigned long long lv = __shfl(v, leader);
+                    const bool same = open && v == lv;
+                    const uint32_t n = __popcll(__ballot(same));
+                    if (same) {
+                        add = lane == leader ? n : 0u;
+                        open = false;
+                    }
+                }
+#endif
+                if (add) {
+                    const int64_t tb = ((int64_t)c * F.ng + ql) * tstride;
+                    facet_add(F.tvals + tb, F.tcnt + tb, umask, v, add);
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < QK_MAX_FACET_COLS; c++)
+            if (c < F.C && n_missing[c]) atomicAdd(&F.missing[(int64_t)c * F.nq + q], n_missing[c]);
+    }
+}
+
+struct FacetSelectParams {
+    unsigned long long *tvals;  // [C][ng][T + 1]; compacted in place
+    uint32_t *tcnt;             // [C][ng][T + 1]
+    const uint32_t *total;      // [nq]
+    const uint32_t *missing;    // [C][nq]
+    int64_t nq, q0, Q;          // the pass's queries are q0 .. q0 + nq of the call's Q
+    int64_t g0, ng;             // the group's are g0 .. g0 + ng of the pass's
+    int64_t T1;                 // T + 1: the stride of a table
+    int64_t max_ids;
+    int n_values;
+    int64_t *out_values, *out_counts;    // [C][Q][n_values]
+    int64_t *out_distinct, *out_missing; // [C][Q] or nullptr
+    int64_t *out_total;                  // [Q] or nullptr
+};
+
+// the 96-bit selection key of a (value, count): smaller = more hits, then the smaller signed value
+struct FKey {
+    uint32_t hi;
+    unsigned long long lo;
+};
+__device__ __forceinline__ FKey facet_key(unsigned long long v, uint32_t c) { return FKey{~c, v ^ 0x8000000000000000ull}; }
+__device__ __forceinline__ bool fkey_less(const FKey &a, const FKey &b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+// byte d (0 = most significant, 11 = least) of a key, and whether the bytes in front of d equal those of p
+__device__ __forceinline__ uint32_t fkey_byte(const FKey &k, int d) {
+    return d < 4 ? (k.hi >> (24 - 8 * d)) & 255u : (uint32_t)(k.lo >> (56 - 8 * (d - 4))) & 255u;
+}
+__device__ __forceinline__ bool fkey_prefix(const FKey &k, const FKey &p, int d) {
+    if (d == 0) return true;
+    if (d <= 4) return d == 4 ? k.hi == p.hi : (k.hi >> (32 - 8 * d)) == (p.hi >> (32 - 8 * d));
+    return k.hi == p.hi && (k.lo >> (64 - 8 * (d - 4))) == (p.lo >> (64 - 8 * (d - 4)));
+}
+
+// blockIdx.x = column * ng + query of the group
+__global__ __launch_bounds__(256) void k_facet_select(FacetSelectParams S) {
+    __shared__ uint32_t s_hi[FC_SEL];
+    __shared__ unsigned long long s_lo[FC_SEL];
+    __shared__ uint32_t s_hist[256];
+    __shared__ uint32_t s_wave[4];
+    __shared__ uint32_t s_n;
+    __shared__ uint32_t s_pick[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t c = blockIdx.x / S.ng, q = S.g0 + (blockIdx.x - c * S.ng);
+    unsigned long long *tv = S.tvals + (int64_t)blockIdx.x * S.T1;
+    uint32_t *tc = S.tcnt + (int64_t)blockIdx.x * S.T1;
+    // ---- 1. the occupied slots (count > 0; the slot behind the used ones holds the value -1 from k_facet_clear on) to the front,
+    //         in any order: a chunk is read into registers before any of it is written, and it is written at or in front of where
+    //         it was read
+    const int64_t used = (int64_t)facet_used_mask(S.total[q], S.max_ids, (uint32_t)(S.T1 - 2)) + 2;
+    uint32_t D = 0;  // (uniform)
+    for (int64_t b0 = 0; b0 < used; b0 += 1024) {
+        unsigned long long v[4];
+        uint32_t n[4];
+        uint32_t mine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int64_t i = b0 + j * 256 + tid;
+            n[j] = i < used ? tc[i] : 0u;
+            v[j] = i < used ? tv[i] : 0ull;
+            mine += n[j] ? 1u : 0u;
+        }
+        uint32_t incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(incl, off);
+            if (lane >= off) incl += o;
+        }
+        __syncthreads();  // (the chunk is in registers; s_wave of the previous chunk has been read)
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t at = D + incl - mine;
+        for (int w = 0; w < wave; w++) at += s_wave[w];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (n[j]) {
+                tv[at] = v[j];
+                tc[at] = n[j];
+                at++;
+            }
+        D += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    }
+    __syncthreads();  // (the compacted entries are visible to the workgroup)
+    // ---- 2. more than FC_SEL entries: the n_values-th smallest key, byte by byte from the top; keys are distinct, so exactly
+    //         n_values entries lie at or below it
+    const uint32_t want = (uint32_t)S.n_values;
+    FKey thr{0xFFFFFFFFu, ~0ull};
+    if (D > FC_SEL) {
+        FKey pre{0u, 0ull};
+        uint32_t need = want;
+        for (int d = 0; d < 12; d++) {
+            s_hist[tid] = 0;
+            __syncthreads();
+            for (uint32_t i = tid; i < D; i += 256) {
+                const FKey k = facet_key(tv[i], tc[i]);
+                if (fkey_prefix(k, pre, d)) atomicAdd(&s_hist[fkey_byte(k, d)], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t run = 0, b = 0;
+                for (; b < 255; b++) {
+                    if (run + s_hist[b] >= need) break;
+                    run += s_hist[b];
+                }
+                s_pick[0] = b;
+                s_pick[1] = need - run;
+            }
+            __syncthreads();
+            const uint32_t b = s_pick[0];
+            need = s_pick[1];
+            if (d < 4) pre.hi |= b << (24 - 8 * d);
+            else pre.lo |= (unsigned long long)b << (56 - 8 * (d - 4));
+            __syncthreads();  // (s_pick and s_hist are rewritten by the next byte)
+        }
+        thr = pre;
+    }
+    // ---- 3. the survivors into LDS (at most FC_SEL of them), padded with the key no entry has, sorted ascending
+    if (tid == 0) s_n = 0;
+    s_hi[tid] = 0xFFFFFFFFu;
+    s_lo[tid] = ~0ull;
+    __syncthreads();
+    for (uint32_t i = tid; i < D; i += 256) {
+        const FKey k = facet_key(tv[i], tc[i]);
+        if (!fkey_less(thr, k)) {
+            const uint32_t at = atomicAdd(&s_n, 1u);
+            if (at < FC_SEL) {
+                s_hi[at] = k.hi;
+                s_lo[at] = k.lo;
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = 2; k <= FC_SEL; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int o = tid ^ j;
+            if (o > tid) {
+                const FKey a{s_hi[tid], s_lo[tid]}, b{s_hi[o], s_lo[o]};
+                const bool up = (tid & k) == 0;
+                if (up ? fkey_less(b, a) : fkey_less(a, b)) {
+                    s_hi[tid] = b.hi;
+                    s_lo[tid] = b.lo;
+                    s_hi[o] = a.hi;
+                    s_lo[o] = a.lo;
+                }
+            }
+            __syncthreads();
+        }
+    // ---- 4. the answer: entries behind the distinct values are padding (value 0, count 0)
+    const int64_t oq = c * S.Q + S.q0 + q;
+    if (tid < S.n_values) {
+        const bool real = (uint32_t)tid < D && s_hi[tid] != 0xFFFFFFFFu;
+        S.out_values[oq * S.n_values + tid] = real ? (int64_t)(s_lo[tid] ^ 0x8000000000000000ull) : 0;
+        S.out_counts[oq * S.n_values + tid] = real ? (int64_t)(~s_hi[tid]) : 0;
+    }
+    if (tid == 0) {
+        if (S.out_distinct) S.out_distinct[oq] = D;
+        if (S.out_missing) S.out_missing[oq] = S.missing[c * S.nq + q];
+        if (S.out_total && c == 0) S.out_total[S.q0 + q] = S.total[q];
+    }
+}
+
+// bytes of the tables one query accounts for: 12 per slot of every column
+inline int64_t facet_table_bytes(int64_t T, int C) { return (int64_t)C * (T + 1) * 12; }
+
+int facet_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *const *cols, int C, int n_values, uint32_t key_lo,
+                 uint32_t key_hi, const uint16_t *mask, int64_t *out_values, int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing,
+                 int64_t *out_total, qk_timing *timing, int64_t *n_passes) {
+    const int64_t Q = a.Q;
+    hipStream_t st = ctx->stream;
+    const int npids = (int)s->parts.size();
+    const int P = a.all_lists ? npids : a.P;
+    *n_passes = 0;
+    qk_phase_events pe;
+    pe.ctx = ctx;
+    pe.tm = ctx->timing && timing;
+    pe.dtm = false;
+    pe.ev_base = 4;
+    if (P <= 0 || npids <= 0) {  // no lists: no hits
+        QK_TRY(pe.mark(0));
+        QK_TRY(qk_prep_flush(ctx));
+        QK_HIP(hipMemsetAsync(out_values, 0, (size_t)C * Q * n_values * 8, st));
+        QK_HIP(hipMemsetAsync(out_counts, 0, (size_t)C * Q * n_values * 8, st));
+        if (out_distinct) QK_HIP(hipMemsetAsync(out_distinct, 0, (size_t)C * Q * 8, st));
+        if (out_missing) QK_HIP(hipMemsetAsync(out_missing, 0, (size_t)C * Q * 8, st));
+        if (out_total) QK_HIP(hipMemsetAsync(out_total, 0, (size_t)Q * 8, st));
+        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
+        return QK_OK;
+    }
+    int64_t max_ids = cols[0]->n_ids;  // one table size for every column of the call: that of the column with the most values
+    for (int c = 1; c < C; c++) max_ids = std::max(max_ids, cols[c]->n_ids);
+    // this pipeline's bytes of the call's buffer, sized for the largest pass: [table values] [table counters] [total] [missing]
+    int64_t T = 0, S = 0, qt = 1;  // qt: queries whose tables fit QK_GROUPED_PASS_BYTES -- a pass's queries are counted in groups of qt
+    size_t o_tcnt = 0, o_total = 0, o_missing = 0;
+    qk_emit_hooks h;
+    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+        T = qk_grouped_table_slots(per_query_ub, max_ids);
+        const int64_t qbytes = facet_table_bytes(T, C);
+        if (qbytes > QK_GROUPED_PASS_BYTES)
+            QK_FAIL(QK_ERR_UNSUPPORTED, "facet counts: the tables of one query need %lld bytes, more than QK_GROUPED_PASS_BYTES", (long long)qbytes);
+        qt = std::max<int64_t>(1, std::min<int64_t>(*qc, QK_GROUPED_PASS_BYTES / qbytes));
+        S = (per_query_ub + FC_SLICE - 1) / FC_SLICE;
+        if (*qc * S > 0x7FFFFFF0LL || *qc * (int64_t)C > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "facet counts: Q too large");
+        const int64_t nslots = qt * C * (T + 1);
+        o_tcnt = qk_al256((size_t)nslots * 8);
+        o_total = o_tcnt + qk_al256((size_t)nslots * 4);
+        o_missing = o_total + qk_al256((size_t)*qc * 4);
+        *extra_bytes = o_missing + qk_al256((size_t)*qc * C * 4);
+        return QK_OK;
+    };
+    h.before_scan = [&](const qk_emit_pass &p) -> int {
+        // total and missing of the pass (missing lies behind total: one memset); the tables are cleared behind the hit count, as far
+        // as they are used (k_facet_clear)
+        QK_HIP(hipMemsetAsync(p.extra + o_total, 0, (o_missing - o_total) + (size_t)p.nq * C * 4, st));
+        return QK_OK;
+    };
+    h.consume = [&](const qk_emit_pass &p) -> int {
+        FacetParams F;
+        F.keys = p.keys;
+        F.pair_base = p.pair_base;
+        F.pids = p.pids;
+        F.pt_off = s->d_off;
+        F.mask = mask;
+        for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+            F.has[c] = cols[c < C ? c : 0]->rv_has;
+            F.rowval[c] = cols[c < C ? c : 0]->rv_vals;
+        }
+        F.tvals = (unsigned long long *)p.extra;
+        F.tcnt = (uint32_t *)(p.extra + o_tcnt);
+        F.total = (uint32_t *)(p.extra + o_total);
+        F.missing = (uint32_t *)(p.extra + o_missing);
+        F.nq = p.nq;
+        F.P = P;
+        F.C = C;
+        F.tmask = (uint32_t)(T - 1);
+        F.key_lo = key_lo;
+        F.key_hi = key_hi;
+        F.max_ids = max_ids;
+        // about 16384 workgroups per launch, whatever S is
+        F.g0 = 0;
+        F.ng = p.nq;
+        F.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));
+        hipLaunchKernelGGL(k_facet_hits, dim3((unsigned)(p.nq * F.Sg)), dim3(256), 0, st, F);
+        FacetSelectParams L;
+        L.tvals = F.tvals;
+        L.tcnt = F.tcnt;
+        L.total = F.total;
+        L.missing = F.missing;
+        L.nq = p.nq;
+        L.q0 = p.q0;
+        L.Q = Q;
+        L.T1 = T + 1;
+        L.max_ids = max_ids;
+        L.n_values = n_values;
+        L.out_values = out_values;
+        L.out_counts = out_counts;
+        L.out_distinct = out_distinct;
+        L.out_missing = out_missing;
+        L.out_total = out_total;
+        // the pass's queries in groups whose tables fit the workspace: the same tables serve one group after the other
+        for (int64_t g0 = 0; g0 < p.nq; g0 += qt) {
+            F.g0 = L.g0 = g0;
+            F.ng = L.ng = std::min(qt, p.nq - g0);
+            F.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / F.ng));
+            hipLaunchKernelGGL(k_facet_clear, dim3((unsigned)(F.ng * C)), dim3(256), 0, st, F);
+            hipLaunchKernelGGL(k_facet_count, dim3((unsigned)(F.ng * F.Sg)), dim3(256), 0, st, F);
+            hipLaunchKernelGGL(k_facet_select, dim3((unsigned)(F.ng * C)), dim3(256), 0, st, L);
+        }
+        QK_HIP(hipGetLastError());
+        return QK_OK;
+    };
+    QK_TRY(qk_emit_passes(ctx, s, a, P, "facet counts", pe, h, n_passes));
+    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
+    ctx->last_scan_kernel = wide ? "k_scan_wide (facet)" : "k_scan (facet)";
+    QK_TRY(pe.mark(3));
+    return QK_OK;
+}
+
+// the body of both entry points: parent == nullptr && pids == nullptr -> every list
+int facet_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+              int metric, float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, int n_values, int64_t *out_values,
+              int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem, qk_timing *timing) {
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    if (radius != radius) QK_FAIL(QK_ERR_INVALID, "%s: the radius is NaN", who);
+    if (n_cols < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_cols=%d must be at least 1", who, n_cols);
+    if (n_cols > QK_MAX_FACET_COLS) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_cols=%d exceeds QK_MAX_FACET_COLS=%d", who, n_cols, QK_MAX_FACET_COLS);
+    if (n_values < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_values=%d must be at least 1", who, n_values);
+    if (n_values > QK_MAX_FACET_VALUES)
+        QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_values=%d exceeds QK_MAX_FACET_VALUES=%d", who, n_values, QK_MAX_FACET_VALUES);
+    if (!facet_by) QK_FAIL(QK_ERR_INVALID, "%s: facet_by is null", who);
+    qk_attr_data *cols[QK_MAX_FACET_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    for (int c = 0; c < n_cols; c++) {
+        if (!facet_by[c]) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d is null", who, c);
+        cols[c] = facet_by[c]->d.get();
+        if (cols[c]->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d belongs to another store", who, c);
+    }
+    if (Q < 0 || (Q > 0 && (!x || !out_values || !out_counts))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
+    QK_TRY(qk_check_overflow(ctx));
+    QK_HIP(hipSetDevice(ctx->device));
+    if (timing) memset(timing, 0, sizeof(*timing));
+    if (Q == 0) return QK_OK;
+    hipStream_t st = ctx->stream;
+    // ---- staging, query preparation, coarse; a host caller's outputs on the device: [values] [counts] [distinct] [missing] [total]
+    const size_t bv = qk_al256((size_t)n_cols * Q * n_values * 8), bc = qk_al256((size_t)n_cols * Q * 8), bt = qk_al256((size_t)Q * 8);
+    qk_scan_args sa;
+    char *out = nullptr;
+    bool have_coarse = false;
+    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, 2 * bv + 2 * bc + bt, timing != nullptr, &sa, &out,
+                             &have_coarse));
+    int64_t *dvalues = out_values, *dcounts = out_counts, *ddistinct = out_distinct, *dmissing = out_missing, *dtotal = out_total;
+    if (mem == QK_MEM_HOST) {
+        dvalues = (int64_t *)out;
+        dcounts = (int64_t *)(out + bv);
+        ddistinct = out_distinct ? (int64_t *)(out + 2 * bv) : nullptr;
+        dmissing = out_missing ? (int64_t *)(out + 2 * bv + bc) : nullptr;
+        dtotal = out_total ? (int64_t *)(out + 2 * bv + 2 * bc) : nullptr;
+    }
+    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
+    if (!qk_range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
+        key_lo = 1;
+        key_hi = 0;
+    }
+    // ---- row values and mask, then emission + counting + selection -------------------------------------------------------------
+    const uint16_t *mask = nullptr;
+    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
+    QK_TRY(qk_store_sync_table(s));
+    for (int c = 0; c < n_cols; c++) {
+        bool seen = false;  // (the same column twice: derived once)
+        for (int e = 0; e < c; e++) seen = seen || cols[e] == cols[c];
+        if (!seen) QK_TRY(qk_rowvals_ensure(ctx, s, *cols[c]));
+    }
+    int64_t n_passes = 0;
+    QK_TRY(facet_device(ctx, s, sa, cols, n_cols, n_values, key_lo, key_hi, mask, dvalues, dcounts, ddistinct, dmissing, dtotal, timing,
+                        &n_passes));
+    // ---- results back ------------------------------------------------------------------------------------------------------------
+    if (mem == QK_MEM_HOST) {
+        QK_HIP(hipMemcpyAsync(out_values, dvalues, (size_t)n_cols * Q * n_values * 8, hipMemcpyDeviceToHost, st));
+        QK_HIP(hipMemcpyAsync(out_counts, dcounts, (size_t)n_cols * Q * n_values * 8, hipMemcpyDeviceToHost, st));
+        if (out_distinct) QK_HIP(hipMemcpyAsync(out_distinct, ddistinct, (size_t)n_cols * Q * 8, hipMemcpyDeviceToHost, st));
+        if (out_missing) QK_HIP(hipMemcpyAsync(out_missing, dmissing, (size_t)n_cols * Q * 8, hipMemcpyDeviceToHost, st));
+        if (out_total) QK_HIP(hipMemcpyAsync(out_total, dtotal, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
+        QK_HIP(hipStreamSynchronize(st));
+    }
+    if (timing) {
+        QK_HIP(hipStreamSynchronize(st));
+        timing->n_items = n_passes;
+        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
+    }
+    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
+    return QK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qk_facet_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int metric, float radius,
+                    qk_filter *filter, qk_attr *const *facet_by, int n_cols, int n_values, int64_t *out_values, int64_t *out_counts,
+                    int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_search: null argument");
+    if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_facet_search: nprobe must be positive");
+    return facet_run("qk_facet_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, facet_by, n_cols, n_values,
+                     out_values, out_counts, out_distinct, out_missing, out_total, mem, timing);
+}
+
+int qk_facet_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric, float radius,
+                  qk_filter *filter, qk_attr *const *facet_by, int n_cols, int n_values, int64_t *out_values, int64_t *out_counts,
+                  int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_scan: null argument");
+    if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_facet_scan: bad partition id list");
+    return facet_run("qk_facet_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, facet_by, n_cols, n_values, out_values,
+                     out_counts, out_distinct, out_missing, out_total, mem, timing);
+}
+
+}  // extern "C"

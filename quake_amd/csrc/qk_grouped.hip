@@ -321,8 +321,11 @@ __global__ __launch_bounds__(256) void k_grouped_rowvals(RowvalParams R) {
     }
 }
 
+}  // namespace
+
 // rv_vals / rv_has of the column brought up to date for the store as it is (the table has been synced) on ctx's stream
-int rowvals_ensure(qk_ctx *ctx, qk_store *s, qk_attr_data &d) {
+// (shared with qk_facet.hip: declared in qk_attr.h)
+int qk_rowvals_ensure(qk_ctx *ctx, qk_store *s, qk_attr_data &d) {
     hipStream_t st = ctx->stream;
     const bool current = d.rv_built && d.rv_store_version == s->version && d.rv_cap_rows == s->cap_rows && d.rv_col_version == d.version;
     if (current) {
@@ -383,14 +386,12 @@ int rowvals_ensure(qk_ctx *ctx, qk_store *s, qk_attr_data &d) {
 
 // slots of a query's table: a power of two, at least twice the distinct values a query can meet -- no more than the keys it can
 // have, no more than the ids that have a value
-int64_t table_slots(int64_t per_query_ub, int64_t n_ids) {
+int64_t qk_grouped_table_slots(int64_t per_query_ub, int64_t n_ids) {
     const int64_t distinct = std::max<int64_t>(1, std::min(per_query_ub, n_ids));
     int64_t T = 16;
     while (T < 2 * distinct) T <<= 1;
     return T;
 }
-
-}  // namespace
 
 // bytes of a pass that one query accounts for (include/quake_hip.h, QK_GROUPED_PASS_BYTES): 8 per key it has room for -- the key and
 // its slot number -- and 20 per table slot; with group_size = m > 1, 12 per key (the selection's copy), 24 per slot (the j of a
@@ -432,7 +433,7 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
     size_t o_tvals = 0, o_tids = 0, o_tkeys = 0, o_tsel = 0, o_skeys = 0, o_sids = 0, o_sdist = 0, o_mkeys = 0;
     qk_emit_hooks h;
     h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
-        T = table_slots(per_query_ub, col.n_ids);
+        T = qk_grouped_table_slots(per_query_ub, col.n_ids);
         const int64_t qbytes = grouped_query_bytes(per_query_ub, T, k, m);
         if (qbytes > QK_GROUPED_PASS_BYTES)
             QK_FAIL(QK_ERR_UNSUPPORTED, "grouped search: one query needs %lld bytes of workspace, more than QK_GROUPED_PASS_BYTES", (long long)qbytes);
@@ -582,7 +583,7 @@ int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, con
     const uint16_t *mask = nullptr;
     if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
     QK_TRY(qk_store_sync_table(s));
-    QK_TRY(rowvals_ensure(ctx, s, col));
+    QK_TRY(qk_rowvals_ensure(ctx, s, col));
     int64_t n_passes = 0;
     QK_TRY(qk_grouped_device(ctx, s, sa, col, mask, m, dgroups, timing, &n_passes));
     // ---- results back ------------------------------------------------------------------------------------------------------------

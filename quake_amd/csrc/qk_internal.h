@@ -505,6 +505,9 @@ int qk_emit_front_end(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x
 // in scan order; `a` as for qk_widek_device (k unused).  lims [Q + 1], out_ids / out_dist [cap] on the device.
 int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask,
                     int64_t cap, int64_t *lims, int64_t *out_ids, float *out_dist, qk_timing *timing, int64_t *n_passes);
+// the closed key interval [*lo, *hi] of "dist <= radius" (L2) / "dist >= radius" (IP) on the float32 distance the caller sees
+// (qk_range.hip; facet counts use the same rule); false: no distance can pass
+bool qk_range_key_bounds(int metric, bool sqrt_l2, float radius, uint32_t *lo, uint32_t *hi);
 // wide rows (a 16-query tile no longer fits the LDS next to what the kernel keeps there): the queries are read from global
 // memory instead (qk_scan_wide.hip).  k_dense_wide: every query against one list -- keys into D, or (argmin) the packed
 // minimum (key << 32 | id) into best64; k_assign_wide: k_assign's nearest centroid of every row of x

@@ -3,7 +3,7 @@
 // The expensive half is the key-emission scan, run pass by pass by qk_emit_passes (qk_dense.hip): one pass over the vectors
 // writes the canonical key of every (query, probed row) to keys[pair_base[pair] + row] -- pairs in (query, rank) order, rows in
 // stored order, which is the order a range result wants.  The host turns the radius into ONE closed interval of keys
-// [key_lo, key_hi] (range_key_bounds below), so "inside the radius" is an integer comparison and inclusive means inclusive.
+// [key_lo, key_hi] (qk_range_key_bounds below), so "inside the radius" is an integer comparison and inclusive means inclusive.
 // This file's device work, per pass of queries:
 //   k_range_count    a query's segment is cut into slices of QK_RANGE_SLICE keys; a workgroup takes one slice at a time, its four waves
 //                    count the hits of their quarter (ballot + popcount), the per-wave counts are kept for the writer
@@ -257,8 +257,10 @@ inline uint32_t host_ord_from_ip(float ip) {
 
 // The closed key interval of "dist <= radius" (L2) / "dist >= radius" (IP) on the float32 distance the caller sees.  The key of a
 // NaN distance (0xFFFFFFFF, qk_device.h) lies outside every interval: the widest one ends at the key of +inf (L2) / -inf (IP).
-// Returns false when no distance can pass.
-bool range_key_bounds(int metric, bool sqrt_l2, float radius, uint32_t *lo, uint32_t *hi) {
+// Returns false when no distance can pass.  (Shared with qk_facet.hip: declared in qk_internal.h.)
+}  // namespace
+
+bool qk_range_key_bounds(int metric, bool sqrt_l2, float radius, uint32_t *lo, uint32_t *hi) {
     if (metric == QK_METRIC_IP) {
         // (+0 >= -0 and -0 >= +0 in float32: both zeros have one key)
         *lo = host_ord_from_ip(INFINITY);
@@ -284,8 +286,6 @@ bool range_key_bounds(int metric, bool sqrt_l2, float radius, uint32_t *lo, uint
     *hi = f2u(t);
     return true;
 }
-
-}  // namespace
 
 int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask, int64_t cap,
                     int64_t *lims, int64_t *out_ids, float *out_dist, qk_timing *timing, int64_t *n_passes) {
@@ -419,7 +419,7 @@ int range_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const
         ddist = cap > 0 && out_dist ? (float *)(out + bl + bi) : nullptr;
     }
     uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
-    if (!range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
+    if (!qk_range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
         key_lo = 1;
         key_hi = 0;
     }

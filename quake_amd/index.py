@@ -304,6 +304,25 @@ class GroupedSearchResult:
         self.timing_info = None
 
 
+MAX_FACET_COLS = header_constant("QK_MAX_FACET_COLS")
+MAX_FACET_VALUES = header_constant("QK_MAX_FACET_VALUES")
+
+
+class FacetResult:
+    """extension (QuakeIndex.facet_counts): per column and query the n_values most frequent values among the query's range hits --
+    values / counts [C, Q, n] (count descending, then value ascending; padding is value 0, count 0), distinct / missing [C, Q],
+    totals [Q] the hits of every query, columns the C column names"""
+
+    def __init__(self):
+        self.values = None
+        self.counts = None
+        self.distinct = None
+        self.missing = None
+        self.totals = None
+        self.columns = None
+        self.timing_info = None
+
+
 _CONTEXTS = {}
 
 
@@ -1036,6 +1055,89 @@ class QuakeIndex:
         res.ids = ids if on_dev else ids.cpu()
         res.distances = dist if on_dev else dist.cpu()
         res.groups = groups if on_dev else groups.cpu()
+        return res
+
+    def facet_counts(self, x, facet_by, search_params, radius=None, n_values=10):
+        """extension (no reference counterpart): of the vectors range_search(x, radius, search_params) returns for each query -- the
+        search_params.nprobe nearest partitions, the inclusive radius test, search_params.filter if set; radius=None: every vector
+        of those partitions -- how many carry each value of the attribute columns `facet_by` (a name or a list of up to 4 names).
+        search_params.k is ignored.  Exact; the values are those of the moment of the call.  Returns a FacetResult on x's device."""
+        self._require_built("[QuakeIndex::facet_counts()] No query coordinator. Did you build the index?")
+        sp = search_params
+        names = [facet_by] if isinstance(facet_by, str) else list(facet_by)
+        if not 1 <= len(names) <= MAX_FACET_COLS:
+            raise RuntimeError("[QuakeIndex::facet_counts()] facet_by must name between 1 and %d columns" % MAX_FACET_COLS)
+        if not 1 <= int(n_values) <= MAX_FACET_VALUES:
+            raise RuntimeError("[QuakeIndex::facet_counts()] n_values must be between 1 and %d" % MAX_FACET_VALUES)
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError("[QuakeIndex::facet_counts()] SearchParams.filters / query_filter (one filter per query) are not "
+                               "supported by facet_counts")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::facet_counts()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
+                               "supported by facet_counts")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::facet_counts()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                               "facet_counts")
+        if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
+            raise RuntimeError("[QuakeIndex::facet_counts()] SearchParams.max_nprobe (adaptive probing) is not supported by facet_counts")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError("[QuakeIndex::facet_counts()] facet_counts is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::facet_counts()] facet_counts is not supported with num_workers > 0")
+        cols = self._attributes()
+        for name in names:
+            if name not in cols:
+                raise RuntimeError("[QuakeIndex::facet_counts()] unknown attribute column '%s'" % name)
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError("[QuakeIndex::facet_counts()] SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError("[QuakeIndex::facet_counts()] the filter was made for another index")
+            flt = flt._h
+        if radius is None:
+            radius = float("-inf") if capi.metric_code(self.metric_) == capi.QK_METRIC_IP else float("inf")
+        radius = float(radius)
+        if radius != radius:
+            raise RuntimeError("[QuakeIndex::facet_counts()] the radius is NaN")
+        n, C_ = int(n_values), len(names)
+        res = FacetResult()
+        res.columns = names
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        nq = 0 if x is None else int(x.shape[0])
+        if nq == 0:
+            res.values = torch.zeros((C_, 0, n), dtype=torch.int64)
+            res.counts = torch.zeros((C_, 0, n), dtype=torch.int64)
+            res.distinct = torch.zeros((C_, 0), dtype=torch.int64)
+            res.missing = torch.zeros((C_, 0), dtype=torch.int64)
+            res.totals = torch.zeros((0,), dtype=torch.int64)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        self._ctx.set_timing(1)
+        try:
+            out = self._ctx.facet_search(self.parent._store if self.parent is not None else None, self._store, xd, nprobe, radius,
+                                         self.metric_, [cols[name] for name in names], n_values=n, filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(0)
+        tm = out[5]
+        ti.n_queries = nq
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.values, res.counts, res.distinct, res.missing, res.totals = (o if on_dev else o.cpu() for o in out[:5])
         return res
 
     def make_filter(self, ids=None, exclude=False, where=None, any_of=None):
