@@ -644,6 +644,72 @@ QK_API int qk_facet_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, co
                          int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem,
                          qk_timing *timing);
 
+/* ---- facet statistics -------------------------------------------------------------------------------
+ * No reference counterpart.  The numeric half of faceted navigation: per query, over its range hits, the count, minimum, maximum,
+ * exact sum and a histogram with caller-chosen bucket edges of up to QK_MAX_FACET_COLS columns -- a price slider, "under 10 /
+ * 10-50 / 50-200 / above", the sum and count behind a rating.  None of these follows from the n_values most frequent values of
+ * facet counts, and a price or timestamp column has almost as many distinct values as rows.
+ * Hits: the hit multiset H(q) is BY DEFINITION that of qk_range_search / qk_range_scan for the same (parent, nprobe | pids, metric,
+ * radius, filter), exactly as for facet counts above: the inclusive float32 radius test, qk_ctx_set_squared_l2 honoured, a NaN
+ * distance never a hit, a NaN radius QK_ERR_INVALID, radius +inf (L2) / -inf (IP) every probed candidate row, a row stored twice
+ * counts twice, -1 / absent / empty lists contribute nothing, a filter or column of another store is QK_ERR_INVALID.
+ * Per column c of facet_by [n_cols] (the same column twice is allowed), val_c being the int64 value the column has for a hit's id
+ * at the moment of the call; every output but out_total may be NULL, each on its own:
+ *   total[q]        = |H(q)|                                                                  out_total [Q]
+ *   missing[c][q]   = hits whose id has no value in c                                         out_missing [n_cols][Q]
+ *   count[c][q]     = total[q] - missing[c][q]                                                out_count [n_cols][Q]
+ *   min / max[c][q] = signed minimum / maximum of val_c over the hits that have a value       out_min, out_max [n_cols][Q]
+ *                     count == 0: the identities INT64_MAX / INT64_MIN -- both are legal values, so it is count == 0, not the
+ *                     value, that says "no value"
+ *   sum[c][q]       = the exact integer sum of val_c, a 128-bit two's-complement number in two words: out_sum_lo [n_cols][Q] its
+ *                     low 64 bits (stored in an int64), out_sum_hi [n_cols][Q] its high 64 bits, signed.  It neither wraps nor
+ *                     saturates: a query has fewer than 2^30 keys (below), and 2^30 * 2^63 fits 128 bits easily
+ *   hist[c][q][b]   : column c comes with n_edges[c] = E edges e_0 < e_1 < ... < e_{E-1}, 0 <= E <= QK_MAX_FACET_EDGES, signed
+ *                     int64, strictly ascending, any int64 (INT64_MIN and INT64_MAX included).  The bucket of a value v is
+ *                     b(v) = |{i : e_i <= v}|: bucket 0 holds v < e_0, bucket i holds e_{i-1} <= v < e_i, bucket E holds
+ *                     v >= e_{E-1}; E == 0: one bucket equal to count.  The buckets of (c, q) add up to count[c][q].
+ *                     out_hist [n_cols][Q][hist_stride], hist_stride = 1 + max_c n_edges[c]; entries behind a column's own
+ *                     E + 1 buckets are 0
+ * edges: the columns' edges one after the other, n_edges [n_cols]: both HOST memory whatever `mem` says (they are small, checked
+ * on the host and uploaded once per call); both NULL: no edges, out_hist is then NULL or receives the single bucket.  `mem`
+ * governs x / pids / the outputs as everywhere.  Both arrays need to stay valid only until the call returns, also where the call
+ * itself returns before the device has finished (device memory, no timing): n_edges and the edges are read on the host inside
+ * the call, and the upload is a stream-ordered copy from pageable memory, whose source the runtime has staged when the copy call
+ * returns -- the rule every host-to-device copy of this library relies on (qk_store.hip, qk_attr.hip).  That copy may make the
+ * host wait once per call, behind the coarse search and in front of the first emission; nothing waits between passes.
+ * Every int64 is a legal value.  The result is a pure function of the store, the columns and the call: only integer additions,
+ * minima and maxima decide it.  Liveness as for facet counts (the per-row values grouped search keeps).
+ * Limits: n_cols < 1, a negative n_edges[c], edges that are not strictly ascending, a NULL column, one of edges / n_edges NULL
+ * while the other names edges: QK_ERR_INVALID; n_cols > QK_MAX_FACET_COLS, n_edges[c] > QK_MAX_FACET_EDGES: QK_ERR_UNSUPPORTED.
+ * Q == 0: QK_OK.  No lists probed: every count is zero, min / max hold their identities.
+ * Inside: the key-emission scan of range search (the same launches, the same pass size), then per pass of queries ONE sweep,
+ * k_facet_stats, over all columns and all queries of the pass -- no table sized by hits, no group loop, no selection: the
+ * decomposition and the hit test of k_facet_hits; every lane keeps per column min / max (on sign-flipped words) and two sum
+ * accumulators in registers (the low 32 bits of every value added unsigned into 64 bits, the high 32 bits added signed into 64
+ * bits: below 2^30 hits neither can overflow, together they are the exact sum); a hit's bucket comes from a branch-free binary
+ * search (8 steps) over the call's edges in LDS and is counted by an LDS atomic add; behind its last slice a workgroup reduces
+ * across the wave (shuffles), across its four waves (LDS) and issues one global atomic per statistic (add / min / max) and per
+ * non-zero bucket.  k_facet_stats_finish widens the counters, undoes the sign flip, combines the sum halves with the carry and
+ * writes the outputs.  No kernel waits or spins (qk_facet.hip, second part).
+ * Workspace: keys as for range search (queries per pass = 2^29 / per_query_ub; a query whose keys exceed 2^30 is
+ * QK_ERR_UNSUPPORTED); next to them 4 + 36 * n_cols bytes of accumulators per query of a pass, plus 4 * n_cols * hist_stride when
+ * a histogram with edges is asked for; a pass is shortened only where these would exceed QK_GROUPED_PASS_BYTES.  Nothing
+ * synchronises between passes.
+ * timing: coarse_ms and scan_ms as for range search, merge_ms = sweep + finish (of the last pass), n_items = the number of query
+ * passes.  qk_ctx_last_scan_kernel names "k_scan (facet stats)" / "k_scan_wide (facet stats)".  There is no form for
+ * qk_search_aps, the device group, per-query filter tables or adaptive probing. */
+#define QK_MAX_FACET_EDGES 255
+QK_API int qk_facet_stats_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int metric,
+                                 float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, const int64_t *edges,
+                                 const int *n_edges, int64_t *out_count, int64_t *out_missing, int64_t *out_min, int64_t *out_max,
+                                 int64_t *out_sum_lo, int64_t *out_sum_hi, int64_t *out_hist, int64_t *out_total, int mem,
+                                 qk_timing *timing);
+QK_API int qk_facet_stats_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric,
+                               float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, const int64_t *edges,
+                               const int *n_edges, int64_t *out_count, int64_t *out_missing, int64_t *out_min, int64_t *out_max,
+                               int64_t *out_sum_lo, int64_t *out_sum_hi, int64_t *out_hist, int64_t *out_total, int mem,
+                               qk_timing *timing);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

@@ -133,6 +133,11 @@ SIGNATURES = {
                         C.POINTER(QkTiming)]),
     "qk_facet_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _int,
                       C.POINTER(QkTiming)]),
+    # facet statistics: (.., radius, filter, facet_by, n_cols, edges, n_edges, count, missing, min, max, sum_lo, sum_hi, hist, total, mem, timing)
+    "qk_facet_stats_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, _vp, _vp, _int, _vp, _vp] + [_vp] * 8 +
+                              [_int, C.POINTER(QkTiming)]),
+    "qk_facet_stats_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _vp, _int, _vp, _vp] + [_vp] * 8 +
+                            [_int, C.POINTER(QkTiming)]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
     "qk_filter_create_expr": (_int, [_vp, C.POINTER(QkExprClause), C.POINTER(_int), _int, C.POINTER(_vp)]),

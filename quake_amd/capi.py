@@ -570,6 +570,55 @@ class Context:
                                      *[_ptr(o) for o in out], mem, C.byref(t) if timing else None))
         return (*out, timing_dict(t)) if timing else tuple(out)
 
+    # ---- facet statistics -------------------------------------------------------------------------------
+    @staticmethod
+    def _facet_stats_args(x, Q, attrs, edges):
+        from .where import lower_edges
+        cols = list(attrs) if isinstance(attrs, (list, tuple)) else [attrs]
+        C_ = len(cols)
+        harr = (C.c_void_p * max(C_, 1))(*[a.h if a is not None else None for a in cols])
+        flat, n_edges = lower_edges(["column %d" % c for c in range(C_)], edges, "[facet_stats]")
+        earr = (C.c_int64 * max(len(flat), 1))(*flat) if edges is not None else None
+        narr = (C.c_int * max(C_, 1))(*n_edges) if edges is not None else None
+        hs = 1 + max(n_edges, default=0)
+        # (the library refuses a count outside its limits before it writes: the buffers only have to exist)
+        out = [_empty_like_mem((C_, Q), np.int64, x) for _ in range(6)]
+        out += [_empty_like_mem((C_, Q, hs), np.int64, x), _empty_like_mem((Q,), np.int64, x)]
+        return harr, C_, earr, narr, out
+
+    def facet_stats_search(self, parent, store, x, nprobe, radius, metric, attrs, edges=None, filter=None, timing=False):
+        """qk_facet_stats_search: per query, count / missing / min / max / exact sum / histogram of the Attr columns `attrs` (one
+        Attr or a list of up to 4) over the hits of range_search with the same arguments.  edges: None, one ascending sequence of
+        integers applied to every column, or a list with one sequence (or None) per column (quake_amd/where.py: lower_edges).
+        Returns (count, missing, min, max, sum_lo, sum_hi [C, Q], hist [C, Q, 1 + the most edges of a column], total [Q][, timing])
+        on x's device; the sum of (c, q) is sum_hi * 2**64 + (sum_lo mod 2**64), and min / max of a count of 0 are INT64_MAX /
+        INT64_MIN."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        harr, C_, earr, narr, out = self._facet_stats_args(x, Q, attrs, edges)
+        t = QkTiming()
+        check(self.lib.qk_facet_stats_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe),
+                                             metric_code(metric), float(radius), filter.h if filter is not None else None, harr, C_,
+                                             earr, narr, *[_ptr(o) for o in out], mem, C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
+    def facet_stats_scan(self, store, x, pids, radius, metric, attrs, edges=None, filter=None, timing=False):
+        """qk_facet_stats_scan: facet_stats_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / absent / empty
+        lists contribute nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        if pids.ndim == 1:
+            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
+                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        mem = _mem_of(x, pids)
+        harr, C_, earr, narr, out = self._facet_stats_args(x, Q, attrs, edges)
+        t = QkTiming()
+        check(self.lib.qk_facet_stats_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]),
+                                           metric_code(metric), float(radius), filter.h if filter is not None else None, harr, C_,
+                                           earr, narr, *[_ptr(o) for o in out], mem, C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):
         """recall-target search (adaptive partition scanning).  Returns (ids, dist, nscanned[, timing])."""

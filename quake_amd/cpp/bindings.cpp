@@ -4,6 +4,8 @@
 #include <pybind11/stl.h>
 #include <torch/extension.h>
 
+#include <algorithm>
+#include <limits>
 #include <sstream>
 
 #include "quake_index.h"
@@ -96,6 +98,81 @@ std::vector<WhereTerm> parse_where(const py::object &where) {
     }
     return out;
 }
+
+// where.py's _is_seq: indexable and sized, no string, no dict (not PySequence_Check: a tensor is indexable through the mapping
+// protocol only)
+bool is_edge_seq(const py::handle &v) {
+    return !py::isinstance<py::str>(v) && !py::isinstance<py::bytes>(v) && !py::isinstance<py::dict>(v) && py::hasattr(v, "__getitem__") &&
+           py::hasattr(v, "__len__");
+}
+
+// the edges of one column of facet_stats: None or a sequence of Python integers (where.py's _edge_list)
+std::vector<WhereOperand> parse_edge_list(py::object v, const std::string &name) {
+    std::vector<WhereOperand> out;
+    if (v.is_none()) return out;
+    if (py::hasattr(v, "tolist")) v = v.attr("tolist")();  // (a tensor, an array)
+    if (!is_edge_seq(v))
+        throw std::runtime_error("[QuakeIndex::facet_stats()] the edges of '" + name + "' must be a sequence of integers, got " +
+                                 std::string(py::repr(v)));
+    for (py::handle e : py::reinterpret_borrow<py::sequence>(v)) {
+        if (PyBool_Check(e.ptr()) || !PyIndex_Check(e.ptr()))
+            throw std::runtime_error("[QuakeIndex::facet_stats()] edges: operands must be integers, got " + std::string(py::repr(e)));
+        out.push_back(parse_operand(e, false));
+    }
+    return out;
+}
+
+// `edges` of facet_stats -> one operand list per column: None, one sequence for every column, a dict name -> sequence, or a list
+// with one sequence or None per column (where.py's lower_edges)
+std::vector<std::vector<WhereOperand>> parse_edges(py::object edges, const std::vector<std::string> &names) {
+    std::vector<std::vector<WhereOperand>> per(names.size());
+    if (edges.is_none()) return per;
+    if (py::isinstance<py::dict>(edges)) {
+        py::dict d = edges.cast<py::dict>();
+        for (auto kv : d) {
+            const std::string k = py::str(kv.first).cast<std::string>();
+            if (std::find(names.begin(), names.end(), k) == names.end())
+                throw std::runtime_error("[QuakeIndex::facet_stats()] edges names '" + k + "', which is not one of the facet columns");
+        }
+        for (size_t c = 0; c < names.size(); c++)
+            if (d.contains(py::str(names[c]))) per[c] = parse_edge_list(d[py::str(names[c])], names[c]);
+        return per;
+    }
+    if (py::hasattr(edges, "tolist")) edges = edges.attr("tolist")();
+    bool per_column = is_edge_seq(edges) && py::len(edges) > 0;
+    std::vector<py::object> s;
+    if (per_column)
+        for (py::handle e : edges) {
+            per_column = per_column && (e.is_none() || is_edge_seq(e));
+            s.push_back(py::reinterpret_borrow<py::object>(e));
+        }
+    if (per_column) {
+        if (s.size() != names.size())
+            throw std::runtime_error("[QuakeIndex::facet_stats()] edges has " + std::to_string(s.size()) + " per-column entries for " +
+                                     std::to_string(names.size()) + " columns");
+        for (size_t c = 0; c < names.size(); c++) per[c] = parse_edge_list(s[c], names[c]);
+        return per;
+    }
+    for (size_t c = 0; c < names.size(); c++) per[c] = parse_edge_list(edges, names[c]);
+    return per;
+}
+
+// sum_hi * 2^64 + (sum_lo mod 2^64) of every (column, query) as Python ints: [C][Q]
+py::list facet_stats_sums(const FacetStatsResult &r) {
+    Tensor lo = r.sum_lo.cpu().contiguous(), hi = r.sum_hi.cpu().contiguous();
+    const int64_t C = lo.size(0), Q = lo.size(1);
+    const int64_t *pl = lo.data_ptr<int64_t>(), *ph = hi.data_ptr<int64_t>();
+    py::list out;
+    for (int64_t c = 0; c < C; c++) {
+        py::list row;
+        for (int64_t q = 0; q < Q; q++) {
+            py::object h = py::int_(ph[c * Q + q]).attr("__lshift__")(64);
+            row.append(h.attr("__add__")(py::int_((unsigned long long)pl[c * Q + q])));
+        }
+        out.append(row);
+    }
+    return out;
+}
 }  // namespace
 
 PYBIND11_MODULE(_bindings, m) {
@@ -163,6 +240,20 @@ PYBIND11_MODULE(_bindings, m) {
              "extension: per query, the value counts of the attribute columns `facet_by` (a name or a list of names) over the vectors "
              "range_search returns for the same arguments (radius None: every vector of the probed partitions): values, counts, "
              "distinct, missing, totals")
+        .def("facet_stats",
+             [](QuakeIndex &self, Tensor x, py::object facet_by, shared_ptr<SearchParams> sp, py::object radius, py::object edges) {
+                 std::vector<std::string> names;
+                 if (py::isinstance<py::str>(facet_by)) names.push_back(facet_by.cast<std::string>());
+                 else names = facet_by.cast<std::vector<std::string>>();
+                 std::optional<float> r;
+                 if (!radius.is_none()) r = radius.cast<float>();
+                 // (the edges are parsed and checked where the Python mirror checks them: behind the refusals and the column lookup)
+                 return self.facet_stats(x, names, sp, r, FacetEdgesFn([&]() { return lower_edges(names, parse_edges(edges, names)); }));
+             },
+             py::arg("x"), py::arg("facet_by"), py::arg("search_params"), py::arg("radius") = py::none(), py::arg("edges") = py::none(),
+             "extension: per query, count / missing / min / max / exact sum / histogram of the attribute columns `facet_by` (a name or "
+             "a list of names) over the vectors range_search returns for the same arguments; edges: None, one ascending sequence of "
+             "integers for all columns, or a dict name -> sequence")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)
@@ -377,6 +468,39 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("totals", &FacetResult::totals)
         .def_readwrite("columns", &FacetResult::columns)
         .def_readwrite("timing_info", &FacetResult::timing_info);
+
+    py::class_<FacetStatsResult, std::shared_ptr<FacetStatsResult>>(m, "FacetStatsResult")
+        .def(py::init<>())
+        .def_readwrite("count", &FacetStatsResult::count)
+        .def_readwrite("missing", &FacetStatsResult::missing)
+        .def_readwrite("min", &FacetStatsResult::min)
+        .def_readwrite("max", &FacetStatsResult::max)
+        .def_readwrite("sum_lo", &FacetStatsResult::sum_lo)
+        .def_readwrite("sum_hi", &FacetStatsResult::sum_hi)
+        .def_readwrite("histogram", &FacetStatsResult::histogram)
+        .def_readwrite("totals", &FacetStatsResult::totals)
+        .def_readwrite("columns", &FacetStatsResult::columns)
+        .def_readwrite("edges", &FacetStatsResult::edges)
+        .def_readwrite("timing_info", &FacetStatsResult::timing_info)
+        .def("sums", &facet_stats_sums, "[C][Q] exact Python ints: sum_hi * 2**64 + (sum_lo mod 2**64)")
+        .def("means",
+             [](const FacetStatsResult &r) {  // float64 [C, Q], NaN where count == 0 (Python's own int / int division)
+                 py::list sums = facet_stats_sums(r), rows;
+                 Tensor cnt = r.count.cpu().contiguous();
+                 const int64_t C = cnt.size(0), Q = cnt.size(1);
+                 const int64_t *pc = cnt.data_ptr<int64_t>();
+                 for (int64_t c = 0; c < C; c++) {
+                     py::list row, srow = sums[c].cast<py::list>();
+                     for (int64_t q = 0; q < Q; q++) {
+                         if (pc[c * Q + q] == 0) row.append(py::float_(std::numeric_limits<double>::quiet_NaN()));
+                         else row.append(srow[q].attr("__truediv__")(py::int_(pc[c * Q + q])));
+                     }
+                     rows.append(row);
+                 }
+                 py::object np = py::module_::import("numpy");
+                 return np.attr("array")(rows, py::arg("dtype") = "float64").attr("reshape")(C, -1);
+             },
+             "[C, Q] float64 numpy array of sum / count, NaN where count == 0");
 
     py::class_<SearchCursor, std::shared_ptr<SearchCursor>>(m, "SearchCursor")
         .def(py::init([](py::object keys, py::object ids) {  // (None: left undefined -- search_after refuses such a cursor)

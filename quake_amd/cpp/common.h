@@ -4,6 +4,7 @@
 #pragma once
 #include <torch/torch.h>
 
+#include <functional>
 #include <memory>
 #include <optional>
 #include <string>
@@ -179,6 +180,28 @@ struct FacetResult {
     Tensor missing;
     Tensor totals;
     std::vector<std::string> columns;
+    shared_ptr<SearchTimingInfo> timing_info;
+};
+
+// extension (QuakeIndex::facet_stats): per column and query, over the query's range hits: count / missing / min / max / sum_lo /
+// sum_hi [C, Q] (min / max of a count of 0 are INT64_MAX / INT64_MIN; the exact sum is sum_hi * 2^64 + (sum_lo mod 2^64)),
+// histogram [C, Q, 1 + the most edges of a column] (bucket b of a value v = the number of the column's edges <= v), totals [Q],
+// columns the C column names, edges the C edge lists
+// the edges of a facet_stats call, one checked list per column, produced when the call has passed its refusals and found its
+// columns -- the point at which the Python mirror lowers them -- so that both mirrors raise the same error for the same call
+using FacetEdgesFn = std::function<std::vector<std::vector<int64_t>>()>;
+
+struct FacetStatsResult {
+    Tensor count;
+    Tensor missing;
+    Tensor min;
+    Tensor max;
+    Tensor sum_lo;
+    Tensor sum_hi;
+    Tensor histogram;
+    Tensor totals;
+    std::vector<std::string> columns;
+    std::vector<std::vector<int64_t>> edges;
     shared_ptr<SearchTimingInfo> timing_info;
 };
 

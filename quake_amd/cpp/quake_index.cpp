@@ -158,6 +158,44 @@ shared_ptr<FacetResult> QuakeIndex::facet_counts(Tensor x, const std::vector<std
     return query_coordinator_->facet_counts(x, cols, facet_by, sp, radius, n_values);
 }
 
+std::vector<std::vector<int64_t>> lower_edges(const std::vector<std::string> &names, const std::vector<std::vector<WhereOperand>> &edges) {
+    const std::string who = "[QuakeIndex::facet_stats()]";
+    if (edges.size() != names.size())
+        throw std::runtime_error(who + " edges has " + std::to_string(edges.size()) + " per-column entries for " + std::to_string(names.size()) +
+                                 " columns");
+    std::vector<std::vector<int64_t>> out(names.size());
+    for (size_t c = 0; c < names.size(); c++) {
+        const std::vector<WhereOperand> &e = edges[c];
+        if (e.size() > QK_MAX_FACET_EDGES)
+            throw std::runtime_error(who + " '" + names[c] + "' has " + std::to_string(e.size()) + " edges, at most " +
+                                     std::to_string(QK_MAX_FACET_EDGES) + " are supported");
+        for (size_t i = 0; i < e.size(); i++) {
+            if (e[i].over) throw std::runtime_error(who + " edge " + std::to_string(i) + " of '" + names[c] + "' does not fit int64");
+            if (i && e[i - 1].v >= e[i].v)
+                throw std::runtime_error(who + " the edges of '" + names[c] + "' are not strictly ascending (edge " + std::to_string(i) + ")");
+            out[c].push_back(e[i].v);
+        }
+    }
+    return out;
+}
+
+shared_ptr<FacetStatsResult> QuakeIndex::facet_stats(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> sp,
+                                                     std::optional<float> radius, const std::vector<std::vector<int64_t>> &edges) {
+    return facet_stats(x, facet_by, sp, radius, FacetEdgesFn([&edges]() { return edges; }));
+}
+
+shared_ptr<FacetStatsResult> QuakeIndex::facet_stats(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> sp,
+                                                     std::optional<float> radius, const FacetEdgesFn &edges_fn) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::facet_stats()] No query coordinator. Did you build the index?");
+    std::vector<qk_attr *> cols(facet_by.size(), nullptr);
+    if (partition_manager_ && partition_manager_->has_lists() && partition_manager_->store() && partition_manager_->store() == attrs_store_)
+        for (size_t c = 0; c < facet_by.size(); c++) {
+            auto it = attrs_.find(facet_by[c]);
+            if (it != attrs_.end()) cols[c] = it->second;
+        }
+    return query_coordinator_->facet_stats(x, cols, facet_by, sp, radius, edges_fn);
+}
+
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?");
     qk_store *s = partition_manager_->store();

@@ -41,6 +41,11 @@ std::vector<LoweredClause> lower_where(const std::vector<WhereTerm> &where);
 // becomes a set clause, a value outside int64 is dropped
 std::vector<std::vector<LoweredClause>> lower_expr(const std::vector<std::vector<WhereTerm>> &any_of);
 
+// the histogram edges of facet_stats (where.py's lower_edges: same rules, same errors as std::runtime_error): one operand list per
+// column of `names` (empty: no edges) -> the lists inside int64; refuses more than QK_MAX_FACET_EDGES edges, an edge outside int64,
+// edges that are not strictly ascending
+std::vector<std::vector<int64_t>> lower_edges(const std::vector<std::string> &names, const std::vector<std::vector<WhereOperand>> &edges);
+
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
     shared_ptr<QuakeIndex> parent_;
@@ -96,6 +101,13 @@ public:
     // same arguments (radius unset: every vector of the probed partitions), the n_values most frequent per column (qk_facet_search)
     shared_ptr<FacetResult> facet_counts(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> search_params,
                                          std::optional<float> radius = std::nullopt, int n_values = 10);
+    // extension: count, min, max, exact sum and a histogram with the given bucket edges (one checked list per column, lower_edges)
+    // of up to QK_MAX_FACET_COLS attribute columns over the same hits (qk_facet_stats_search)
+    shared_ptr<FacetStatsResult> facet_stats(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> search_params,
+                                             std::optional<float> radius, const std::vector<std::vector<int64_t>> &edges);
+    // the same with the edges produced on demand, behind the call's refusals (the binding: Python objects are parsed there)
+    shared_ptr<FacetStatsResult> facet_stats(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> search_params,
+                                             std::optional<float> radius, const FacetEdgesFn &edges_fn);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

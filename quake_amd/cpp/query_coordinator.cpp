@@ -714,6 +714,103 @@ shared_ptr<FacetResult> QueryCoordinator::facet_counts(Tensor x, const std::vect
     return res;
 }
 
+shared_ptr<FacetStatsResult> QueryCoordinator::facet_stats(Tensor x, const std::vector<qk_attr *> &cols, const std::vector<std::string> &names,
+                                                          shared_ptr<SearchParams> sp, std::optional<float> radius_opt,
+                                                          const FacetEdgesFn &edges_fn) {
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::facet_stats] partition_manager_ is null.");
+    if (names.size() < 1 || names.size() > QK_MAX_FACET_COLS)
+        throw std::runtime_error("[QuakeIndex::facet_stats()] facet_by must name between 1 and " + std::to_string(QK_MAX_FACET_COLS) + " columns");
+    if (!sp->filters.empty() || sp->query_filter.defined())
+        throw std::runtime_error("[QuakeIndex::facet_stats()] SearchParams.filters / query_filter (one filter per query) are not "
+                                 "supported by facet_stats");
+    if (sp->filters_exact_rows != 0)
+        throw std::runtime_error("[QuakeIndex::facet_stats()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
+                                 "supported by facet_stats");
+    if (sp->filter_exact_rows != 0)
+        throw std::runtime_error("[QuakeIndex::facet_stats()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                                 "facet_stats");
+    if (sp->max_nprobe > 0)
+        throw std::runtime_error("[QuakeIndex::facet_stats()] SearchParams.max_nprobe (adaptive probing) is not supported by facet_stats");
+    if (sp->recall_target > 0.0f) throw std::runtime_error("[QuakeIndex::facet_stats()] facet_stats is not supported with recall_target > 0");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group()) throw std::runtime_error("[QuakeIndex::facet_stats()] facet_stats is not supported with num_workers > 0");
+    if (!store) throw std::runtime_error("[QueryCoordinator::facet_stats] partitions are not initialized.");
+    for (size_t c = 0; c < names.size(); c++)
+        if (!cols[c]) throw std::runtime_error("[QuakeIndex::facet_stats()] unknown attribute column '" + names[c] + "'");
+    const std::vector<std::vector<int64_t>> edges = edges_fn();  // (here, as in the Python mirror: an edge error comes behind these)
+    if (edges.size() != names.size()) throw std::runtime_error("[QuakeIndex::facet_stats()] edges needs one list per facet column");
+    qk_filter *flt = nullptr;
+    if (sp->filter) {
+        if (!sp->filter->h) throw std::runtime_error("[QuakeIndex::facet_stats()] SearchParams.filter must come from make_filter()");
+        if (sp->filter->owner != store) throw std::runtime_error("[QuakeIndex::facet_stats()] the filter was made for another index");
+        flt = sp->filter->h;
+    }
+    const float inf = std::numeric_limits<float>::infinity();
+    const float radius = radius_opt ? *radius_opt : ((int)metric_ == QK_METRIC_IP ? -inf : inf);
+    if (radius != radius) throw std::runtime_error("[QuakeIndex::facet_stats()] the radius is NaN");
+    const int64_t C = (int64_t)names.size();
+    std::vector<int64_t> flat;
+    std::vector<int> n_edges;
+    int64_t hs = 1;
+    for (int64_t c = 0; c < C; c++) {
+        const std::vector<int64_t> &e = edges[c];
+        flat.insert(flat.end(), e.begin(), e.end());
+        n_edges.push_back((int)e.size());
+        hs = std::max<int64_t>(hs, 1 + (int64_t)e.size());
+    }
+    auto res = std::make_shared<FacetStatsResult>();
+    res->columns = names;
+    res->edges = edges;
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->search_params = sp;
+    ti->n_clusters = partition_manager_->nlist();
+    if (!x.defined() || x.size(0) == 0) {
+        for (Tensor *t : {&res->count, &res->missing, &res->min, &res->max, &res->sum_lo, &res->sum_hi}) *t = torch::zeros({C, 0}, torch::kInt64);
+        res->histogram = torch::zeros({C, 0, hs}, torch::kInt64);
+        res->totals = torch::zeros({0}, torch::kInt64);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x);
+    BoundToTorchStream bound(ctx, xq);
+    const int64_t Q = xq.size(0);
+    const int nprobe = std::max(sp->nprobe, 1);
+    const int mem = on_dev ? QK_MEM_DEVICE : QK_MEM_HOST;
+    ti->n_queries = Q;
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
+    for (Tensor *t : {&res->count, &res->missing, &res->min, &res->max, &res->sum_lo, &res->sum_hi}) *t = torch::empty({C, Q}, i64);
+    res->histogram = torch::empty({C, Q, hs}, i64);
+    res->totals = torch::empty({Q}, i64);
+    qk_check(qk_facet_stats_search(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, (int)metric_, radius, flt,
+                                   cols.data(), (int)C, flat.data(), n_edges.data(), res->count.data_ptr<int64_t>(),
+                                   res->missing.data_ptr<int64_t>(), res->min.data_ptr<int64_t>(), res->max.data_ptr<int64_t>(),
+                                   res->sum_lo.data_ptr<int64_t>(), res->sum_hi.data_ptr<int64_t>(), res->histogram.data_ptr<int64_t>(),
+                                   res->totals.data_ptr<int64_t>(), mem, &tm));
+    ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    if (parent_) {
+        ti->parent_info = std::make_shared<SearchTimingInfo>();
+        ti->parent_info->n_queries = Q;
+        ti->parent_info->n_clusters = 1;
+        ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
+    }
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
 shared_ptr<SearchResult> QueryCoordinator::scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> sp) {  // :659-673
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::scan_partitions] partition_manager_ is null.");
     if (!x.defined() || x.size(0) == 0) return empty_result(sp);

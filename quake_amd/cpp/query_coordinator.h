@@ -47,6 +47,11 @@ public:
     // extension (qk_facet_search): value counts of `cols` -- columns of this index's store, nullptr: unknown -- over the range hits
     shared_ptr<FacetResult> facet_counts(Tensor x, const std::vector<qk_attr *> &cols, const std::vector<std::string> &names,
                                          shared_ptr<SearchParams> search_params, std::optional<float> radius, int n_values);
+    // extension (qk_facet_stats_search): count / missing / min / max / exact sum / histogram of `cols` over the range hits; edges_fn:
+    // one checked list per column (lower_edges), asked for behind the refusals and the column lookup
+    shared_ptr<FacetStatsResult> facet_stats(Tensor x, const std::vector<qk_attr *> &cols, const std::vector<std::string> &names,
+                                             shared_ptr<SearchParams> search_params, std::optional<float> radius,
+                                             const FacetEdgesFn &edges_fn);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

@@ -21,6 +21,8 @@
 // No thread waits for another and every loop is bounded.  Only integer additions decide a counter, so the result is a pure function
 // of the store, the columns and the call.  The value whose bits are all ones (-1) is the table's empty marker: it owns the slot
 // behind the used ones.
+// Second part (behind facet_run): facet statistics -- count, min, max, exact sum and fixed-edge histograms over the same hits, one
+// sweep per pass and no table (k_facet_stats, k_facet_stats_finish).
 #include "qk_attr.h"
 
 #include <cstring>
@@ -546,6 +548,443 @@ int facet_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const
     return QK_OK;
 }
 
+// ---- second part: facet statistics (include/quake_hip.h, "facet statistics") ----------------------------------------
+// Count, minimum, maximum, exact sum and a histogram with fixed bucket edges of every column over the same hits.  Fixed edges need no
+// table sized by hits, no group loop over a pass's queries and no selection: per pass ONE sweep over the emitted keys, k_facet_stats,
+// for all columns and all queries, then k_facet_stats_finish.  The accumulators of a pass -- [total] [missing] [sum_lo] [sum_hi]
+// [max] [min] [bins] -- lie in the caller's bytes of qk_emit_passes; all start at zero bytes except min, which starts at all ones
+// (two memsets on the stream, in front of the emission).  min / max work on sign-flipped words (v ^ 2^63 orders the signed values
+// as unsigned ones), so their identities are all ones and zero.  The sum of a query's values is kept as two 64-bit words: SL, the
+// low 32 bits of every value added as unsigned, and SH, the high 32 bits added as signed; a query has fewer than 2^30 keys, so
+// SL < 2^62 and |SH| < 2^61, and SH * 2^32 + SL is the exact sum.
+//
+// QK_FACET_STATS_HIT_ATOMICS: 0 (shipped): a lane accumulates in registers, a workgroup reduces through shuffles and LDS and issues
+// one global atomic per statistic; 1: every hit issues its global atomics itself (min, max, two adds per column) -- the variant
+// DESIGN.md 5.17 prices.  The histogram goes through the workgroup's LDS bins in both.
+#ifndef QK_FACET_STATS_HIT_ATOMICS
+#define QK_FACET_STATS_HIT_ATOMICS 0
+#endif
+
+constexpr unsigned long long FS_SIGN = 0x8000000000000000ull;
+constexpr int FS_BINS = QK_MAX_FACET_EDGES + 1;
+
+struct FacetStatsParams {
+    FacetParams F;              // keys, segments, mask, columns, total, missing, nq, P, Sg, C, key interval (the tables are unused)
+    const int64_t *edges;       // the call's edges, column after column (device)
+    int e_off[QK_MAX_FACET_COLS], n_edges[QK_MAX_FACET_COLS];
+    int hist_stride;            // of bins; 0: no column has edges to search (no LDS bins, no global ones)
+    unsigned long long *sum_lo, *sum_hi, *vmax, *vmin;  // [C][nq]
+    uint32_t *bins;             // [C][nq][hist_stride]
+};
+
+__device__ __forceinline__ unsigned long long fs_wave_min(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, (unsigned long long)__shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ unsigned long long fs_wave_max(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned long long)__shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ unsigned long long fs_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (unsigned long long)__shfl_xor(v, off);
+    return v;
+}
+
+// b(v) = |{i : e_i <= v}| over E <= 255 ascending edges in LDS: the branch-free binary search of k_filter_build_expr's set
+// membership, 8 steps; the probe index stays below 255 and is read only where it is below E
+__device__ __forceinline__ int fs_bucket(const long long *ed, int E, long long v) {
+    int b = 0;
+#pragma unroll
+    for (int step = 128; step > 0; step >>= 1) {
+        const int i = b + step - 1;
+        const bool le = i < E && ed[min(i, E - 1)] <= v;
+        b += le ? step : 0;
+    }
+    return b;
+}
+
+// The decomposition of k_facet_hits: blockIdx.x = query * Sg + g, slices of FC_SLICE keys, whole waves per step.  Nothing global is
+// written inside the key loop (QK_FACET_STATS_HIT_ATOMICS=0); no thread waits for another, every loop is bounded
+__global__ __launch_bounds__(256) void k_facet_stats(FacetStatsParams S) {
+    __shared__ long long s_edges[QK_MAX_FACET_COLS * QK_MAX_FACET_EDGES];
+    __shared__ uint32_t s_bins[QK_MAX_FACET_COLS * FS_BINS];
+    __shared__ unsigned long long s_red[4][QK_MAX_FACET_COLS][4];
+    __shared__ uint32_t s_cnt[4][QK_MAX_FACET_COLS + 1];
+    const FacetParams &F = S.F;
+    const int64_t q = blockIdx.x / F.Sg;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t *pbase = F.pair_base + q * F.P;
+    const int64_t *qpids = F.pids ? F.pids + q * F.P : nullptr;
+    const int64_t beg = pbase[0], end = pbase[F.P];
+    const int64_t first = beg + (int64_t)(blockIdx.x - q * F.Sg) * FC_SLICE;
+    if (first >= end) return;  // (the whole workgroup: it has no slice)
+    const bool bins = S.hist_stride > 0;
+    if (bins) {
+#pragma unroll
+        for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+            if (c >= F.C) break;
+            for (int i = tid; i < S.n_edges[c]; i += 256) s_edges[c * QK_MAX_FACET_EDGES + i] = S.edges[S.e_off[c] + i];
+        }
+        for (int i = tid; i < QK_MAX_FACET_COLS * FS_BINS; i += 256) s_bins[i] = 0u;
+        __syncthreads();
+    }
+    uint32_t n_total = 0, n_missing[QK_MAX_FACET_COLS] = {0, 0, 0, 0};  // (wave-uniform)
+    unsigned long long vmin[QK_MAX_FACET_COLS], vmax[QK_MAX_FACET_COLS], sl[QK_MAX_FACET_COLS], sh[QK_MAX_FACET_COLS];
+#pragma unroll
+    for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+        vmin[c] = ~0ull;
+        vmax[c] = sl[c] = sh[c] = 0ull;
+    }
+    for (int64_t s0 = first; s0 < end; s0 += (int64_t)F.Sg * FC_SLICE) {
+        const int64_t lim = min(end, s0 + FC_SLICE);
+        for (int64_t w0 = s0 + (tid & ~63); w0 < lim; w0 += 256) {
+            int64_t row;
+            const bool hit = facet_hit(F, pbase, qpids, w0 + lane, lim, &row);
+            const uint64_t hm = __ballot(hit);
+            if (hm == 0) continue;
+            n_total += __popcll(hm);
+#pragma unroll
+            for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+                if (c >= F.C) break;
+                const bool has = hit && ((F.has[c][row >> 4] >> (row & 15)) & 1);
+                n_missing[c] += __popcll(hm) - __popcll(__ballot(has));
+                if (has) {
+                    const long long v = (long long)F.rowval[c][row];
+                    const unsigned long long u = (unsigned long long)v ^ FS_SIGN;
+                    const unsigned long long lo = (unsigned long long)(uint32_t)v, hi = (unsigned long long)(v >> 32);  // (hi: sign-extended)
+#if QK_FACET_STATS_HIT_ATOMICS
+                    const int64_t a = (int64_t)c * F.nq + q;
+                    atomicMin(&S.vmin[a], u);
+                    atomicMax(&S.vmax[a], u);
+                    atomicAdd(&S.sum_lo[a], lo);
+                    atomicAdd(&S.sum_hi[a], hi);
+#else
+                    vmin[c] = min(vmin[c], u);
+                    vmax[c] = max(vmax[c], u);
+                    sl[c] += lo;
+                    sh[c] += hi;
+#endif
+                    if (bins && S.n_edges[c] > 0)
+                        atomicAdd(&s_bins[c * FS_BINS + fs_bucket(s_edges + c * QK_MAX_FACET_EDGES, S.n_edges[c], v)], 1u);
+                }
+            }
+        }
+    }
+    // ---- the workgroup's statistics: across the wave by shuffles, across the four waves through LDS, one global atomic each
+#pragma unroll
+    for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+        if (c >= F.C) break;
+        const unsigned long long a = fs_wave_min(vmin[c]), b = fs_wave_max(vmax[c]), l = fs_wave_sum(sl[c]), h = fs_wave_sum(sh[c]);
+        if (lane == 0) {
+            s_red[wave][c][0] = a;
+            s_red[wave][c][1] = b;
+            s_red[wave][c][2] = l;
+            s_red[wave][c][3] = h;
+            s_cnt[wave][1 + c] = n_missing[c];
+        }
+    }
+    if (lane == 0) s_cnt[wave][0] = n_total;
+    __syncthreads();  // (also: every LDS add of the key loop has landed)
+    if (tid < 4 * F.C) {
+        const int c = tid >> 2, k = tid & 3;
+        const int64_t a = (int64_t)c * F.nq + q;
+        const unsigned long long w0 = s_red[0][c][k], w1 = s_red[1][c][k], w2 = s_red[2][c][k], w3 = s_red[3][c][k];
+        if (k == 0) {
+            const unsigned long long m = min(min(w0, w1), min(w2, w3));
+            if (m != ~0ull) atomicMin(&S.vmin[a], m);
+        } else if (k == 1) {
+            const unsigned long long m = max(max(w0, w1), max(w2, w3));
+            if (m != 0ull) atomicMax(&S.vmax[a], m);
+        } else {
+            const unsigned long long m = w0 + w1 + w2 + w3;
+            if (m != 0ull) atomicAdd(k == 2 ? &S.sum_lo[a] : &S.sum_hi[a], m);
+        }
+    } else if (tid >= 64 && tid < 64 + 1 + F.C) {
+        const int k = tid - 64;
+        const uint32_t n = s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k];
+        if (n) atomicAdd(k == 0 ? &F.total[q] : &F.missing[(int64_t)(k - 1) * F.nq + q], n);
+    }
+    if (bins) {
+        for (int i = tid; i < F.C * FS_BINS; i += 256) {
+            const int c = i / FS_BINS, b = i - c * FS_BINS;
+            const uint32_t n = s_bins[i];
+            if (n) atomicAdd(&S.bins[((int64_t)c * F.nq + q) * S.hist_stride + b], n);  // (n > 0: b <= n_edges[c] < hist_stride)
+        }
+    }
+}
+
+struct FacetStatsFinishParams {
+    const uint32_t *total, *missing;                         // [nq], [C][nq]
+    const unsigned long long *sum_lo, *sum_hi, *vmax, *vmin;  // [C][nq]
+    const uint32_t *bins;                                    // [C][nq][bin_stride], or nullptr: no column has edges
+    int64_t nq, q0, Q;
+    int C, bin_stride, hist_stride;                           // hist_stride: of out_hist
+    int n_edges[QK_MAX_FACET_COLS];
+    int64_t *out_count, *out_missing, *out_min, *out_max, *out_sum_lo, *out_sum_hi;  // [C][Q] or nullptr
+    int64_t *out_hist;                                       // [C][Q][hist_stride] or nullptr
+    int64_t *out_total;                                      // [Q]
+};
+
+// thread i < C * nq: the statistics of (column, query) i; thread i < C * nq * hist_stride: one bucket of the histogram
+__global__ __launch_bounds__(256) void k_facet_stats_finish(FacetStatsFinishParams L) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (int64_t)L.C * L.nq) {
+        const int64_t c = i / L.nq, q = i - c * L.nq, oq = c * L.Q + L.q0 + q;
+        const int64_t tot = L.total[q], mis = L.missing[i];
+        if (L.out_count) L.out_count[oq] = tot - mis;
+        if (L.out_missing) L.out_missing[oq] = mis;
+        if (L.out_min) L.out_min[oq] = (int64_t)(L.vmin[i] ^ FS_SIGN);
+        if (L.out_max) L.out_max[oq] = (int64_t)(L.vmax[i] ^ FS_SIGN);
+        // SH * 2^32 + SL as a 128-bit number: SH << 32 has the low word SH << 32 and the high word SH >> 32 (arithmetic)
+        const unsigned long long sl = L.sum_lo[i], shl = L.sum_hi[i] << 32, lo = shl + sl;
+        if (L.out_sum_lo) L.out_sum_lo[oq] = (int64_t)lo;
+        if (L.out_sum_hi) L.out_sum_hi[oq] = ((int64_t)L.sum_hi[i] >> 32) + (lo < shl ? 1 : 0);
+        if (c == 0) L.out_total[L.q0 + q] = tot;
+    }
+    if (L.out_hist && i < (int64_t)L.C * L.nq * L.hist_stride) {
+        const int64_t cq = i / L.hist_stride, b = i - cq * L.hist_stride;
+        const int64_t c = cq / L.nq, q = cq - c * L.nq;
+        int64_t n = 0;
+        if (L.n_edges[c] == 0) n = b == 0 ? (int64_t)L.total[q] - (int64_t)L.missing[cq] : 0;  // the single bucket: count
+        else if (b <= L.n_edges[c]) n = L.bins[cq * L.bin_stride + b];
+        L.out_hist[(c * L.Q + L.q0 + q) * L.hist_stride + b] = n;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_facet_stats_fill(int64_t *p, int64_t n, int64_t v) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+struct FacetStatsOut {
+    int64_t *count, *missing, *vmin, *vmax, *sum_lo, *sum_hi, *hist, *total;
+};
+
+int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *const *cols, int C, const int64_t *edges,
+                       const int *n_edges, int hist_stride, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask, const FacetStatsOut &o,
+                       qk_timing *timing, int64_t *n_passes) {
+    const int64_t Q = a.Q;
+    hipStream_t st = ctx->stream;
+    const int npids = (int)s->parts.size();
+    const int P = a.all_lists ? npids : a.P;
+    *n_passes = 0;
+    qk_phase_events pe;
+    pe.ctx = ctx;
+    pe.tm = ctx->timing && timing;
+    pe.dtm = false;
+    pe.ev_base = 4;
+    const int64_t CQ = (int64_t)C * Q;
+    if (P <= 0 || npids <= 0) {  // no lists: no hits -- zeros, and the identities of min / max
+        QK_TRY(pe.mark(0));
+        QK_TRY(qk_prep_flush(ctx));
+        for (int64_t *p : {o.count, o.missing, o.sum_lo, o.sum_hi})
+            if (p) QK_HIP(hipMemsetAsync(p, 0, (size_t)CQ * 8, st));
+        if (o.hist) QK_HIP(hipMemsetAsync(o.hist, 0, (size_t)CQ * hist_stride * 8, st));
+        QK_HIP(hipMemsetAsync(o.total, 0, (size_t)Q * 8, st));
+        if (o.vmin) hipLaunchKernelGGL(k_facet_stats_fill, dim3((unsigned)((CQ + 255) / 256)), dim3(256), 0, st, o.vmin, CQ, INT64_MAX);
+        if (o.vmax) hipLaunchKernelGGL(k_facet_stats_fill, dim3((unsigned)((CQ + 255) / 256)), dim3(256), 0, st, o.vmax, CQ, INT64_MIN);
+        QK_HIP(hipGetLastError());
+        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
+        return QK_OK;
+    }
+    int n_all = 0, e_off[QK_MAX_FACET_COLS] = {0, 0, 0, 0}, ne[QK_MAX_FACET_COLS] = {0, 0, 0, 0};
+    for (int c = 0; c < C; c++) {
+        e_off[c] = n_all;
+        ne[c] = n_edges ? n_edges[c] : 0;
+        n_all += ne[c];
+    }
+    // bins are kept only where some column of a wanted histogram has edges to search: the single bucket of E == 0 is the count
+    const int bin_stride = o.hist && n_all > 0 ? hist_stride : 0;
+    // this pipeline's bytes of the call's buffer, sized for the largest pass:
+    // [total] [missing] [sum_lo] [sum_hi] [max] [bins] | [min] | [edges]   (zero bytes | all ones | uploaded once)
+    int64_t S = 0;
+    size_t o_missing = 0, o_sum_lo = 0, o_sum_hi = 0, o_max = 0, o_bins = 0, o_min = 0, o_edges = 0;
+    qk_emit_hooks h;
+    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+        const int64_t qbytes = 4 + (int64_t)C * 36 + (int64_t)C * bin_stride * 4;
+        *qc = std::max<int64_t>(1, std::min<int64_t>(*qc, QK_GROUPED_PASS_BYTES / qbytes));
+        S = (per_query_ub + FC_SLICE - 1) / FC_SLICE;
+        if (*qc * S > 0x7FFFFFF0LL || *qc * (int64_t)C > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "facet statistics: Q too large");
+        const size_t w = qk_al256((size_t)*qc * C * 8);
+        o_missing = qk_al256((size_t)*qc * 4);
+        o_sum_lo = o_missing + qk_al256((size_t)*qc * C * 4);
+        o_sum_hi = o_sum_lo + w;
+        o_max = o_sum_hi + w;
+        o_bins = o_max + w;
+        o_min = o_bins + qk_al256((size_t)*qc * C * bin_stride * 4);
+        o_edges = o_min + w;
+        *extra_bytes = o_edges + qk_al256((size_t)n_all * 8);
+        return QK_OK;
+    };
+    h.before_scan = [&](const qk_emit_pass &p) -> int {
+        QK_HIP(hipMemsetAsync(p.extra, 0, o_min, st));
+        QK_HIP(hipMemsetAsync(p.extra + o_min, 0xFF, (size_t)p.nq * C * 8, st));
+        // the edges, once per call: a stream-ordered copy from the caller's pageable memory.  As everywhere in this library
+        // (qk_attr.hip, qk_store.hip) it relies on the runtime having staged a pageable source when hipMemcpyAsync returns, so the
+        // caller's array may go when the call returns; the host may wait here once, in front of the first emission, never
+        // between passes
+        if (p.q0 == 0 && bin_stride > 0)
+            QK_HIP(hipMemcpyAsync(p.extra + o_edges, edges, (size_t)n_all * 8, hipMemcpyHostToDevice, st));
+        return QK_OK;
+    };
+    h.consume = [&](const qk_emit_pass &p) -> int {
+        FacetStatsParams T;
+        FacetParams &F = T.F;
+        F.keys = p.keys;
+        F.pair_base = p.pair_base;
+        F.pids = p.pids;
+        F.pt_off = s->d_off;
+        F.mask = mask;
+        for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+            F.has[c] = cols[c < C ? c : 0]->rv_has;
+            F.rowval[c] = cols[c < C ? c : 0]->rv_vals;
+            T.e_off[c] = e_off[c];
+            T.n_edges[c] = ne[c];
+        }
+        F.tvals = nullptr;
+        F.tcnt = nullptr;
+        F.total = (uint32_t *)p.extra;
+        F.missing = (uint32_t *)(p.extra + o_missing);
+        F.nq = p.nq;
+        F.g0 = 0;
+        F.ng = p.nq;
+        F.P = P;
+        F.C = C;
+        F.tmask = 0;
+        F.key_lo = key_lo;
+        F.key_hi = key_hi;
+        F.max_ids = 0;
+        F.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));  // about 16384 workgroups, whatever S is
+        T.edges = (const int64_t *)(p.extra + o_edges);
+        T.hist_stride = bin_stride;
+        T.sum_lo = (unsigned long long *)(p.extra + o_sum_lo);
+        T.sum_hi = (unsigned long long *)(p.extra + o_sum_hi);
+        T.vmax = (unsigned long long *)(p.extra + o_max);
+        T.vmin = (unsigned long long *)(p.extra + o_min);
+        T.bins = (uint32_t *)(p.extra + o_bins);
+        hipLaunchKernelGGL(k_facet_stats, dim3((unsigned)(p.nq * F.Sg)), dim3(256), 0, st, T);
+        FacetStatsFinishParams L;
+        L.total = F.total;
+        L.missing = F.missing;
+        L.sum_lo = T.sum_lo;
+        L.sum_hi = T.sum_hi;
+        L.vmax = T.vmax;
+        L.vmin = T.vmin;
+        L.bins = bin_stride > 0 ? T.bins : nullptr;
+        L.nq = p.nq;
+        L.q0 = p.q0;
+        L.Q = Q;
+        L.C = C;
+        L.bin_stride = bin_stride;
+        L.hist_stride = hist_stride;
+        for (int c = 0; c < QK_MAX_FACET_COLS; c++) L.n_edges[c] = ne[c];
+        L.out_count = o.count;
+        L.out_missing = o.missing;
+        L.out_min = o.vmin;
+        L.out_max = o.vmax;
+        L.out_sum_lo = o.sum_lo;
+        L.out_sum_hi = o.sum_hi;
+        L.out_hist = o.hist;
+        L.out_total = o.total;
+        const int64_t nthr = (int64_t)C * p.nq * (o.hist ? hist_stride : 1);
+        hipLaunchKernelGGL(k_facet_stats_finish, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, L);
+        QK_HIP(hipGetLastError());
+        return QK_OK;
+    };
+    QK_TRY(qk_emit_passes(ctx, s, a, P, "facet statistics", pe, h, n_passes));
+    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
+    ctx->last_scan_kernel = wide ? "k_scan_wide (facet stats)" : "k_scan (facet stats)";
+    QK_TRY(pe.mark(3));
+    return QK_OK;
+}
+
+// the body of both entry points: parent == nullptr && pids == nullptr -> every list
+int facet_stats_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P,
+                    int nprobe, int metric, float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, const int64_t *edges,
+                    const int *n_edges, const FacetStatsOut &out, int mem, qk_timing *timing) {
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    if (radius != radius) QK_FAIL(QK_ERR_INVALID, "%s: the radius is NaN", who);
+    if (n_cols < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_cols=%d must be at least 1", who, n_cols);
+    if (n_cols > QK_MAX_FACET_COLS) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_cols=%d exceeds QK_MAX_FACET_COLS=%d", who, n_cols, QK_MAX_FACET_COLS);
+    if (!facet_by) QK_FAIL(QK_ERR_INVALID, "%s: facet_by is null", who);
+    qk_attr_data *cols[QK_MAX_FACET_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    for (int c = 0; c < n_cols; c++) {
+        if (!facet_by[c]) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d is null", who, c);
+        cols[c] = facet_by[c]->d.get();
+        if (cols[c]->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d belongs to another store", who, c);
+    }
+    // ---- the edges: host memory, checked here, uploaded once (facet_stats_device)
+    if (edges && !n_edges) QK_FAIL(QK_ERR_INVALID, "%s: edges without n_edges", who);
+    int max_e = 0;
+    int64_t n_all = 0;
+    if (n_edges)
+        for (int c = 0; c < n_cols; c++) {
+            const int E = n_edges[c];
+            if (E < 0) QK_FAIL(QK_ERR_INVALID, "%s: n_edges[%d]=%d is negative", who, c, E);
+            if (E > QK_MAX_FACET_EDGES)
+                QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_edges[%d]=%d exceeds QK_MAX_FACET_EDGES=%d", who, c, E, QK_MAX_FACET_EDGES);
+            if (E > 0 && !edges) QK_FAIL(QK_ERR_INVALID, "%s: n_edges names edges, edges is null", who);
+            for (int i = 1; i < E; i++)
+                if (edges[n_all + i - 1] >= edges[n_all + i])
+                    QK_FAIL(QK_ERR_INVALID, "%s: the edges of column %d are not strictly ascending (edge %d)", who, c, i);
+            n_all += E;
+            max_e = std::max(max_e, E);
+        }
+    const int hist_stride = 1 + max_e;
+    if (Q < 0 || (Q > 0 && (!x || !out.total))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
+    QK_TRY(qk_check_overflow(ctx));
+    QK_HIP(hipSetDevice(ctx->device));
+    if (timing) memset(timing, 0, sizeof(*timing));
+    if (Q == 0) return QK_OK;
+    hipStream_t st = ctx->stream;
+    // ---- staging, query preparation, coarse; a host caller's outputs on the device: six [C][Q] words, [hist], [total]
+    const size_t bc = qk_al256((size_t)n_cols * Q * 8), bh = qk_al256((size_t)n_cols * Q * hist_stride * 8), bt = qk_al256((size_t)Q * 8);
+    qk_scan_args sa;
+    char *stage = nullptr;
+    bool have_coarse = false;
+    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, 6 * bc + bh + bt, timing != nullptr, &sa, &stage,
+                             &have_coarse));
+    FacetStatsOut dv = out;
+    int64_t *const host[8] = {out.count, out.missing, out.vmin, out.vmax, out.sum_lo, out.sum_hi, out.hist, out.total};
+    int64_t **const dev[8] = {&dv.count, &dv.missing, &dv.vmin, &dv.vmax, &dv.sum_lo, &dv.sum_hi, &dv.hist, &dv.total};
+    const size_t bytes[8] = {(size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8,
+                             (size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8, (size_t)n_cols * Q * hist_stride * 8, (size_t)Q * 8};
+    if (mem == QK_MEM_HOST)
+        for (int i = 0; i < 8; i++) *dev[i] = host[i] ? (int64_t *)(stage + (i < 7 ? i * bc : 6 * bc + bh)) : nullptr;
+    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
+    if (!qk_range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
+        key_lo = 1;
+        key_hi = 0;
+    }
+    // ---- row values and mask, then emission + sweep + finish -----------------------------------------------------------------------
+    const uint16_t *mask = nullptr;
+    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
+    QK_TRY(qk_store_sync_table(s));
+    for (int c = 0; c < n_cols; c++) {
+        bool seen = false;  // (the same column twice: derived once)
+        for (int e = 0; e < c; e++) seen = seen || cols[e] == cols[c];
+        if (!seen) QK_TRY(qk_rowvals_ensure(ctx, s, *cols[c]));
+    }
+    int64_t n_passes = 0;
+    QK_TRY(facet_stats_device(ctx, s, sa, cols, n_cols, edges, n_edges, hist_stride, key_lo, key_hi, mask, dv, timing, &n_passes));
+    // ---- results back ------------------------------------------------------------------------------------------------------------
+    if (mem == QK_MEM_HOST) {
+        for (int i = 0; i < 8; i++)
+            if (host[i]) QK_HIP(hipMemcpyAsync(host[i], *dev[i], bytes[i], hipMemcpyDeviceToHost, st));
+        QK_HIP(hipStreamSynchronize(st));
+    }
+    if (timing) {
+        QK_HIP(hipStreamSynchronize(st));
+        timing->n_items = n_passes;
+        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
+    }
+    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
+    return QK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -566,6 +1005,28 @@ int qk_facet_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_facet_scan: bad partition id list");
     return facet_run("qk_facet_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, facet_by, n_cols, n_values, out_values,
                      out_counts, out_distinct, out_missing, out_total, mem, timing);
+}
+
+int qk_facet_stats_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int metric, float radius,
+                          qk_filter *filter, qk_attr *const *facet_by, int n_cols, const int64_t *edges, const int *n_edges,
+                          int64_t *out_count, int64_t *out_missing, int64_t *out_min, int64_t *out_max, int64_t *out_sum_lo,
+                          int64_t *out_sum_hi, int64_t *out_hist, int64_t *out_total, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_search: null argument");
+    if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_search: nprobe must be positive");
+    const FacetStatsOut out{out_count, out_missing, out_min, out_max, out_sum_lo, out_sum_hi, out_hist, out_total};
+    return facet_stats_run("qk_facet_stats_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, facet_by, n_cols,
+                           edges, n_edges, out, mem, timing);
+}
+
+int qk_facet_stats_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric, float radius,
+                        qk_filter *filter, qk_attr *const *facet_by, int n_cols, const int64_t *edges, const int *n_edges,
+                        int64_t *out_count, int64_t *out_missing, int64_t *out_min, int64_t *out_max, int64_t *out_sum_lo,
+                        int64_t *out_sum_hi, int64_t *out_hist, int64_t *out_total, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_scan: null argument");
+    if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_scan: bad partition id list");
+    const FacetStatsOut out{out_count, out_missing, out_min, out_max, out_sum_lo, out_sum_hi, out_hist, out_total};
+    return facet_stats_run("qk_facet_stats_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, facet_by, n_cols, edges,
+                           n_edges, out, mem, timing);
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_expr
+from .where import lower_edges, lower_expr
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -321,6 +321,41 @@ class FacetResult:
         self.totals = None
         self.columns = None
         self.timing_info = None
+
+
+MAX_FACET_EDGES = header_constant("QK_MAX_FACET_EDGES")
+
+
+class FacetStatsResult:
+    """extension (QuakeIndex.facet_stats): per column and query, over the query's range hits: count / missing / min / max /
+    sum_lo / sum_hi [C, Q] (min / max of a count of 0 are INT64_MAX / INT64_MIN; the exact sum is sum_hi * 2**64 + (sum_lo mod
+    2**64)), histogram [C, Q, 1 + the most edges of a column] (bucket b of a value v = the number of the column's edges <= v;
+    entries behind a column's own buckets are 0), totals [Q] the hits of every query, columns the C column names, edges the C
+    edge lists"""
+
+    def __init__(self):
+        self.count = None
+        self.missing = None
+        self.min = None
+        self.max = None
+        self.sum_lo = None
+        self.sum_hi = None
+        self.histogram = None
+        self.totals = None
+        self.columns = None
+        self.edges = None
+        self.timing_info = None
+
+    def sums(self):
+        """[C][Q] exact Python ints (a host convenience: the tensors are the contract)"""
+        lo, hi = self.sum_lo.cpu().tolist(), self.sum_hi.cpu().tolist()
+        return [[h * (1 << 64) + (l % (1 << 64)) for l, h in zip(rl, rh)] for rl, rh in zip(lo, hi)]
+
+    def means(self):
+        """[C, Q] float64 numpy array, NaN where count == 0"""
+        cnt = self.count.cpu().tolist()
+        return np.array([[s / n if n else float("nan") for s, n in zip(rs, rn)] for rs, rn in zip(self.sums(), cnt)],
+                        dtype=np.float64).reshape(len(cnt), -1)
 
 
 _CONTEXTS = {}
@@ -1138,6 +1173,94 @@ class QuakeIndex:
             ti.parent_info = pi
         ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
         res.values, res.counts, res.distinct, res.missing, res.totals = (o if on_dev else o.cpu() for o in out[:5])
+        return res
+
+    def facet_stats(self, x, facet_by, search_params, radius=None, edges=None):
+        """extension (no reference counterpart): over the vectors range_search(x, radius, search_params) returns for each query
+        (as facet_counts defines them), the count, minimum, maximum, exact sum and a histogram of the attribute columns `facet_by`
+        (a name or a list of up to 4 names).  edges: None (one bucket per column), one strictly ascending sequence of integers for
+        all columns, or a dict name -> sequence; at most 255 per column; bucket b of a value v = the number of edges <= v.
+        search_params.k is ignored.  Exact; the values are those of the moment of the call.  Returns a FacetStatsResult on x's
+        device."""
+        self._require_built("[QuakeIndex::facet_stats()] No query coordinator. Did you build the index?")
+        sp = search_params
+        names = [facet_by] if isinstance(facet_by, str) else list(facet_by)
+        if not 1 <= len(names) <= MAX_FACET_COLS:
+            raise RuntimeError("[QuakeIndex::facet_stats()] facet_by must name between 1 and %d columns" % MAX_FACET_COLS)
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError("[QuakeIndex::facet_stats()] SearchParams.filters / query_filter (one filter per query) are not "
+                               "supported by facet_stats")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::facet_stats()] SearchParams.filters_exact_rows (exact per-query filtered search) is not "
+                               "supported by facet_stats")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::facet_stats()] SearchParams.filter_exact_rows (exact filtered search) is not supported by "
+                               "facet_stats")
+        if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
+            raise RuntimeError("[QuakeIndex::facet_stats()] SearchParams.max_nprobe (adaptive probing) is not supported by facet_stats")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError("[QuakeIndex::facet_stats()] facet_stats is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::facet_stats()] facet_stats is not supported with num_workers > 0")
+        cols = self._attributes()
+        for name in names:
+            if name not in cols:
+                raise RuntimeError("[QuakeIndex::facet_stats()] unknown attribute column '%s'" % name)
+        flat, n_edges = lower_edges(names, edges, "[QuakeIndex::facet_stats()]")
+        per, at = [], 0
+        for n in n_edges:
+            per.append(flat[at:at + n])
+            at += n
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError("[QuakeIndex::facet_stats()] SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError("[QuakeIndex::facet_stats()] the filter was made for another index")
+            flt = flt._h
+        if radius is None:
+            radius = float("-inf") if capi.metric_code(self.metric_) == capi.QK_METRIC_IP else float("inf")
+        radius = float(radius)
+        if radius != radius:
+            raise RuntimeError("[QuakeIndex::facet_stats()] the radius is NaN")
+        C_, hs = len(names), 1 + max(n_edges)
+        res = FacetStatsResult()
+        res.columns = names
+        res.edges = per
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        nq = 0 if x is None else int(x.shape[0])
+        if nq == 0:
+            res.count, res.missing, res.min, res.max, res.sum_lo, res.sum_hi = (torch.zeros((C_, 0), dtype=torch.int64) for _ in range(6))
+            res.histogram = torch.zeros((C_, 0, hs), dtype=torch.int64)
+            res.totals = torch.zeros((0,), dtype=torch.int64)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        self._ctx.set_timing(1)
+        try:
+            out = self._ctx.facet_stats_search(self.parent._store if self.parent is not None else None, self._store, xd, nprobe, radius,
+                                               self.metric_, [cols[name] for name in names], edges=per, filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(0)
+        tm = out[8]
+        ti.n_queries = nq
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        (res.count, res.missing, res.min, res.max, res.sum_lo, res.sum_hi, res.histogram,
+         res.totals) = (o if on_dev else o.cpu() for o in out[:8])
         return res
 
     def make_filter(self, ids=None, exclude=False, where=None, any_of=None):

@@ -5,6 +5,7 @@ ABI knows five ops over int64: RANGE / NOT_RANGE over a closed interval [a, b] (
 Python integers of any size and are saturated, not wrapped: a comparison with a number outside int64 means what it means over the
 integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
+lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search).
 Pure Python: importable without the library or a GPU."""
 
 INT64_MIN = -(1 << 63)
@@ -16,6 +17,8 @@ QK_MAX_CLAUSES = 8
 QK_MAX_TERMS = 8
 QK_MAX_EXPR_CLAUSES = 32
 QK_MAX_SET_VALUES = 1 << 20
+
+QK_MAX_FACET_EDGES = 255
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
 SET_OPS = ("in", "not_in")  # lower_expr only
@@ -135,3 +138,54 @@ def lower_expr(where=None, any_of=None, who="[QuakeIndex::make_filter()]"):
     if total > QK_MAX_EXPR_CLAUSES:
         raise RuntimeError("%s any_of has %d clauses in total, at most %d are supported" % (who, total, QK_MAX_EXPR_CLAUSES))
     return terms
+
+
+def _is_seq(v):
+    return not isinstance(v, (str, bytes, dict)) and hasattr(v, "__getitem__") and hasattr(v, "__len__")
+
+
+def _edge_list(v, name, who):
+    """the edges of one column: None or a sequence of strictly ascending int64 integers, at most QK_MAX_FACET_EDGES"""
+    if v is None:
+        return []
+    if hasattr(v, "tolist"):  # (a tensor, an array: its elements as Python numbers)
+        v = v.tolist()
+    if not _is_seq(v):
+        raise RuntimeError("%s the edges of '%s' must be a sequence of integers, got %r" % (who, name, v))
+    if len(v) > QK_MAX_FACET_EDGES:
+        raise RuntimeError("%s '%s' has %d edges, at most %d are supported" % (who, name, len(v), QK_MAX_FACET_EDGES))
+    out = [_int(x, who + " edges:") for x in v]
+    for i, x in enumerate(out):
+        if not INT64_MIN <= x <= INT64_MAX:
+            raise RuntimeError("%s edge %d of '%s' does not fit int64: %d" % (who, i, name, x))
+        if i and out[i - 1] >= x:
+            raise RuntimeError("%s the edges of '%s' are not strictly ascending (edge %d)" % (who, name, i))
+    return out
+
+
+def lower_edges(names, edges, who="[QuakeIndex::facet_stats()]"):
+    """The histogram edges of facet statistics (include/quake_hip.h, "facet statistics") for the columns `names` ->
+    (flat, n_edges): the columns' edges one after the other as a list of Python ints inside int64, and their number per column.
+    `edges` is None (no edges: one bucket per column), one sequence of integers applied to every column, a dict name -> sequence
+    (a column it does not name has no edges), or a list with one sequence or None per column; a tensor or an array stands for
+    its tolist() wherever a sequence may stand.  RuntimeError: edges that are not strictly ascending, more than
+    QK_MAX_FACET_EDGES of them, an edge that is no integer or does not fit int64, a dict that names a column not in `names`, a
+    per-column list of another length."""
+    names = list(names)
+    if hasattr(edges, "tolist"):  # (a tensor, an array)
+        edges = edges.tolist()
+    if edges is None:
+        per = [None] * len(names)
+    elif isinstance(edges, dict):
+        for k in edges:
+            if k not in names:
+                raise RuntimeError("%s edges names '%s', which is not one of the facet columns" % (who, k))
+        per = [edges.get(n) for n in names]
+    elif _is_seq(edges) and len(edges) > 0 and all(e is None or _is_seq(e) for e in edges):
+        if len(edges) != len(names):
+            raise RuntimeError("%s edges has %d per-column entries for %d columns" % (who, len(edges), len(names)))
+        per = list(edges)
+    else:
+        per = [edges] * len(names)
+    lists = [_edge_list(e, n, who) for e, n in zip(per, names)]
+    return [x for l in lists for x in l], [len(l) for l in lists]
