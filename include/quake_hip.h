@@ -710,6 +710,60 @@ QK_API int qk_facet_stats_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t
                                int64_t *out_sum_lo, int64_t *out_sum_hi, int64_t *out_hist, int64_t *out_total, int mem,
                                qk_timing *timing);
 
+/* ---- ordered search ---------------------------------------------------------------------------------
+ * No reference counterpart.  "Sort by": per query, the k first of its range hits by an attribute column -- the 10 cheapest items
+ * near this query, the 20 newest documents within this radius, highest rated first.
+ * Hits: the hit multiset H(q) is BY DEFINITION that of qk_range_search / qk_range_scan for the same (parent, nprobe | pids, metric,
+ * radius, filter), exactly as for facet counts above: the inclusive float32 radius test, qk_ctx_set_squared_l2 honoured, a NaN
+ * distance never a hit, a NaN radius QK_ERR_INVALID, radius +inf (L2) / -inf (IP) every probed candidate row, a row stored twice
+ * is two hits, -1 / absent / empty lists contribute nothing.
+ * order_by: one column of the store.  flags: QK_ORDER_DESC | QK_ORDER_MISSING_LAST.  1 <= k <= QK_MAX_ORDER_K; below:
+ * QK_ERR_INVALID, above: QK_ERR_UNSUPPORTED.
+ * Order: every hit has a record (class, value, key, id), compared field by field:
+ *   class  0 if the row's id has a value in the column at the moment of the call, 1 if not
+ *   value  the signed int64 value, ascending; descending under QK_ORDER_DESC.  Every int64 is legal (INT64_MIN, INT64_MAX, -1).
+ *          Records of class 1 compare equal on it
+ *   key    the search order's uint32 key of the pair: smaller = nearer under both metrics, -0 and +0 share a key (the key
+ *          qk_search_after documents) -- ascending in BOTH directions
+ *   id     signed, ascending
+ * -- by the column in the direction asked, ties to the nearer row, ties of those to the smaller id, as qk_search breaks them.
+ * Two hits that tie on all four fields (a row stored twice) are indistinguishable; each is an entry.
+ * Returned: without QK_ORDER_MISSING_LAST the first min(k, count[q]) records of class 0; with it the first min(k, total[q]) records
+ * of both classes, class 1 behind class 0 -- entry j has a value iff j < count[q].
+ *   out_ids     [Q][k]               padding -1
+ *   out_dist    [Q][k], may be NULL  the float32 distance qk_search reports for the pair; padding +inf (L2) / -inf (IP)
+ *   out_values  [Q][k], may be NULL  0 for entries without a value and for padding
+ *   out_count   [Q], may be NULL     hits with a value   } as int64; equal to count, missing and total of
+ *   out_missing [Q], may be NULL     hits without one    } qk_facet_stats_search for the same arguments
+ *   out_total   [Q], may be NULL     count + missing     }
+ * Q == 0: QK_OK.  No lists probed: all padding and zeros.  The result is a pure function of the store, the column and the call.
+ * Liveness as for facets: values are read when the call runs, through the per-row values grouped search keeps; a later
+ * set / add / remove / maintenance is seen by the next call.
+ * Limits: a NULL column, a column or filter of another store, unknown flag bits: QK_ERR_INVALID.  A query whose keys exceed 2^30 is
+ * QK_ERR_UNSUPPORTED (qk_emit_passes).  There is no form for qk_search_aps, the device group, per-query filter tables or adaptive
+ * probing.
+ * Inside (qk_order.hip): the key-emission scan of range search (the same launches), then per pass k_order_partial -- the
+ * decomposition and hit test of k_facet_stats; every workgroup keeps the k smallest records it met in an LDS buffer of 512 / 1024 /
+ * 2048 records (k <= 64 / 256 / 1024 = KP) that a bitonic pass cuts back to k whenever fewer than 256 slots are free, the k-th record
+ * being the bound later hits are compared against in registers -- and k_order_merge, one workgroup per query, which streams the
+ * workgroups' sorted lists through the same buffer and writes the outputs.  No kernel waits or spins.
+ * Workspace: keys as for range search; next to them 8 bytes of counters per query and Sg lists of KP records of 24 bytes per
+ * query, Sg = min(slices of a query, 256, 16384 / queries of the pass, 128 MiB / (queries per pass * list bytes)), at least 1: a
+ * large k lowers Sg, never refuses; a pass is shortened only where one list per query would exceed QK_GROUPED_PASS_BYTES.
+ * timing: coarse_ms and scan_ms as for range search, merge_ms = partial + merge (of the last pass), n_items = the number of query
+ * passes.  qk_ctx_last_scan_kernel names "k_scan (order)" / "k_scan_wide (order)". */
+#define QK_MAX_ORDER_K 1024
+#define QK_ORDER_DESC 1
+#define QK_ORDER_MISSING_LAST 2
+QK_API int qk_order_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int metric, float radius,
+                           qk_filter *filter, qk_attr *order_by, int flags, int k, int64_t *out_ids, float *out_dist,
+                           int64_t *out_values, int64_t *out_count, int64_t *out_missing, int64_t *out_total, int mem,
+                           qk_timing *timing);
+QK_API int qk_order_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric, float radius,
+                         qk_filter *filter, qk_attr *order_by, int flags, int k, int64_t *out_ids, float *out_dist,
+                         int64_t *out_values, int64_t *out_count, int64_t *out_missing, int64_t *out_total, int mem,
+                         qk_timing *timing);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

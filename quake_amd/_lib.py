@@ -138,6 +138,11 @@ SIGNATURES = {
                               [_int, C.POINTER(QkTiming)]),
     "qk_facet_stats_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _vp, _int, _vp, _vp] + [_vp] * 8 +
                             [_int, C.POINTER(QkTiming)]),
+    # ordered search: (.., radius, filter, order_by, flags, k, ids, dist, values, count, missing, total, mem, timing)
+    "qk_order_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_float, _vp, _vp, _int, _int] + [_vp] * 6 +
+                        [_int, C.POINTER(QkTiming)]),
+    "qk_order_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _vp, _int, _int] + [_vp] * 6 +
+                      [_int, C.POINTER(QkTiming)]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
     "qk_filter_create_expr": (_int, [_vp, C.POINTER(QkExprClause), C.POINTER(_int), _int, C.POINTER(_vp)]),

@@ -98,6 +98,11 @@ def _empty_like_mem(shape, dtype, ref):
     return np.empty(shape, dtype)
 
 
+QK_ORDER_DESC = 1          # include/quake_hip.h: the flags of ordered search
+QK_ORDER_MISSING_LAST = 2
+QK_MAX_ORDER_K = 1024
+
+
 def timing_dict(t):
     return {f: getattr(t, f) for f, _ in QkTiming._fields_}
 
@@ -617,6 +622,51 @@ class Context:
         check(self.lib.qk_facet_stats_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]),
                                            metric_code(metric), float(radius), filter.h if filter is not None else None, harr, C_,
                                            earr, narr, *[_ptr(o) for o in out], mem, C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
+    # ---- ordered search ---------------------------------------------------------------------------------
+    @staticmethod
+    def _order_args(x, Q, k, descending, missing_last):
+        k = int(k)
+        flags = (QK_ORDER_DESC if descending else 0) | (QK_ORDER_MISSING_LAST if missing_last else 0)
+        # (the library refuses a k outside its limits before it writes: the buffers of such a call only have to exist)
+        kk = k if 1 <= k <= QK_MAX_ORDER_K else 1
+        out = [_empty_like_mem((Q, kk), np.int64, x), _empty_like_mem((Q, kk), np.float32, x), _empty_like_mem((Q, kk), np.int64, x)]
+        out += [_empty_like_mem((Q,), np.int64, x) for _ in range(3)]
+        return k, flags, out
+
+    def order_search(self, parent, store, x, nprobe, radius, metric, order_by, k, descending=False, missing_last=False, filter=None,
+                     timing=False):
+        """qk_order_search: per query, the k first hits of range_search with the same arguments ordered by the Attr column
+        `order_by` (ascending, or descending), ties to the nearer row, then to the smaller id.  missing_last: hits whose id has no
+        value follow those that have one instead of being left out.  Returns (ids [Q, k] padded with -1, dist [Q, k] padded as
+        search pads, values [Q, k] (0 without a value), count, missing, total [Q][, timing]) on x's device."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        k, flags, out = self._order_args(x, Q, k, descending, missing_last)
+        t = QkTiming()
+        check(self.lib.qk_order_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe),
+                                       metric_code(metric), float(radius), filter.h if filter is not None else None,
+                                       order_by.h if order_by is not None else None, flags, k, *[_ptr(o) for o in out], mem,
+                                       C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
+    def order_scan(self, store, x, pids, radius, metric, order_by, k, descending=False, missing_last=False, filter=None, timing=False):
+        """qk_order_scan: order_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / absent / empty lists
+        contribute nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        if pids.ndim == 1:
+            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
+                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        mem = _mem_of(x, pids)
+        k, flags, out = self._order_args(x, Q, k, descending, missing_last)
+        t = QkTiming()
+        check(self.lib.qk_order_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]),
+                                     metric_code(metric), float(radius), filter.h if filter is not None else None,
+                                     order_by.h if order_by is not None else None, flags, k, *[_ptr(o) for o in out], mem,
+                                     C.byref(t) if timing else None))
         return (*out, timing_dict(t)) if timing else tuple(out)
 
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,

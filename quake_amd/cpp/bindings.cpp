@@ -176,6 +176,13 @@ py::list facet_stats_sums(const FacetStatsResult &r) {
 }  // namespace
 
 PYBIND11_MODULE(_bindings, m) {
+    m.def("lower_order",
+          [](const std::vector<std::string> &columns, const std::string &order_by, int64_t k, bool descending, const std::string &missing) {
+              const int flags = lower_order(columns, order_by, k, descending, missing);
+              return py::make_tuple(order_by, k, flags);
+          },
+          py::arg("columns"), py::arg("order_by"), py::arg("k"), py::arg("descending") = false, py::arg("missing") = "exclude",
+          "the arguments of ordered_search -> (column name, k, flags of qk_order_search); needs no device (where.py's lower_order)");
     m.doc() = "quake_amd: MI355X-native Quake search path (same surface as quake._bindings)";
 
     py::class_<QuakeIndex, std::shared_ptr<QuakeIndex>>(m, "QuakeIndex")
@@ -254,6 +261,18 @@ PYBIND11_MODULE(_bindings, m) {
              "extension: per query, count / missing / min / max / exact sum / histogram of the attribute columns `facet_by` (a name or "
              "a list of names) over the vectors range_search returns for the same arguments; edges: None, one ascending sequence of "
              "integers for all columns, or a dict name -> sequence")
+        .def("ordered_search",
+             [](QuakeIndex &self, Tensor x, const std::string &order_by, shared_ptr<SearchParams> sp, py::object radius, bool descending,
+                const std::string &missing) {
+                 std::optional<float> r;
+                 if (!radius.is_none()) r = radius.cast<float>();
+                 return self.ordered_search(x, order_by, sp, r, descending, missing);
+             },
+             py::arg("x"), py::arg("order_by"), py::arg("search_params"), py::arg("radius") = py::none(), py::arg("descending") = false,
+             py::arg("missing") = "exclude",
+             "extension: per query, the search_params.k first of the vectors range_search returns for the same arguments by the "
+             "attribute column `order_by` (ascending, or descending), ties to the nearer vector, then to the smaller id; missing: "
+             "'exclude' or 'last'")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)
@@ -501,6 +520,17 @@ PYBIND11_MODULE(_bindings, m) {
                  return np.attr("array")(rows, py::arg("dtype") = "float64").attr("reshape")(C, -1);
              },
              "[C, Q] float64 numpy array of sum / count, NaN where count == 0");
+
+    py::class_<OrderedSearchResult, std::shared_ptr<OrderedSearchResult>>(m, "OrderedSearchResult")
+        .def(py::init<>())
+        .def_readwrite("ids", &OrderedSearchResult::ids)
+        .def_readwrite("distances", &OrderedSearchResult::distances)
+        .def_readwrite("values", &OrderedSearchResult::values)
+        .def_readwrite("counts", &OrderedSearchResult::counts)
+        .def_readwrite("missing", &OrderedSearchResult::missing)
+        .def_readwrite("totals", &OrderedSearchResult::totals)
+        .def_readwrite("column", &OrderedSearchResult::column)
+        .def_readwrite("timing_info", &OrderedSearchResult::timing_info);
 
     py::class_<SearchCursor, std::shared_ptr<SearchCursor>>(m, "SearchCursor")
         .def(py::init([](py::object keys, py::object ids) {  // (None: left undefined -- search_after refuses such a cursor)

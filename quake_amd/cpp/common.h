@@ -205,6 +205,19 @@ struct FacetStatsResult {
     shared_ptr<SearchTimingInfo> timing_info;
 };
 
+// extension (QuakeIndex::ordered_search): per query the k first range hits by an attribute column: ids [Q, k] (padding -1),
+// distances [Q, k] (padding as search pads), values [Q, k] (0 without a value and at padding), counts / missing / totals [Q]
+struct OrderedSearchResult {
+    Tensor ids;
+    Tensor distances;
+    Tensor values;
+    Tensor counts;
+    Tensor missing;
+    Tensor totals;
+    std::string column;
+    shared_ptr<SearchTimingInfo> timing_info;
+};
+
 struct Clustering {  // common.h:249-276
     Tensor centroids;
     Tensor partition_ids;

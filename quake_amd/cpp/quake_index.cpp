@@ -196,6 +196,29 @@ shared_ptr<FacetStatsResult> QuakeIndex::facet_stats(Tensor x, const std::vector
     return query_coordinator_->facet_stats(x, cols, facet_by, sp, radius, edges_fn);
 }
 
+int lower_order(const std::vector<std::string> &columns, const std::string &order_by, int64_t k, bool descending, const std::string &missing) {
+    const std::string who = "[QuakeIndex::ordered_search()]";
+    if (std::find(columns.begin(), columns.end(), order_by) == columns.end())
+        throw std::runtime_error(who + " unknown attribute column '" + order_by + "'");
+    if (k < 1 || k > QK_MAX_ORDER_K)
+        throw std::runtime_error(who + " k=" + std::to_string(k) + " must be between 1 and " + std::to_string(QK_MAX_ORDER_K));
+    if (missing != "exclude" && missing != "last") throw std::runtime_error(who + " missing must be 'exclude' or 'last', got '" + missing + "'");
+    return (descending ? QK_ORDER_DESC : 0) | (missing == "last" ? QK_ORDER_MISSING_LAST : 0);
+}
+
+shared_ptr<OrderedSearchResult> QuakeIndex::ordered_search(Tensor x, const std::string &order_by, shared_ptr<SearchParams> sp,
+                                                           std::optional<float> radius, bool descending, const std::string &missing) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::ordered_search()] No query coordinator. Did you build the index?");
+    std::vector<std::string> known;
+    qk_attr *col = nullptr;
+    if (partition_manager_ && partition_manager_->has_lists() && partition_manager_->store() && partition_manager_->store() == attrs_store_)
+        for (const auto &kv : attrs_) {
+            known.push_back(kv.first);
+            if (kv.first == order_by) col = kv.second;
+        }
+    return query_coordinator_->ordered_search(x, col, known, order_by, sp, radius, descending, missing);
+}
+
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?");
     qk_store *s = partition_manager_->store();

@@ -46,6 +46,10 @@ std::vector<std::vector<LoweredClause>> lower_expr(const std::vector<std::vector
 // edges that are not strictly ascending
 std::vector<std::vector<int64_t>> lower_edges(const std::vector<std::string> &names, const std::vector<std::vector<WhereOperand>> &edges);
 
+// the arguments of ordered_search (where.py's lower_order: same rules, same errors as std::runtime_error, in the same order): an
+// unknown column, k outside 1 .. QK_MAX_ORDER_K, a `missing` that is neither "exclude" nor "last" -> the flags of qk_order_search
+int lower_order(const std::vector<std::string> &columns, const std::string &order_by, int64_t k, bool descending, const std::string &missing);
+
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
     shared_ptr<QuakeIndex> parent_;
@@ -108,6 +112,11 @@ public:
     // the same with the edges produced on demand, behind the call's refusals (the binding: Python objects are parsed there)
     shared_ptr<FacetStatsResult> facet_stats(Tensor x, const std::vector<std::string> &facet_by, shared_ptr<SearchParams> search_params,
                                              std::optional<float> radius, const FacetEdgesFn &edges_fn);
+    // extension: "sort by" -- the search_params->k first range hits by the attribute column `order_by`, ascending or descending, ties
+    // to the nearer vector, then to the smaller id; missing: "exclude" | "last" (qk_order_search)
+    shared_ptr<OrderedSearchResult> ordered_search(Tensor x, const std::string &order_by, shared_ptr<SearchParams> search_params,
+                                                   std::optional<float> radius = std::nullopt, bool descending = false,
+                                                   const std::string &missing = "exclude");
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

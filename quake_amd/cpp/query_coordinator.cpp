@@ -811,6 +811,89 @@ shared_ptr<FacetStatsResult> QueryCoordinator::facet_stats(Tensor x, const std::
     return res;
 }
 
+shared_ptr<OrderedSearchResult> QueryCoordinator::ordered_search(Tensor x, qk_attr *col, const std::vector<std::string> &known,
+                                                                const std::string &order_by, shared_ptr<SearchParams> sp,
+                                                                std::optional<float> radius_opt, bool descending, const std::string &missing) {
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::ordered_search] partition_manager_ is null.");
+    if (!sp->filters.empty() || sp->query_filter.defined())
+        throw std::runtime_error("[QuakeIndex::ordered_search()] SearchParams.filters / query_filter (one filter per query) are not "
+                                 "supported by ordered_search");
+    if (sp->filters_exact_rows != 0)
+        throw std::runtime_error("[QuakeIndex::ordered_search()] SearchParams.filters_exact_rows (exact per-query filtered search) is "
+                                 "not supported by ordered_search");
+    if (sp->filter_exact_rows != 0)
+        throw std::runtime_error("[QuakeIndex::ordered_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported "
+                                 "by ordered_search");
+    if (sp->max_nprobe > 0)
+        throw std::runtime_error("[QuakeIndex::ordered_search()] SearchParams.max_nprobe (adaptive probing) is not supported by "
+                                 "ordered_search");
+    if (sp->recall_target > 0.0f) throw std::runtime_error("[QuakeIndex::ordered_search()] ordered_search is not supported with recall_target > 0");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group()) throw std::runtime_error("[QuakeIndex::ordered_search()] ordered_search is not supported with num_workers > 0");
+    if (!store) throw std::runtime_error("[QueryCoordinator::ordered_search] partitions are not initialized.");
+    const int flags = lower_order(known, order_by, sp->k, descending, missing);
+    const int64_t k = sp->k;
+    qk_filter *flt = nullptr;
+    if (sp->filter) {
+        if (!sp->filter->h) throw std::runtime_error("[QuakeIndex::ordered_search()] SearchParams.filter must come from make_filter()");
+        if (sp->filter->owner != store) throw std::runtime_error("[QuakeIndex::ordered_search()] the filter was made for another index");
+        flt = sp->filter->h;
+    }
+    const float inf = std::numeric_limits<float>::infinity();
+    const float radius = radius_opt ? *radius_opt : ((int)metric_ == QK_METRIC_IP ? -inf : inf);
+    if (radius != radius) throw std::runtime_error("[QuakeIndex::ordered_search()] the radius is NaN");
+    auto res = std::make_shared<OrderedSearchResult>();
+    res->column = order_by;
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->search_params = sp;
+    ti->n_clusters = partition_manager_->nlist();
+    if (!x.defined() || x.size(0) == 0) {
+        res->ids = torch::zeros({0, k}, torch::kInt64);
+        res->distances = torch::zeros({0, k}, torch::kFloat32);
+        res->values = torch::zeros({0, k}, torch::kInt64);
+        for (Tensor *t : {&res->counts, &res->missing, &res->totals}) *t = torch::zeros({0}, torch::kInt64);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x);
+    BoundToTorchStream bound(ctx, xq);
+    const int64_t Q = xq.size(0);
+    const int nprobe = std::max(sp->nprobe, 1);
+    const int mem = on_dev ? QK_MEM_DEVICE : QK_MEM_HOST;
+    ti->n_queries = Q;
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
+    res->ids = torch::empty({Q, k}, i64);
+    res->distances = torch::empty({Q, k}, i64.dtype(torch::kFloat32));
+    res->values = torch::empty({Q, k}, i64);
+    for (Tensor *t : {&res->counts, &res->missing, &res->totals}) *t = torch::empty({Q}, i64);
+    qk_check(qk_order_search(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, (int)metric_, radius, flt, col,
+                             flags, (int)k, res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), res->values.data_ptr<int64_t>(),
+                             res->counts.data_ptr<int64_t>(), res->missing.data_ptr<int64_t>(), res->totals.data_ptr<int64_t>(), mem, &tm));
+    ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    if (parent_) {
+        ti->parent_info = std::make_shared<SearchTimingInfo>();
+        ti->parent_info->n_queries = Q;
+        ti->parent_info->n_clusters = 1;
+        ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
+    }
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
 shared_ptr<SearchResult> QueryCoordinator::scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> sp) {  // :659-673
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::scan_partitions] partition_manager_ is null.");
     if (!x.defined() || x.size(0) == 0) return empty_result(sp);

@@ -52,6 +52,11 @@ public:
     shared_ptr<FacetStatsResult> facet_stats(Tensor x, const std::vector<qk_attr *> &cols, const std::vector<std::string> &names,
                                              shared_ptr<SearchParams> search_params, std::optional<float> radius,
                                              const FacetEdgesFn &edges_fn);
+    // extension (qk_order_search): the search_params->k first range hits by `col` -- the column `order_by` of this index's store,
+    // nullptr: unknown; `known`: the names of the store's columns (lower_order runs behind the refusals)
+    shared_ptr<OrderedSearchResult> ordered_search(Tensor x, qk_attr *col, const std::vector<std::string> &known, const std::string &order_by,
+                                                   shared_ptr<SearchParams> search_params, std::optional<float> radius, bool descending,
+                                                   const std::string &missing);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

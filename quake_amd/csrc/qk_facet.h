@@ -1,0 +1,39 @@
+// qk_facet.h -- what qk_facet.hip (facet counts, facet statistics) and qk_order.hip (ordered search) share: the sweep over the keys
+// of an emission pass in slices of FC_SLICE keys, its parameters and the hit test (not part of the C ABI).
+#pragma once
+#include "qk_attr.h"
+
+#include "qk_device.h"
+
+constexpr int FC_SLICE = 1024;      // keys per workgroup step: 256 threads x 4 (the decomposition of GROUPED_FOR_EACH_KEY)
+
+struct FacetParams {
+    const uint32_t *keys;
+    const int64_t *pair_base;  // [npairs + 1]
+    const int64_t *pids;       // [nq][P] or nullptr (pair r -> list r)
+    const int64_t *pt_off;
+    const uint16_t *mask;      // row mask of a filter, or nullptr
+    const uint16_t *has[QK_MAX_FACET_COLS];   // has-value mask of every column
+    const int64_t *rowval[QK_MAX_FACET_COLS]; // its value per arena row
+    unsigned long long *tvals; // [C][ng][T + 1]: the tables of the query group g0 .. g0 + ng of the pass
+    uint32_t *tcnt;            // [C][ng][T + 1]
+    uint32_t *total;           // [nq]
+    uint32_t *missing;         // [C][nq]
+    int64_t nq, g0, ng;
+    int P, Sg, C;
+    uint32_t tmask;            // T - 1 of the reserved tables: the stride of a table is T + 1 slots
+    uint32_t key_lo, key_hi;
+    int64_t max_ids;           // the largest number of ids with a value among the call's columns
+};
+
+// is the key at absolute position pos a hit (k_range_count's test); *row: its arena row when it passed the key interval
+__device__ __forceinline__ bool facet_hit(const FacetParams &F, const int64_t *pbase, const int64_t *qpids, int64_t pos, int64_t lim, int64_t *row) {
+    const uint32_t key = pos < lim ? F.keys[pos] : 0xFFFFFFFFu;
+    bool hit = pos < lim && key >= F.key_lo && key <= F.key_hi;  // (0xFFFFFFFF lies outside every interval)
+    *row = 0;
+    if (hit) {
+        *row = emit_key_row(pbase, qpids, F.P, F.pt_off, pos);
+        if (F.mask) hit = (F.mask[*row >> 4] >> (*row & 15)) & 1;
+    }
+    return hit;
+}

@@ -23,10 +23,9 @@
 // behind the used ones.
 // Second part (behind facet_run): facet statistics -- count, min, max, exact sum and fixed-edge histograms over the same hits, one
 // sweep per pass and no table (k_facet_stats, k_facet_stats_finish).
-#include "qk_attr.h"
+#include "qk_facet.h"
 
 #include <cstring>
-#include "qk_device.h"
 
 // 0 (shipped): every hit adds 1 to its slot with its own atomic; 1: equal values of a wave are first counted in registers and added
 // by one lane.  Measured with scripts/facet_probe.py: at a radius that keeps 1-2 % of the probed rows a wave step
@@ -38,28 +37,8 @@
 namespace {
 
 constexpr unsigned long long FC_EMPTY = ~0ull;
-constexpr int FC_SLICE = 1024;      // keys per workgroup step: 256 threads x 4 (the decomposition of GROUPED_FOR_EACH_KEY)
 constexpr int FC_AGG_ROUNDS = 4;    // leaders a wave elects per column and step before the lanes that are left add for themselves
 constexpr int FC_SEL = QK_MAX_FACET_VALUES;  // entries the selection sorts in LDS
-
-struct FacetParams {
-    const uint32_t *keys;
-    const int64_t *pair_base;  // [npairs + 1]
-    const int64_t *pids;       // [nq][P] or nullptr (pair r -> list r)
-    const int64_t *pt_off;
-    const uint16_t *mask;      // row mask of a filter, or nullptr
-    const uint16_t *has[QK_MAX_FACET_COLS];   // has-value mask of every column
-    const int64_t *rowval[QK_MAX_FACET_COLS]; // its value per arena row
-    unsigned long long *tvals; // [C][ng][T + 1]: the tables of the query group g0 .. g0 + ng of the pass
-    uint32_t *tcnt;            // [C][ng][T + 1]
-    uint32_t *total;           // [nq]
-    uint32_t *missing;         // [C][nq]
-    int64_t nq, g0, ng;
-    int P, Sg, C;
-    uint32_t tmask;            // T - 1 of the reserved tables: the stride of a table is T + 1 slots
-    uint32_t key_lo, key_hi;
-    int64_t max_ids;           // the largest number of ids with a value among the call's columns
-};
 
 // The slots a query's tables USE of the T + 1 reserved ones: the power of two >= max(16, 2 * min(hits of the query, max_ids)),
 // known once the hits are counted (k_facet_hits) and never more than T -- a query has no more distinct values than hits.  Clearing,
@@ -100,18 +79,6 @@ __device__ __forceinline__ void facet_add(unsigned long long *tv, uint32_t *tc, 
         }
         h = (h + 1) & tmask;
     }
-}
-
-// is the key at absolute position pos a hit (k_range_count's test); *row: its arena row when it passed the key interval
-__device__ __forceinline__ bool facet_hit(const FacetParams &F, const int64_t *pbase, const int64_t *qpids, int64_t pos, int64_t lim, int64_t *row) {
-    const uint32_t key = pos < lim ? F.keys[pos] : 0xFFFFFFFFu;
-    bool hit = pos < lim && key >= F.key_lo && key <= F.key_hi;  // (0xFFFFFFFF lies outside every interval)
-    *row = 0;
-    if (hit) {
-        *row = emit_key_row(pbase, qpids, F.P, F.pt_off, pos);
-        if (F.mask) hit = (F.mask[*row >> 4] >> (*row & 15)) & 1;
-    }
-    return hit;
 }
 
 // blockIdx.x = query * Sg + g: the workgroup takes slices g, g + Sg, ... of its query's segment; every wave runs the same number

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_edges, lower_expr
+from .where import lower_edges, lower_expr, lower_order
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -356,6 +356,22 @@ class FacetStatsResult:
         cnt = self.count.cpu().tolist()
         return np.array([[s / n if n else float("nan") for s, n in zip(rs, rn)] for rs, rn in zip(self.sums(), cnt)],
                         dtype=np.float64).reshape(len(cnt), -1)
+
+
+class OrderedSearchResult:
+    """extension (QuakeIndex.ordered_search): per query the k first range hits by an attribute column: ids [Q, k] (padding -1),
+    distances [Q, k] as search() reports them (padding as search pads), values [Q, k] (0 for an entry without a value and for
+    padding), counts / missing / totals [Q] the hits with a value, without one, and all of them; column the column's name"""
+
+    def __init__(self):
+        self.ids = None
+        self.distances = None
+        self.values = None
+        self.counts = None
+        self.missing = None
+        self.totals = None
+        self.column = None
+        self.timing_info = None
 
 
 _CONTEXTS = {}
@@ -1261,6 +1277,83 @@ class QuakeIndex:
         ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
         (res.count, res.missing, res.min, res.max, res.sum_lo, res.sum_hi, res.histogram,
          res.totals) = (o if on_dev else o.cpu() for o in out[:8])
+        return res
+
+    def ordered_search(self, x, order_by, search_params, radius=None, descending=False, missing="exclude"):
+        """extension (no reference counterpart): "sort by" -- of the vectors range_search(x, radius, search_params) returns for each
+        query (as facet_counts defines them; radius None: every vector of the probed partitions), the search_params.k first by the
+        attribute column `order_by`, ascending or descending; ties go to the nearer vector, then to the smaller id.  missing:
+        "exclude" leaves hits without a value out, "last" puts them behind the others.  1 <= k <= 1024.  Exact; the values are those
+        of the moment of the call.  Returns an OrderedSearchResult on x's device."""
+        self._require_built("[QuakeIndex::ordered_search()] No query coordinator. Did you build the index?")
+        sp = search_params
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError("[QuakeIndex::ordered_search()] SearchParams.filters / query_filter (one filter per query) are not "
+                               "supported by ordered_search")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::ordered_search()] SearchParams.filters_exact_rows (exact per-query filtered search) is "
+                               "not supported by ordered_search")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) != 0:
+            raise RuntimeError("[QuakeIndex::ordered_search()] SearchParams.filter_exact_rows (exact filtered search) is not supported "
+                               "by ordered_search")
+        if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
+            raise RuntimeError("[QuakeIndex::ordered_search()] SearchParams.max_nprobe (adaptive probing) is not supported by "
+                               "ordered_search")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError("[QuakeIndex::ordered_search()] ordered_search is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError("[QuakeIndex::ordered_search()] ordered_search is not supported with num_workers > 0")
+        cols = self._attributes()
+        name, k, flags = lower_order(cols, order_by, sp.k, descending, missing, "[QuakeIndex::ordered_search()]")
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError("[QuakeIndex::ordered_search()] SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError("[QuakeIndex::ordered_search()] the filter was made for another index")
+            flt = flt._h
+        if radius is None:
+            radius = float("-inf") if capi.metric_code(self.metric_) == capi.QK_METRIC_IP else float("inf")
+        radius = float(radius)
+        if radius != radius:
+            raise RuntimeError("[QuakeIndex::ordered_search()] the radius is NaN")
+        res = OrderedSearchResult()
+        res.column = name
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        nq = 0 if x is None else int(x.shape[0])
+        if nq == 0:
+            res.ids = torch.zeros((0, k), dtype=torch.int64)
+            res.distances = torch.zeros((0, k), dtype=torch.float32)
+            res.values = torch.zeros((0, k), dtype=torch.int64)
+            res.counts, res.missing, res.totals = (torch.zeros((0,), dtype=torch.int64) for _ in range(3))
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        self._ctx.set_timing(1)
+        try:
+            out = self._ctx.order_search(self.parent._store if self.parent is not None else None, self._store, xd, nprobe, radius,
+                                         self.metric_, cols[name], k, descending=bool(flags & 1), missing_last=bool(flags & 2),
+                                         filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(0)
+        tm = out[6]
+        ti.n_queries = nq
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.ids, res.distances, res.values, res.counts, res.missing, res.totals = (o if on_dev else o.cpu() for o in out[:6])
         return res
 
     def make_filter(self, ids=None, exclude=False, where=None, any_of=None):

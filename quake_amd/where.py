@@ -5,7 +5,8 @@ ABI knows five ops over int64: RANGE / NOT_RANGE over a closed interval [a, b] (
 Python integers of any size and are saturated, not wrapped: a comparison with a number outside int64 means what it means over the
 integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
-lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search).
+lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search), lower_order
+the arguments of ordered search (QuakeIndex.ordered_search).
 Pure Python: importable without the library or a GPU."""
 
 INT64_MIN = -(1 << 63)
@@ -19,6 +20,9 @@ QK_MAX_EXPR_CLAUSES = 32
 QK_MAX_SET_VALUES = 1 << 20
 
 QK_MAX_FACET_EDGES = 255
+QK_MAX_ORDER_K = 1024
+QK_ORDER_DESC, QK_ORDER_MISSING_LAST = 1, 2
+MISSING = ("exclude", "last")
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
 SET_OPS = ("in", "not_in")  # lower_expr only
@@ -189,3 +193,20 @@ def lower_edges(names, edges, who="[QuakeIndex::facet_stats()]"):
         per = [edges] * len(names)
     lists = [_edge_list(e, n, who) for e, n in zip(per, names)]
     return [x for l in lists for x in l], [len(l) for l in lists]
+
+
+def lower_order(columns, order_by, k, descending=False, missing="exclude", who="[QuakeIndex::ordered_search()]"):
+    """The arguments of ordered search (include/quake_hip.h, "ordered search") -> (column name, k, flags): `columns` are the names
+    of the index's attribute columns, order_by one of them, 1 <= k <= QK_MAX_ORDER_K, missing "exclude" (hits without a value are
+    left out) or "last" (they follow the hits that have one); flags = QK_ORDER_DESC | QK_ORDER_MISSING_LAST as asked.  RuntimeError,
+    in this order: a name that is no string, an unknown column, k outside its bounds, another `missing`."""
+    if not isinstance(order_by, str):
+        raise RuntimeError("%s order_by must be the name of one attribute column, got %r" % (who, order_by))
+    if order_by not in columns:
+        raise RuntimeError("%s unknown attribute column '%s'" % (who, order_by))
+    k = _int(k, who + " k:")
+    if not 1 <= k <= QK_MAX_ORDER_K:
+        raise RuntimeError("%s k=%d must be between 1 and %d" % (who, k, QK_MAX_ORDER_K))
+    if not isinstance(missing, str) or missing not in MISSING:
+        raise RuntimeError("%s missing must be 'exclude' or 'last', got '%s'" % (who, missing))
+    return order_by, k, (QK_ORDER_DESC if descending else 0) | (QK_ORDER_MISSING_LAST if missing == "last" else 0)
