@@ -764,6 +764,54 @@ QK_API int qk_order_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, co
                          int64_t *out_values, int64_t *out_count, int64_t *out_missing, int64_t *out_total, int mem,
                          qk_timing *timing);
 
+/* ---- diversified search ------------------------------------------------------------------------------
+ * No reference counterpart.  Maximal marginal relevance (MMR): of the fetch_k nearest rows of a query keep k, chosen greedily -- each
+ * step takes the candidate that is close to the query and far from everything already taken (the near-duplicate chunks of a
+ * document that crowd a plain top-k).  Exact and bit for bit, like every other call.
+ * All values below are float32 in the domain the caller sees from qk_search: sqrt L2, squared L2 after qk_ctx_set_squared_l2(ctx, 1),
+ * the dot product for IP.  C = fetch_k, lambda in [0, 1], mu = fl(1 - lambda).
+ * Candidates: c_0 .. c_{n-1}, n <= C, are the non-padding entries of the row that qk_search (qk_search_filtered with a filter;
+ *   qk_scan / qk_scan_filtered for the pids form) returns for the query with k = C and the same other arguments, in that order --
+ *   the total order (key, id) -- with the reported distances r_0 .. r_{n-1}.  The index i is the candidate's RANK.
+ * Pairwise values: p(i, j) = the distance qk_search would report for the stored row of c_i when the query is the stored vector of
+ *   c_j: one k-ordered fp32 fmaf chain for the dot product, the expanded L2 form over the two stored norms with its clamp, the
+ *   correctly rounded sqrt unless squared L2 is set.  Symmetric.
+ * Selection: the first pick is rank 0.  While fewer than min(k, n) are picked, for every unpicked i:
+ *   N_i    = the most similar pairwise value to the picked set S: min over s in S of p(i, s) for L2, max for IP; NaN values are
+ *            ignored; if all are NaN the term is dropped and cost_i = fl(lambda * r_i)
+ *   cost_i = fl( fl(lambda * r_i) - fl(mu * N_i) ) -- three separately rounded float32 operations, no contraction
+ *   pick the smallest cost for L2, the largest for IP; a NaN cost (inf - inf, 0 * inf) loses to every non-NaN cost; ties, and the
+ *   all-NaN case, go to the smaller rank.
+ * Returned, in selection order:
+ *   out_ids  [Q][k]               padding -1 behind min(k, n)
+ *   out_dist [Q][k], may be NULL  the r values; padding +inf (L2) / -inf (IP)
+ *   out_rank [Q][k], may be NULL  int32, the rank of each pick; padding -1
+ * Consequences: lambda = 1 returns the first k entries of the qk_search(k = C) row, ids and distance bits equal; C == k returns a
+ * permutation of the qk_search(k) row; row q equals the call made with query q alone.  An id stored more than once takes the vector
+ * of its smallest arena row.
+ * Limits: 1 <= k <= fetch_k <= QK_MAX_FETCH_K = 256 (inside QK_MAX_K: the filtered tile form serves every C); k < 1 or
+ * fetch_k < k: QK_ERR_INVALID, fetch_k > 256: QK_ERR_UNSUPPORTED; a lambda that is NaN or outside [0, 1]: QK_ERR_INVALID; d up to
+ * QK_MAX_D; Q == 0: QK_OK; a filter of another store: QK_ERR_INVALID.  qk_diverse_scan: P >= 1, pids as for qk_scan_filtered (-1 /
+ * empty lists contribute nothing; host pids naming an absent list: QK_ERR_NOT_FOUND).  There is no form for qk_search_aps, the
+ * device group, per-query filter tables, adaptive probing or exact filtered search.
+ * Inside (qk_diverse.hip): the candidate search is the shipped one, called unchanged with k = C into a buffer of the context; behind
+ * it in the same enqueue, without a host wait, per group of at most 2^22 / C queries: k_diverse_insert (the distinct candidate ids
+ * claim slots of an open-addressing table of at least 2 * queries * C slots, atomicCAS), k_diverse_rows (one sweep over the stored
+ * ids of every live arena row; a row whose id is in the table writes its row there, atomicMin) and k_diverse_select (one workgroup
+ * per query, one lane per candidate; the query's C rows staged in LDS once when C * (dpad + 4) * 4 bytes fit 144 KiB, else the
+ * picked vector staged per step and the candidate rows re-read from the arena).  No kernel waits or spins on another.
+ * Workspace, kept on the context: Q * C * 12 bytes of candidates, 16 bytes per table slot (at most 128 MiB), and a host caller's
+ * staged buffers.
+ * timing: as the candidate search fills it; the re-ranking tail lies behind that search's events and is part of total_ms only,
+ * like the cut of an adaptive call.  qk_ctx_last_scan_kernel names the candidate search's kernel. */
+#define QK_MAX_FETCH_K 256
+QK_API int qk_diverse_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k,
+                             float lambda, int metric, qk_filter *filter /* or NULL */, int64_t *out_ids, float *out_dist,
+                             int32_t *out_rank, int mem, qk_timing *timing);
+QK_API int qk_diverse_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k,
+                           float lambda, int metric, qk_filter *filter /* or NULL */, int64_t *out_ids, float *out_dist, int32_t *out_rank,
+                           int mem, qk_timing *timing);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

@@ -143,6 +143,9 @@ SIGNATURES = {
                         [_int, C.POINTER(QkTiming)]),
     "qk_order_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _vp, _int, _int] + [_vp] * 6 +
                       [_int, C.POINTER(QkTiming)]),
+    # diversified search: (.., k, fetch_k, lambda, metric, filter, ids, dist, rank, mem, timing)
+    "qk_diverse_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, C.c_float, _int, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_diverse_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, C.c_float, _int, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
     "qk_filter_create_expr": (_int, [_vp, C.POINTER(QkExprClause), C.POINTER(_int), _int, C.POINTER(_vp)]),

@@ -101,6 +101,7 @@ def _empty_like_mem(shape, dtype, ref):
 QK_ORDER_DESC = 1          # include/quake_hip.h: the flags of ordered search
 QK_ORDER_MISSING_LAST = 2
 QK_MAX_ORDER_K = 1024
+QK_MAX_FETCH_K = 256       # diversified search
 
 
 def timing_dict(t):
@@ -668,6 +669,50 @@ class Context:
                                      order_by.h if order_by is not None else None, flags, k, *[_ptr(o) for o in out], mem,
                                      C.byref(t) if timing else None))
         return (*out, timing_dict(t)) if timing else tuple(out)
+
+    # ---- diversified search ------------------------------------------------------------------------------
+    @staticmethod
+    def _diverse_out(x, Q, k, fetch_k, want_dist, want_rank):
+        # (the library refuses a k outside its limits before it writes: the buffers of such a call only have to exist)
+        kk = k if 1 <= k <= fetch_k <= QK_MAX_FETCH_K else 1
+        return (_empty_like_mem((Q, kk), np.int64, x), _empty_like_mem((Q, kk), np.float32, x) if want_dist else None,
+                _empty_like_mem((Q, kk), np.int32, x) if want_rank else None)
+
+    def diverse_search(self, parent, store, x, nprobe, k, fetch_k, lambda_mult, metric, filter=None, want_dist=True, want_rank=True,
+                       timing=False):
+        """qk_diverse_search: per query, k of the fetch_k nearest rows (the row search / search_filtered returns with k = fetch_k)
+        chosen greedily by maximal marginal relevance with weight lambda_mult in [0, 1] (1: the plain top-k, 0: diversity only).
+        Returns (ids [Q, k] in selection order padded with -1, dist [Q, k] padded as search pads, rank [Q, k] int32 -- the position
+        of each pick in the candidate row, padding -1 --[, timing]) on x's device; dist / rank are None where not wanted."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        k, fetch_k = int(k), int(fetch_k)
+        ids, dist, rank = self._diverse_out(x, Q, k, fetch_k, want_dist, want_rank)
+        t = QkTiming()
+        check(self.lib.qk_diverse_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
+                                         float(lambda_mult), metric_code(metric), filter.h if filter is not None else None, _ptr(ids),
+                                         _ptr(dist) if dist is not None else None, _ptr(rank) if rank is not None else None, mem,
+                                         C.byref(t) if timing else None))
+        return (ids, dist, rank, timing_dict(t)) if timing else (ids, dist, rank)
+
+    def diverse_scan(self, store, x, pids, k, fetch_k, lambda_mult, metric, filter=None, want_dist=True, want_rank=True, timing=False):
+        """qk_diverse_scan: diverse_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
+        nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        if pids.ndim == 1:
+            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
+                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        mem = _mem_of(x, pids)
+        k, fetch_k = int(k), int(fetch_k)
+        ids, dist, rank = self._diverse_out(x, Q, k, fetch_k, want_dist, want_rank)
+        t = QkTiming()
+        check(self.lib.qk_diverse_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
+                                       fetch_k, float(lambda_mult), metric_code(metric), filter.h if filter is not None else None,
+                                       _ptr(ids), _ptr(dist) if dist is not None else None, _ptr(rank) if rank is not None else None,
+                                       mem, C.byref(t) if timing else None))
+        return (ids, dist, rank, timing_dict(t)) if timing else (ids, dist, rank)
 
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):

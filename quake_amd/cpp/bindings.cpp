@@ -183,6 +183,13 @@ PYBIND11_MODULE(_bindings, m) {
           },
           py::arg("columns"), py::arg("order_by"), py::arg("k"), py::arg("descending") = false, py::arg("missing") = "exclude",
           "the arguments of ordered_search -> (column name, k, flags of qk_order_search); needs no device (where.py's lower_order)");
+    m.def("lower_diverse",
+          [](int64_t k, int64_t fetch_k, double lambda_mult) {
+              const float lambda = lower_diverse(k, fetch_k, lambda_mult);
+              return py::make_tuple(k, fetch_k, (double)lambda);
+          },
+          py::arg("k"), py::arg("fetch_k"), py::arg("lambda_mult") = 0.5,
+          "the arguments of diverse_search -> (k, fetch_k, lambda_mult rounded to float32); needs no device (where.py's lower_diverse)");
     m.doc() = "quake_amd: MI355X-native Quake search path (same surface as quake._bindings)";
 
     py::class_<QuakeIndex, std::shared_ptr<QuakeIndex>>(m, "QuakeIndex")
@@ -273,6 +280,10 @@ PYBIND11_MODULE(_bindings, m) {
              "extension: per query, the search_params.k first of the vectors range_search returns for the same arguments by the "
              "attribute column `order_by` (ascending, or descending), ties to the nearer vector, then to the smaller id; missing: "
              "'exclude' or 'last'")
+        .def("diverse_search", &QuakeIndex::diverse_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
+             py::arg("lambda_mult") = 0.5,
+             "extension: per query, search_params.k of its fetch_k nearest vectors (what search() returns with k = fetch_k) chosen "
+             "greedily by maximal marginal relevance; lambda_mult in [0, 1]: 1 is the plain top-k, 0 diversity alone")
         .def("save", &QuakeIndex::save)
         .def("load", &QuakeIndex::load, py::arg("path"), py::arg("n_workers") = 0)
         .def("ntotal", &QuakeIndex::ntotal)
@@ -531,6 +542,13 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("totals", &OrderedSearchResult::totals)
         .def_readwrite("column", &OrderedSearchResult::column)
         .def_readwrite("timing_info", &OrderedSearchResult::timing_info);
+
+    py::class_<DiverseSearchResult, std::shared_ptr<DiverseSearchResult>>(m, "DiverseSearchResult")
+        .def(py::init<>())
+        .def_readwrite("ids", &DiverseSearchResult::ids)
+        .def_readwrite("distances", &DiverseSearchResult::distances)
+        .def_readwrite("ranks", &DiverseSearchResult::ranks)
+        .def_readwrite("timing_info", &DiverseSearchResult::timing_info);
 
     py::class_<SearchCursor, std::shared_ptr<SearchCursor>>(m, "SearchCursor")
         .def(py::init([](py::object keys, py::object ids) {  // (None: left undefined -- search_after refuses such a cursor)

@@ -218,6 +218,15 @@ struct OrderedSearchResult {
     shared_ptr<SearchTimingInfo> timing_info;
 };
 
+// extension (QuakeIndex::diverse_search): per query k of its fetch_k nearest vectors chosen by maximal marginal relevance, in
+// selection order: ids [Q, k] (padding -1), distances [Q, k] (padding as search pads), ranks [Q, k] int32 (padding -1)
+struct DiverseSearchResult {
+    Tensor ids;
+    Tensor distances;
+    Tensor ranks;
+    shared_ptr<SearchTimingInfo> timing_info;
+};
+
 struct Clustering {  // common.h:249-276
     Tensor centroids;
     Tensor partition_ids;

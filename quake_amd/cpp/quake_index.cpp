@@ -3,6 +3,7 @@
 #include "quake_index.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <chrono>
 #include <filesystem>
 #include <fstream>
@@ -217,6 +218,26 @@ shared_ptr<OrderedSearchResult> QuakeIndex::ordered_search(Tensor x, const std::
             if (kv.first == order_by) col = kv.second;
         }
     return query_coordinator_->ordered_search(x, col, known, order_by, sp, radius, descending, missing);
+}
+
+float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult) {
+    const std::string who = "[QuakeIndex::diverse_search()]";
+    if (k < 1) throw std::runtime_error(who + " k=" + std::to_string(k) + " must be at least 1");
+    if (fetch_k < k) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must be at least k=" + std::to_string(k));
+    if (fetch_k > QK_MAX_FETCH_K)
+        throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must not exceed " + std::to_string(QK_MAX_FETCH_K));
+    if (lambda_mult != lambda_mult) throw std::runtime_error(who + " lambda_mult is NaN");
+    if (!(lambda_mult >= 0.0 && lambda_mult <= 1.0)) {
+        char buf[64];
+        snprintf(buf, sizeof(buf), "%g", lambda_mult);
+        throw std::runtime_error(who + " lambda_mult=" + buf + " must lie in [0, 1]");
+    }
+    return (float)lambda_mult;
+}
+
+shared_ptr<DiverseSearchResult> QuakeIndex::diverse_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, double lambda_mult) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::diverse_search()] No query coordinator. Did you build the index?");
+    return query_coordinator_->diverse_search(x, sp, fetch_k, lambda_mult);
 }
 
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {

@@ -50,6 +50,10 @@ std::vector<std::vector<int64_t>> lower_edges(const std::vector<std::string> &na
 // unknown column, k outside 1 .. QK_MAX_ORDER_K, a `missing` that is neither "exclude" nor "last" -> the flags of qk_order_search
 int lower_order(const std::vector<std::string> &columns, const std::string &order_by, int64_t k, bool descending, const std::string &missing);
 
+// the arguments of diverse_search (where.py's lower_diverse: same rules, same errors as std::runtime_error, in the same order):
+// k < 1, fetch_k < k, fetch_k > QK_MAX_FETCH_K, a lambda_mult that is NaN or outside [0, 1] -> lambda_mult rounded to float32
+float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult);
+
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
     shared_ptr<QuakeIndex> parent_;
@@ -117,6 +121,9 @@ public:
     shared_ptr<OrderedSearchResult> ordered_search(Tensor x, const std::string &order_by, shared_ptr<SearchParams> search_params,
                                                    std::optional<float> radius = std::nullopt, bool descending = false,
                                                    const std::string &missing = "exclude");
+    // extension: diversified search -- search_params->k of the fetch_k nearest vectors of each query, chosen greedily by maximal
+    // marginal relevance with weight lambda_mult in [0, 1] (qk_diverse_search)
+    shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult = 0.5);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

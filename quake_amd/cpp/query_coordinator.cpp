@@ -894,6 +894,78 @@ shared_ptr<OrderedSearchResult> QueryCoordinator::ordered_search(Tensor x, qk_at
     return res;
 }
 
+shared_ptr<DiverseSearchResult> QueryCoordinator::diverse_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, double lambda_mult) {
+    const std::string who = "[QuakeIndex::diverse_search()]";
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::diverse_search] partition_manager_ is null.");
+    if (!sp->filters.empty() || sp->query_filter.defined())
+        throw std::runtime_error(who + " SearchParams.filters / query_filter (one filter per query) are not supported by diverse_search");
+    if (sp->filters_exact_rows != 0)
+        throw std::runtime_error(who + " SearchParams.filters_exact_rows (exact per-query filtered search) is not supported by "
+                                       "diverse_search");
+    if (sp->filter_exact_rows != 0)
+        throw std::runtime_error(who + " SearchParams.filter_exact_rows (exact filtered search) is not supported by diverse_search");
+    if (sp->max_nprobe > 0) throw std::runtime_error(who + " SearchParams.max_nprobe (adaptive probing) is not supported by diverse_search");
+    if (sp->recall_target > 0.0f) throw std::runtime_error(who + " diverse_search is not supported with recall_target > 0");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group()) throw std::runtime_error(who + " diverse_search is not supported with num_workers > 0");
+    if (!store) throw std::runtime_error("[QueryCoordinator::diverse_search] partitions are not initialized.");
+    const float lambda = lower_diverse(sp->k, fetch_k, lambda_mult);
+    const int64_t k = sp->k;
+    qk_filter *flt = nullptr;
+    if (sp->filter) {
+        if (!sp->filter->h) throw std::runtime_error(who + " SearchParams.filter must come from make_filter()");
+        if (sp->filter->owner != store) throw std::runtime_error(who + " the filter was made for another index");
+        flt = sp->filter->h;
+    }
+    auto res = std::make_shared<DiverseSearchResult>();
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->search_params = sp;
+    ti->n_clusters = partition_manager_->nlist();
+    if (!x.defined() || x.size(0) == 0) {
+        res->ids = torch::zeros({0, k}, torch::kInt64);
+        res->distances = torch::zeros({0, k}, torch::kFloat32);
+        res->ranks = torch::zeros({0, k}, torch::kInt32);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x);
+    BoundToTorchStream bound(ctx, xq);
+    const int64_t Q = xq.size(0);
+    const int nprobe = std::max(sp->nprobe, 1);
+    const int mem = on_dev ? QK_MEM_DEVICE : QK_MEM_HOST;
+    ti->n_queries = Q;
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
+    res->ids = torch::empty({Q, k}, i64);
+    res->distances = torch::empty({Q, k}, i64.dtype(torch::kFloat32));
+    res->ranks = torch::empty({Q, k}, i64.dtype(torch::kInt32));
+    qk_check(qk_diverse_search(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), Q, nprobe, (int)k, (int)fetch_k, lambda,
+                               (int)metric_, flt, res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(),
+                               res->ranks.data_ptr<int32_t>(), mem, &tm));
+    ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    if (parent_) {
+        ti->parent_info = std::make_shared<SearchTimingInfo>();
+        ti->parent_info->n_queries = Q;
+        ti->parent_info->n_clusters = 1;
+        ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
+    }
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
 shared_ptr<SearchResult> QueryCoordinator::scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> sp) {  // :659-673
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::scan_partitions] partition_manager_ is null.");
     if (!x.defined() || x.size(0) == 0) return empty_result(sp);

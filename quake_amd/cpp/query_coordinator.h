@@ -57,6 +57,9 @@ public:
     shared_ptr<OrderedSearchResult> ordered_search(Tensor x, qk_attr *col, const std::vector<std::string> &known, const std::string &order_by,
                                                    shared_ptr<SearchParams> search_params, std::optional<float> radius, bool descending,
                                                    const std::string &missing);
+    // extension (qk_diverse_search): search_params->k of the fetch_k nearest vectors of each query by maximal marginal relevance
+    // (lower_diverse runs behind the refusals)
+    shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

@@ -73,6 +73,7 @@ int qk_ctx_destroy(qk_ctx *c) {
     if (c->fb_qfilter) hipFree(c->fb_qfilter);
     if (c->after_buf) hipFree(c->after_buf);
     if (c->pool_buf) hipFree(c->pool_buf);
+    if (c->div_buf) hipFree(c->div_buf);
     if (c->xcd_host) hipHostFree(c->xcd_host);
     if (c->xcd_ev) hipEventDestroy(c->xcd_ev);
     for (auto &f : c->form_stats) {

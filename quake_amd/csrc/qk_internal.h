@@ -199,6 +199,10 @@ struct qk_ctx {
     char *pool_buf = nullptr;
     size_t pool_buf_cap = 0;
     std::vector<int64_t> pool_key;
+    // diversified search (qk_diverse.hip): the candidates of a call (ids, distances), the id -> arena row table of a group of its
+    // queries and the staging of a host caller's buffers; its own buffer because the candidate search recycles `ws` and `stage`
+    char *div_buf = nullptr;
+    size_t div_cap = 0;
 };
 
 int qk_ws_reserve(qk_ctx *ctx, size_t bytes);          // make sure the workspace can hold `bytes` (may sync+realloc)

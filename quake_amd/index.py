@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_edges, lower_expr, lower_order
+from .where import lower_diverse, lower_edges, lower_expr, lower_order
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -371,6 +371,18 @@ class OrderedSearchResult:
         self.missing = None
         self.totals = None
         self.column = None
+        self.timing_info = None
+
+
+class DiverseSearchResult:
+    """extension (QuakeIndex.diverse_search): per query k of its fetch_k nearest vectors, chosen by maximal marginal relevance, in
+    selection order: ids [Q, k] (padding -1), distances [Q, k] as search() reports them (padding as search pads), ranks [Q, k]
+    int32, the position of each pick among the query's fetch_k nearest (padding -1)"""
+
+    def __init__(self):
+        self.ids = None
+        self.distances = None
+        self.ranks = None
         self.timing_info = None
 
 
@@ -1354,6 +1366,73 @@ class QuakeIndex:
             ti.parent_info = pi
         ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
         res.ids, res.distances, res.values, res.counts, res.missing, res.totals = (o if on_dev else o.cpu() for o in out[:6])
+        return res
+
+    def diverse_search(self, x, search_params, fetch_k, lambda_mult=0.5):
+        """extension (no reference counterpart): diversified search -- of the fetch_k nearest vectors of each query (what search()
+        returns with k = fetch_k and the same nprobe / filter), search_params.k chosen greedily by maximal marginal relevance: the
+        first is the nearest, every further one minimises lambda_mult * distance to the query - (1 - lambda_mult) * distance to the
+        nearest vector already chosen (inner product: maximises, with the largest product to a chosen vector).  lambda_mult = 1 is
+        the plain top-k, 0 asks for diversity alone.  1 <= k <= fetch_k <= 256.  Exact (include/quake_hip.h, "diversified search").
+        Returns a DiverseSearchResult on x's device."""
+        who = "[QuakeIndex::diverse_search()]"
+        self._require_built(who + " No query coordinator. Did you build the index?")
+        sp = search_params
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError(who + " SearchParams.filters / query_filter (one filter per query) are not supported by diverse_search")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError(who + " SearchParams.filters_exact_rows (exact per-query filtered search) is not supported by "
+                               "diverse_search")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) != 0:
+            raise RuntimeError(who + " SearchParams.filter_exact_rows (exact filtered search) is not supported by diverse_search")
+        if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
+            raise RuntimeError(who + " SearchParams.max_nprobe (adaptive probing) is not supported by diverse_search")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError(who + " diverse_search is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError(who + " diverse_search is not supported with num_workers > 0")
+        k, fetch_k, lam = lower_diverse(sp.k, fetch_k, lambda_mult, who)
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError(who + " SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError(who + " the filter was made for another index")
+            flt = flt._h
+        res = DiverseSearchResult()
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        nq = 0 if x is None else int(x.shape[0])
+        if nq == 0:
+            res.ids = torch.zeros((0, k), dtype=torch.int64)
+            res.distances = torch.zeros((0, k), dtype=torch.float32)
+            res.ranks = torch.zeros((0, k), dtype=torch.int32)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        self._ctx.set_timing(1)
+        try:
+            out = self._ctx.diverse_search(self.parent._store if self.parent is not None else None, self._store, xd, nprobe, k, fetch_k,
+                                           lam, self.metric_, filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(0)
+        tm = out[3]
+        ti.n_queries = nq
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.ids, res.distances, res.ranks = (o if on_dev else o.cpu() for o in out[:3])
         return res
 
     def make_filter(self, ids=None, exclude=False, where=None, any_of=None):

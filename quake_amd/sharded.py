@@ -288,6 +288,11 @@ class ShardedIndex:
         self.dist.all_gather_into_tensor(buf.view(-1, t.shape[-1]), t.contiguous())
         return buf
 
+    def diverse_search(self, q, nprobe, k, fetch_k, lambda_mult=0.5):
+        """diversified search (QuakeIndex.diverse_search, qk_diverse_search) has no sharded form: the re-ranking needs the vectors
+        of every candidate of a query, which live on different ranks"""
+        raise RuntimeError("[ShardedIndex::diverse_search()] diverse_search is not supported by sharded.py")
+
     def search(self, q, nprobe, k, out=None):
         import torch
         Q = q.shape[0]

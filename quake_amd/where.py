@@ -6,7 +6,7 @@ Python integers of any size and are saturated, not wrapped: a comparison with a 
 integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
 lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search), lower_order
-the arguments of ordered search (QuakeIndex.ordered_search).
+the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search).
 Pure Python: importable without the library or a GPU."""
 
 INT64_MIN = -(1 << 63)
@@ -23,6 +23,7 @@ QK_MAX_FACET_EDGES = 255
 QK_MAX_ORDER_K = 1024
 QK_ORDER_DESC, QK_ORDER_MISSING_LAST = 1, 2
 MISSING = ("exclude", "last")
+QK_MAX_FETCH_K = 256
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
 SET_OPS = ("in", "not_in")  # lower_expr only
@@ -210,3 +211,38 @@ def lower_order(columns, order_by, k, descending=False, missing="exclude", who="
     if not isinstance(missing, str) or missing not in MISSING:
         raise RuntimeError("%s missing must be 'exclude' or 'last', got '%s'" % (who, missing))
     return order_by, k, (QK_ORDER_DESC if descending else 0) | (QK_ORDER_MISSING_LAST if missing == "last" else 0)
+
+
+def _to_f32(v):
+    """v in [0, 1] rounded to the nearest float32, ties to even (this module imports nothing)"""
+    if v == 0.0:
+        return v
+    e, p = 0, 1.0
+    while p > v and e > -126:   # p = 2^e <= v < 2^(e + 1), or the subnormal range
+        p /= 2.0
+        e -= 1
+    ulp = p / 8388608.0          # 2^(e - 23): every step is a scaling by a power of two, so nothing but round() rounds
+    return round(v / ulp) * ulp
+
+
+def lower_diverse(k, fetch_k, lambda_mult=0.5, who="[QuakeIndex::diverse_search()]"):
+    """The arguments of diversified search (include/quake_hip.h, "diversified search") -> (k, fetch_k, lambda): 1 <= k <= fetch_k <=
+    QK_MAX_FETCH_K, lambda_mult a number in [0, 1]; lambda is lambda_mult rounded to float32, the value qk_diverse_search computes
+    with.  RuntimeError, in this order: k or fetch_k no integer, k < 1, fetch_k < k, fetch_k above the limit, a lambda_mult that is
+    no number, NaN, or outside [0, 1]."""
+    k = _int(k, who + " k:")
+    fetch_k = _int(fetch_k, who + " fetch_k:")
+    if k < 1:
+        raise RuntimeError("%s k=%d must be at least 1" % (who, k))
+    if fetch_k < k:
+        raise RuntimeError("%s fetch_k=%d must be at least k=%d" % (who, fetch_k, k))
+    if fetch_k > QK_MAX_FETCH_K:
+        raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_MAX_FETCH_K))
+    if isinstance(lambda_mult, bool) or not isinstance(lambda_mult, (int, float)):
+        raise RuntimeError("%s lambda_mult must be a number in [0, 1], got %r" % (who, lambda_mult))
+    lam = float(lambda_mult)
+    if lam != lam:
+        raise RuntimeError("%s lambda_mult is NaN" % who)
+    if not 0.0 <= lam <= 1.0:
+        raise RuntimeError("%s lambda_mult=%g must lie in [0, 1]" % (who, lam))
+    return k, fetch_k, _to_f32(lam)
