@@ -63,6 +63,15 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _pids_rows(pids, Q):
+    """pids as [Q, P]: a one-dimensional list is the same set for every query (query_coordinator.cpp:506-508)"""
+    if pids.ndim != 1:
+        return pids
+    if _is_torch(pids):
+        return pids[None, :].expand(Q, -1).contiguous()
+    return np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0])))
+
+
 def _i32_with(a, ref):
     """`a` as a contiguous int32 vector in the memory space of `ref` (numpy on the host, torch on ref's device)"""
     if _is_torch(ref) and ref.is_cuda:
@@ -205,9 +214,7 @@ class Context:
         an int32 array / tensor of shape [Q], on the host or on the device with x (qk_scan_filtered_batch)"""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:  # same set for every query (query_coordinator.cpp:506-508)
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
         out_i = _empty_like_mem((Q, k), np.int64, x)
         out_d = _empty_like_mem((Q, k), np.float32, x)
@@ -401,9 +408,7 @@ class Context:
         """qk_scan_after: search_after over the given lists (pids as in scan())"""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
         ak, ai = self._after(after, x)
         out_i = _empty_like_mem((Q, k), np.int64, x)
@@ -473,9 +478,7 @@ class Context:
         contribute nothing; a query's hits follow the order of its pids row."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
 
         def call(c, lims, ids, dist, t):
@@ -517,9 +520,7 @@ class Context:
         contribute nothing.  group_size as for search_grouped (qk_scan_grouped_n)."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
         out_i, out_d, out_g = self._grouped_out(x, Q, k, group_size, out)
         t = QkTiming()
@@ -565,9 +566,7 @@ class Context:
         contribute nothing."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
         harr, C_, n, out = self._facet_args(x, Q, facet_by, n_values, out)
         t = QkTiming()
@@ -614,9 +613,7 @@ class Context:
         lists contribute nothing."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
         harr, C_, earr, narr, out = self._facet_stats_args(x, Q, attrs, edges)
         t = QkTiming()
@@ -658,9 +655,7 @@ class Context:
         contribute nothing."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
         k, flags, out = self._order_args(x, Q, k, descending, missing_last)
         t = QkTiming()
@@ -701,9 +696,7 @@ class Context:
         nothing."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         mem = _mem_of(x, pids)
         k, fetch_k = int(k), int(fetch_k)
         ids, dist, rank = self._diverse_out(x, Q, k, fetch_k, want_dist, want_rank)
@@ -1396,9 +1389,7 @@ class Group:
         """scan_partitions with workers (worker_scan): pids [Q, P] (or [P]: the same set for every query), -1 = skip"""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
-        if pids.ndim == 1:
-            pids = (pids[None, :].expand(Q, -1).contiguous() if _is_torch(pids)
-                    else np.ascontiguousarray(np.broadcast_to(pids[None, :], (Q, pids.shape[0]))))
+        pids = _pids_rows(pids, Q)
         out_i = _empty_like_mem((Q, k), np.int64, x)
         out_d = _empty_like_mem((Q, k), np.float32, x)
         t = QkTiming()

@@ -179,11 +179,6 @@ int qk_launch_filter_build_expr(qk_ctx *ctx, qk_store *s, qk_filter *f);
 // are the clauses' stamps those of their columns (both predicate kinds)
 bool qk_filter_where_current(const qk_filter *f);
 
-// qk_grouped.hip: the k best groups of `col` per query over the probed lists (`a` as for qk_range_device, k and out_* set);
-// col's row values are up to date (the caller ensured them), mask: a filter's row mask or nullptr; out_groups [Q][k] or nullptr.
-// m = group_size: out_ids / out_dist are [Q][k][m], the m best rows of every group; m == 1 is the one-row call, launch for launch
-int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data &col, const uint16_t *mask, int m, int64_t *out_groups,
-                      qk_timing *timing, int64_t *n_passes);
 // qk_grouped.hip: rv_vals / rv_has of the column brought up to date for the store as it is (the table has been synced) on ctx's
 // stream, and the slots of a query's open-addressing table: the power of two >= max(16, 2 * min(per_query_ub, n_ids))
 int qk_rowvals_ensure(qk_ctx *ctx, qk_store *s, qk_attr_data &d);

@@ -26,6 +26,35 @@ struct FacetParams {
     int64_t max_ids;           // the largest number of ids with a value among the call's columns
 };
 
+// F for a sweep over the whole pass p (one group): every field set, no tables, total and missing still to be placed in the
+// caller's bytes of the pass; the entries of has / rowval behind column C repeat column 0.  S: slices a query can have
+inline void facet_params_fill(FacetParams &F, const qk_emit_pass &p, const qk_store *s, const uint16_t *mask, qk_attr_data *const *cols, int C,
+                              uint32_t key_lo, uint32_t key_hi, int P, int64_t S) {
+    F.keys = p.keys;
+    F.pair_base = p.pair_base;
+    F.pids = p.pids;
+    F.pt_off = s->d_off;
+    F.mask = mask;
+    for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
+        F.has[c] = cols[c < C ? c : 0]->rv_has;
+        F.rowval[c] = cols[c < C ? c : 0]->rv_vals;
+    }
+    F.tvals = nullptr;
+    F.tcnt = nullptr;
+    F.total = nullptr;
+    F.missing = nullptr;
+    F.nq = p.nq;
+    F.g0 = 0;
+    F.ng = p.nq;
+    F.P = P;
+    F.Sg = qk_emit_sg(S, p.nq);
+    F.C = C;
+    F.tmask = 0;
+    F.key_lo = key_lo;
+    F.key_hi = key_hi;
+    F.max_ids = 0;
+}
+
 // is the key at absolute position pos a hit (k_range_count's test); *row: its arena row when it passed the key interval
 __device__ __forceinline__ bool facet_hit(const FacetParams &F, const int64_t *pbase, const int64_t *qpids, int64_t pos, int64_t lim, int64_t *row) {
     const uint32_t key = pos < lim ? F.keys[pos] : 0xFFFFFFFFu;

@@ -21,8 +21,11 @@
 // No thread waits for another and every loop is bounded.  Only integer additions decide a counter, so the result is a pure function
 // of the store, the columns and the call.  The value whose bits are all ones (-1) is the table's empty marker: it owns the slot
 // behind the used ones.
-// Second part (behind facet_run): facet statistics -- count, min, max, exact sum and fixed-edge histograms over the same hits, one
+// Second part (behind facet_call): facet statistics -- count, min, max, exact sum and fixed-edge histograms over the same hits, one
 // sweep per pass and no table (k_facet_stats, k_facet_stats_finish).
+// The host side of both parts is their kernels plus one description each: facet_call / facet_stats_call state the call for
+// qk_emit_run (qk_emit.hip), the host body of every entry point on the emission scan, and facet_device / facet_stats_device hang
+// the launches into qk_emit_device's skeleton.  FacetParams is filled in one place (facet_params_fill, qk_facet.h).
 #include "qk_facet.h"
 
 #include <cstring>
@@ -328,37 +331,27 @@ __global__ __launch_bounds__(256) void k_facet_select(FacetSelectParams S) {
 // bytes of the tables one query accounts for: 12 per slot of every column
 inline int64_t facet_table_bytes(int64_t T, int C) { return (int64_t)C * (T + 1) * 12; }
 
-int facet_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *const *cols, int C, int n_values, uint32_t key_lo,
-                 uint32_t key_hi, const uint16_t *mask, int64_t *out_values, int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing,
-                 int64_t *out_total, qk_timing *timing, int64_t *n_passes) {
-    const int64_t Q = a.Q;
-    hipStream_t st = ctx->stream;
-    const int npids = (int)s->parts.size();
-    const int P = a.all_lists ? npids : a.P;
-    *n_passes = 0;
-    qk_phase_events pe;
-    pe.ctx = ctx;
-    pe.tm = ctx->timing && timing;
-    pe.dtm = false;
-    pe.ev_base = 4;
-    if (P <= 0 || npids <= 0) {  // no lists: no hits
-        QK_TRY(pe.mark(0));
-        QK_TRY(qk_prep_flush(ctx));
-        QK_HIP(hipMemsetAsync(out_values, 0, (size_t)C * Q * n_values * 8, st));
-        QK_HIP(hipMemsetAsync(out_counts, 0, (size_t)C * Q * n_values * 8, st));
-        if (out_distinct) QK_HIP(hipMemsetAsync(out_distinct, 0, (size_t)C * Q * 8, st));
-        if (out_missing) QK_HIP(hipMemsetAsync(out_missing, 0, (size_t)C * Q * 8, st));
-        if (out_total) QK_HIP(hipMemsetAsync(out_total, 0, (size_t)Q * 8, st));
-        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
+// the device half of facet counts; o: the call's output table on the device -- values, counts, distinct, missing, total
+int facet_device(const qk_emit_call &c, qk_emit_env &e, int n_values, const qk_emit_out *o) {
+    qk_store *s = c.s;
+    qk_attr_data *const *cols = c.cols;
+    const int C = c.n_cols, P = e.P;
+    const int64_t Q = e.a.Q;
+    hipStream_t st = c.ctx->stream;
+    int64_t *out_values = (int64_t *)o[0].dev, *out_counts = (int64_t *)o[1].dev, *out_distinct = (int64_t *)o[2].dev;
+    int64_t *out_missing = (int64_t *)o[3].dev, *out_total = (int64_t *)o[4].dev;
+    qk_emit_stages g;
+    g.pad = [&]() -> int {  // no hits
+        for (int i = 0; i < 5; i++)
+            if (o[i].dev) QK_HIP(hipMemsetAsync(o[i].dev, 0, o[i].bytes, st));
         return QK_OK;
-    }
+    };
     int64_t max_ids = cols[0]->n_ids;  // one table size for every column of the call: that of the column with the most values
-    for (int c = 1; c < C; c++) max_ids = std::max(max_ids, cols[c]->n_ids);
+    for (int i = 1; i < C; i++) max_ids = std::max(max_ids, cols[i]->n_ids);
     // this pipeline's bytes of the call's buffer, sized for the largest pass: [table values] [table counters] [total] [missing]
     int64_t T = 0, S = 0, qt = 1;  // qt: queries whose tables fit QK_GROUPED_PASS_BYTES -- a pass's queries are counted in groups of qt
     size_t o_tcnt = 0, o_total = 0, o_missing = 0;
-    qk_emit_hooks h;
-    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+    g.h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
         T = qk_grouped_table_slots(per_query_ub, max_ids);
         const int64_t qbytes = facet_table_bytes(T, C);
         if (qbytes > QK_GROUPED_PASS_BYTES)
@@ -373,38 +366,21 @@ int facet_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *
         *extra_bytes = o_missing + qk_al256((size_t)*qc * C * 4);
         return QK_OK;
     };
-    h.before_scan = [&](const qk_emit_pass &p) -> int {
+    g.h.before_scan = [&](const qk_emit_pass &p) -> int {
         // total and missing of the pass (missing lies behind total: one memset); the tables are cleared behind the hit count, as far
         // as they are used (k_facet_clear)
         QK_HIP(hipMemsetAsync(p.extra + o_total, 0, (o_missing - o_total) + (size_t)p.nq * C * 4, st));
         return QK_OK;
     };
-    h.consume = [&](const qk_emit_pass &p) -> int {
+    g.h.consume = [&](const qk_emit_pass &p) -> int {
         FacetParams F;
-        F.keys = p.keys;
-        F.pair_base = p.pair_base;
-        F.pids = p.pids;
-        F.pt_off = s->d_off;
-        F.mask = mask;
-        for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
-            F.has[c] = cols[c < C ? c : 0]->rv_has;
-            F.rowval[c] = cols[c < C ? c : 0]->rv_vals;
-        }
+        facet_params_fill(F, p, s, e.mask, cols, C, e.key_lo, e.key_hi, P, S);
         F.tvals = (unsigned long long *)p.extra;
         F.tcnt = (uint32_t *)(p.extra + o_tcnt);
         F.total = (uint32_t *)(p.extra + o_total);
         F.missing = (uint32_t *)(p.extra + o_missing);
-        F.nq = p.nq;
-        F.P = P;
-        F.C = C;
         F.tmask = (uint32_t)(T - 1);
-        F.key_lo = key_lo;
-        F.key_hi = key_hi;
         F.max_ids = max_ids;
-        // about 16384 workgroups per launch, whatever S is
-        F.g0 = 0;
-        F.ng = p.nq;
-        F.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));
         hipLaunchKernelGGL(k_facet_hits, dim3((unsigned)(p.nq * F.Sg)), dim3(256), 0, st, F);
         FacetSelectParams L;
         L.tvals = F.tvals;
@@ -426,7 +402,7 @@ int facet_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *
         for (int64_t g0 = 0; g0 < p.nq; g0 += qt) {
             F.g0 = L.g0 = g0;
             F.ng = L.ng = std::min(qt, p.nq - g0);
-            F.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / F.ng));
+            F.Sg = qk_emit_sg(S, F.ng);
             hipLaunchKernelGGL(k_facet_clear, dim3((unsigned)(F.ng * C)), dim3(256), 0, st, F);
             hipLaunchKernelGGL(k_facet_count, dim3((unsigned)(F.ng * F.Sg)), dim3(256), 0, st, F);
             hipLaunchKernelGGL(k_facet_select, dim3((unsigned)(F.ng * C)), dim3(256), 0, st, L);
@@ -434,85 +410,47 @@ int facet_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *
         QK_HIP(hipGetLastError());
         return QK_OK;
     };
-    QK_TRY(qk_emit_passes(ctx, s, a, P, "facet counts", pe, h, n_passes));
-    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
-    ctx->last_scan_kernel = wide ? "k_scan_wide (facet)" : "k_scan (facet)";
-    QK_TRY(pe.mark(3));
+    return qk_emit_device(c, e, g);
+}
+
+// the checks both facet calls make of their columns, behind those of n_cols; fills c.cols / c.n_cols
+int facet_check_cols(qk_emit_call &c, qk_attr *const *facet_by, int n_cols) {
+    if (!facet_by) QK_FAIL(QK_ERR_INVALID, "%s: facet_by is null", c.who);
+    for (int i = 0; i < n_cols; i++) {
+        if (!facet_by[i]) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d is null", c.who, i);
+        c.cols[i] = facet_by[i]->d.get();
+        if (c.cols[i]->store_uid != c.s->uid) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d belongs to another store", c.who, i);
+    }
+    c.n_cols = n_cols;
     return QK_OK;
 }
 
-// the body of both entry points: parent == nullptr && pids == nullptr -> every list
-int facet_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
-              int metric, float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, int n_values, int64_t *out_values,
-              int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem, qk_timing *timing) {
-    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
-    if (radius != radius) QK_FAIL(QK_ERR_INVALID, "%s: the radius is NaN", who);
-    if (n_cols < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_cols=%d must be at least 1", who, n_cols);
-    if (n_cols > QK_MAX_FACET_COLS) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_cols=%d exceeds QK_MAX_FACET_COLS=%d", who, n_cols, QK_MAX_FACET_COLS);
-    if (n_values < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_values=%d must be at least 1", who, n_values);
-    if (n_values > QK_MAX_FACET_VALUES)
-        QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_values=%d exceeds QK_MAX_FACET_VALUES=%d", who, n_values, QK_MAX_FACET_VALUES);
-    if (!facet_by) QK_FAIL(QK_ERR_INVALID, "%s: facet_by is null", who);
-    qk_attr_data *cols[QK_MAX_FACET_COLS] = {nullptr, nullptr, nullptr, nullptr};
-    for (int c = 0; c < n_cols; c++) {
-        if (!facet_by[c]) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d is null", who, c);
-        cols[c] = facet_by[c]->d.get();
-        if (cols[c]->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d belongs to another store", who, c);
-    }
-    if (Q < 0 || (Q > 0 && (!x || !out_values || !out_counts))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
-    QK_TRY(qk_check_overflow(ctx));
-    QK_HIP(hipSetDevice(ctx->device));
-    if (timing) memset(timing, 0, sizeof(*timing));
-    if (Q == 0) return QK_OK;
-    hipStream_t st = ctx->stream;
-    // ---- staging, query preparation, coarse; a host caller's outputs on the device: [values] [counts] [distinct] [missing] [total]
-    const size_t bv = qk_al256((size_t)n_cols * Q * n_values * 8), bc = qk_al256((size_t)n_cols * Q * 8), bt = qk_al256((size_t)Q * 8);
-    qk_scan_args sa;
-    char *out = nullptr;
-    bool have_coarse = false;
-    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, 2 * bv + 2 * bc + bt, timing != nullptr, &sa, &out,
-                             &have_coarse));
-    int64_t *dvalues = out_values, *dcounts = out_counts, *ddistinct = out_distinct, *dmissing = out_missing, *dtotal = out_total;
-    if (mem == QK_MEM_HOST) {
-        dvalues = (int64_t *)out;
-        dcounts = (int64_t *)(out + bv);
-        ddistinct = out_distinct ? (int64_t *)(out + 2 * bv) : nullptr;
-        dmissing = out_missing ? (int64_t *)(out + 2 * bv + bc) : nullptr;
-        dtotal = out_total ? (int64_t *)(out + 2 * bv + 2 * bc) : nullptr;
-    }
-    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
-    if (!qk_range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
-        key_lo = 1;
-        key_hi = 0;
-    }
-    // ---- row values and mask, then emission + counting + selection -------------------------------------------------------------
-    const uint16_t *mask = nullptr;
-    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
-    QK_TRY(qk_store_sync_table(s));
-    for (int c = 0; c < n_cols; c++) {
-        bool seen = false;  // (the same column twice: derived once)
-        for (int e = 0; e < c; e++) seen = seen || cols[e] == cols[c];
-        if (!seen) QK_TRY(qk_rowvals_ensure(ctx, s, *cols[c]));
-    }
-    int64_t n_passes = 0;
-    QK_TRY(facet_device(ctx, s, sa, cols, n_cols, n_values, key_lo, key_hi, mask, dvalues, dcounts, ddistinct, dmissing, dtotal, timing,
-                        &n_passes));
-    // ---- results back ------------------------------------------------------------------------------------------------------------
-    if (mem == QK_MEM_HOST) {
-        QK_HIP(hipMemcpyAsync(out_values, dvalues, (size_t)n_cols * Q * n_values * 8, hipMemcpyDeviceToHost, st));
-        QK_HIP(hipMemcpyAsync(out_counts, dcounts, (size_t)n_cols * Q * n_values * 8, hipMemcpyDeviceToHost, st));
-        if (out_distinct) QK_HIP(hipMemcpyAsync(out_distinct, ddistinct, (size_t)n_cols * Q * 8, hipMemcpyDeviceToHost, st));
-        if (out_missing) QK_HIP(hipMemcpyAsync(out_missing, dmissing, (size_t)n_cols * Q * 8, hipMemcpyDeviceToHost, st));
-        if (out_total) QK_HIP(hipMemcpyAsync(out_total, dtotal, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
-        QK_HIP(hipStreamSynchronize(st));
-    }
-    if (timing) {
-        QK_HIP(hipStreamSynchronize(st));
-        timing->n_items = n_passes;
-        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
-    }
-    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
-    return QK_OK;
+// both entry points behind their first two checks: the description of the call for qk_emit_run (qk_emit.hip)
+int facet_call(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+               int metric, float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, int n_values, int64_t *out_values,
+               int64_t *out_counts, int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem, qk_timing *timing) {
+    // [values] [counts] [distinct] [missing] [total]
+    const size_t bv = (size_t)n_cols * Q * n_values * 8, bc = (size_t)n_cols * Q * 8;
+    qk_emit_out outs[5] = {{out_values, bv, true}, {out_counts, bv, true}, {out_distinct, bc, false}, {out_missing, bc, false},
+                           {out_total, (size_t)Q * 8, false}};
+    qk_emit_call c;
+    c.who = who;
+    c.pipeline = "facet counts";
+    c.label = "k_scan (facet)";
+    c.label_wide = "k_scan_wide (facet)";
+    c.ctx = ctx, c.parent = parent, c.s = s, c.x = x, c.Q = Q, c.pids = pids, c.P = P, c.nprobe = nprobe, c.metric = metric, c.mem = mem;
+    c.radius = radius, c.filter = filter, c.timing = timing;
+    c.outs = outs, c.n_outs = 5;
+    c.check = [&]() -> int {
+        if (n_cols < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_cols=%d must be at least 1", who, n_cols);
+        if (n_cols > QK_MAX_FACET_COLS) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_cols=%d exceeds QK_MAX_FACET_COLS=%d", who, n_cols, QK_MAX_FACET_COLS);
+        if (n_values < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_values=%d must be at least 1", who, n_values);
+        if (n_values > QK_MAX_FACET_VALUES)
+            QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_values=%d exceeds QK_MAX_FACET_VALUES=%d", who, n_values, QK_MAX_FACET_VALUES);
+        return facet_check_cols(c, facet_by, n_cols);
+    };
+    c.device = [&](qk_emit_env &e) -> int { return facet_device(c, e, n_values, outs); };
+    return qk_emit_run(c);
 }
 
 // ---- second part: facet statistics (include/quake_hip.h, "facet statistics") ----------------------------------------
@@ -730,23 +668,16 @@ struct FacetStatsOut {
     int64_t *count, *missing, *vmin, *vmax, *sum_lo, *sum_hi, *hist, *total;
 };
 
-int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *const *cols, int C, const int64_t *edges,
-                       const int *n_edges, int hist_stride, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask, const FacetStatsOut &o,
-                       qk_timing *timing, int64_t *n_passes) {
-    const int64_t Q = a.Q;
-    hipStream_t st = ctx->stream;
-    const int npids = (int)s->parts.size();
-    const int P = a.all_lists ? npids : a.P;
-    *n_passes = 0;
-    qk_phase_events pe;
-    pe.ctx = ctx;
-    pe.tm = ctx->timing && timing;
-    pe.dtm = false;
-    pe.ev_base = 4;
+// the device half of facet statistics; o: the call's outputs on the device (nullptr: not wanted), edges / n_edges: host memory
+int facet_stats_device(const qk_emit_call &c, qk_emit_env &e, const int64_t *edges, const int *n_edges, int hist_stride,
+                       const FacetStatsOut &o) {
+    qk_store *s = c.s;
+    const int C = c.n_cols, P = e.P;
+    const int64_t Q = e.a.Q;
+    hipStream_t st = c.ctx->stream;
     const int64_t CQ = (int64_t)C * Q;
-    if (P <= 0 || npids <= 0) {  // no lists: no hits -- zeros, and the identities of min / max
-        QK_TRY(pe.mark(0));
-        QK_TRY(qk_prep_flush(ctx));
+    qk_emit_stages g;
+    g.pad = [&]() -> int {  // no hits: zeros, and the identities of min / max
         for (int64_t *p : {o.count, o.missing, o.sum_lo, o.sum_hi})
             if (p) QK_HIP(hipMemsetAsync(p, 0, (size_t)CQ * 8, st));
         if (o.hist) QK_HIP(hipMemsetAsync(o.hist, 0, (size_t)CQ * hist_stride * 8, st));
@@ -754,14 +685,13 @@ int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_
         if (o.vmin) hipLaunchKernelGGL(k_facet_stats_fill, dim3((unsigned)((CQ + 255) / 256)), dim3(256), 0, st, o.vmin, CQ, INT64_MAX);
         if (o.vmax) hipLaunchKernelGGL(k_facet_stats_fill, dim3((unsigned)((CQ + 255) / 256)), dim3(256), 0, st, o.vmax, CQ, INT64_MIN);
         QK_HIP(hipGetLastError());
-        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
         return QK_OK;
-    }
+    };
     int n_all = 0, e_off[QK_MAX_FACET_COLS] = {0, 0, 0, 0}, ne[QK_MAX_FACET_COLS] = {0, 0, 0, 0};
-    for (int c = 0; c < C; c++) {
-        e_off[c] = n_all;
-        ne[c] = n_edges ? n_edges[c] : 0;
-        n_all += ne[c];
+    for (int i = 0; i < C; i++) {
+        e_off[i] = n_all;
+        ne[i] = n_edges ? n_edges[i] : 0;
+        n_all += ne[i];
     }
     // bins are kept only where some column of a wanted histogram has edges to search: the single bucket of E == 0 is the count
     const int bin_stride = o.hist && n_all > 0 ? hist_stride : 0;
@@ -769,8 +699,7 @@ int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_
     // [total] [missing] [sum_lo] [sum_hi] [max] [bins] | [min] | [edges]   (zero bytes | all ones | uploaded once)
     int64_t S = 0;
     size_t o_missing = 0, o_sum_lo = 0, o_sum_hi = 0, o_max = 0, o_bins = 0, o_min = 0, o_edges = 0;
-    qk_emit_hooks h;
-    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+    g.h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
         const int64_t qbytes = 4 + (int64_t)C * 36 + (int64_t)C * bin_stride * 4;
         *qc = std::max<int64_t>(1, std::min<int64_t>(*qc, QK_GROUPED_PASS_BYTES / qbytes));
         S = (per_query_ub + FC_SLICE - 1) / FC_SLICE;
@@ -786,7 +715,7 @@ int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_
         *extra_bytes = o_edges + qk_al256((size_t)n_all * 8);
         return QK_OK;
     };
-    h.before_scan = [&](const qk_emit_pass &p) -> int {
+    g.h.before_scan = [&](const qk_emit_pass &p) -> int {
         QK_HIP(hipMemsetAsync(p.extra, 0, o_min, st));
         QK_HIP(hipMemsetAsync(p.extra + o_min, 0xFF, (size_t)p.nq * C * 8, st));
         // the edges, once per call: a stream-ordered copy from the caller's pageable memory.  As everywhere in this library
@@ -797,34 +726,16 @@ int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_
             QK_HIP(hipMemcpyAsync(p.extra + o_edges, edges, (size_t)n_all * 8, hipMemcpyHostToDevice, st));
         return QK_OK;
     };
-    h.consume = [&](const qk_emit_pass &p) -> int {
+    g.h.consume = [&](const qk_emit_pass &p) -> int {
         FacetStatsParams T;
         FacetParams &F = T.F;
-        F.keys = p.keys;
-        F.pair_base = p.pair_base;
-        F.pids = p.pids;
-        F.pt_off = s->d_off;
-        F.mask = mask;
-        for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
-            F.has[c] = cols[c < C ? c : 0]->rv_has;
-            F.rowval[c] = cols[c < C ? c : 0]->rv_vals;
-            T.e_off[c] = e_off[c];
-            T.n_edges[c] = ne[c];
-        }
-        F.tvals = nullptr;
-        F.tcnt = nullptr;
+        facet_params_fill(F, p, s, e.mask, c.cols, C, e.key_lo, e.key_hi, P, S);
         F.total = (uint32_t *)p.extra;
         F.missing = (uint32_t *)(p.extra + o_missing);
-        F.nq = p.nq;
-        F.g0 = 0;
-        F.ng = p.nq;
-        F.P = P;
-        F.C = C;
-        F.tmask = 0;
-        F.key_lo = key_lo;
-        F.key_hi = key_hi;
-        F.max_ids = 0;
-        F.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));  // about 16384 workgroups, whatever S is
+        for (int i = 0; i < QK_MAX_FACET_COLS; i++) {
+            T.e_off[i] = e_off[i];
+            T.n_edges[i] = ne[i];
+        }
         T.edges = (const int64_t *)(p.extra + o_edges);
         T.hist_stride = bin_stride;
         T.sum_lo = (unsigned long long *)(p.extra + o_sum_lo);
@@ -847,7 +758,7 @@ int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_
         L.C = C;
         L.bin_stride = bin_stride;
         L.hist_stride = hist_stride;
-        for (int c = 0; c < QK_MAX_FACET_COLS; c++) L.n_edges[c] = ne[c];
+        for (int i = 0; i < QK_MAX_FACET_COLS; i++) L.n_edges[i] = ne[i];
         L.out_count = o.count;
         L.out_missing = o.missing;
         L.out_min = o.vmin;
@@ -861,95 +772,57 @@ int facet_stats_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_
         QK_HIP(hipGetLastError());
         return QK_OK;
     };
-    QK_TRY(qk_emit_passes(ctx, s, a, P, "facet statistics", pe, h, n_passes));
-    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
-    ctx->last_scan_kernel = wide ? "k_scan_wide (facet stats)" : "k_scan (facet stats)";
-    QK_TRY(pe.mark(3));
-    return QK_OK;
+    return qk_emit_device(c, e, g);
 }
 
-// the body of both entry points: parent == nullptr && pids == nullptr -> every list
-int facet_stats_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P,
-                    int nprobe, int metric, float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, const int64_t *edges,
-                    const int *n_edges, const FacetStatsOut &out, int mem, qk_timing *timing) {
-    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
-    if (radius != radius) QK_FAIL(QK_ERR_INVALID, "%s: the radius is NaN", who);
-    if (n_cols < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_cols=%d must be at least 1", who, n_cols);
-    if (n_cols > QK_MAX_FACET_COLS) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_cols=%d exceeds QK_MAX_FACET_COLS=%d", who, n_cols, QK_MAX_FACET_COLS);
-    if (!facet_by) QK_FAIL(QK_ERR_INVALID, "%s: facet_by is null", who);
-    qk_attr_data *cols[QK_MAX_FACET_COLS] = {nullptr, nullptr, nullptr, nullptr};
-    for (int c = 0; c < n_cols; c++) {
-        if (!facet_by[c]) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d is null", who, c);
-        cols[c] = facet_by[c]->d.get();
-        if (cols[c]->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: facet column %d belongs to another store", who, c);
-    }
-    // ---- the edges: host memory, checked here, uploaded once (facet_stats_device)
-    if (edges && !n_edges) QK_FAIL(QK_ERR_INVALID, "%s: edges without n_edges", who);
-    int max_e = 0;
-    int64_t n_all = 0;
-    if (n_edges)
-        for (int c = 0; c < n_cols; c++) {
-            const int E = n_edges[c];
-            if (E < 0) QK_FAIL(QK_ERR_INVALID, "%s: n_edges[%d]=%d is negative", who, c, E);
-            if (E > QK_MAX_FACET_EDGES)
-                QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_edges[%d]=%d exceeds QK_MAX_FACET_EDGES=%d", who, c, E, QK_MAX_FACET_EDGES);
-            if (E > 0 && !edges) QK_FAIL(QK_ERR_INVALID, "%s: n_edges names edges, edges is null", who);
-            for (int i = 1; i < E; i++)
-                if (edges[n_all + i - 1] >= edges[n_all + i])
-                    QK_FAIL(QK_ERR_INVALID, "%s: the edges of column %d are not strictly ascending (edge %d)", who, c, i);
-            n_all += E;
-            max_e = std::max(max_e, E);
-        }
-    const int hist_stride = 1 + max_e;
-    if (Q < 0 || (Q > 0 && (!x || !out.total))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
-    QK_TRY(qk_check_overflow(ctx));
-    QK_HIP(hipSetDevice(ctx->device));
-    if (timing) memset(timing, 0, sizeof(*timing));
-    if (Q == 0) return QK_OK;
-    hipStream_t st = ctx->stream;
-    // ---- staging, query preparation, coarse; a host caller's outputs on the device: six [C][Q] words, [hist], [total]
-    const size_t bc = qk_al256((size_t)n_cols * Q * 8), bh = qk_al256((size_t)n_cols * Q * hist_stride * 8), bt = qk_al256((size_t)Q * 8);
-    qk_scan_args sa;
-    char *stage = nullptr;
-    bool have_coarse = false;
-    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, 6 * bc + bh + bt, timing != nullptr, &sa, &stage,
-                             &have_coarse));
-    FacetStatsOut dv = out;
-    int64_t *const host[8] = {out.count, out.missing, out.vmin, out.vmax, out.sum_lo, out.sum_hi, out.hist, out.total};
-    int64_t **const dev[8] = {&dv.count, &dv.missing, &dv.vmin, &dv.vmax, &dv.sum_lo, &dv.sum_hi, &dv.hist, &dv.total};
-    const size_t bytes[8] = {(size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8,
-                             (size_t)n_cols * Q * 8, (size_t)n_cols * Q * 8, (size_t)n_cols * Q * hist_stride * 8, (size_t)Q * 8};
-    if (mem == QK_MEM_HOST)
-        for (int i = 0; i < 8; i++) *dev[i] = host[i] ? (int64_t *)(stage + (i < 7 ? i * bc : 6 * bc + bh)) : nullptr;
-    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
-    if (!qk_range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
-        key_lo = 1;
-        key_hi = 0;
-    }
-    // ---- row values and mask, then emission + sweep + finish -----------------------------------------------------------------------
-    const uint16_t *mask = nullptr;
-    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
-    QK_TRY(qk_store_sync_table(s));
-    for (int c = 0; c < n_cols; c++) {
-        bool seen = false;  // (the same column twice: derived once)
-        for (int e = 0; e < c; e++) seen = seen || cols[e] == cols[c];
-        if (!seen) QK_TRY(qk_rowvals_ensure(ctx, s, *cols[c]));
-    }
-    int64_t n_passes = 0;
-    QK_TRY(facet_stats_device(ctx, s, sa, cols, n_cols, edges, n_edges, hist_stride, key_lo, key_hi, mask, dv, timing, &n_passes));
-    // ---- results back ------------------------------------------------------------------------------------------------------------
-    if (mem == QK_MEM_HOST) {
-        for (int i = 0; i < 8; i++)
-            if (host[i]) QK_HIP(hipMemcpyAsync(host[i], *dev[i], bytes[i], hipMemcpyDeviceToHost, st));
-        QK_HIP(hipStreamSynchronize(st));
-    }
-    if (timing) {
-        QK_HIP(hipStreamSynchronize(st));
-        timing->n_items = n_passes;
-        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
-    }
-    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
-    return QK_OK;
+// both entry points behind their first two checks: the description of the call for qk_emit_run (qk_emit.hip)
+int facet_stats_call(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P,
+                     int nprobe, int metric, float radius, qk_filter *filter, qk_attr *const *facet_by, int n_cols, const int64_t *edges,
+                     const int *n_edges, const FacetStatsOut &out, int mem, qk_timing *timing) {
+    // six [C][Q] words, [hist], [total]; the histogram's bytes are known once the edges are checked
+    const size_t bc = (size_t)n_cols * Q * 8;
+    qk_emit_out outs[8] = {{out.count, bc, false},  {out.missing, bc, false}, {out.vmin, bc, false}, {out.vmax, bc, false},
+                           {out.sum_lo, bc, false}, {out.sum_hi, bc, false},  {out.hist, 0, false},  {out.total, (size_t)Q * 8, true}};
+    int hist_stride = 1;
+    qk_emit_call c;
+    c.who = who;
+    c.pipeline = "facet statistics";
+    c.label = "k_scan (facet stats)";
+    c.label_wide = "k_scan_wide (facet stats)";
+    c.ctx = ctx, c.parent = parent, c.s = s, c.x = x, c.Q = Q, c.pids = pids, c.P = P, c.nprobe = nprobe, c.metric = metric, c.mem = mem;
+    c.radius = radius, c.filter = filter, c.timing = timing;
+    c.outs = outs, c.n_outs = 8;
+    c.check = [&]() -> int {
+        if (n_cols < 1) QK_FAIL(QK_ERR_INVALID, "%s: n_cols=%d must be at least 1", who, n_cols);
+        if (n_cols > QK_MAX_FACET_COLS) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_cols=%d exceeds QK_MAX_FACET_COLS=%d", who, n_cols, QK_MAX_FACET_COLS);
+        QK_TRY(facet_check_cols(c, facet_by, n_cols));
+        // ---- the edges: host memory, checked here, uploaded once (facet_stats_device)
+        if (edges && !n_edges) QK_FAIL(QK_ERR_INVALID, "%s: edges without n_edges", who);
+        int max_e = 0;
+        int64_t n_all = 0;
+        if (n_edges)
+            for (int i = 0; i < n_cols; i++) {
+                const int E = n_edges[i];
+                if (E < 0) QK_FAIL(QK_ERR_INVALID, "%s: n_edges[%d]=%d is negative", who, i, E);
+                if (E > QK_MAX_FACET_EDGES)
+                    QK_FAIL(QK_ERR_UNSUPPORTED, "%s: n_edges[%d]=%d exceeds QK_MAX_FACET_EDGES=%d", who, i, E, QK_MAX_FACET_EDGES);
+                if (E > 0 && !edges) QK_FAIL(QK_ERR_INVALID, "%s: n_edges names edges, edges is null", who);
+                for (int j = 1; j < E; j++)
+                    if (edges[n_all + j - 1] >= edges[n_all + j])
+                        QK_FAIL(QK_ERR_INVALID, "%s: the edges of column %d are not strictly ascending (edge %d)", who, i, j);
+                n_all += E;
+                max_e = std::max(max_e, E);
+            }
+        hist_stride = 1 + max_e;
+        outs[6].bytes = bc * hist_stride;
+        return QK_OK;
+    };
+    c.device = [&](qk_emit_env &e) -> int {
+        int64_t *d[8];
+        for (int i = 0; i < 8; i++) d[i] = (int64_t *)outs[i].dev;
+        return facet_stats_device(c, e, edges, n_edges, hist_stride, FacetStatsOut{d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]});
+    };
+    return qk_emit_run(c);
 }
 
 }  // namespace
@@ -961,7 +834,7 @@ int qk_facet_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, 
                     int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_search: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_facet_search: nprobe must be positive");
-    return facet_run("qk_facet_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, facet_by, n_cols, n_values,
+    return facet_call("qk_facet_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, facet_by, n_cols, n_values,
                      out_values, out_counts, out_distinct, out_missing, out_total, mem, timing);
 }
 
@@ -970,7 +843,7 @@ int qk_facet_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int
                   int64_t *out_distinct, int64_t *out_missing, int64_t *out_total, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_scan: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_facet_scan: bad partition id list");
-    return facet_run("qk_facet_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, facet_by, n_cols, n_values, out_values,
+    return facet_call("qk_facet_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, facet_by, n_cols, n_values, out_values,
                      out_counts, out_distinct, out_missing, out_total, mem, timing);
 }
 
@@ -981,8 +854,8 @@ int qk_facet_stats_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const floa
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_search: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_search: nprobe must be positive");
     const FacetStatsOut out{out_count, out_missing, out_min, out_max, out_sum_lo, out_sum_hi, out_hist, out_total};
-    return facet_stats_run("qk_facet_stats_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, facet_by, n_cols,
-                           edges, n_edges, out, mem, timing);
+    return facet_stats_call("qk_facet_stats_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, facet_by, n_cols,
+                            edges, n_edges, out, mem, timing);
 }
 
 int qk_facet_stats_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric, float radius,
@@ -992,8 +865,8 @@ int qk_facet_stats_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, con
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_scan: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_facet_stats_scan: bad partition id list");
     const FacetStatsOut out{out_count, out_missing, out_min, out_max, out_sum_lo, out_sum_hi, out_hist, out_total};
-    return facet_stats_run("qk_facet_stats_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, facet_by, n_cols, edges,
-                           n_edges, out, mem, timing);
+    return facet_stats_call("qk_facet_stats_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, facet_by, n_cols, edges,
+                            n_edges, out, mem, timing);
 }
 
 }  // extern "C"

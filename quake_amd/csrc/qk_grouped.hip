@@ -25,6 +25,9 @@
 // No thread waits for another: a slot's key and id words hold "nothing yet" (all ones) from the memset on, so whoever finds a value
 // claimed proceeds at once, and the phases are separated by kernel boundaries.  Only commutative minima decide a slot, so the result
 // does not depend on who came first.  The value whose bits are all ones (-1) is the table's empty marker: it owns slot T of every query.
+// The host side is this file's kernels plus one description: grouped_call states the call for qk_emit_run (qk_emit.hip), the host
+// body of every entry point on the emission scan -- no radius, one column -- and grouped_device hangs the launches above into
+// qk_emit_device's skeleton.
 #include "qk_attr.h"
 
 #include <cstring>
@@ -401,38 +404,35 @@ static inline int64_t grouped_query_bytes(int64_t per_query_ub, int64_t T, int k
     return per_query_ub * 12 + (T + 1) * 24 + (int64_t)k * 12 + (int64_t)k * m * 4;
 }
 
-int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data &col, const uint16_t *mask, int m, int64_t *out_groups,
-                      qk_timing *timing, int64_t *n_passes) {
+namespace {
+
+// the device half: the k best groups of `col` per query over the probed lists, m rows of each; a.k, a.out_ids [Q][k][m] and
+// a.out_dist (or nullptr) set, out_groups [Q][k] or nullptr, all on the device; m == 1 is the one-row call, launch for launch
+int grouped_device(const qk_emit_call &c, qk_emit_env &e, qk_attr_data &col, int m, int64_t *out_groups) {
+    qk_ctx *ctx = c.ctx;
+    qk_store *s = c.s;
+    const qk_scan_args &a = e.a;
+    const uint16_t *mask = e.mask;
     const int64_t Q = a.Q;
     const int k = a.k;
     hipStream_t st = ctx->stream;
-    const int npids = (int)s->parts.size();
-    const int P = a.all_lists ? npids : a.P;
-    *n_passes = 0;
-    qk_phase_events pe;
-    pe.ctx = ctx;
-    pe.tm = ctx->timing && timing;
-    pe.dtm = false;
-    pe.ev_base = 4;
-    if (P <= 0 || npids <= 0) {  // no lists: padding
-        QK_TRY(pe.mark(0));
-        QK_TRY(qk_prep_flush(ctx));
+    const int P = e.P;
+    qk_emit_stages g;
+    g.pad = [&]() -> int {
         const int64_t nw = Q * k * m;  // (m > 1: the groups, [Q][k], are cleared apart)
         hipLaunchKernelGGL(k_grouped_pad, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, nw,
                            a.metric == QK_METRIC_IP ? -INFINITY : INFINITY, a.out_ids, a.out_dist, m == 1 ? out_groups : nullptr);
         QK_HIP(hipGetLastError());
         if (m > 1 && out_groups) QK_HIP(hipMemsetAsync(out_groups, 0, (size_t)Q * k * 8, st));
-        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
         return QK_OK;
-    }
+    };
     int kp = 2;  // (k_select_pairs_large keeps kp keys and kp ids in LDS, the ids behind the keys: kp >= 2 keeps them 8-byte aligned)
     while (kp < k) kp <<= 1;
     // this pipeline's bytes of the call's buffer, sized for the largest pass: [slots] [table values] [table ids] [table keys], and
     // for m > 1 [selected j per slot] [the selection's keys] [the selection's ids] [its distances] [member keys]
     int64_t T = 0, S = 0;
     size_t o_tvals = 0, o_tids = 0, o_tkeys = 0, o_tsel = 0, o_skeys = 0, o_sids = 0, o_sdist = 0, o_mkeys = 0;
-    qk_emit_hooks h;
-    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+    g.h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
         T = qk_grouped_table_slots(per_query_ub, col.n_ids);
         const int64_t qbytes = grouped_query_bytes(per_query_ub, T, k, m);
         if (qbytes > QK_GROUPED_PASS_BYTES)
@@ -455,14 +455,14 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
         }
         return QK_OK;
     };
-    h.before_scan = [&](const qk_emit_pass &p) -> int {
+    g.h.before_scan = [&](const qk_emit_pass &p) -> int {
         // every slot of the pass: value = empty, min key = min id = "nothing yet"
         QK_HIP(hipMemsetAsync(p.extra + o_tvals, 0xFF, (size_t)p.nq * (T + 1) * 8, st));
         QK_HIP(hipMemsetAsync(p.extra + o_tids, 0xFF, (size_t)p.nq * (T + 1) * 8, st));
         QK_HIP(hipMemsetAsync(p.extra + o_tkeys, 0xFF, (size_t)p.nq * (T + 1) * 4, st));
         return QK_OK;
     };
-    h.consume = [&](const qk_emit_pass &p) -> int {
+    g.h.consume = [&](const qk_emit_pass &p) -> int {
         GroupedParams G;
         G.keys = p.keys;
         G.slot = (int32_t *)p.extra;
@@ -485,8 +485,7 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
         G.k = k;
         G.m = m;
         G.r = 0;
-        // about 16384 workgroups per pass, whatever S is
-        G.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));
+        G.Sg = qk_emit_sg(S, p.nq);
         const unsigned grid = (unsigned)(p.nq * G.Sg);
         hipLaunchKernelGGL(k_grouped_claim, dim3(grid), dim3(256), 0, st, G);
         hipLaunchKernelGGL(k_grouped_minid, dim3(grid), dim3(256), 0, st, G);
@@ -531,76 +530,49 @@ int qk_grouped_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_d
         QK_HIP(hipGetLastError());
         return QK_OK;
     };
-    QK_TRY(qk_emit_passes(ctx, s, a, P, "grouped search", pe, h, n_passes));
-    if (out_groups && m == 1) {
-        hipLaunchKernelGGL(k_grouped_values, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, col_of(col), (const int64_t *)a.out_ids,
-                           Q * k, out_groups);
-        QK_HIP(hipGetLastError());
-    }
-    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
-    ctx->last_scan_kernel = wide ? "k_scan_wide (grouped)" : "k_scan (grouped)";
-    QK_TRY(pe.mark(3));
-    return QK_OK;
+    g.tail = [&]() -> int {
+        if (out_groups && m == 1) {
+            hipLaunchKernelGGL(k_grouped_values, dim3((unsigned)((Q * k + 255) / 256)), dim3(256), 0, st, col_of(col),
+                               (const int64_t *)a.out_ids, Q * k, out_groups);
+            QK_HIP(hipGetLastError());
+        }
+        return QK_OK;
+    };
+    return qk_emit_device(c, e, g);
 }
 
-namespace {
-
-// the body of both entry points: parent == nullptr && pids == nullptr -> every list
-int grouped_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
-                int k, int m, int metric, qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
-                qk_timing *timing) {
-    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
-    if (!group_by) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column is null", who);
-    qk_attr_data &col = *group_by->d;
-    if (col.store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column belongs to another store", who);
-    if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
-    if (k > QK_MAX_WIDE_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds %d", who, k, QK_MAX_WIDE_K);
-    if (m < 1) QK_FAIL(QK_ERR_INVALID, "%s: group_size=%d must be at least 1", who, m);
-    if (m > QK_MAX_GROUP_SIZE) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: group_size=%d exceeds QK_MAX_GROUP_SIZE=%d", who, m, QK_MAX_GROUP_SIZE);
-    if (Q < 0 || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
-    QK_TRY(qk_check_overflow(ctx));
-    QK_HIP(hipSetDevice(ctx->device));
-    if (timing) memset(timing, 0, sizeof(*timing));
-    if (Q == 0) return QK_OK;
-    hipStream_t st = ctx->stream;
-    // ---- staging, query preparation, coarse; a host caller's outputs on the device: [ids] [groups] [distances] ---------------------
-    const size_t bi = qk_al256((size_t)Q * k * m * 8), bg = qk_al256((size_t)Q * k * 8), bd = qk_al256((size_t)Q * k * m * 4);
-    qk_scan_args sa;
-    char *out = nullptr;
-    bool have_coarse = false;
-    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, bi + bg + bd, timing != nullptr, &sa, &out, &have_coarse));
-    int64_t *dids = out_ids, *dgroups = out_groups;
-    float *ddist = out_dist;
-    if (mem == QK_MEM_HOST) {
-        dids = (int64_t *)out;
-        dgroups = out_groups ? (int64_t *)(out + bi) : nullptr;
-        ddist = out_dist ? (float *)(out + bi + bg) : nullptr;
-    }
-    sa.k = k;
-    sa.out_ids = dids;
-    sa.out_dist = ddist;
-    // ---- row values and mask, then emission + reduction + selection -----------------------------------------------------------------
-    const uint16_t *mask = nullptr;
-    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
-    QK_TRY(qk_store_sync_table(s));
-    QK_TRY(qk_rowvals_ensure(ctx, s, col));
-    int64_t n_passes = 0;
-    QK_TRY(qk_grouped_device(ctx, s, sa, col, mask, m, dgroups, timing, &n_passes));
-    // ---- results back ------------------------------------------------------------------------------------------------------------
-    if (mem == QK_MEM_HOST) {
-        QK_HIP(hipMemcpyAsync(out_ids, dids, (size_t)Q * k * m * 8, hipMemcpyDeviceToHost, st));
-        if (out_groups) QK_HIP(hipMemcpyAsync(out_groups, dgroups, (size_t)Q * k * 8, hipMemcpyDeviceToHost, st));
-        if (out_dist) QK_HIP(hipMemcpyAsync(out_dist, ddist, (size_t)Q * k * m * 4, hipMemcpyDeviceToHost, st));
-        QK_HIP(hipStreamSynchronize(st));
-    }
-    if (timing) {
-        // the scalars of the wide-k path: no list statistics; n_items = the query passes of the call
-        QK_HIP(hipStreamSynchronize(st));
-        timing->n_items = n_passes;
-        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
-    }
-    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
-    return QK_OK;
+// both entry points behind their first two checks: the description of the call for qk_emit_run (qk_emit.hip)
+int grouped_call(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+                 int k, int m, int metric, qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem,
+                 qk_timing *timing) {
+    // [ids] [groups] [distances]
+    qk_emit_out outs[3] = {{out_ids, (size_t)Q * k * m * 8, true}, {out_groups, (size_t)Q * k * 8, false}, {out_dist, (size_t)Q * k * m * 4, false}};
+    qk_emit_call c;
+    c.who = who;
+    c.pipeline = "grouped search";
+    c.label = "k_scan (grouped)";
+    c.label_wide = "k_scan_wide (grouped)";
+    c.ctx = ctx, c.parent = parent, c.s = s, c.x = x, c.Q = Q, c.pids = pids, c.P = P, c.nprobe = nprobe, c.metric = metric, c.mem = mem;
+    c.has_radius = false, c.filter = filter, c.timing = timing;
+    c.outs = outs, c.n_outs = 3;
+    c.check = [&]() -> int {
+        if (!group_by) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column is null", who);
+        c.cols[0] = group_by->d.get();
+        c.n_cols = 1;
+        if (c.cols[0]->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: the group-by column belongs to another store", who);
+        if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
+        if (k > QK_MAX_WIDE_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds %d", who, k, QK_MAX_WIDE_K);
+        if (m < 1) QK_FAIL(QK_ERR_INVALID, "%s: group_size=%d must be at least 1", who, m);
+        if (m > QK_MAX_GROUP_SIZE) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: group_size=%d exceeds QK_MAX_GROUP_SIZE=%d", who, m, QK_MAX_GROUP_SIZE);
+        return QK_OK;
+    };
+    c.device = [&](qk_emit_env &e) -> int {
+        e.a.k = k;
+        e.a.out_ids = (int64_t *)outs[0].dev;
+        e.a.out_dist = (float *)outs[2].dev;
+        return grouped_device(c, e, *c.cols[0], m, (int64_t *)outs[1].dev);
+    };
+    return qk_emit_run(c);
 }
 
 }  // namespace
@@ -611,16 +583,16 @@ int qk_search_grouped_n(qk_ctx *ctx, qk_store *parent, qk_store *s, const float 
                         qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_search_grouped: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search_grouped: nprobe must be positive");
-    return grouped_run("qk_search_grouped", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, group_size, metric, group_by, filter, out_ids, out_dist,
-                       out_groups, mem, timing);
+    return grouped_call("qk_search_grouped", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, group_size, metric, group_by, filter, out_ids, out_dist,
+                        out_groups, mem, timing);
 }
 
 int qk_scan_grouped_n(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int group_size, int metric,
                       qk_attr *group_by, qk_filter *filter, int64_t *out_ids, float *out_dist, int64_t *out_groups, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_scan_grouped: bad partition id list");
-    return grouped_run("qk_scan_grouped", ctx, nullptr, s, x, Q, pids, P, 0, k, group_size, metric, group_by, filter, out_ids, out_dist,
-                       out_groups, mem, timing);
+    return grouped_call("qk_scan_grouped", ctx, nullptr, s, x, Q, pids, P, 0, k, group_size, metric, group_by, filter, out_ids, out_dist,
+                        out_groups, mem, timing);
 }
 
 int qk_search_grouped(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric, qk_attr *group_by,

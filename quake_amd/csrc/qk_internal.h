@@ -498,20 +498,75 @@ int qk_emit_passes(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, int P, const
 // the exact selection of the wide-k path over the keys of a pass (k_select_pairs_large): nq queries, kp a power of two >= k
 int qk_launch_select_pairs(qk_ctx *ctx, qk_store *s, const uint32_t *keys, const int64_t *pair_base, const int64_t *pids, int64_t nq, int P,
                            int k, int kp, int metric, bool sqrt_l2, int64_t *out_ids, float *out_dist);
-// The front end of an emission-based entry point (range, grouped) behind its own argument checks, Q > 0; every caller pointer in
+// The front end of an emission-based entry point (qk_emit_run, below) behind the argument checks, Q > 0; every caller pointer in
 // `mem`; parent == nullptr && pids == nullptr -> every list.  Stages x and pids of a host caller plus out_bytes for the caller's
 // outputs (*out: that region, 256-byte aligned; nullptr for device memory, where only the coarse result is staged), prepares the
 // queries, runs the coarse scan (the unfiltered qk_search's) and fills sa's x, xq4, xn, Q, metric, sqrt_l2 and all_lists or pids / P.
 // *have_coarse: a coarse scan ran, its events are ctx->ev[0..3] when record_events.
 int qk_emit_front_end(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                       int metric, int mem, size_t out_bytes, bool record_events, qk_scan_args *sa, char **out, bool *have_coarse);
-// range search (qk_range.hip): every row of the probed lists whose key lies in [key_lo, key_hi] (and is a candidate of `mask`),
-// in scan order; `a` as for qk_widek_device (k unused).  lims [Q + 1], out_ids / out_dist [cap] on the device.
-int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask,
-                    int64_t cap, int64_t *lims, int64_t *out_ids, float *out_dist, qk_timing *timing, int64_t *n_passes);
 // the closed key interval [*lo, *hi] of "dist <= radius" (L2) / "dist >= radius" (IP) on the float32 distance the caller sees
-// (qk_range.hip; facet counts use the same rule); false: no distance can pass
+// (qk_range.hip); false: no distance can pass
 bool qk_range_key_bounds(int metric, bool sqrt_l2, float radius, uint32_t *lo, uint32_t *hi);
+// workgroups per query of a sweep over an emission pass (nq queries, a query's segment cut into at most S slices): about 16384
+// per launch, whatever S is -- few queries -> every slice its own workgroup, many -> a few slices per workgroup
+inline int qk_emit_sg(int64_t S, int64_t nq) { return (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / nq)); }
+
+// ---- the entry points on the emission scan (range, grouped, facet counts, facet statistics, ordered search): qk_emit.hip ----------
+// An entry point describes its call in a qk_emit_call and hands it to qk_emit_run, which is the host body of all of them:
+// checks, staging, front end, key interval, filter mask and row values, the pipeline's device half, results back, qk_timing.
+struct qk_attr_data;
+// one output of the call; the table's order is the order of the host caller's staging region (256-byte aligned entries)
+struct qk_emit_out {
+    void *host;           // the caller's pointer, in the call's `mem`
+    size_t bytes;
+    bool required;        // a null pointer is refused ("null argument"); otherwise null means "not wanted"
+    void *dev = nullptr;  // set by the driver: the caller's own pointer (device memory) or the entry's place in the staging region
+                          // (host memory); nullptr where the caller passed none -- such an output is neither written nor copied
+};
+// what the driver has worked out by the time it runs the device half
+struct qk_emit_env {
+    qk_scan_args a;                   // the front end's (qk_emit_front_end); the pipeline may add what its kernels read from it
+    const uint16_t *mask = nullptr;   // row mask of the call's filter
+    uint32_t key_lo = 1, key_hi = 0;  // the radius as a closed key interval; empty where no distance can pass (or no radius)
+    int P = 0, npids = 0;             // lists per query (every list of the store for all_lists), lists of the store
+    int64_t n_passes = 0;             // set by qk_emit_device
+};
+struct qk_emit_call {
+    const char *who = nullptr;        // the entry point, for messages
+    const char *pipeline = nullptr;   // the pipeline, for qk_emit_passes' refusal
+    const char *label = nullptr, *label_wide = nullptr;  // ctx->last_scan_kernel behind k_scan / k_scan_wide
+    qk_ctx *ctx = nullptr;
+    qk_store *parent = nullptr, *s = nullptr;  // parent == nullptr && pids == nullptr -> every list
+    const float *x = nullptr;
+    int64_t Q = 0;
+    const int64_t *pids = nullptr;
+    int P = 0, nprobe = 0, metric = 0, mem = 0;
+    bool has_radius = true;           // (grouped search has none)
+    float radius = 0.0f;
+    qk_filter *filter = nullptr;
+    qk_timing *timing = nullptr;
+    // the pipeline's own argument checks, behind the metric and radius checks and in front of the null-argument check; what
+    // depends on checked arguments (cols, the bytes of an output) may be filled in here.  Optional.
+    std::function<int()> check;
+    qk_attr_data *cols[QK_MAX_FACET_COLS] = {nullptr, nullptr, nullptr, nullptr};  // columns whose row values the kernels read
+    int n_cols = 0;                   // (a column named twice is derived once)
+    qk_emit_out *outs = nullptr;
+    int n_outs = 0;
+    std::function<int(qk_emit_env &)> device;  // the device half: builds its stages and runs qk_emit_device
+    // range search only.  on_empty: the answer of Q == 0.  copy_back: replaces the copy of every non-null output to a host
+    // caller (and the wait behind it).  fill_timing: further fields of qk_timing, the stream drained.
+    std::function<int()> on_empty, copy_back, fill_timing;
+};
+int qk_emit_run(qk_emit_call &c);
+// The skeleton of a device half: the per-call phase events, the no-lists branch (event 0, the deferred query preparation,
+// `pad`, events 1 .. 3) or qk_emit_passes with `h`, `tail` (optional), the relabelling of ctx->last_scan_kernel and event 3.
+struct qk_emit_stages {
+    std::function<int()> pad;   // no lists to scan: write the padded answer
+    qk_emit_hooks h;
+    std::function<int()> tail;  // behind the last pass, in front of event 3
+};
+int qk_emit_device(const qk_emit_call &c, qk_emit_env &e, const qk_emit_stages &st);
 // wide rows (a 16-query tile no longer fits the LDS next to what the kernel keeps there): the queries are read from global
 // memory instead (qk_scan_wide.hip).  k_dense_wide: every query against one list -- keys into D, or (argmin) the packed
 // minimum (key << 32 | id) into best64; k_assign_wide: k_assign's nearest centroid of every row of x

@@ -19,6 +19,8 @@
 // KP is the instantiation's 64 / 256 / 1024 >= k, B its 512 / 1024 / 2048: behind a cut at least B - KP >= 448 slots are free.
 // No thread waits for another, every loop is bounded, only comparisons of integers decide the result: it is a pure function of
 // the store, the column and the call.
+// The host side is this file's kernels plus one description: order_call states the call for qk_emit_run (qk_emit.hip), the host
+// body of every entry point on the emission scan, and order_device hangs the launches above into qk_emit_device's skeleton.
 #include "qk_facet.h"
 
 #include <cstring>
@@ -264,21 +266,15 @@ struct OrderOut {
     int64_t *values, *count, *missing, *total;
 };
 
-int order_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *col, int desc, int missing_last, int k, uint32_t key_lo,
-                 uint32_t key_hi, const uint16_t *mask, const OrderOut &o, qk_timing *timing, int64_t *n_passes) {
+// the device half; o: the call's outputs on the device (nullptr: not wanted)
+int order_device(const qk_emit_call &c, qk_emit_env &e, int desc, int missing_last, int k, const OrderOut &o) {
+    qk_store *s = c.s;
+    const qk_scan_args &a = e.a;
     const int64_t Q = a.Q;
-    hipStream_t st = ctx->stream;
-    const int npids = (int)s->parts.size();
-    const int P = a.all_lists ? npids : a.P;
-    *n_passes = 0;
-    qk_phase_events pe;
-    pe.ctx = ctx;
-    pe.tm = ctx->timing && timing;
-    pe.dtm = false;
-    pe.ev_base = 4;
-    if (P <= 0 || npids <= 0) {  // no lists: no hits -- padding and zeros
-        QK_TRY(pe.mark(0));
-        QK_TRY(qk_prep_flush(ctx));
+    const int P = e.P;
+    hipStream_t st = c.ctx->stream;
+    qk_emit_stages g;
+    g.pad = [&]() -> int {  // no hits: padding and zeros
         QK_HIP(hipMemsetAsync(o.ids, 0xFF, (size_t)Q * k * 8, st));
         if (o.values) QK_HIP(hipMemsetAsync(o.values, 0, (size_t)Q * k * 8, st));
         if (o.dist)
@@ -287,15 +283,13 @@ int order_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *
         for (int64_t *p : {o.count, o.missing, o.total})
             if (p) QK_HIP(hipMemsetAsync(p, 0, (size_t)Q * 8, st));
         QK_HIP(hipGetLastError());
-        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
         return QK_OK;
-    }
+    };
     const int KP = k <= 64 ? 64 : k <= 256 ? 256 : 1024;
     // this pipeline's bytes of the call's buffer, sized for the largest pass: [total] [missing] [pcnt] [pv] [pid] [pk] [pc]
     int64_t S = 0, Sg_cap = 1;
     size_t o_missing = 0, o_pcnt = 0, o_pv = 0, o_pid = 0, o_pk = 0, o_pc = 0;
-    qk_emit_hooks h;
-    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+    g.h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
         S = (per_query_ub + FC_SLICE - 1) / FC_SLICE;
         // the partial lists: Sg of KP records per query.  A large k lowers Sg (down to 1) before it shortens the pass, and the pass
         // is shortened only where one list per query would exceed QK_GROUPED_PASS_BYTES
@@ -313,37 +307,17 @@ int order_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *
         *extra_bytes = o_pc + qk_al256((size_t)nl * KP * 4);
         return QK_OK;
     };
-    h.before_scan = [&](const qk_emit_pass &p) -> int {
+    g.h.before_scan = [&](const qk_emit_pass &p) -> int {
         QK_HIP(hipMemsetAsync(p.extra, 0, o_pcnt, st));  // total and missing; every partial list's counter is written by its workgroup
         return QK_OK;
     };
-    h.consume = [&](const qk_emit_pass &p) -> int {
+    g.h.consume = [&](const qk_emit_pass &p) -> int {
         OrderParams T;
         FacetParams &F = T.F;
-        F.keys = p.keys;
-        F.pair_base = p.pair_base;
-        F.pids = p.pids;
-        F.pt_off = s->d_off;
-        F.mask = mask;
-        for (int c = 0; c < QK_MAX_FACET_COLS; c++) {
-            F.has[c] = col->rv_has;
-            F.rowval[c] = col->rv_vals;
-        }
-        F.tvals = nullptr;
-        F.tcnt = nullptr;
+        facet_params_fill(F, p, s, e.mask, c.cols, 1, e.key_lo, e.key_hi, P, S);
         F.total = (uint32_t *)p.extra;
         F.missing = (uint32_t *)(p.extra + o_missing);
-        F.nq = p.nq;
-        F.g0 = 0;
-        F.ng = p.nq;
-        F.P = P;
-        F.C = 1;
-        F.tmask = 0;
-        F.key_lo = key_lo;
-        F.key_hi = key_hi;
-        F.max_ids = 0;
-        // about 16384 workgroups, whatever S is -- and no more partial lists per query than the workspace was planned for
-        F.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S, Sg_cap), 16384 / p.nq));
+        F.Sg = qk_emit_sg(std::min(S, Sg_cap), p.nq);  // no more partial lists per query than the workspace was planned for
         T.ids = s->ids;
         T.desc = desc;
         T.missing_last = missing_last;
@@ -386,77 +360,41 @@ int order_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_attr_data *
         QK_HIP(hipGetLastError());
         return QK_OK;
     };
-    QK_TRY(qk_emit_passes(ctx, s, a, P, "ordered search", pe, h, n_passes));
-    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
-    ctx->last_scan_kernel = wide ? "k_scan_wide (order)" : "k_scan (order)";
-    QK_TRY(pe.mark(3));
-    return QK_OK;
+    return qk_emit_device(c, e, g);
 }
 
-// the body of both entry points: parent == nullptr && pids == nullptr -> every list
-int order_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
-              int metric, float radius, qk_filter *filter, qk_attr *order_by, int flags, int k, const OrderOut &out, int mem,
-              qk_timing *timing) {
-    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
-    if (radius != radius) QK_FAIL(QK_ERR_INVALID, "%s: the radius is NaN", who);
-    if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
-    if (k > QK_MAX_ORDER_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds QK_MAX_ORDER_K=%d", who, k, QK_MAX_ORDER_K);
-    if (flags & ~(QK_ORDER_DESC | QK_ORDER_MISSING_LAST)) QK_FAIL(QK_ERR_INVALID, "%s: unknown flags %d", who, flags);
-    if (!order_by) QK_FAIL(QK_ERR_INVALID, "%s: order_by is null", who);
-    qk_attr_data *col = order_by->d.get();
-    if (col->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: the order column belongs to another store", who);
-    if (Q < 0 || (Q > 0 && (!x || !out.ids))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
-    QK_TRY(qk_check_overflow(ctx));
-    QK_HIP(hipSetDevice(ctx->device));
-    if (timing) memset(timing, 0, sizeof(*timing));
-    if (Q == 0) return QK_OK;
-    hipStream_t st = ctx->stream;
-    // ---- staging, query preparation, coarse; a host caller's outputs on the device: [ids] [values] [dist] [count] [missing] [total]
-    const size_t b8 = qk_al256((size_t)Q * k * 8), b4 = qk_al256((size_t)Q * k * 4), bq = qk_al256((size_t)Q * 8);
-    qk_scan_args sa;
-    char *stage = nullptr;
-    bool have_coarse = false;
-    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, 2 * b8 + b4 + 3 * bq, timing != nullptr, &sa, &stage,
-                             &have_coarse));
-    OrderOut dv = out;
-    if (mem == QK_MEM_HOST) {
-        dv.ids = (int64_t *)stage;
-        dv.values = out.values ? (int64_t *)(stage + b8) : nullptr;
-        dv.dist = out.dist ? (float *)(stage + 2 * b8) : nullptr;
-        dv.count = out.count ? (int64_t *)(stage + 2 * b8 + b4) : nullptr;
-        dv.missing = out.missing ? (int64_t *)(stage + 2 * b8 + b4 + bq) : nullptr;
-        dv.total = out.total ? (int64_t *)(stage + 2 * b8 + b4 + 2 * bq) : nullptr;
-    }
-    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
-    if (!qk_range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
-        key_lo = 1;
-        key_hi = 0;
-    }
-    // ---- row values and mask, then emission + partial selection + merge ----------------------------------------------------------
-    const uint16_t *mask = nullptr;
-    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
-    QK_TRY(qk_store_sync_table(s));
-    QK_TRY(qk_rowvals_ensure(ctx, s, *col));
-    int64_t n_passes = 0;
-    QK_TRY(order_device(ctx, s, sa, col, (flags & QK_ORDER_DESC) ? 1 : 0, (flags & QK_ORDER_MISSING_LAST) ? 1 : 0, k, key_lo, key_hi, mask,
-                        dv, timing, &n_passes));
-    // ---- results back ------------------------------------------------------------------------------------------------------------
-    if (mem == QK_MEM_HOST) {
-        QK_HIP(hipMemcpyAsync(out.ids, dv.ids, (size_t)Q * k * 8, hipMemcpyDeviceToHost, st));
-        if (out.values) QK_HIP(hipMemcpyAsync(out.values, dv.values, (size_t)Q * k * 8, hipMemcpyDeviceToHost, st));
-        if (out.dist) QK_HIP(hipMemcpyAsync(out.dist, dv.dist, (size_t)Q * k * 4, hipMemcpyDeviceToHost, st));
-        if (out.count) QK_HIP(hipMemcpyAsync(out.count, dv.count, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
-        if (out.missing) QK_HIP(hipMemcpyAsync(out.missing, dv.missing, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
-        if (out.total) QK_HIP(hipMemcpyAsync(out.total, dv.total, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
-        QK_HIP(hipStreamSynchronize(st));
-    }
-    if (timing) {
-        QK_HIP(hipStreamSynchronize(st));
-        timing->n_items = n_passes;
-        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
-    }
-    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
-    return QK_OK;
+// both entry points behind their first two checks: the description of the call for qk_emit_run (qk_emit.hip)
+int order_call(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+               int metric, float radius, qk_filter *filter, qk_attr *order_by, int flags, int k, const OrderOut &out, int mem,
+               qk_timing *timing) {
+    // [ids] [values] [dist] [count] [missing] [total]
+    const size_t b8 = (size_t)Q * k * 8, bq = (size_t)Q * 8;
+    qk_emit_out outs[6] = {{out.ids, b8, true},     {out.values, b8, false},  {out.dist, (size_t)Q * k * 4, false},
+                           {out.count, bq, false}, {out.missing, bq, false}, {out.total, bq, false}};
+    qk_emit_call c;
+    c.who = who;
+    c.pipeline = "ordered search";
+    c.label = "k_scan (order)";
+    c.label_wide = "k_scan_wide (order)";
+    c.ctx = ctx, c.parent = parent, c.s = s, c.x = x, c.Q = Q, c.pids = pids, c.P = P, c.nprobe = nprobe, c.metric = metric, c.mem = mem;
+    c.radius = radius, c.filter = filter, c.timing = timing;
+    c.outs = outs, c.n_outs = 6;
+    c.check = [&]() -> int {
+        if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
+        if (k > QK_MAX_ORDER_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds QK_MAX_ORDER_K=%d", who, k, QK_MAX_ORDER_K);
+        if (flags & ~(QK_ORDER_DESC | QK_ORDER_MISSING_LAST)) QK_FAIL(QK_ERR_INVALID, "%s: unknown flags %d", who, flags);
+        if (!order_by) QK_FAIL(QK_ERR_INVALID, "%s: order_by is null", who);
+        c.cols[0] = order_by->d.get();
+        c.n_cols = 1;
+        if (c.cols[0]->store_uid != s->uid) QK_FAIL(QK_ERR_INVALID, "%s: the order column belongs to another store", who);
+        return QK_OK;
+    };
+    c.device = [&](qk_emit_env &e) -> int {
+        const OrderOut dv{(int64_t *)outs[0].dev, (float *)outs[2].dev,   (int64_t *)outs[1].dev,
+                          (int64_t *)outs[3].dev, (int64_t *)outs[4].dev, (int64_t *)outs[5].dev};
+        return order_device(c, e, (flags & QK_ORDER_DESC) ? 1 : 0, (flags & QK_ORDER_MISSING_LAST) ? 1 : 0, k, dv);
+    };
+    return qk_emit_run(c);
 }
 
 }  // namespace
@@ -469,7 +407,7 @@ int qk_order_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, 
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_order_search: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_order_search: nprobe must be positive");
     const OrderOut out{out_ids, out_dist, out_values, out_count, out_missing, out_total};
-    return order_run("qk_order_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, order_by, flags, k, out, mem,
+    return order_call("qk_order_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, order_by, flags, k, out, mem,
                      timing);
 }
 
@@ -479,7 +417,7 @@ int qk_order_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_order_scan: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_order_scan: bad partition id list");
     const OrderOut out{out_ids, out_dist, out_values, out_count, out_missing, out_total};
-    return order_run("qk_order_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, order_by, flags, k, out, mem, timing);
+    return order_call("qk_order_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, order_by, flags, k, out, mem, timing);
 }
 
 }  // extern "C"

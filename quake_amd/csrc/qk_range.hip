@@ -16,6 +16,10 @@
 //                    key i: emit_key_row (qk_device.h); the id from the arena; the distance from the key, converted like every
 //                    selection kernel does.
 // A filter is tested here, not in the scan (the emission kernels take no mask): the mask bit of arena row pt_off[list] + row.
+// The host side is this file's kernels plus one description: range_call states the call for qk_emit_run (qk_emit.hip), the host
+// body of every entry point on the emission scan, and range_device hangs the launches above into qk_emit_device's skeleton.
+// Only range search uses the driver's three hooks: lims[0] = 0 for Q == 0, the copy of lims first and then of the written prefix
+// of ids and distances, and the list statistics of qk_timing.
 #include "qk_internal.h"
 
 #include <cmath>
@@ -287,31 +291,17 @@ bool qk_range_key_bounds(int metric, bool sqrt_l2, float radius, uint32_t *lo, u
     return true;
 }
 
-int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t key_lo, uint32_t key_hi, const uint16_t *mask, int64_t cap,
-                    int64_t *lims, int64_t *out_ids, float *out_dist, qk_timing *timing, int64_t *n_passes) {
-    const int64_t Q = a.Q;
+
+namespace {
+
+// the device half: lims [Q + 1], out_ids / out_dist [cap] on the device
+int range_device(const qk_emit_call &c, qk_emit_env &e, int64_t cap, int64_t *lims, int64_t *out_ids, float *out_dist) {
+    qk_ctx *ctx = c.ctx;
+    qk_store *s = c.s;
+    const qk_scan_args &a = e.a;
+    qk_timing *timing = c.timing;
     hipStream_t st = ctx->stream;
-    QK_TRY(qk_store_sync_table(s));
-    const int npids = (int)s->parts.size();
-    const int P = a.all_lists ? npids : a.P;
-    *n_passes = 0;
-    qk_phase_events pe;
-    pe.ctx = ctx;
-    pe.tm = ctx->timing && timing;
-    pe.dtm = false;
-    pe.ev_base = 4;
-    if (P <= 0 || npids <= 0) {  // no lists: no hits
-        QK_TRY(pe.mark(0));
-        QK_TRY(qk_prep_flush(ctx));
-        QK_HIP(hipMemsetAsync(lims, 0, (size_t)(Q + 1) * 8, st));
-        for (int i = 1; i <= 3; i++) QK_TRY(pe.mark(i));
-        if (timing) {
-            QK_TRY(qk_pinned_reserve(ctx, 64));
-            QK_HIP(hipStreamSynchronize(st));
-            memset(ctx->pinned, 0, 32);
-        }
-        return QK_OK;
-    }
+    const int npids = e.npids, P = e.P;
     // this pipeline's bytes of the call's buffer, sized for the largest pass:
     // [run: total hits, live pairs, rows of the lists reached, -] [list flags] [cnt] [cnt4] [excl] [qtot]
     int S = 0;
@@ -319,8 +309,12 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
     size_t o_cnt4 = 0, o_excl = 0, o_qtot = 0;
     int64_t *run = nullptr;
     unsigned char *flags = nullptr;
-    qk_emit_hooks h;
-    h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
+    qk_emit_stages g;
+    g.pad = [&]() -> int {  // no hits
+        QK_HIP(hipMemsetAsync(lims, 0, (size_t)(a.Q + 1) * 8, st));
+        return QK_OK;
+    };
+    g.h.plan = [&](int64_t per_query_ub, int64_t *qc, size_t *extra_bytes) -> int {
         S = (int)((per_query_ub + QK_RANGE_SLICE - 1) / QK_RANGE_SLICE);
         if (*qc * (int64_t)S > 0x7FFFFFF0LL) QK_FAIL(QK_ERR_UNSUPPORTED, "range search: Q too large");
         const int64_t nsl_max = *qc * S;
@@ -330,7 +324,7 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
         *extra_bytes = o_qtot + qk_al256((size_t)*qc * 4);
         return QK_OK;
     };
-    h.before_scan = [&](const qk_emit_pass &p) -> int {
+    g.h.before_scan = [&](const qk_emit_pass &p) -> int {
         if (p.q0 == 0) {
             run = (int64_t *)p.extra;
             flags = (unsigned char *)(p.extra + o_flags);
@@ -341,18 +335,18 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
                                flags, (unsigned long long *)(run + 1));
         return QK_OK;
     };
-    h.consume = [&](const qk_emit_pass &p) -> int {
+    g.h.consume = [&](const qk_emit_pass &p) -> int {
         RangeParams R;
         R.keys = p.keys;
         R.pair_base = p.pair_base;
         R.pids = p.pids;
         R.pt_off = s->d_off;
         R.ids = s->ids;
-        R.mask = mask;
+        R.mask = e.mask;
         R.P = P;
         R.S = S;
-        R.key_lo = key_lo;
-        R.key_hi = key_hi;
+        R.key_lo = e.key_lo;
+        R.key_hi = e.key_hi;
         R.metric = a.metric;
         R.sqrt_l2 = a.sqrt_l2 ? 1 : 0;
         R.cnt = (int32_t *)(p.extra + o_cnt);
@@ -362,8 +356,7 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
         R.cap = cap;
         R.out_ids = out_ids;
         R.out_dist = out_dist;
-        // about 16384 workgroups per pass, whatever S is: few queries -> every slice its own workgroup, many -> a few per query
-        R.Sg = (int)std::max<int64_t>(1, std::min<int64_t>(S, 16384 / p.nq));
+        R.Sg = qk_emit_sg(S, p.nq);
         const unsigned grid = (unsigned)(p.nq * R.Sg);
         hipLaunchKernelGGL(k_range_count, dim3(grid), dim3(256), 0, st, R);
         hipLaunchKernelGGL(k_range_qscan, dim3((unsigned)((p.nq + 3) / 4)), dim3(256), 0, st, R, p.nq);
@@ -372,84 +365,73 @@ int qk_range_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, uint32_t ke
         QK_HIP(hipGetLastError());
         return QK_OK;
     };
-    QK_TRY(qk_emit_passes(ctx, s, a, P, "range search", pe, h, n_passes));
-    const bool wide = strcmp(ctx->last_scan_kernel, "k_scan_wide") == 0;
-    ctx->last_scan_kernel = wide ? "k_scan_wide (range)" : "k_scan (range)";
-    if (timing) hipLaunchKernelGGL(k_range_rows, dim3(1), dim3(256), 0, st, flags, s->d_size, npids, run + 2);
-    QK_TRY(pe.mark(3));
-    if (timing) {
+    g.tail = [&]() -> int {
+        if (timing) hipLaunchKernelGGL(k_range_rows, dim3(1), dim3(256), 0, st, flags, s->d_size, npids, run + 2);
+        return QK_OK;
+    };
+    QK_TRY(qk_emit_device(c, e, g));
+    if (timing) {  // the scalars qk_timing reports, into pinned memory behind the last event: zeros where no pass ran
         QK_TRY(qk_pinned_reserve(ctx, 64));
-        QK_HIP(hipMemcpyAsync(ctx->pinned, run, 32, hipMemcpyDeviceToHost, st));
+        if (run) {
+            QK_HIP(hipMemcpyAsync(ctx->pinned, run, 32, hipMemcpyDeviceToHost, st));
+        } else {
+            QK_HIP(hipStreamSynchronize(st));
+            memset(ctx->pinned, 0, 32);
+        }
     }
     return QK_OK;
 }
 
-namespace {
-
-// the body of both entry points: parent == nullptr && pids == nullptr -> every list
-int range_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
-              int metric, float radius, qk_filter *filter, int64_t cap, int64_t *out_lims, int64_t *out_ids, float *out_dist, int mem,
-              qk_timing *timing) {
-    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
-    if (radius != radius) QK_FAIL(QK_ERR_INVALID, "%s: the radius is NaN", who);
-    if (cap < 0) QK_FAIL(QK_ERR_INVALID, "%s: cap must not be negative", who);
-    if (!out_lims) QK_FAIL(QK_ERR_INVALID, "%s: out_lims is null", who);
-    if (cap > 0 && !out_ids) QK_FAIL(QK_ERR_INVALID, "%s: cap > 0 needs an id buffer", who);
-    if (Q < 0 || (Q > 0 && !x)) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
-    QK_TRY(qk_check_overflow(ctx));
-    QK_HIP(hipSetDevice(ctx->device));
-    if (timing) memset(timing, 0, sizeof(*timing));
+// both entry points behind their first two checks: the description of the call for qk_emit_run (qk_emit.hip)
+int range_call(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+               int metric, float radius, qk_filter *filter, int64_t cap, int64_t *out_lims, int64_t *out_ids, float *out_dist, int mem,
+               qk_timing *timing) {
     hipStream_t st = ctx->stream;
-    if (Q == 0) {
+    // [lims] [ids] [distances]; cap == 0 counts only
+    qk_emit_out outs[3] = {{out_lims, (size_t)(Q + 1) * 8, false},
+                           {cap > 0 ? out_ids : nullptr, (size_t)cap * 8, false},
+                           {cap > 0 ? out_dist : nullptr, (size_t)cap * 4, false}};
+    qk_emit_call c;
+    c.who = who;
+    c.pipeline = "range search";
+    c.label = "k_scan (range)";
+    c.label_wide = "k_scan_wide (range)";
+    c.ctx = ctx, c.parent = parent, c.s = s, c.x = x, c.Q = Q, c.pids = pids, c.P = P, c.nprobe = nprobe, c.metric = metric, c.mem = mem;
+    c.radius = radius, c.filter = filter, c.timing = timing;
+    c.outs = outs, c.n_outs = 3;
+    c.check = [&]() -> int {
+        if (cap < 0) QK_FAIL(QK_ERR_INVALID, "%s: cap must not be negative", who);
+        if (!out_lims) QK_FAIL(QK_ERR_INVALID, "%s: out_lims is null", who);
+        if (cap > 0 && !out_ids) QK_FAIL(QK_ERR_INVALID, "%s: cap > 0 needs an id buffer", who);
+        return QK_OK;
+    };
+    c.on_empty = [&]() -> int {
         if (mem == QK_MEM_HOST) out_lims[0] = 0;
         else QK_HIP(hipMemsetAsync(out_lims, 0, 8, st));
         return QK_OK;
-    }
-    // ---- staging, query preparation, coarse; a host caller's outputs on the device: [lims] [ids] [distances] -----------------------
-    const size_t bl = qk_al256((size_t)(Q + 1) * 8), bi = qk_al256((size_t)cap * 8), bd = qk_al256((size_t)cap * 4);
-    qk_scan_args sa;
-    char *out = nullptr;
-    bool have_coarse = false;
-    QK_TRY(qk_emit_front_end(ctx, parent, s, x, Q, pids, P, nprobe, metric, mem, bl + bi + bd, timing != nullptr, &sa, &out, &have_coarse));
-    int64_t *dlims = out_lims, *dids = out_ids;
-    float *ddist = out_dist;
-    if (mem == QK_MEM_HOST) {
-        dlims = (int64_t *)out;
-        dids = cap > 0 ? (int64_t *)(out + bl) : nullptr;
-        ddist = cap > 0 && out_dist ? (float *)(out + bl + bi) : nullptr;
-    }
-    uint32_t key_lo = 1, key_hi = 0;  // (empty interval)
-    if (!qk_range_key_bounds(metric, sa.sqrt_l2, radius, &key_lo, &key_hi)) {
-        key_lo = 1;
-        key_hi = 0;
-    }
-    // ---- emission scan + counting + compaction ----------------------------------------------------------------------------------
-    const uint16_t *mask = nullptr;
-    if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &mask));
-    int64_t n_passes = 0;
-    QK_TRY(qk_range_device(ctx, s, sa, key_lo, key_hi, mask, cap, dlims, dids, ddist, timing, &n_passes));
-    // ---- results back ------------------------------------------------------------------------------------------------------------
-    if (mem == QK_MEM_HOST) {
-        QK_HIP(hipMemcpyAsync(out_lims, dlims, (size_t)(Q + 1) * 8, hipMemcpyDeviceToHost, st));
+    };
+    c.device = [&](qk_emit_env &e) -> int {
+        return range_device(c, e, cap, (int64_t *)outs[0].dev, (int64_t *)outs[1].dev, (float *)outs[2].dev);
+    };
+    c.copy_back = [&]() -> int {
+        QK_HIP(hipMemcpyAsync(out_lims, outs[0].dev, outs[0].bytes, hipMemcpyDeviceToHost, st));
         QK_HIP(hipStreamSynchronize(st));
         const int64_t n = std::min<int64_t>(cap, out_lims[Q]);  // the prefix that was written: nothing behind it is touched
         if (n > 0) {
-            QK_HIP(hipMemcpyAsync(out_ids, dids, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-            if (out_dist) QK_HIP(hipMemcpyAsync(out_dist, ddist, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+            QK_HIP(hipMemcpyAsync(out_ids, outs[1].dev, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            if (out_dist) QK_HIP(hipMemcpyAsync(out_dist, outs[2].dev, (size_t)n * 4, hipMemcpyDeviceToHost, st));
             QK_HIP(hipStreamSynchronize(st));
         }
-    }
-    if (timing) {
-        QK_HIP(hipStreamSynchronize(st));
+        return QK_OK;
+    };
+    c.fill_timing = [&]() -> int {
         int64_t sc[4];
         memcpy(sc, ctx->pinned, 32);
-        timing->n_items = n_passes;
         timing->partitions_scanned = sc[1];
         timing->scan_bytes = sc[2] * (int64_t)s->d * 4;
-        QK_TRY(qk_read_phase_ms(ctx, timing, have_coarse, 4));
-    }
-    if (timing || mem == QK_MEM_HOST) QK_TRY(qk_check_overflow(ctx));
-    return QK_OK;
+        return QK_OK;
+    };
+    return qk_emit_run(c);
 }
 
 }  // namespace
@@ -460,16 +442,16 @@ int qk_range_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, 
                     qk_filter *filter, int64_t cap, int64_t *out_lims, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_range_search: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_range_search: nprobe must be positive");
-    return range_run("qk_range_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, cap, out_lims, out_ids, out_dist,
-                     mem, timing);
+    return range_call("qk_range_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, metric, radius, filter, cap, out_lims, out_ids, out_dist,
+                      mem, timing);
 }
 
 int qk_range_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int metric, float radius,
                   qk_filter *filter, int64_t cap, int64_t *out_lims, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_range_scan: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_range_scan: bad partition id list");
-    return range_run("qk_range_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, cap, out_lims, out_ids, out_dist, mem,
-                     timing);
+    return range_call("qk_range_scan", ctx, nullptr, s, x, Q, pids, P, 0, metric, radius, filter, cap, out_lims, out_ids, out_dist, mem,
+                      timing);
 }
 
 }  // extern "C"
