@@ -861,7 +861,11 @@ QK_API int qk_search_aps(qk_ctx *ctx, qk_store *parent, qk_store *s, const float
 /* Multi-GPU merge step (the cross-worker batch_add of worker_scan, query_coordinator.cpp:167-173,231-235):
  * merge G per-rank results [G][Q][k] (already all-gathered by the caller, e.g. torch.distributed over RCCL) into
  * [Q][k] under the same (key,id) order.  in_key are SQUARED L2 distances / inner products, i.e. what qk_search
- * returns after qk_ctx_set_squared_l2(ctx, 1); the output distances are sqrt'd.  Device pointers only. */
+ * returns after qk_ctx_set_squared_l2(ctx, 1); the output distances are sqrt'd.  Device pointers only.
+ * Precondition: every rank's row of k entries is a SORTED run under the (key, id) order with its -1 padding as a suffix -- what
+ * qk_search returns.  (k <= 960 pools the entries and would take any order; k > 960 merges the runs by binary search and relies
+ * on it.)  An entry with id < 0 or a NaN key is no candidate, whatever k: it is not returned.  The same (key, id) on two ranks is
+ * returned twice. */
 QK_API int qk_merge_topk(qk_ctx *ctx, const int64_t *in_ids, const float *in_key, int G, int64_t Q, int k, int metric,
                          int64_t *out_ids, float *out_dist);
 /* The same exchange as ONE collective (the ids + keys of an entry travel together, 12 bytes): qk_pack_topk turns a rank's local
@@ -873,6 +877,22 @@ QK_API size_t qk_topk_block_bytes(int64_t per, int k);
 QK_API int qk_pack_topk(qk_ctx *ctx, const int64_t *ids, const float *key, int G, int64_t per, int k, void *packed);
 QK_API int qk_merge_topk_packed(qk_ctx *ctx, const void *packed, int G, int64_t per, int k, int metric, int64_t *out_ids,
                                 float *out_dist);
+/* Test and diagnosis hook: the per-query merge stage of qk_scan / qk_search on records the CALLER laid out, so that a test decides
+ * the geometry the merge kernels meet (behind a scan it is a by-product of the scan plan and the CU count).  Device pointers only.
+ * The layout is the scan's: pair_slots [Q*P][32] = {record count of the pair, its first 31 record numbers (-1: a record that did
+ * not fit)}; pair_head [Q*P] = head of the chain of the records beyond 31 (-1: none), linked through rec_hdr[r][0]; rec_hdr
+ * [max_recs][2] = {next record of the chain or -1, entry count n <= k}; rec_ord / rec_id [max_recs][k] = the record's n entries
+ * sorted under (key, id), keys as the merge orders them (L2: the bits of the squared distance; IP: the descending map; 0xFFFFFFFF =
+ * NaN).  form: 0 = the rule a search applies to (k, P); 1 = the chained walk k_merge<MAXCH>; 2 = k_merge_flat (k <= 32, P <= 64);
+ * 3 = k_merge_wide.  out_ids / out_dist [Q][k] as qk_scan writes them (out_dist may be NULL; sqrt_l2: L2 distances leave as
+ * sqrt); next_key / next_id [Q] (both NULL, or both set): the next cursor of qk_search_after, written by the same kernel behind
+ * the merge.  kernel_name (may be NULL): the kernel and instantiation launched, e.g. "k_merge_flat<2>".  A form the arguments do
+ * not admit, k > QK_MAX_K: QK_ERR_INVALID, nothing is launched.  The structures must be WELL FORMED -- every record number -1 or
+ * below max_recs, every chain ending in -1: the kernels trust them as they trust the scan.  No reference counterpart. */
+QK_API int qk_debug_merge_records(qk_ctx *ctx, int64_t Q, int P, int k, int metric, int sqrt_l2, int form, const int32_t *pair_slots,
+                                  const int32_t *pair_head, const int32_t *rec_hdr, const uint32_t *rec_ord, const int64_t *rec_id,
+                                  int32_t max_recs, int64_t *out_ids, float *out_dist, uint32_t *next_key, int64_t *next_id,
+                                  char *kernel_name, int name_len);
 /* When enabled, qk_scan/qk_search return squared L2 distances (the merge key) instead of sqrt distances. */
 QK_API int qk_ctx_set_squared_l2(qk_ctx *ctx, int enabled);
 

@@ -155,6 +155,9 @@ SIGNATURES = {
     "qk_topk_block_bytes": (C.c_size_t, [_i64, _int]),
     "qk_pack_topk": (_int, [_vp, _vp, _vp, _int, _i64, _int, _vp]),
     "qk_merge_topk_packed": (_int, [_vp, _vp, _int, _i64, _int, _int, _vp, _vp]),
+    # merge stage on caller-built records: (ctx, Q, P, k, metric, sqrt_l2, form, pair_slots, pair_head, rec_hdr, rec_ord, rec_id,
+    #                                        max_recs, out_ids, out_dist, next_key, next_id, kernel_name, name_len)
+    "qk_debug_merge_records": (_int, [_vp, _i64, _int, _int, _int, _int, _int] + [_vp] * 5 + [C.c_int32] + [_vp] * 4 + [C.c_char_p, _int]),
     "qk_kmeans_assign": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _int]),
     "qk_kmeans_accumulate": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp, _int]),
     "qk_kmeans_accumulate_blocked": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp, _int]),

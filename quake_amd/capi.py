@@ -759,6 +759,36 @@ class Context:
         check(self.lib.qk_merge_topk_packed(self.h, _ptr(packed), G, int(per), int(k), metric_code(metric), _ptr(out_i), _ptr(out_d)))
         return out_i, out_d
 
+    MERGE_FORMS = {"rule": 0, "chain": 1, "flat": 2, "wide": 3}
+
+    def merge_records(self, pair_slots, pair_head, rec_hdr, rec_ord, rec_id, k, metric, form=0, sqrt_l2=True, dist=True, cursor=False):
+        """the per-query merge stage on caller-built records (qk_debug_merge_records; test and diagnosis hook).  CUDA tensors in the
+        scan's layout: pair_slots int32 [Q, P, 32], pair_head int32 [Q, P], rec_hdr int32 [max_recs, 2], rec_ord int32 (the uint32
+        keys' bits) [max_recs, k], rec_id int64 [max_recs, k].  form: 0 / "rule" = what a search launches, 1 / "chain", 2 / "flat",
+        3 / "wide".  Returns a dict: ids [Q, k], dist [Q, k] (None with dist=False), kernel (the kernel launched) and, with
+        cursor=True, next_key int32 [Q] (bits) / next_id int64 [Q]."""
+        import torch
+        Q, P = int(pair_head.shape[0]), int(pair_head.shape[1])
+        k = int(k)
+        max_recs = int(rec_hdr.shape[0])
+        for t, dt, shape in ((pair_slots, torch.int32, (Q, P, 32)), (pair_head, torch.int32, (Q, P)), (rec_hdr, torch.int32, (max_recs, 2)),
+                             (rec_ord, torch.int32, (max_recs, k)), (rec_id, torch.int64, (max_recs, k))):
+            if not (_is_torch(t) and t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError("merge_records: expected a contiguous CUDA %s tensor of shape %s" % (dt, shape))
+        dev = pair_head.device
+        out_i = torch.empty((Q, k), dtype=torch.int64, device=dev)
+        out_d = torch.empty((Q, k), dtype=torch.float32, device=dev) if dist else None
+        nk = torch.empty((Q,), dtype=torch.int32, device=dev) if cursor else None
+        ni = torch.empty((Q,), dtype=torch.int64, device=dev) if cursor else None
+        name = C.create_string_buffer(64)
+        check(self.lib.qk_debug_merge_records(self.h, Q, P, k, metric_code(metric), int(bool(sqrt_l2)), int(self.MERGE_FORMS.get(form, form)),
+                                              _ptr(pair_slots), _ptr(pair_head), _ptr(rec_hdr), _ptr(rec_ord), _ptr(rec_id), max_recs,
+                                              _ptr(out_i), _ptr(out_d), _ptr(nk), _ptr(ni), name, 64))
+        out = dict(ids=out_i, dist=out_d, kernel=name.value.decode())
+        if cursor:
+            out.update(next_key=nk, next_id=ni)
+        return out
+
     # ---- k-means ----------------------------------------------------------------------------------------
     def kmeans_assign(self, x, c, metric, values=True):
         """nearest centroid of every row (and, with values, its distance / dot product); values=False passes val = NULL, the

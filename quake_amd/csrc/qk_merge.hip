@@ -588,12 +588,14 @@ __global__ __launch_bounds__(256) void k_merge_ranks_large(const int64_t *__rest
     const int64_t q = blockIdx.x, base0 = q * k;
     auto ids_of = [&](int r) { return (const int64_t *)((const unsigned char *)in_ids0 + (size_t)r * id_stride) + base0; };
     auto key_of = [&](int r) { return (const float *)((const unsigned char *)in_key0 + (size_t)r * key_stride) + base0; };
-    if (tid < G) {  // valid entries of rank tid: the first -1 id (padding is a suffix)
+    if (tid < G) {  // candidates of rank tid: up to the first -1 id or NaN key (a NaN key is no candidate; both are a suffix of a sorted run)
         const int64_t *ids = ids_of(tid);
+        const float *key = key_of(tid);
         int lo = 0, hi = k;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (ids[mid] >= 0) lo = mid + 1; else hi = mid;
+            const float v = key[mid];
+            if (ids[mid] >= 0 && v == v) lo = mid + 1; else hi = mid;
         }
         nvalid[tid] = lo;
     }
@@ -706,12 +708,53 @@ int qk_merge_topk_packed_device(qk_ctx *ctx, const void *packed, int G, int64_t 
 }
 
 
+// ---- the form of the per-query merge ---------------------------------------------------------------------------------------
+// THE rule: which of the three forms merges (k, P).  qk_launch_merge asks it for every search; qk_debug_merge_records asks it for
+// form 0, so that what the hook runs there is what a search launches.  `clocked`: the QK_MERGE_CLOCK probe is on (the flat form has
+// no clock fields).
+enum { QK_MERGE_CHAIN = 1, QK_MERGE_FLAT = 2, QK_MERGE_WIDE = 3 };
+static int merge_form_rule(int k, int P, bool clocked) {
+    static const int merge_wide_min_k = qk_env_int("QK_MERGE_WIDE_MIN_K", 33);
+    static const bool merge_flat = qk_env_int("QK_MERGE_FLAT", 1) != 0;
+    if (k >= merge_wide_min_k) return QK_MERGE_WIDE;
+    if (P <= 64 && k <= 32 && !clocked && merge_flat) return QK_MERGE_FLAT;
+    return QK_MERGE_CHAIN;
+}
+
+// does the form take (k, P) at all?  The flat form holds the slot lines of 64 pairs and reads 64 / k records per load.  (It
+// implies a pool of 128 entries, MAXCH 2: the one instantiation it has.)
+static bool merge_form_admits(int form, int k, int P) { return form != QK_MERGE_FLAT || (k <= 32 && P <= 64); }
+
+// launches `form`; *name (may be null) = the kernel and its instantiation
+static int launch_merge_form(qk_ctx *ctx, const MergeParams &mp, dim3 mgrid, int form, const char **name) {
+    hipStream_t st = ctx->stream;
+    const int Cm = mp.Cm;
+    const int maxch_m = Cm <= 128 ? 2 : Cm <= 256 ? 4 : Cm <= 512 ? 8 : 16;
+    const size_t lds_merge = (((size_t)Cm * 12 + 15) & ~(size_t)15) + (size_t)64 * QK_SLOTS * 4;  // pool + 64 pair slot lines
+    const char *nm = "";
+    if (form == QK_MERGE_WIDE) {
+        hipLaunchKernelGGL(k_merge_wide, mgrid, dim3(256), 0, st, mp);
+        nm = "k_merge_wide";
+    } else if (form == QK_MERGE_FLAT) {
+        if (maxch_m != 2) QK_FAIL(QK_ERR_INVALID, "flat merge: k=%d, pool of %d entries (it holds 128)", mp.k, Cm);
+        const size_t lds_flat = lds_merge + (size_t)2 * 64 * (QK_SLOTS - 1) * 4;  // + record list, record sizes
+        hipLaunchKernelGGL((k_merge_flat<2>), mgrid, dim3(64), lds_flat, st, mp);
+        nm = "k_merge_flat<2>";
+    } else
+    switch (maxch_m) {
+        case 2: hipLaunchKernelGGL((k_merge<2>), mgrid, dim3(64), lds_merge, st, mp); nm = "k_merge<2>"; break;
+        case 4: hipLaunchKernelGGL((k_merge<4>), mgrid, dim3(64), lds_merge, st, mp); nm = "k_merge<4>"; break;
+        case 8: hipLaunchKernelGGL((k_merge<8>), mgrid, dim3(64), lds_merge, st, mp); nm = "k_merge<8>"; break;
+        default: hipLaunchKernelGGL((k_merge<16>), mgrid, dim3(64), lds_merge, st, mp); nm = "k_merge<16>"; break;
+    }
+    QK_HIP(hipGetLastError());
+    if (name) *name = nm;
+    return QK_OK;
+}
+
 // the merge launch of qk_scan_device: one wave (k <= 32: the flat form; else the chained walk) or one workgroup (k >= 33) per query
 int qk_launch_merge(qk_ctx *ctx, MergeParams mp, dim3 mgrid) {
     hipStream_t st = ctx->stream;
-    const int k = mp.k, Cm = mp.Cm;
-    const int maxch_m = Cm <= 128 ? 2 : Cm <= 256 ? 4 : Cm <= 512 ? 8 : 16;
-    const size_t lds_merge = (((size_t)Cm * 12 + 15) & ~(size_t)15) + (size_t)64 * QK_SLOTS * 4;  // pool + 64 pair slot lines
     static const bool merge_clock = qk_env_set("QK_MERGE_CLOCK");
     static long long *d_mclock = nullptr;
     mp.clock = nullptr;
@@ -719,23 +762,7 @@ int qk_launch_merge(qk_ctx *ctx, MergeParams mp, dim3 mgrid) {
         if (!d_mclock) QK_HIP(hipMalloc((void **)&d_mclock, (size_t)1 << 24));
         mp.clock = d_mclock;
     }
-    static const int merge_wide_min_k = qk_env_int("QK_MERGE_WIDE_MIN_K", 33);
-    static const bool merge_flat = qk_env_int("QK_MERGE_FLAT", 1) != 0;
-    if (k >= merge_wide_min_k) {
-        hipLaunchKernelGGL(k_merge_wide, mgrid, dim3(256), 0, st, mp);
-    } else
-    if (mp.P <= 64 && k <= 32 && !mp.clock && merge_flat) {
-        const size_t lds_flat = lds_merge + (size_t)2 * 64 * (QK_SLOTS - 1) * 4;  // + record list, record sizes
-        if (maxch_m == 2) hipLaunchKernelGGL((k_merge_flat<2>), mgrid, dim3(64), lds_flat, st, mp);
-        else hipLaunchKernelGGL((k_merge_flat<4>), mgrid, dim3(64), lds_flat, st, mp);
-    } else
-    switch (maxch_m) {
-        case 2: hipLaunchKernelGGL((k_merge<2>), mgrid, dim3(64), lds_merge, st, mp); break;
-        case 4: hipLaunchKernelGGL((k_merge<4>), mgrid, dim3(64), lds_merge, st, mp); break;
-        case 8: hipLaunchKernelGGL((k_merge<8>), mgrid, dim3(64), lds_merge, st, mp); break;
-        default: hipLaunchKernelGGL((k_merge<16>), mgrid, dim3(64), lds_merge, st, mp); break;
-    }
-    QK_HIP(hipGetLastError());
+    QK_TRY(launch_merge_form(ctx, mp, mgrid, merge_form_rule(mp.k, mp.P, mp.clock != nullptr), nullptr));
 #ifdef QK_PROBES
     if (mp.clock) {  // debug probe: where a merge wave spends its time (mean / max over the queries, 100 MHz ticks)
         std::vector<long long> h((size_t)mgrid.x * 8);
@@ -764,5 +791,50 @@ int qk_launch_merge(qk_ctx *ctx, MergeParams mp, dim3 mgrid) {
         fprintf(stderr, "\n");
     }
 #endif
+    return QK_OK;
+}
+
+// ---- test and diagnosis hook: the merge stage on caller-built records ---------------------------------------------------------
+// What qk_scan_device does behind its scan, on records the caller laid out (MergeParams' layout; device pointers).  form 0 asks
+// merge_form_rule like a search does; 1 / 2 / 3 force the chained walk / the flat form / k_merge_wide, where the form takes (k, P).
+// The structures must be well formed (record numbers -1 or below max_recs, chains that end in -1): the kernels trust the scan.
+int qk_debug_merge_records(qk_ctx *ctx, int64_t Q, int P, int k, int metric, int sqrt_l2, int form, const int32_t *pair_slots,
+                           const int32_t *pair_head, const int32_t *rec_hdr, const uint32_t *rec_ord, const int64_t *rec_id,
+                           int32_t max_recs, int64_t *out_ids, float *out_dist, uint32_t *next_key, int64_t *next_id, char *kernel_name,
+                           int name_len) {
+    if (!ctx) QK_FAIL(QK_ERR_INVALID, "qk_debug_merge_records: ctx is null");
+    if (kernel_name && name_len > 0) kernel_name[0] = 0;
+    if (Q < 0 || Q > INT32_MAX || P < 1 || k < 1 || max_recs < 0)
+        QK_FAIL(QK_ERR_INVALID, "qk_debug_merge_records: bad sizes (Q=%lld P=%d k=%d max_recs=%d)", (long long)Q, P, k, (int)max_recs);
+    if (k > QK_MAX_K) QK_FAIL(QK_ERR_INVALID, "qk_debug_merge_records: k=%d exceeds QK_MAX_K=%d (no merge form pools more)", k, QK_MAX_K);
+    if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
+    if (form < 0 || form > QK_MERGE_WIDE) QK_FAIL(QK_ERR_INVALID, "qk_debug_merge_records: form=%d (0 rule, 1 chained walk, 2 flat, 3 wide)", form);
+    if ((next_key == nullptr) != (next_id == nullptr)) QK_FAIL(QK_ERR_INVALID, "qk_debug_merge_records: next_key and next_id go together");
+    if (Q > 0 && (!pair_slots || !pair_head || !out_ids || (max_recs > 0 && (!rec_hdr || !rec_ord || !rec_id))))
+        QK_FAIL(QK_ERR_INVALID, "qk_debug_merge_records: null argument");
+    const int f = form ? form : merge_form_rule(k, P, false);
+    if (!merge_form_admits(f, k, P))
+        QK_FAIL(QK_ERR_INVALID, "qk_debug_merge_records: the flat form takes k <= 32 and P <= 64 (k=%d P=%d)", k, P);
+    if (Q == 0) return QK_OK;
+    QK_HIP(hipSetDevice(ctx->device));
+    MergeParams mp;
+    mp.P = P;
+    mp.pair_head = pair_head;
+    mp.pair_slots = pair_slots;
+    mp.rec_hdr = (const int2 *)rec_hdr;
+    mp.rec_ord = rec_ord;
+    mp.rec_id = rec_id;
+    mp.max_recs = max_recs;
+    mp.k = k;
+    mp.Cm = qk_round_up(k + 64, 64);  // (qk_scan_device's pool)
+    mp.metric = metric;
+    mp.out_ids = out_ids;
+    mp.out_dist = out_dist;
+    mp.sqrt_l2 = sqrt_l2 ? 1 : 0;
+    mp.clock = nullptr;
+    const char *nm = "";
+    QK_TRY(launch_merge_form(ctx, mp, dim3((unsigned)Q), f, &nm));
+    if (kernel_name && name_len > 0) snprintf(kernel_name, (size_t)name_len, "%s", nm);
+    if (next_key) QK_TRY(qk_launch_next_cursor(ctx, mp, Q, out_ids, next_key, next_id));
     return QK_OK;
 }

@@ -177,6 +177,11 @@ def test_packed_exchange_layout_and_merge(G, per, k, metric):
     mi, md = ctx.merge_topk(torch.from_numpy(rid).cuda(), torch.from_numpy(rk).cuda(), metric)
     torch.cuda.synchronize()
     assert torch.equal(pi, mi) and torch.equal(pd.view(torch.int32), md.view(torch.int32))
+    # ... and both equal an answer neither of them made: the first k of the union of the candidates under (key, id)
+    import merge_yardstick as Y
+    yi, yd = Y.merge_ranks_reference(rid, rk, metric, sqrt_l2=True)
+    np.testing.assert_array_equal(mi.cpu().numpy(), yi)
+    np.testing.assert_array_equal(md.cpu().numpy().view(np.uint32), yd.view(np.uint32))
     ctx.close()
 
 
