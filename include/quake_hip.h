@@ -108,6 +108,27 @@ QK_API int qk_ctx_set_form_feedback(qk_ctx *ctx, int enabled);
  * function of the call sequence (tests/test_scan_feedback_gpu.py asserts the sequence).  NULL: measured times again.  The
  * environment variable QK_FORM_FEEDBACK=0 creates every context with feedback off. */
 QK_API int qk_ctx_set_form_times(qk_ctx *ctx, const float *ms3);
+/* The fp16 shadow form: qk_search with one list per query (nprobe = 1), k <= 16, d <= 256, L2 or IP, streams an
+ * fp16 mirror of the store's rows -- half the bytes --, keeps the 32 best approximate keys per segment and finishes in fp32: every
+ * candidate's canonical key is recomputed, the answer is verified against a bound of the approximation error, and a query that
+ * does not verify is answered by an exact scan of its list.  Same bits as every other form.  mode 0 = never, 1 = automatic (the
+ * default; QK_SHADOW in the environment overrides it at creation): the form feedback measures the form next to the tile form and
+ * uses it where it is faster -- batches of >= 1024 queries; the shadow is built at the second such call on an unchanged store,
+ * again after 8 calls once the store was modified --, 2 = forced: whenever eligible, whatever the batch size and the feedback,
+ * building the shadow at once (tests).  qk_ctx_last_scan_kernel names "k_scan (fp16 shadow)".  No reference counterpart. */
+QK_API int qk_ctx_set_shadow(qk_ctx *ctx, int mode);
+/* queries the shadow form's finish verified / answered by the exact scan of their list, candidates re-scored in fp32, and queries
+ * whose pair left more records than its slot line lists (the finish walked the record chain), since the context was created
+ * (synchronises the stream).  Any pointer may be NULL. */
+QK_API int qk_ctx_shadow_stats(qk_ctx *ctx, int64_t *verified, int64_t *fallback, int64_t *candidates, int64_t *chained);
+/* The fourth figure of qk_ctx_set_form_times: ms > 0 is what a harvested measurement of the shadow form reads; 0 clears it.  While
+ * three figures are injected and this one is not, the form is not admissible. */
+QK_API int qk_ctx_set_shadow_form_time(qk_ctx *ctx, float ms);
+/* The bound E the shadow form works with: |approximate key - canonical fp32 key| <= E for a query of norm qnorm whose fp16 image is
+ * rho_q away from it, against rows of a store whose fp16 images are at most rho away and at most xmax long (Euclidean norms; a
+ * distance to the image counts an fp16 subnormal as the farther of itself and zero).  Pure host arithmetic, no GPU needed;
+ * DESIGN.md 5.20 has the derivation, tests/test_shadow_bound.py checks it against emulated arithmetic. */
+QK_API float qk_shadow_error_bound(int metric, int d, float qnorm, float rho_q, float rho, float xmax);
 QK_API int qk_ctx_synchronize(qk_ctx *ctx);
 /* hipEvent timing of the phases, recorded on the context's stream around the kernels:
  *   0 off; 1 per call (the qk_timing* passed to qk_scan/qk_search is filled, which synchronises the stream);
@@ -183,8 +204,14 @@ QK_API int qk_store_get_vectors(qk_store *s, const int64_t *ids_host, int64_t n,
  * not pay.  No reference counterpart (its lists are host vectors). */
 QK_API int qk_store_publish(qk_store *s);
 QK_API int qk_store_counters(qk_store *s, int64_t *out, int n);
-/* bytes of HBM held by the arena (vectors+norms+ids), for capacity planning */
+/* bytes of HBM held by the arena (vectors+norms+ids) and, once built, its fp16 shadow, for capacity planning */
 QK_API int64_t qk_store_device_bytes(qk_store *s);
+/* The fp16 shadow of the store (qk_ctx_set_shadow): *valid = 1 when a shadow mirrors the store as it is now, *bytes = HBM it holds,
+ * *builds = conversions that left a valid shadow so far.  Any pointer may be NULL.  A store that holds a non-finite value or one
+ * beyond the fp16 range (65504) has no shadow. */
+QK_API int qk_store_shadow_info(qk_store *s, int *valid, int64_t *bytes, int64_t *builds);
+/* frees the shadow (qk_store_destroy and qk_store_reset do so too); the next eligible searches build it again */
+QK_API int qk_store_shadow_drop(qk_store *s);
 
 /* ---- search ------------------------------------------------------------------------------------ */
 /* Coarse step = parent_->search(x, {k = min(nprobe, nlist), batched_scan = true})

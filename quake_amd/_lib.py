@@ -58,6 +58,10 @@ SIGNATURES = {
     "qk_ctx_get_stream": (_int, [_vp, C.POINTER(_vp), C.POINTER(_int)]),
     "qk_ctx_set_form_feedback": (_int, [_vp, _int]),
     "qk_ctx_set_form_times": (_int, [_vp, C.POINTER(C.c_float)]),
+    "qk_ctx_set_shadow": (_int, [_vp, _int]),
+    "qk_ctx_shadow_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "qk_ctx_set_shadow_form_time": (_int, [_vp, C.c_float]),
+    "qk_shadow_error_bound": (C.c_float, [_int, _int, C.c_float, C.c_float, C.c_float, C.c_float]),
     "qk_ctx_synchronize": (_int, [_vp]),
     "qk_ctx_set_timing": (_int, [_vp, _int]),
     "qk_ctx_get_timing": (_int, [_vp, C.POINTER(_int)]),
@@ -87,6 +91,8 @@ SIGNATURES = {
     "qk_store_get_vector": (_int, [_vp, _i64, _vp, C.POINTER(_int)]),
     "qk_store_device_bytes": (_i64, [_vp]),
     "qk_store_counters": (_int, [_vp, _vp, _int]),
+    "qk_store_shadow_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64)]),
+    "qk_store_shadow_drop": (_int, [_vp]),
     "qk_coarse": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _int]),
     "qk_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),

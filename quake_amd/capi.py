@@ -149,6 +149,21 @@ class Context:
         else:
             check(self.lib.qk_ctx_set_form_times(self.h, (C.c_float * 3)(*[float(v) for v in ms3])))
 
+    def set_shadow(self, mode):
+        """the fp16 shadow form of the single-probe search (qk_ctx_set_shadow): 0 never, 1 automatic, 2 forced"""
+        check(self.lib.qk_ctx_set_shadow(self.h, int(mode)))
+
+    def shadow_stats(self):
+        """{verified, fallback, candidates}: queries the shadow form's finish verified / answered by the exact scan of their
+        list, and candidates it re-scored in fp32, since the context was created (qk_ctx_shadow_stats)"""
+        v, f, c, ch = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.lib.qk_ctx_shadow_stats(self.h, C.byref(v), C.byref(f), C.byref(c), C.byref(ch)))
+        return {"verified": v.value, "fallback": f.value, "candidates": c.value, "chained": ch.value}
+
+    def set_shadow_form_time(self, ms):
+        """the fourth injected figure of set_form_times (the shadow form's); None or 0 clears it"""
+        check(self.lib.qk_ctx_set_shadow_form_time(self.h, C.c_float(float(ms or 0.0))))
+
     def set_stream(self, hip_stream):
         """hip_stream: a hipStream_t handle (e.g. torch.cuda.current_stream().cuda_stream); 0 = the device's NULL stream
         (torch's default stream); None = back to the context's private stream.
@@ -1008,6 +1023,16 @@ class Store:
 
     def device_bytes(self):
         return self.lib.qk_store_device_bytes(self.h)
+
+    def shadow_info(self):
+        """{valid, bytes, builds} of the store's fp16 shadow (qk_store_shadow_info)"""
+        v, b, n = C.c_int(), C.c_int64(), C.c_int64()
+        check(self.lib.qk_store_shadow_info(self.h, C.byref(v), C.byref(b), C.byref(n)))
+        return {"valid": bool(v.value), "bytes": b.value, "builds": n.value}
+
+    def shadow_drop(self):
+        """free the fp16 shadow (qk_store_shadow_drop); eligible searches build it again"""
+        check(self.lib.qk_store_shadow_drop(self.h))
 
     def exact_pool_info(self):
         """{slots, rows, cap_rows, builds, evictions, device_bytes} of the candidate pool of exact per-query search

@@ -1,6 +1,7 @@
 // qk_api.hip -- C-ABI search entry points (include/quake_hip.h): marshalling between caller memory and the
 // device pipeline of qk_scan.hip.  No arithmetic lives here.
 #include "qk_internal.h"
+#include "qk_scan_types.h"
 
 #include <algorithm>
 #include <cstring>
@@ -29,7 +30,9 @@ int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, i
     t->partitions_scanned = hs[7];  // (query, partition) pairs that reached a present, non-empty partition
     int64_t rows_unique;
     memcpy(&rows_unique, hs + 2, sizeof(int64_t));
-    t->scan_bytes = rows_unique * (int64_t)s->d * 4;
+    // (the scan of this call left MINUS the bytes per row of the form that ran in t->scan_bytes -- the fp16 image where the shadow
+    //  form answered --; anything else, a total already filled in included, means fp32 rows)
+    t->scan_bytes = rows_unique * (t->scan_bytes < 0 ? -t->scan_bytes : (int64_t)s->d * 4);
     return qk_read_phase_ms(ctx, t, have_coarse, scan_ev_base);
 }
 
@@ -64,7 +67,7 @@ int check_metric(int metric) {
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
                   bool defer_finish, int64_t *probed_out, qk_filter *filter, const qk_filter_batch *fbatch, const qk_adaptive *adaptive,
-                  const qk_cursors *cursors) {
+                  const qk_cursors *cursors, bool shadow_entry) {
     QK_TRY(qk_check_overflow(ctx));  // a record-buffer overflow of an earlier launch is reported by the next call
     QK_HIP(hipSetDevice(ctx->device));
     if (timing) memset(timing, 0, sizeof(*timing));
@@ -150,7 +153,12 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
     }
     // small batches: the whole search in one launch (qk_small.hip) -- no prep / group / seed / merge launches
     // (not a filtered search: that kernel seeds its bound from a sample of rows)
-    if (use_parent && !coarse_only && kk > 0 && !probed_out && !filter && !fbatch && qk_small_supported(ctx, parent, s, Q, kk, k)) {
+    // the fp16 shadow form serves qk_search alone -- plain top-k, one list per query; forced mode (tests) keeps such a call away from
+    // the one-launch search of small batches, so that the form it asks for answers
+    const bool shadow_call = shadow_entry && ctx->shadow_mode != 0 && use_parent && !coarse_only && kk == 1 && !probed_out && !filter &&
+                             !fbatch && !adaptive && !cursors && !defer_finish && k <= QK_SHADOW_MAX_K && d <= QK_SHADOW_MAX_D;
+    if (use_parent && !coarse_only && kk > 0 && !probed_out && !filter && !fbatch && !(shadow_call && ctx->shadow_mode == 2) &&
+        qk_small_supported(ctx, parent, s, Q, kk, k)) {
         const bool tm = ctx->timing && timing;
         // one event pair around the one kernel (an event record costs the stream a few microseconds): ev[4], ev[7] per call,
         // the scan pair of a deferred group otherwise
@@ -235,6 +243,7 @@ int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
             }
         }
         sa.sqrt_l2 = !ctx->squared_l2;
+        sa.shadow_ok = shadow_call;
         // filtered search: the row mask, re-derived here (on this stream, in front of the scan) if the store changed
         if (filter) QK_TRY(qk_filter_ensure(ctx, s, filter, &sa.mask));
         if (cursors) {  // paged search
@@ -358,7 +367,9 @@ int qk_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_
     if (k <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search: k must be positive");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_search: nprobe must be positive");
     QK_TRY(check_metric(metric));
-    return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, out_ids, out_dist, mem, timing, false, false);
+    // (the one entry point the fp16 shadow form may answer: the last argument; qk_run_search decides)
+    return qk_run_search(ctx, parent, s, x, Q, nullptr, 0, nprobe, k, metric, out_ids, out_dist, mem, timing, false, false, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, true);
 }
 
 int qk_search_tracked(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int metric,

@@ -1,6 +1,7 @@
 // qk_ctx.hip -- error state, context, scratch memory.
 #include "qk_internal.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 #include <cstdarg>
@@ -40,6 +41,8 @@ int qk_ctx_create(int device, qk_ctx **out) {
     // (the one environment switch of the product library, read at context creation: a whole test suite or a deployment that wants
     //  the static rule alone for every context, including the ones the mirrors create; include/quake_hip.h)
     if (const char *e = getenv("QK_FORM_FEEDBACK")) c->form_feedback = atoi(e) != 0;
+    // (and the mode of the fp16 shadow form, qk_ctx_set_shadow: 0 never, 1 automatic, 2 forced)
+    if (const char *e = getenv("QK_SHADOW")) c->shadow_mode = std::min(2, std::max(0, atoi(e)));
     QK_HIP(hipGetDeviceProperties(&c->prop, device));
     QK_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
@@ -74,6 +77,7 @@ int qk_ctx_destroy(qk_ctx *c) {
     if (c->after_buf) hipFree(c->after_buf);
     if (c->pool_buf) hipFree(c->pool_buf);
     if (c->div_buf) hipFree(c->div_buf);
+    if (c->shadow_counters) hipFree(c->shadow_counters);
     if (c->xcd_host) hipHostFree(c->xcd_host);
     if (c->xcd_ev) hipEventDestroy(c->xcd_ev);
     for (auto &f : c->form_stats) {
@@ -134,6 +138,35 @@ int qk_ctx_set_form_times(qk_ctx *c, const float *ms3) {
         if (ms3 && !(ms3[f] > 0.f)) QK_FAIL(QK_ERR_INVALID, "qk_ctx_set_form_times: ms3[%d] must be > 0", f);
         c->form_times[f] = ms3 ? ms3[f] : 0.f;
     }
+    return QK_OK;
+}
+
+int qk_ctx_set_shadow(qk_ctx *c, int mode) {
+    if (!c) QK_FAIL(QK_ERR_INVALID, "qk_ctx_set_shadow: ctx is null");
+    if (mode < 0 || mode > 2) QK_FAIL(QK_ERR_INVALID, "qk_ctx_set_shadow: mode=%d (0 never, 1 automatic, 2 forced)", mode);
+    c->shadow_mode = mode;
+    return QK_OK;
+}
+
+int qk_ctx_set_shadow_form_time(qk_ctx *c, float ms) {
+    if (!c) QK_FAIL(QK_ERR_INVALID, "qk_ctx_set_shadow_form_time: ctx is null");
+    if (!(ms >= 0.f)) QK_FAIL(QK_ERR_INVALID, "qk_ctx_set_shadow_form_time: ms must be >= 0 (0 clears the figure)");
+    c->shadow_form_time = ms;
+    return QK_OK;
+}
+
+int qk_ctx_shadow_stats(qk_ctx *c, int64_t *verified, int64_t *fallback, int64_t *candidates, int64_t *chained) {
+    if (!c) QK_FAIL(QK_ERR_INVALID, "qk_ctx_shadow_stats: ctx is null");
+    unsigned long long h[4] = {0, 0, 0, 0};
+    if (c->shadow_counters) {
+        QK_HIP(hipSetDevice(c->device));
+        QK_HIP(hipStreamSynchronize(c->stream));
+        QK_HIP(hipMemcpy(h, c->shadow_counters, sizeof(h), hipMemcpyDeviceToHost));
+    }
+    if (verified) *verified = (int64_t)h[0];
+    if (fallback) *fallback = (int64_t)h[1];
+    if (candidates) *candidates = (int64_t)h[2];
+    if (chained) *chained = (int64_t)h[3];
     return QK_OK;
 }
 

@@ -119,8 +119,9 @@ struct qk_ctx {
     // kernel, merge: HIP events around it, read back without synchronising -- under each of the forms the shape admits.
     struct form_stat {
         uint64_t key = 0;
-        float ms[3] = {0.f, 0.f, 0.f};  // 0: 16 x 16 tile form (k_scan, plain or query-sharing), 1: per-wave walk (k_scan_rl), 2: mixed
-        int n[3] = {0, 0, 0};           // measurements taken
+        float ms[4] = {0.f, 0.f, 0.f, 0.f};  // 0: 16 x 16 tile form (k_scan, plain or query-sharing), 1: per-wave walk (k_scan_rl), 2: mixed,
+                                             // 3: tile form over the fp16 shadow + exact finish (qk_shadow.hip)
+        int n[4] = {0, 0, 0, 0};        // measurements taken
         int64_t calls = 0, last_use = 0;
         int pending = -1;               // form whose event pair is in flight
         int rr = 0;
@@ -131,6 +132,12 @@ struct qk_ctx {
     bool form_feedback = true;          // qk_ctx_set_form_feedback (QK_FORM_FEEDBACK=0 in the environment: off from the start)
     bool form_times_set = false;        // qk_ctx_set_form_times: a harvested measurement reads form_times[form], not the event pair
     float form_times[3] = {0.f, 0.f, 0.f};
+    // fp16 shadow form (qk_shadow.hip): 0 never, 1 when the form feedback measures it fastest, 2 whenever eligible (tests);
+    // shadow_form_time: the fourth injected figure (qk_ctx_set_shadow_form_time; 0 = none: with three figures injected and this
+    // one missing the form is not admissible)
+    int shadow_mode = 1;
+    float shadow_form_time = 0.f;
+    unsigned long long *shadow_counters = nullptr;  // device [4]: verified, fallback, candidates (qk_ctx_shadow_stats)
     int *overflow_host = nullptr;    // pinned, device-visible: a scan kernel sets it when its record buffer overflows
     int *overflow_dev = nullptr;
     char *qprep_zero = nullptr;      // region cleared by the prep kernel for the scan of the same batch
@@ -169,7 +176,7 @@ struct qk_ctx {
         long long launches = 0;
         int samples = 0;  // samples folded in so far
     };
-    std::unordered_map<uint64_t, xcd_state> xcd;  // by store uid
+    std::unordered_map<uint64_t, xcd_state> xcd;  // by store uid and form (the shadow form streams another arena: top bit set)
     unsigned long long *xcd_host = nullptr;       // pinned [16]: ticks per class, waves per class
     hipEvent_t xcd_ev = nullptr;
     bool xcd_pending = false;
@@ -273,7 +280,26 @@ struct qk_store {
     // exact search per query (qk_filter.hip, "the candidate pool"): made by the first qk_search_filtered_exact_batch, freed by
     // qk_store_exact_pool_drop and qk_store_destroy
     struct qk_pool *pool = nullptr;
+    // fp16 shadow of the arena (qk_shadow.hip): arena row r <-> shadow row r, two 16-column blocks per 1 KiB shadow
+    // block.  Built lazily by qk_store_shadow_consider, valid for exactly one `version`.
+    void *shadow = nullptr;
+    int64_t shadow_cap_rows = 0;       // rows the allocation holds
+    bool shadow_valid = false;         // the shadow mirrors the arena as of shadow_version
+    uint64_t shadow_version = 0;
+    uint64_t shadow_refused_version = 0;  // a build for this version found an invalid list or no memory: no shadow until it changes
+    bool shadow_refused = false;
+    bool shadow_ever = false;          // a build was attempted before: the next one waits for 8 stable calls, not 2
+    uint64_t shadow_seen_version = 0;  // consecutive eligible calls that saw this version
+    int shadow_seen_calls = 0;
+    float shadow_rho = 0.f, shadow_xmax = 0.f;  // max ||x - fp16(x)||, max ||fp16(x)|| over the live rows, rounded up
+    uint32_t *shadow_stats = nullptr;  // device [4]: what a conversion reduces (kept with the store: no allocation per build)
+    int64_t shadow_builds = 0;
 };
+// the shadow of `s` for the search that is being planned on ctx (the store's table is synced): *usable = a valid shadow of the
+// current version exists (built here if the call count -- or force -- says so).  Never fails for want of memory or validity.
+int qk_store_shadow_consider(qk_ctx *ctx, qk_store *s, bool force, bool *usable);
+void qk_store_shadow_free(qk_store *s);
+inline int qk_shadow_nblk(int nblk) { return (nblk + 1) / 2; }
 void qk_pool_destroy(qk_store *s);
 void qk_store_ensure_index(qk_store *s);
 int qk_store_add_batch_host_assign(qk_store *s, int64_t n, const int64_t *ids_dev, const float *vecs_dev, const std::vector<int64_t> &h_assign,
@@ -337,6 +363,7 @@ struct qk_scan_args {
     // the conversion kernel and its launch boundary are skipped.  packed_out: filled by the coarse stage when it can do so.
     const unsigned long long *pids_packed = nullptr;
     const unsigned long long **packed_out = nullptr;
+    bool shadow_ok = false;      // the call may be served by the fp16 shadow form (qk_search, plain top-k: qk_run_search sets it)
     const float4 *xq4 = nullptr;  // [Q][nblk][4] fragment-ordered queries (qk_prep_queries), required
     const float *xn = nullptr;    // [Q] squared norms, required
     // filtered scan: the row mask of a qk_filter that qk_filter_ensure has just brought up to date for this store (one 16-bit
@@ -410,7 +437,7 @@ struct qk_cursors {
 int qk_run_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                   int k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool coarse_only,
                   bool defer_finish, int64_t *probed_out = nullptr, qk_filter *filter = nullptr, const qk_filter_batch *fbatch = nullptr,
-                  const qk_adaptive *adaptive = nullptr, const qk_cursors *cursors = nullptr);
+                  const qk_adaptive *adaptive = nullptr, const qk_cursors *cursors = nullptr, bool shadow_entry = false);
 int qk_finish_timing(qk_ctx *ctx, qk_store *s, qk_timing *t, bool have_coarse, int scan_ev_base);
 // the event half of it: coarse_ms .. total_ms from ctx->ev of a drained stream (nothing unless the context records per-call events)
 int qk_read_phase_ms(qk_ctx *ctx, qk_timing *t, bool have_coarse, int scan_ev_base);

@@ -762,6 +762,12 @@ __global__ __launch_bounds__(64 * W) void k_seed_tau_wg(SeedParams S) {
 // the XCD (workgroups with blockIdx % 8 in {1, 6, 7} end 3 % later) -- neither is known when the cut is made.
 #define QK_DYN_PCT_DEFAULT 0     // share of the tile sequence handed out dynamically (0 = static cut only)
 #endif
+#ifndef QK_SHADOW_WAVES_PER_CU_DEFAULT
+// Resident waves per CU of the fp16 shadow form (0: the tile form's rule, 4 on the bench index).  A load step of the form carries half
+// the bytes of the tile form's, so more waves are needed to keep the same bytes in flight.  Measured on the bench index, forced mode,
+// ms per step at 4 / 6 / 8 waves per CU: 0.2566 / 0.2342 / 0.2412 (profiles/shadow_bench_parent_branch.txt).
+#define QK_SHADOW_WAVES_PER_CU_DEFAULT 6
+#endif
 #ifndef QK_DYN_CHUNK_DEFAULT
 #define QK_DYN_CHUNK_DEFAULT 16  // tiles per dynamic chunk
 #endif
@@ -941,7 +947,12 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     ScanPlan plan;
     QK_TRY(qk_scan_plan(ctx, s, a, emit, k, P, npairs, &plan));
     const int nblk = s->nblk;
-    const size_t q_bytes = (size_t)nblk * 1024;
+    // fp16 shadow form (qk_shadow.hip): the tile form's launch over the shadow -- blocks of 32 columns, records of k' entries that hold
+    // approximate keys and arena rows -- and k_shadow_finish in the merge's place
+    const bool shadow = plan.form == 3;
+    const int nblk_scan = shadow ? qk_shadow_nblk(nblk) : nblk;  // 1 KiB blocks per tile of what the scan kernel streams
+    const int k_rec = shadow ? QK_SHADOW_KP : k;                 // entries per record
+    const size_t q_bytes = (size_t)nblk_scan * 1024;
     int DB = plan.DB;
     const int C = plan.C, nw = plan.nw, qshare = plan.qshare;
     const bool use_rl = plan.use_rl;
@@ -982,10 +993,15 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         static const int wpc = qk_env_int("QK_SCAN_WAVES_PER_CU", 0);  // probe override
         if (wpc > 0) waves_per_cu = std::max(nw, wpc / nw * nw);
     }
+    if (shadow) {
+        // (half the bytes per load step: resident waves per CU measured at 4 / 6 / 8 on the bench index, profiles/shadow_bench_parent_branch.txt)
+        static const int sh_wpc = qk_env_int("QK_SHADOW_WAVES_PER_CU", QK_SHADOW_WAVES_PER_CU_DEFAULT);
+        if (sh_wpc > 0) waves_per_cu = std::min(sh_wpc, (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds_scan + 512))));
+    }
     if (use_rl) waves_per_cu = rl_waves;  // one wave per SIMD: 256+ registers of row data per wave
     // wide rows (d >= 256: the LDS query tile leaves room for <= 4 waves per CU): 16 blocks = 16 KB per load step, so
     // that the few resident waves still keep enough bytes in flight to cover the HBM latency
-    if (nblk % 16 == 0 && waves_per_cu <= 4 && !qshare && !use_rl && !qk_env_set("QK_SCAN_NO_DB16")) DB = 16;
+    if (nblk % 16 == 0 && waves_per_cu <= 4 && !qshare && !use_rl && !shadow && !qk_env_set("QK_SCAN_NO_DB16")) DB = 16;
     const int wgs_per_cu = waves_per_cu / nw;
     const int64_t n_wgs = (int64_t)num_cus * wgs_per_cu;
     const int64_t n_waves = n_wgs * nw;
@@ -1024,8 +1040,12 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     add((size_t)(std::min<int64_t>(npids, np1) + 1) * 4 + 64);
     add((size_t)Q * 4);
     add((size_t)max_recs * 8);
-    add((size_t)max_recs * k * 4);
-    add((size_t)max_recs * k * 8);
+    add((size_t)max_recs * k_rec * 4);
+    add((size_t)max_recs * k_rec * 8);
+    if (shadow) {
+        add((size_t)Q * nblk_scan * 64);
+        add((size_t)Q * 4);
+    }
     need += 8192;
     QK_TRY(qk_ws_reserve(ctx, need));
     const float4 *xq4 = a.xq4;
@@ -1054,8 +1074,15 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     int32_t *act_list = (int32_t *)qk_ws_alloc(ctx, (size_t)(std::min<int64_t>(npids, np1) + 1) * 4 + 64);
     uint32_t *gtau = (uint32_t *)(scal + 64);
     int2 *rec_hdr = (int2 *)qk_ws_alloc(ctx, (size_t)max_recs * 8);
-    uint32_t *rec_ord = (uint32_t *)qk_ws_alloc(ctx, (size_t)max_recs * k * 4);
-    int64_t *rec_id = (int64_t *)qk_ws_alloc(ctx, (size_t)max_recs * k * 8);
+    uint32_t *rec_ord = (uint32_t *)qk_ws_alloc(ctx, (size_t)max_recs * k_rec * 4);
+    int64_t *rec_id = (int64_t *)qk_ws_alloc(ctx, (size_t)max_recs * k_rec * 8);
+    float4 *sh_xqh = shadow ? (float4 *)qk_ws_alloc(ctx, (size_t)Q * nblk_scan * 64) : nullptr;  // fp16 copy of the prepared queries
+    float *sh_E = shadow ? (float *)qk_ws_alloc(ctx, (size_t)Q * 4) : nullptr;                   // every query's error bound
+    if (shadow && (!sh_xqh || !sh_E)) QK_FAIL(QK_ERR_OOM, "qk_scan: workspace exhausted");
+    if (shadow && !ctx->shadow_counters) {
+        QK_HIP(hipMalloc((void **)&ctx->shadow_counters, 4 * sizeof(unsigned long long)));
+        QK_HIP(hipMemsetAsync(ctx->shadow_counters, 0, 4 * sizeof(unsigned long long), st));
+    }
     if (!g_cnt || !active || !g_qoff || !act_hoff || !grouped_q || !pair_slots || !act_list || !gtau || !rec_hdr || !rec_ord || !rec_id)
         QK_FAIL(QK_ERR_OOM, "qk_scan: workspace exhausted");
 
@@ -1197,6 +1224,8 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(1024), 0, st, G);
         if (npairs > 0) hipLaunchKernelGGL(k_group_scatter, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, G);
     }
+    if (shadow && npairs > 0 && npids > 0)
+        QK_TRY(qk_launch_shadow_prep(st, xq4, xn, Q, s->d, nblk, a.metric, s->shadow_rho, s->shadow_xmax, sh_xqh, sh_E));
     QK_TRY(pe.mark(1));
 
     // ---- scan ------------------------------------------------------------------------------------------------
@@ -1236,7 +1265,17 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             QK_HIP(hipMemsetAsync(gtau, 0xFF, (size_t)Q * 4, st));
             sp.gtau = gtau;
         }
-        sp.k = k;
+        sp.sh_E = nullptr;
+        if (shadow) {  // the mirror and the fp16 queries in the arena's and the prepared queries' places; the seed is read, never written
+            sp.vecs = (const float4 *)s->shadow;
+            sp.nblk = nblk_scan;
+            sp.xq4 = sh_xqh;
+            sp.sh_E = sh_E;
+            sp.gtau = gtau;
+            sp.tau_refresh = 0;
+            sp.tau_publish = 0;
+        }
+        sp.k = k_rec;
         sp.C = C;
         sp.metric = a.metric;
         sp.pair_head = pair_head;
@@ -1323,7 +1362,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         if (ctx->xcd_pending && !xcd_ready) (void)hipGetLastError();  // "not ready" is not an error: keep it out of the later checks
         if (xcd_ready) {  // a finished sample: speed = share / time
             ctx->xcd_pending = false;
-            qk_ctx::xcd_state &xs = ctx->xcd[ctx->xcd_key];
+            qk_ctx::xcd_state &xs = ctx->xcd[ctx->xcd_key];  // (the key of the launch that was sampled: store and form)
             double sp8[8], mean = 0;
             int nz = 0;
             for (int c = 0; c < 8; c++) {
@@ -1351,7 +1390,8 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         for (int c = 0; c < 8; c++) sp.xcd_w[c] = 1024;
         // (a filtered launch neither uses nor feeds the weights: how long a class takes depends on the tiles its mask leaves)
         if (xcd_adapt && !wide && !filtered && (sp.dyn_counter == nullptr || use_rl) && grid >= 64 && tiles_est >= (int64_t)grid * wpw * 32) {
-            qk_ctx::xcd_state &xs = ctx->xcd[s->uid];
+            const uint64_t xkey = s->uid ^ (shadow ? 0x8000000000000000ull : 0ull);  // (the shadow is another allocation: its own weights)
+            qk_ctx::xcd_state &xs = ctx->xcd[xkey];
             sp.xcd_on = 1;
             for (int c = 0; c < 8; c++) sp.xcd_w[c] = std::max(1, (int)(xs.w[c] * 1024.0 + 0.5));
             const long long nl = xs.launches++;
@@ -1360,7 +1400,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
                 if (!ctx->xcd_host) QK_HIP(hipHostMalloc((void **)&ctx->xcd_host, 16 * sizeof(unsigned long long)));
                 if (!ctx->xcd_ev) QK_HIP(hipEventCreateWithFlags(&ctx->xcd_ev, hipEventDisableTiming));
                 sp.xcd_stat = (unsigned long long *)(scal + 32);  // zeroed with the counters
-                ctx->xcd_key = s->uid;
+                ctx->xcd_key = xkey;
                 for (int c = 0; c < 8; c++) ctx->xcd_wsnap[c] = sp.xcd_w[c] / 1024.0;
             }
         }
@@ -1372,8 +1412,14 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             QK_HIP(hipMemsetAsync(d_clock, 0, (size_t)grid * wpw * 64 * 2, st));
             sp.wave_clock = d_clock;
         }
-        ctx->last_scan_kernel = paged ? (wide ? "k_scan_wide (after)" : "k_scan (after)") : a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
-        if (wide)
+        ctx->last_scan_kernel = paged ? (wide ? "k_scan_wide (after)" : "k_scan (after)") : a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : shadow ? "k_scan (fp16 shadow)" : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
+        // (until qk_finish_timing fills it in, qk_timing::scan_bytes holds MINUS the bytes per row of the form that ran, or 0 = fp32
+        //  rows: the call's own result, not context state -- a later call cannot inherit it --, and a negative value is no byte count,
+        //  so finishing the same struct twice cannot multiply rows by a total)
+        if (timing) timing->scan_bytes = shadow ? -(int64_t)nblk_scan * 64 : 0;
+        if (shadow)
+            QK_TRY(qk_launch_scan_shadow(DB, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
+        else if (wide)
             QK_TRY(qk_launch_scan_wide(maxch, (unsigned)grid, lds_launch, st, sp));
         else if (use_rl)
             QK_TRY(qk_launch_scan_rl(nblk, dim3((unsigned)grid), lds_launch, st, sp));
@@ -1524,6 +1570,36 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     mp.out_dist = a.out_dist;
     mp.sqrt_l2 = a.sqrt_l2 ? 1 : 0;
     const dim3 mgrid((unsigned)(a.per_pair ? Q * P : Q));
+    if (shadow) {  // the exact finish (qk_shadow.hip): candidates re-scored in fp32, verified, or the list scanned exactly
+        ShadowFinishParams fp;
+        fp.pair_head = pair_head;
+        fp.pair_slots = pair_slots;
+        fp.rec_hdr = rec_hdr;
+        fp.rec_ord = rec_ord;
+        fp.rec_id = rec_id;
+        fp.max_recs = (int32_t)max_recs;
+        fp.k = k;
+        fp.metric = a.metric;
+        fp.sqrt_l2 = a.sqrt_l2 ? 1 : 0;
+        fp.out_ids = a.out_ids;
+        fp.out_dist = a.out_dist;
+        fp.E = sh_E;
+        fp.x = a.x;
+        fp.xn = xn;
+        fp.vecs = (const float4 *)s->vecs;
+        fp.norms = s->norms;
+        fp.ids = s->ids;
+        fp.nblk = nblk;
+        fp.d = s->d;
+        fp.pids = a.pids;
+        fp.pids_packed = a.pids_packed;
+        fp.pt_off = s->d_off;
+        fp.pt_size = s->d_size;
+        fp.npids = npids;
+        fp.counters = ctx->shadow_counters;
+        if (npairs > 0 && npids > 0) QK_TRY(qk_launch_shadow_finish(st, fp, Q));
+        else QK_TRY(qk_launch_merge(ctx, mp, mgrid));
+    } else
     QK_TRY(qk_launch_merge(ctx, mp, mgrid));
     // paged search: every query's next cursor, from the keys the merge has just compared
     if (paged && a.next_key) QK_TRY(qk_launch_next_cursor(ctx, mp, Q, a.out_ids, a.next_key, a.next_id));

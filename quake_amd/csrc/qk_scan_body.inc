@@ -11,6 +11,10 @@
 // QK_SCAN_AFTER (with QK_SCAN_FILT 1) = k_scan_after, paged search: the filtered body plus one more test in the epilogue -- the
 // row's (key, id) must lie behind the lane's own query's cursor (ScanParams::after_key / after_id).  Everything it adds sits
 // behind #ifdef QK_SCAN_AFTER: the preprocessed text of the three kernels above does not change.
+// QK_SCAN_SHADOW (with QK_SCAN_FILT 0) = k_scan_shadow (qk_shadow.hip), the fp16 shadow form: P.vecs is the fp16 mirror of the arena
+// (P.nblk blocks of 32 columns per tile, 16 B per lane as before), P.xq4 the fp16 copy of the queries in the same lane order, one
+// v_mfma_f32_16x16x32_f16 per block; no ids are loaded -- a candidate's "id" is its arena row --, the start bound is the seed's
+// widened by the query's error bound P.sh_E, P.k is the k' of the form.  Everything it changes sits behind #ifdef QK_SCAN_SHADOW.
 // Expects: template parameters DB, MAXCH, MODE, L2 and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     // nw waves per workgroup (1, 2 or 4) share ONE LDS query tile and split every segment's tiles between them; each
@@ -157,6 +161,9 @@
         int cnt = 0;
         dbg_seg++;
         float xnj = 0.0f;
+#ifdef QK_SCAN_SHADOW
+        bool sh_dead = false;  // this lane's query takes no part (its bound is negative: the finish answers it exactly)
+#endif
         {
             // (a wave whose share is empty still issues the static loads: keep them inside the segment)
             const int64_t tile_abs0 = (row_off >> 4) + min(tl, tend_wg - 1);
@@ -267,6 +274,23 @@
             }                                                         \
         }                                                             \
     }
+#elif defined(QK_SCAN_SHADOW)
+#define QK_EPI_M(Y)
+#define QK_NEXT_TILE tile++
+#define QK_LOAD(A, Y, I0, I1)                                         \
+    {                                                                 \
+        const float4 *pp_ = src + (int64_t)lS * (DB * 64);            \
+        _Pragma("unroll") for (int b_ = 0; b_ < DB; b_++)             \
+            A[b_] = qk_ld_stream(pp_ + b_ * 64);                      \
+        Y = nsrc[(int64_t)ltile * 4];                                 \
+        if (lS < nsteps - 1) {                                        \
+            lS++;                                                     \
+            if (++ldch == ncd) {                                      \
+                ldch = 0;                                             \
+                ltile++;                                              \
+            }                                                         \
+        }                                                             \
+    }
 #else
 #define QK_EPI_M(Y)
 #define QK_NEXT_TILE tile++
@@ -292,6 +316,15 @@
     }
 #endif
 
+#ifdef QK_SCAN_SHADOW
+#define QK_DOT(A_, B_) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(qk_as_h8(A_), qk_as_h8(B_), acc, 0, 0, 0);
+#else
+#define QK_DOT(A_, B_)                                                        \
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A_.x, B_.x, acc, 0, 0, 0);     \
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A_.y, B_.y, acc, 0, 0, 0);     \
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A_.z, B_.z, acc, 0, 0, 0);     \
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A_.w, B_.w, acc, 0, 0, 0);
+#endif
 #define QK_STEP(A, Y, I0, I1, LIVE)                                                                                    \
     {                                                                                                      \
         if (dch == 0) acc = (f32x4){0.f, 0.f, 0.f, 0.f};                                                   \
@@ -303,10 +336,7 @@
                 acc[3] += A[b_].w;                                                                         \
             } else {                                                                                       \
                 const float4 bq_ = qs[(dch * DB + b_) * 64 + lane];                                        \
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[b_].x, bq_.x, acc, 0, 0, 0);                  \
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[b_].y, bq_.y, acc, 0, 0, 0);                  \
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[b_].z, bq_.z, acc, 0, 0, 0);                  \
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[b_].w, bq_.w, acc, 0, 0, 0);                  \
+                QK_DOT(A[b_], bq_)                                                                         \
             }                                                                                              \
         }                                                                                                  \
         if (++dch == ncd) {                                                                                \
@@ -327,7 +357,12 @@
 #endif
                 const int row0 = tl_ << 4;
                 const float yv[4] = {yn.x, yn.y, yn.z, yn.w};
+#ifdef QK_SCAN_SHADOW
+                const int64_t row_abs_ = row_off + row0 + 4 * g;
+                const int64_t idv[4] = {row_abs_, row_abs_ + 1, row_abs_ + 2, row_abs_ + 3};
+#else
                 const int64_t idv[4] = {ia.x, ia.y, ib.x, ib.y};
+#endif
                 if (EMIT) {
                     if (live && myq >= 0) {
                         uint32_t *dst = P.key_out + P.pair_base[mypair] + row0 + 4 * g;
@@ -354,6 +389,8 @@
                     const int row = row0 + 4 * g + reg;
 #if QK_SCAN_FILT
                     const bool valid = live && (myq >= 0) && (row < size_p) && ((mw >> (4 * g + reg)) & 1u);
+#elif defined(QK_SCAN_SHADOW)
+                    const bool valid = live && (myq >= 0) && (row < size_p) && !sh_dead;
 #else
                     const bool valid = live && (myq >= 0) && (row < size_p);
 #endif
@@ -421,6 +458,13 @@
                 const float4 *qsrc = P.xq4 + (int64_t)qsafe * nblk * 4 + g;
                 if (P.gtau) tau = ~__hip_atomic_load(&P.gtau[qsafe], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (l2) xnj = P.xn[qsafe];
+#ifdef QK_SCAN_SHADOW
+                {  // the seed's exact bound, widened by what an approximate key may lie above its exact one
+                    const float she_ = P.sh_E[qsafe];
+                    sh_dead = !(she_ >= 0.0f);
+                    tau = qk_ord_widen(tau, sh_dead ? 0.0f : she_, l2);
+                }
+#endif
                 // LDS only (no vmcnt wait: the first tile stays in flight): every wave has left the previous tile
                 const bool coop = nw > 1 && !qshare;  // split mode: one query tile staged by all waves, fenced by barriers
                 if (coop) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -456,6 +500,7 @@
             }
 #undef QK_LOAD
 #undef QK_STEP
+#undef QK_DOT
 #undef QK_EPI_M
 #undef QK_NEXT_TILE
 #if QK_SCAN_FILT

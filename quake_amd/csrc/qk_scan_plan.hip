@@ -7,6 +7,8 @@
 //   1  k_scan_rl       row-per-lane per-wave walk (v_mfma_f32_4x4x1, passes of 32 queries)            qk_scan_rl.hip
 //   2  k_scan_rl mixed the walk for cold lists + dense workgroup items behind a bf16 prefilter for lists
 //                      probed by >= hot.min queries                                                  qk_scan_rl.hip
+//   3  k_scan_shadow   the tile form over the fp16 shadow of the store + exact fp32 finish (one list per query, k <= 16): never
+//                      the static choice -- admissible, measured by the feedback                      qk_shadow.hip
 // Replaces the choice the reference makes by SearchParams (serial_scan / batched_serial_scan / worker_scan,
 // src/cpp/src/query_coordinator.cpp:659-673).
 #include "qk_internal.h"
@@ -16,7 +18,7 @@
 
 // form feedback (see qk_scan_device): the form to use for this call of the shape `key`; *measure is set when the call is to be
 // timed (the caller records measure->e0 / e1 around its launches)
-static int qk_pick_form(qk_ctx *ctx, uint64_t key, int form_static, const bool admissible[3], qk_ctx::form_stat **measure) {
+static int qk_pick_form(qk_ctx *ctx, uint64_t key, int form_static, const bool admissible[4], qk_ctx::form_stat **measure) {
     *measure = nullptr;
     // (at most 32 entries, reserved once: the entry handed back through *measure stays where it is while the caller's launches are
     //  in flight, whatever is looked up meanwhile)
@@ -51,13 +53,14 @@ static int qk_pick_form(qk_ctx *ctx, uint64_t key, int form_static, const bool a
         if (q == hipSuccess) {
             float ms = 0.f;
             hipError_t eq = hipEventElapsedTime(&ms, st->e0, st->e1);
-            if (ctx->form_times_set) ms = ctx->form_times[st->pending];  // (qk_ctx_set_form_times: the rule on injected figures)
+            // (qk_ctx_set_form_times / qk_ctx_set_shadow_form_time: the rule on injected figures)
+            if (ctx->form_times_set) ms = st->pending == 3 ? ctx->shadow_form_time : ctx->form_times[st->pending];
             if (eq == hipSuccess && ms > 0.f) {
                 const int f = st->pending;
                 if (st->n[f] >= 2 && (ms > 1.5f * st->ms[f] || ms < 0.6f * st->ms[f])) {
                     // the same shape takes a very different time: the batches changed (how the queries concentrate on lists is
                     // not part of the key) -- every form is measured again, starting from this figure
-                    for (int g = 0; g < 3; g++) st->n[g] = 0;
+                    for (int g = 0; g < 4; g++) st->n[g] = 0;
                 }
                 // (the first call of a form pays one-off costs -- function attributes, cold instruction cache: keep the smaller
                 //  of the first two, then a running mean)
@@ -66,7 +69,7 @@ static int qk_pick_form(qk_ctx *ctx, uint64_t key, int form_static, const bool a
                 // a form whose FIRST call took more than twice the best figure known is not tried a second time in this
                 // comparison (on a 50M index a losing form costs a 5 ms call where the winner takes 1.2)
                 if (st->n[f] == 1)
-                    for (int g = 0; g < 3; g++)
+                    for (int g = 0; g < 4; g++)
                         if (g != f && st->n[g] >= 2 && ms > 2.0f * st->ms[g]) st->n[f] = 2;
             } else {
                 (void)hipGetLastError();
@@ -77,25 +80,26 @@ static int qk_pick_form(qk_ctx *ctx, uint64_t key, int form_static, const bool a
         }
     }
     int best = -1;
-    for (int f = 0; f < 3; f++)
+    for (int f = 0; f < 4; f++)
         if (admissible[f] && st->n[f] >= 2 && (best < 0 || st->ms[f] < st->ms[best])) best = f;
     if (st->pending >= 0) return best >= 0 ? best : form_static;  // one measurement at a time
     int next = -1;
     if (st->n[form_static] < 2) {
         next = form_static;
     } else {
-        for (int f = 0; f < 3 && next < 0; f++)
+        for (int f = 0; f < 4 && next < 0; f++)
             if (admissible[f] && st->n[f] < 2) next = f;
     }
     if (next < 0 && best >= 0 && st->calls % 512 == 0) {  // re-check a form that lost (the data under the index changes)
         // ... unless its last figure was more than twice the winner's: such a call is a latency spike on the serving path (5 ms
         // against 1.2 on a 50M index) and a form that far behind does not come back without the index changing -- which changes
         // the key (size bucket below) and starts a fresh comparison
-        for (int t = 0; t < 3 && next < 0; t++) {
-            const int f = (st->rr + t) % 3;
+        const int nf = admissible[3] ? 4 : 3;  // (the rotation of the three-form shapes is what it was)
+        for (int t = 0; t < nf && next < 0; t++) {
+            const int f = (st->rr + t) % nf;
             if (admissible[f] && f != best && !(st->n[f] >= 1 && st->ms[f] > 2.0f * st->ms[best])) next = f;
         }
-        if (next >= 0) st->rr = (next + 1) % 3;
+        if (next >= 0) st->rr = (next + 1) % nf;
     }
     if (next < 0 && best >= 0 && st->calls % 16 == 0) next = best;  // keep the winner's figure current (and notice a change of regime)
     if (next >= 0) {
@@ -346,9 +350,22 @@ int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int
     const int form_static = rl_small_pools ? 0 : mixed_static ? 2 : use_rl ? 1 : 0;
     int form = form_static;
     qk_ctx::form_stat *fmeasure = nullptr;
+    // fp16 shadow form (qk_shadow.hip): qk_search with one list per query, plain top-k.  Never the static choice (the static rule and
+    // its labels are pinned); in automatic mode it is admissible where the feedback runs, and only with a valid shadow of the store
+    // as it is now -- which qk_store_shadow_consider builds once the store has been seen unchanged for a few such calls.  With
+    // three figures injected (qk_ctx_set_form_times) it needs its own (qk_ctx_set_shadow_form_time).
+    const bool shadow_elig = a.shadow_ok && ctx->shadow_mode != 0 && P == 1 && !emit && !a.per_pair && !a.all_lists && !a.tau_init && !a.mask &&
+                             a.share_tau && k <= QK_SHADOW_MAX_K && s->d <= QK_SHADOW_MAX_D;
+    const bool shadow_forced = shadow_elig && ctx->shadow_mode == 2;
+    const bool shadow_auto = shadow_elig && !shadow_forced && ctx->form_feedback && npairs >= 1024 &&
+                             !(ctx->form_times_set && !(ctx->shadow_form_time > 0.f));
+    bool shadow_adm = false;
+    if (shadow_forced || shadow_auto) QK_TRY(qk_store_shadow_consider(ctx, s, shadow_forced, &shadow_adm));
     {
-        const bool admissible[3] = {true, rl_avail, mixed_avail};
-        if (ctx->form_feedback && !emit && npairs >= 1024 && P > 1 && (rl_avail || mixed_avail)) {
+        const bool admissible[4] = {true, rl_avail, mixed_avail, shadow_adm};
+        if (shadow_forced && shadow_adm) {
+            form = 3;
+        } else if (ctx->form_feedback && !emit && npairs >= 1024 && ((P > 1 && (rl_avail || mixed_avail)) || (shadow_auto && shadow_adm))) {
             // (size bucket: the store's row count to a quarter of a power of two and its list count to a power of two -- a store that
             //  grew, shrank or was re-partitioned by maintenance is a new shape with a fresh comparison, not a stale winner)
             int sb = 0, lb = 0;
@@ -366,7 +383,15 @@ int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int
         fmeasure->pending = -1;
         fmeasure = nullptr;
     }
-    if (form == 2) {
+    if (form == 3) {
+        // the tile form's geometry over the shadow: blocks of 32 columns, pools of k' + 32 entries, one wave per workgroup
+        const int nbs = qk_shadow_nblk(nblk);
+        DB = (nbs % 8 == 0) ? 8 : (nbs % 4 == 0) ? 4 : (nbs % 2 == 0) ? 2 : 1;
+        use_rl = false;
+        nw = 1;
+        qshare = 0;
+        C = 2 * QK_SHADOW_KP;
+    } else if (form == 2) {
         hot = hot_cand;
         use_rl = true;
         nw = 1;

@@ -152,6 +152,9 @@ struct ScanParams {
     // its cursor (after_key[i], after_id[i]) -- unsigned key, signed id, lexicographic.  nullptr = no cursor
     const uint32_t *after_key;      // [Q]
     const int64_t *after_id;        // [Q]
+    // fp16 shadow form (k_scan_shadow, qk_shadow.hip): vecs is the shadow, nblk its 32-column blocks, xq4 the fp16 query copy; sh_E
+    // [Q] is the error bound of every query's approximate keys, negative = the query takes no part (the finish answers it exactly)
+    const float *sh_E;
 };
 
 // ---- merge stage (qk_merge.hip) ------------------------------------------------------------------------------------------
@@ -212,7 +215,7 @@ struct ScanPlan {
     int C = 0;               // pool capacity per query
     int nw = 1, qshare = 0;  // waves per workgroup of the tile form; query-sharing workgroups
     bool use_rl = false;     // row-per-lane kernel (forms 1 and 2)
-    int form = 0;            // 0 tile form, 1 per-wave walk, 2 mixed sequence
+    int form = 0;            // 0 tile form, 1 per-wave walk, 2 mixed sequence, 3 tile form over the fp16 shadow (DB, C: the shadow's)
     int64_t rl_per_list = 0; // batch average of probing queries per list (what the static rule looks at)
     RlCost rlc{12, 8, 1, 16, 4, 32};
     int rl_app = 32, rl_waves = 4;
@@ -226,4 +229,41 @@ int qk_launch_scan_wide(int maxch, unsigned grid, size_t lds, hipStream_t st, co
 // paged search (qk_after.hip): k_scan_after, launched like k_scan_filt; and the kernel behind the merge that writes every query's
 // next cursor -- the (key, id) of its k-th result, the exhausted cursor where the row holds fewer than k
 int qk_launch_scan_after(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
+// fp16 shadow form (qk_shadow.hip)
+constexpr int QK_SHADOW_KP = 32;     // entries per record of the shadow scan (k' of DESIGN.md 5.20)
+constexpr int QK_SHADOW_MAX_K = 16;
+constexpr int QK_SHADOW_MAX_D = 256;
+struct ShadowFinishParams {
+    const int32_t *pair_head;
+    const int32_t *pair_slots;
+    const int2 *rec_hdr;
+    const uint32_t *rec_ord;   // [max_recs][QK_SHADOW_KP] approximate keys, ascending
+    const int64_t *rec_id;     // [max_recs][QK_SHADOW_KP] arena rows
+    int32_t max_recs;
+    int k, metric, sqrt_l2;
+    int64_t *out_ids;
+    float *out_dist;
+    const float *E;            // [Q] (negative: answer by the exact scan of the list)
+    const float *x;            // [Q][d] queries, row-major
+    const float *xn;           // [Q]
+    const float4 *vecs;        // fp32 arena
+    const float *norms;
+    const int64_t *ids;
+    int nblk, d;
+    const int64_t *pids;                    // [Q] or nullptr
+    const unsigned long long *pids_packed;  // [Q] or nullptr
+    const int64_t *pt_off;
+    const int32_t *pt_size;
+    int npids;
+    unsigned long long *counters;  // [4] verified, fallback, candidates, queries with chained records
+};
+int qk_launch_scan_shadow(int db, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
+int qk_launch_shadow_finish(hipStream_t st, const ShadowFinishParams &fp, int64_t Q);
+// fp16 copy of the prepared queries in B-operand order ([Q][nblk_s][4] x 16 B) and every query's error bound
+int qk_launch_shadow_prep(hipStream_t st, const float4 *xq4, const float *xn, int64_t Q, int d, int nblk, int metric, float rho, float xmax,
+                          float4 *xqh, float *E);
+// fp32 arena -> shadow for the lists of the table (device: pt_off / pt_size), statistics into stats [4] (zeroed by the caller):
+// bits of max err^2, bits of max ||fp16(x)||^2, "a value is not finite or beyond 65504"
+int qk_launch_shadow_convert(hipStream_t st, const float4 *vecs, int nblk, const int64_t *pt_off, const int32_t *pt_size, int npids, void *shadow,
+                             uint32_t *stats);
 int qk_launch_next_cursor(qk_ctx *ctx, const MergeParams &mp, int64_t Q, const int64_t *out_ids, uint32_t *next_key, int64_t *next_id);

@@ -6,11 +6,13 @@
 // layout is NOT the reference's row-major malloc array: it is the MFMA-fragment tile-major layout
 // described in qk_internal.h / DESIGN.md section 4, plus a per-row squared norm.
 #include "qk_internal.h"
+#include "qk_scan_types.h"
 
 #include <unordered_map>
 #include <atomic>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <functional>
 #include <thread>
@@ -200,6 +202,7 @@ int qk_store_sync_table(qk_store *s) {
     s->version++;
     s->counters[5]++;
     s->rowmajor_valid = false;
+    s->shadow_valid = false;  // (the fp16 shadow mirrors one version; it is rebuilt once the store has been stable again)
     qk_ctx *c = s->ctx;
     int64_t n = (int64_t)s->parts.size();
     if (n > s->table_cap) {
@@ -672,6 +675,9 @@ int qk_store_destroy(qk_store *s) {
     if (s->bounce_i) hipFree(s->bounce_i);
     if (s->allow_all) qk_filter_destroy(s->allow_all);
     qk_pool_destroy(s);
+    hipDeviceSynchronize();  // (as above: another context's search may still read the shadow)
+    qk_store_shadow_free(s);
+    if (s->shadow_stats) hipFree(s->shadow_stats);
     delete s;
     return QK_OK;
 }
@@ -686,6 +692,11 @@ int qk_store_reset(qk_store *s) {
     s->table_dirty = true;
     s->id_to_list.clear();
     s->index_valid = false;
+    if (s->shadow) {
+        hipSetDevice(s->ctx->device);
+        hipDeviceSynchronize();  // (searches of other contexts may be reading it: the rule of every place that frees it)
+        qk_store_shadow_free(s);
+    }
     return QK_OK;
 }
 
@@ -1337,7 +1348,105 @@ int qk_store_counters(qk_store *s, int64_t *out, int n) {
 
 int64_t qk_store_device_bytes(qk_store *s) {
     if (!s) return 0;
-    return s->cap_rows * ((int64_t)s->dpad * 4 + 4 + 8);
+    return s->cap_rows * ((int64_t)s->dpad * 4 + 4 + 8) + (s->shadow ? s->shadow_cap_rows * (int64_t)qk_shadow_nblk(s->nblk) * 64 : 0);
+}
+
+int qk_store_shadow_info(qk_store *s, int *valid, int64_t *bytes, int64_t *builds) {
+    if (!s) QK_FAIL(QK_ERR_INVALID, "qk_store_shadow_info: null store");
+    // (a store with pending changes has no current shadow: the next search bumps the version)
+    if (valid) *valid = s->shadow && s->shadow_valid && !s->table_dirty && s->shadow_version == s->version ? 1 : 0;
+    if (bytes) *bytes = s->shadow ? s->shadow_cap_rows * (int64_t)qk_shadow_nblk(s->nblk) * 64 : 0;
+    if (builds) *builds = s->shadow_builds;
+    return QK_OK;
+}
+
+int qk_store_shadow_drop(qk_store *s) {
+    if (!s) QK_FAIL(QK_ERR_INVALID, "qk_store_shadow_drop: null store");
+    QK_HIP(hipSetDevice(s->ctx->device));
+    QK_HIP(hipDeviceSynchronize());  // (searches of other contexts may be reading it)
+    qk_store_shadow_free(s);
+    return QK_OK;
 }
 
 }  // extern "C"
+
+// ---- the fp16 shadow (qk_shadow.hip) -------------------------------------------------------------------------------------------
+void qk_store_shadow_free(qk_store *s) {
+    if (s->shadow) hipFree(s->shadow);
+    s->shadow = nullptr;
+    s->shadow_cap_rows = 0;
+    s->shadow_valid = false;
+    s->shadow_refused = false;
+    s->shadow_seen_calls = 0;
+}
+
+// Called by the plan of a search the shadow form could serve, behind qk_store_sync_table: the store's `version` is what this search
+// sees, and every function that writes vecs / norms / ids / the list table marks the table dirty, so a changed store has a new
+// version here (qk_store_sync_table also clears shadow_valid).  Lazy: nothing is allocated before the second such call in a row on
+// one version -- the eighth once a shadow was built or refused before, so that a store that is modified between batches never
+// pays for conversions -- or a forced call.  The conversion runs on the calling context's stream and is WAITED for (its three
+// scalars come back to the host): when this returns, every stream of the device may read the shadow.  No memory, or a value the
+// fp16 range does not hold: no shadow for this version, and no error.
+int qk_store_shadow_consider(qk_ctx *ctx, qk_store *s, bool force, bool *usable) {
+    *usable = false;
+    if (s->table_dirty || s->ntotal <= 0 || s->parts.empty()) return QK_OK;
+    if (s->shadow && s->shadow_valid && s->shadow_version == s->version) {
+        *usable = true;
+        return QK_OK;
+    }
+    if (s->shadow_refused && s->shadow_refused_version == s->version) return QK_OK;
+    if (s->shadow_seen_version != s->version || s->shadow_seen_calls <= 0) {
+        s->shadow_seen_version = s->version;
+        s->shadow_seen_calls = 0;
+    }
+    s->shadow_seen_calls++;
+    if (!force && s->shadow_seen_calls < (s->shadow_ever ? 8 : 2)) return QK_OK;
+    s->shadow_ever = true;
+    auto refuse = [&]() {
+        s->shadow_refused = true;
+        s->shadow_refused_version = s->version;
+        return QK_OK;
+    };
+    const int nbs = qk_shadow_nblk(s->nblk);
+    if (s->shadow_cap_rows < s->cap_rows) {
+        QK_HIP(hipDeviceSynchronize());  // (a search in flight on another stream may read the old one)
+        qk_store_shadow_free(s);
+        if (hipMalloc(&s->shadow, (size_t)s->cap_rows * nbs * 64) != hipSuccess) {
+            (void)hipGetLastError();
+            s->shadow = nullptr;
+            return refuse();
+        }
+        s->shadow_cap_rows = s->cap_rows;
+    }
+    if (!s->shadow_stats && hipMalloc((void **)&s->shadow_stats, 16) != hipSuccess) {
+        (void)hipGetLastError();
+        s->shadow_stats = nullptr;
+        return refuse();
+    }
+    uint32_t *d_stats = s->shadow_stats;
+    uint32_t h_stats[4] = {0, 0, 1, 0};
+    hipError_t e = hipMemsetAsync(d_stats, 0, 16, ctx->stream);
+    int rc = QK_OK;
+    if (e == hipSuccess)
+        rc = qk_launch_shadow_convert(ctx->stream, (const float4 *)s->vecs, s->nblk, s->d_off, s->d_size, (int)s->parts.size(), s->shadow, d_stats);
+    if (e == hipSuccess && rc == QK_OK) e = hipMemcpyAsync(h_stats, d_stats, 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && rc == QK_OK) e = hipStreamSynchronize(ctx->stream);
+    if (rc != QK_OK) return rc;
+    QK_HIP(e);
+    float err2, nrm2;
+    memcpy(&err2, &h_stats[0], 4);
+    memcpy(&nrm2, &h_stats[1], 4);
+    if (h_stats[2] != 0 || !(err2 >= 0.f) || !(nrm2 >= 0.f) || !(nrm2 < 1e38f)) {  // a list the fp16 range does not hold
+        QK_HIP(hipDeviceSynchronize());
+        qk_store_shadow_free(s);
+        return refuse();
+    }
+    // (sums of squares in fp32: relative error under d 2^-24; rounded up by 2^-10)
+    s->shadow_rho = (float)(std::sqrt((double)err2) * (1.0 + 1.0 / 1024));
+    s->shadow_xmax = (float)(std::sqrt((double)nrm2) * (1.0 + 1.0 / 1024));
+    s->shadow_valid = true;
+    s->shadow_version = s->version;
+    s->shadow_builds++;
+    *usable = true;
+    return QK_OK;
+}
