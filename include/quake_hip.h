@@ -791,6 +791,70 @@ QK_API int qk_order_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, co
                          int64_t *out_values, int64_t *out_count, int64_t *out_missing, int64_t *out_total, int mem,
                          qk_timing *timing);
 
+/* ---- multi-vector search ------------------------------------------------------------------------------
+ * No reference counterpart.  Late interaction (ColBERT / ColPali token embeddings, a question expanded into several vectors): a
+ * logical query is T sub-queries, a document is the rows whose ids share a value of an attribute column, and
+ *   score(doc) = sum over the sub-queries t of the best hit of t among the document's rows     (sum of MaxSim)
+ * x: [L * T][d], logical query l owns the sub-queries l * T .. l * T + T - 1; qk_maxsim_scan: pids [L * T][P].  n_tokens: int32 [L]
+ * in `mem`, or NULL meaning T for every logical query; only the first n_tokens[l] sub-queries of l take part.  A host value outside
+ * [0, T] is QK_ERR_INVALID, a device value is clamped to [0, T].
+ * 1 <= T <= QK_MAXSIM_MAX_TOKENS, 1 <= k <= QK_MAXSIM_MAX_K; below: QK_ERR_INVALID, above: QK_ERR_UNSUPPORTED.  `missing` NaN:
+ * QK_ERR_INVALID.  L == 0: QK_OK.
+ * Hits: the hit multiset H(l, t) is BY DEFINITION that of qk_range_search / qk_range_scan for sub-query l * T + t with the same
+ * (parent, nprobe | pids, metric, radius, filter), exactly as for facet counts and ordered search above: the inclusive float32 radius
+ * test, qk_ctx_set_squared_l2 honoured, a NaN distance never a hit, a NaN radius QK_ERR_INVALID, radius +inf (L2) / -inf (IP) every
+ * probed candidate row.  A sub-query with t >= n_tokens[l] has no hits.
+ * Terms: a hit whose id has a value g in group_by at the moment of the call is a candidate of (l, t, g).  best(l, t, g) is the
+ * candidate with the smallest search key (the uint32 key qk_search_after documents; ids do not matter), term(l, t, g) the float32
+ * distance qk_range_search reports for that key -- sqrtf for L2 unless qk_ctx_set_squared_l2, the product for IP.  Without a
+ * candidate term(l, t, g) = missing; every float but NaN is a legal `missing`, +-inf included (0 is the usual choice for IP).
+ * Score: s = +0.0f, then for t = 0 .. n_tokens[l] - 1 in that order s = s + term(l, t, g): one separately rounded float32 addition
+ * each, no reassociation, no tree, no wider accumulator (the library is built with -ffp-contract=off and without fast-math).
+ * Candidates of l: every value g with a candidate in at least one participating t.
+ * Order: the better score first -- larger for IP, smaller for L2 -- compared as float32 values (-0 equals +0); a NaN score
+ * (inf + -inf) sorts behind every number; ties, and NaN among NaN, go to the smaller signed value.  Every int64 is a legal value:
+ * -1, INT64_MIN, INT64_MAX.
+ * Returned, entries behind min(k, n_groups[l]) being padding:
+ *   out_groups   [L][k]   int64                 padding 0
+ *   out_scores   [L][k]   float32, may be NULL  padding +inf (L2) / -inf (IP); a NaN score is reported as 0x7FC00000
+ *   out_matched  [L][k]   int32, may be NULL    the number of t with a candidate; padding 0
+ *   out_n_groups [L]      int64, may be NULL    the exact number of candidate values
+ *   out_hits     [L][T]   int64, may be NULL    |H(l, t)| = lims[q + 1] - lims[q] of the range call for q = l * T + t; 0 for a t that
+ *                                               does not take part
+ * No lists probed: all padding and zeros.  The result is a pure function of the store, the column, the filter and the call, and row
+ * l equals the call made with logical query l alone.  Liveness as for facets: values are read when the call runs, through the
+ * per-row values grouped search keeps; a later set / add / remove / maintenance is seen by the next call.
+ * Limits: a NULL column, a column or filter of another store: QK_ERR_INVALID.  A sub-query whose keys exceed 2^30 is
+ * QK_ERR_UNSUPPORTED (qk_emit_passes).  There is no form for qk_search_aps, the device group, per-query filter tables or adaptive
+ * probing.
+ * Inside (qk_maxsim.hip): the key-emission scan of range search over the L * T sub-queries (the same launches), then per pass
+ * k_maxsim_hits (the hits of every sub-query) and, per group of logical queries that fits the pool of table slots, k_maxsim_clear, k_maxsim_claim -- a candidate finds
+ * or claims the slot of its value in the table of its LOGICAL query (atomicCAS, linear probing bounded by the table) and lowers key
+ * word t of the slot (atomicMin) -- and k_maxsim_select, one workgroup per logical query: terms, sequential sum and matched count of
+ * every occupied slot, an exact byte-wise selection on (score word, value ^ sign bit) down to k when more than 1024 values are met,
+ * a bitonic sort in LDS, outputs and padding.  No kernel waits or spins.
+ * Workspace: keys as for range search over the sub-queries, except that queries per pass = the wide-k rule (min(L * T, 2^29 /
+ * per_query_ub)) lowered to a multiple of T -- a logical query never straddles a pass; fewer than T is QK_ERR_UNSUPPORTED.  Next to
+ * the keys 4 bytes per sub-query, 8 per logical query and a POOL of table slots of 16 + 4 * T bytes each: min(logical queries per
+ * pass * (S + 1), QK_GROUPED_PASS_BYTES / slot bytes) slots, S = the power of two >= max(16, 2 * min(T * per_query_ub, ids of the
+ * column)) being the most one logical query can ever use.  The pool is laid out per pass by the HITS: behind k_maxsim_hits the host
+ * reads the pass's hit counts back (4 bytes per sub-query, the one wait inside a pass), gives every logical query a table of the
+ * power of two >= max(16, 2 * min(its hits, ids of the column)) slots plus 2, and sends the pass's logical queries through the pool
+ * in groups that fit it.  So the workspace follows what a query hits, not the largest list of the store; only a single logical query
+ * whose own table exceeds the pool -- more than about QK_GROUPED_PASS_BYTES / (2 * slot bytes) hits -- is QK_ERR_UNSUPPORTED.
+ * timing: coarse_ms and scan_ms as for range search, merge_ms = everything behind the last emission, n_items = the number of query
+ * passes.  qk_ctx_last_scan_kernel names "k_scan (maxsim)" / "k_scan_wide (maxsim)". */
+#define QK_MAXSIM_MAX_TOKENS 64
+#define QK_MAXSIM_MAX_K 1024
+QK_API int qk_maxsim_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t L, int T, const int32_t *n_tokens,
+                            int nprobe, int metric, float radius, qk_filter *filter, qk_attr *group_by, float missing, int k,
+                            int64_t *out_groups, float *out_scores, int32_t *out_matched, int64_t *out_n_groups, int64_t *out_hits,
+                            int mem, qk_timing *timing);
+QK_API int qk_maxsim_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t L, int T, const int32_t *n_tokens, const int64_t *pids,
+                          int P, int metric, float radius, qk_filter *filter, qk_attr *group_by, float missing, int k,
+                          int64_t *out_groups, float *out_scores, int32_t *out_matched, int64_t *out_n_groups, int64_t *out_hits,
+                          int mem, qk_timing *timing);
+
 /* ---- diversified search ------------------------------------------------------------------------------
  * No reference counterpart.  Maximal marginal relevance (MMR): of the fetch_k nearest rows of a query keep k, chosen greedily -- each
  * step takes the candidate that is close to the query and far from everything already taken (the near-duplicate chunks of a

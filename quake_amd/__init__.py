@@ -8,5 +8,5 @@ Drop-in surface (same names as the reference's `quake` package, src/python/__ini
 Everything computes in libquake_hip.so (hand-written HIP for gfx950, quake_amd/csrc/); there is no CPU fallback.
 """
 from .index import (BuildTimingInfo, IndexBuildParams, MaintenancePolicyParams, MaintenanceTimingInfo,  # noqa: F401
-                    ModifyTimingInfo, QuakeHipError, DiverseSearchResult, FacetResult, FacetStatsResult, GroupedSearchResult, OrderedSearchResult, QuakeIndex, RangeSearchResult, SearchCursor, SearchFilter, SearchParams, SearchResult, SearchTimingInfo,
+                    ModifyTimingInfo, QuakeHipError, DiverseSearchResult, FacetResult, FacetStatsResult, GroupedSearchResult, MultiVectorSearchResult, OrderedSearchResult, QuakeIndex, RangeSearchResult, SearchCursor, SearchFilter, SearchParams, SearchResult, SearchTimingInfo,
                     compute_recall)

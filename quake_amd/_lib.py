@@ -149,6 +149,11 @@ SIGNATURES = {
                         [_int, C.POINTER(QkTiming)]),
     "qk_order_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, C.c_float, _vp, _vp, _int, _int] + [_vp] * 6 +
                       [_int, C.POINTER(QkTiming)]),
+    # multi-vector search: (.., x, L, T, n_tokens, .., radius, filter, group_by, missing, k, groups, scores, matched, n_groups, hits, mem, timing)
+    "qk_maxsim_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp, _int, _int, C.c_float, _vp, _vp, C.c_float, _int] + [_vp] * 5 +
+                         [_int, C.POINTER(QkTiming)]),
+    "qk_maxsim_scan": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _int, _int, C.c_float, _vp, _vp, C.c_float, _int] + [_vp] * 5 +
+                       [_int, C.POINTER(QkTiming)]),
     # diversified search: (.., k, fetch_k, lambda, metric, filter, ids, dist, rank, mem, timing)
     "qk_diverse_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, C.c_float, _int, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_diverse_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, C.c_float, _int, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),

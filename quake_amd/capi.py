@@ -111,6 +111,8 @@ QK_ORDER_DESC = 1          # include/quake_hip.h: the flags of ordered search
 QK_ORDER_MISSING_LAST = 2
 QK_MAX_ORDER_K = 1024
 QK_MAX_FETCH_K = 256       # diversified search
+QK_MAXSIM_MAX_TOKENS = 64  # multi-vector search
+QK_MAXSIM_MAX_K = 1024
 
 
 def timing_dict(t):
@@ -678,6 +680,55 @@ class Context:
                                      metric_code(metric), float(radius), filter.h if filter is not None else None,
                                      order_by.h if order_by is not None else None, flags, k, *[_ptr(o) for o in out], mem,
                                      C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
+    # ---- multi-vector search ------------------------------------------------------------------------------
+    @staticmethod
+    def _maxsim_args(x, n_tokens, k):
+        """x [L, T, d] -> the flat sub-queries [L * T, d], L, T, n_tokens as int32 in x's memory, k, the output buffers"""
+        if x.ndim != 3:
+            raise ValueError("multi-vector queries are [L, T, d], got %d dimensions" % x.ndim)
+        L, T = int(x.shape[0]), int(x.shape[1])
+        xf = _f32(x).reshape(L * T, x.shape[2])
+        nt = _i32_with(n_tokens, xf) if n_tokens is not None else None
+        if nt is not None and nt.shape[0] != L:
+            raise ValueError("n_tokens has %d entries for %d logical queries" % (nt.shape[0], L))
+        k = int(k)
+        # (the library refuses a k or T outside its limits before it writes: the buffers of such a call only have to exist)
+        kk = k if 1 <= k <= QK_MAXSIM_MAX_K else 1
+        out = [_empty_like_mem((L, kk), np.int64, xf), _empty_like_mem((L, kk), np.float32, xf), _empty_like_mem((L, kk), np.int32, xf),
+               _empty_like_mem((L,), np.int64, xf), _empty_like_mem((L, T), np.int64, xf)]
+        return xf, L, T, nt, k, out
+
+    def maxsim_search(self, parent, store, x, nprobe, radius, metric, group_by, k, missing=0.0, n_tokens=None, filter=None, timing=False):
+        """qk_maxsim_search: multi-vector (late interaction) search.  x [L, T, d]: T sub-queries per logical query; per logical query
+        the k best values of the Attr column `group_by` by the sum over the sub-queries of the best hit of range_search (same
+        arguments) among the rows of the value, `missing` where a sub-query has none; n_tokens [L]: only the first n_tokens[l]
+        sub-queries take part.  Returns (groups [L, k] padded with 0, scores [L, k] padded as search pads, matched [L, k] int32,
+        n_groups [L], hits [L, T][, timing]) on x's device."""
+        xf, L, T, nt, k, out = self._maxsim_args(x, n_tokens, k)
+        mem = _mem_of(xf)
+        t = QkTiming()
+        check(self.lib.qk_maxsim_search(self.h, parent.h if parent is not None else None, store.h, _ptr(xf), L, T, _ptr(nt), int(nprobe),
+                                        metric_code(metric), float(radius), filter.h if filter is not None else None,
+                                        group_by.h if group_by is not None else None, float(missing), k, *[_ptr(o) for o in out], mem,
+                                        C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
+    def maxsim_scan(self, store, x, pids, radius, metric, group_by, k, missing=0.0, n_tokens=None, filter=None, timing=False):
+        """qk_maxsim_scan: maxsim_search over the given lists -- pids [L, T, P] or [L * T, P] (or [P] for every sub-query); -1 /
+        absent / empty lists contribute nothing."""
+        xf, L, T, nt, k, out = self._maxsim_args(x, n_tokens, k)
+        pids = _i64(pids)
+        if pids.ndim == 3:
+            pids = pids.reshape(L * T, pids.shape[2])
+        pids = _pids_rows(pids, L * T)
+        mem = _mem_of(xf, pids)
+        t = QkTiming()
+        check(self.lib.qk_maxsim_scan(self.h, store.h, _ptr(xf), L, T, _ptr(nt), _ptr(pids) if pids.shape[1] > 0 else None,
+                                      int(pids.shape[1]), metric_code(metric), float(radius), filter.h if filter is not None else None,
+                                      group_by.h if group_by is not None else None, float(missing), k, *[_ptr(o) for o in out], mem,
+                                      C.byref(t) if timing else None))
         return (*out, timing_dict(t)) if timing else tuple(out)
 
     # ---- diversified search ------------------------------------------------------------------------------

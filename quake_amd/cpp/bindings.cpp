@@ -5,6 +5,7 @@
 #include <torch/extension.h>
 
 #include <algorithm>
+#include <cctype>
 #include <limits>
 #include <sstream>
 
@@ -183,6 +184,23 @@ PYBIND11_MODULE(_bindings, m) {
           },
           py::arg("columns"), py::arg("order_by"), py::arg("k"), py::arg("descending") = false, py::arg("missing") = "exclude",
           "the arguments of ordered_search -> (column name, k, flags of qk_order_search); needs no device (where.py's lower_order)");
+    m.def("lower_maxsim",
+          [](const std::vector<std::string> &columns, const std::string &group_by, int64_t k, int64_t T, py::object n_tokens, py::object missing,
+             const std::string &metric) {
+              std::optional<std::vector<int64_t>> nt;
+              if (!n_tokens.is_none()) nt = n_tokens.cast<std::vector<int64_t>>();
+              std::optional<double> ms;
+              if (!missing.is_none()) ms = missing.cast<double>();
+              std::string m = metric;
+              std::transform(m.begin(), m.end(), m.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
+              const double mv = lower_maxsim(columns, group_by, k, T, nt, ms, m == "ip");
+              py::object ntl = py::none();   // (a list, whatever sequence came in: what where.py returns)
+              if (nt) ntl = py::cast(*nt);
+              return py::make_tuple(group_by, k, T, ntl, mv);
+          },
+          py::arg("columns"), py::arg("group_by"), py::arg("k"), py::arg("T"), py::arg("n_tokens") = py::none(), py::arg("missing") = py::none(),
+          py::arg("metric") = "ip",
+          "the arguments of multi_vector_search -> (column name, k, T, n_tokens, missing); needs no device (where.py's lower_maxsim)");
     m.def("lower_diverse",
           [](int64_t k, int64_t fetch_k, double lambda_mult) {
               const float lambda = lower_diverse(k, fetch_k, lambda_mult);
@@ -280,6 +298,26 @@ PYBIND11_MODULE(_bindings, m) {
              "extension: per query, the search_params.k first of the vectors range_search returns for the same arguments by the "
              "attribute column `order_by` (ascending, or descending), ties to the nearer vector, then to the smaller id; missing: "
              "'exclude' or 'last'")
+        .def("multi_vector_search",
+             [](QuakeIndex &self, Tensor x, const std::string &group_by, shared_ptr<SearchParams> sp, py::object radius, py::object n_tokens,
+                py::object missing) {
+                 std::optional<float> r;
+                 if (!radius.is_none()) r = radius.cast<float>();
+                 std::optional<std::vector<int64_t>> nt;
+                 if (!n_tokens.is_none()) {
+                     if (py::hasattr(n_tokens, "tolist")) n_tokens = n_tokens.attr("reshape")(-1).attr("tolist")();
+                     nt = n_tokens.cast<std::vector<int64_t>>();
+                 }
+                 std::optional<double> ms;
+                 if (!missing.is_none()) ms = missing.cast<double>();
+                 return self.multi_vector_search(x, group_by, sp, r, nt, ms);
+             },
+             py::arg("x"), py::arg("group_by"), py::arg("search_params"), py::arg("radius") = py::none(), py::arg("n_tokens") = py::none(),
+             py::arg("missing") = py::none(),
+             "extension: multi-vector (late interaction) search -- x [L, T, d]; per logical query the search_params.k best values of the "
+             "attribute column `group_by` by the sum over the query's vectors of the best vector range_search returns among the value's "
+             "vectors; n_tokens [L]: the vectors of each query that take part; missing: the term of a vector without a match (None: 0 "
+             "for the inner product)")
         .def("diverse_search", &QuakeIndex::diverse_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
              py::arg("lambda_mult") = 0.5,
              "extension: per query, search_params.k of its fetch_k nearest vectors (what search() returns with k = fetch_k) chosen "
@@ -532,6 +570,15 @@ PYBIND11_MODULE(_bindings, m) {
              },
              "[C, Q] float64 numpy array of sum / count, NaN where count == 0");
 
+    py::class_<MultiVectorSearchResult, std::shared_ptr<MultiVectorSearchResult>>(m, "MultiVectorSearchResult")
+        .def(py::init<>())
+        .def_readwrite("groups", &MultiVectorSearchResult::groups)
+        .def_readwrite("scores", &MultiVectorSearchResult::scores)
+        .def_readwrite("matched", &MultiVectorSearchResult::matched)
+        .def_readwrite("n_groups", &MultiVectorSearchResult::n_groups)
+        .def_readwrite("hits", &MultiVectorSearchResult::hits)
+        .def_readwrite("column", &MultiVectorSearchResult::column)
+        .def_readwrite("timing_info", &MultiVectorSearchResult::timing_info);
     py::class_<OrderedSearchResult, std::shared_ptr<OrderedSearchResult>>(m, "OrderedSearchResult")
         .def(py::init<>())
         .def_readwrite("ids", &OrderedSearchResult::ids)

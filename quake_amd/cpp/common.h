@@ -218,6 +218,19 @@ struct OrderedSearchResult {
     shared_ptr<SearchTimingInfo> timing_info;
 };
 
+// extension (QuakeIndex::multi_vector_search): per logical query the k best values of an attribute column by the sum over the query's
+// vectors of the best hit among the value's rows: groups [L, k] (padding 0), scores [L, k] (padding as search pads), matched [L, k]
+// int32 (padding 0), n_groups [L], hits [L, T]
+struct MultiVectorSearchResult {
+    Tensor groups;
+    Tensor scores;
+    Tensor matched;
+    Tensor n_groups;
+    Tensor hits;
+    std::string column;
+    shared_ptr<SearchTimingInfo> timing_info;
+};
+
 // extension (QuakeIndex::diverse_search): per query k of its fetch_k nearest vectors chosen by maximal marginal relevance, in
 // selection order: ids [Q, k] (padding -1), distances [Q, k] (padding as search pads), ranks [Q, k] int32 (padding -1)
 struct DiverseSearchResult {

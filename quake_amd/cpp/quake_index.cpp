@@ -220,6 +220,46 @@ shared_ptr<OrderedSearchResult> QuakeIndex::ordered_search(Tensor x, const std::
     return query_coordinator_->ordered_search(x, col, known, order_by, sp, radius, descending, missing);
 }
 
+double lower_maxsim(const std::vector<std::string> &columns, const std::string &group_by, int64_t k, int64_t T,
+                    const std::optional<std::vector<int64_t>> &n_tokens, std::optional<double> missing, bool is_ip) {
+    const std::string who = "[QuakeIndex::multi_vector_search()]";
+    if (std::find(columns.begin(), columns.end(), group_by) == columns.end())
+        throw std::runtime_error(who + " unknown attribute column '" + group_by + "'");
+    if (k < 1 || k > QK_MAXSIM_MAX_K)
+        throw std::runtime_error(who + " k=" + std::to_string(k) + " must be between 1 and " + std::to_string(QK_MAXSIM_MAX_K));
+    if (T < 1 || T > QK_MAXSIM_MAX_TOKENS)
+        throw std::runtime_error(who + " T=" + std::to_string(T) + " vectors per query must be between 1 and " +
+                                 std::to_string(QK_MAXSIM_MAX_TOKENS));
+    if (n_tokens)
+        for (size_t i = 0; i < n_tokens->size(); i++)
+            if ((*n_tokens)[i] < 0 || (*n_tokens)[i] > T)
+                throw std::runtime_error(who + " n_tokens[" + std::to_string(i) + "]=" + std::to_string((*n_tokens)[i]) +
+                                         " must be between 0 and T=" + std::to_string(T));
+    if (!missing) {
+        if (!is_ip)
+            throw std::runtime_error(who + " missing must be given for the l2 metric: the term of a vector without a match has no default");
+        missing = 0.0;
+    }
+    if (*missing != *missing) throw std::runtime_error(who + " missing is NaN");
+    return *missing;
+}
+
+shared_ptr<MultiVectorSearchResult> QuakeIndex::multi_vector_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> sp,
+                                                                    std::optional<float> radius,
+                                                                    const std::optional<std::vector<int64_t>> &n_tokens,
+                                                                    std::optional<double> missing) {
+    if (!query_coordinator_)
+        throw std::runtime_error("[QuakeIndex::multi_vector_search()] No query coordinator. Did you build the index?");
+    std::vector<std::string> known;
+    qk_attr *col = nullptr;
+    if (partition_manager_ && partition_manager_->has_lists() && partition_manager_->store() && partition_manager_->store() == attrs_store_)
+        for (const auto &kv : attrs_) {
+            known.push_back(kv.first);
+            if (kv.first == group_by) col = kv.second;
+        }
+    return query_coordinator_->multi_vector_search(x, col, known, group_by, sp, radius, n_tokens, missing);
+}
+
 float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult) {
     const std::string who = "[QuakeIndex::diverse_search()]";
     if (k < 1) throw std::runtime_error(who + " k=" + std::to_string(k) + " must be at least 1");

@@ -50,6 +50,12 @@ std::vector<std::vector<int64_t>> lower_edges(const std::vector<std::string> &na
 // unknown column, k outside 1 .. QK_MAX_ORDER_K, a `missing` that is neither "exclude" nor "last" -> the flags of qk_order_search
 int lower_order(const std::vector<std::string> &columns, const std::string &order_by, int64_t k, bool descending, const std::string &missing);
 
+// the arguments of multi_vector_search (where.py's lower_maxsim: same rules, same errors as std::runtime_error, in the same order):
+// an unknown column, k outside 1 .. QK_MAXSIM_MAX_K, T outside 1 .. QK_MAXSIM_MAX_TOKENS, an n_tokens entry outside [0, T], no
+// `missing` under l2, a NaN `missing` -> missing (0.0 for the inner product when none is given)
+double lower_maxsim(const std::vector<std::string> &columns, const std::string &group_by, int64_t k, int64_t T,
+                    const std::optional<std::vector<int64_t>> &n_tokens, std::optional<double> missing, bool is_ip);
+
 // the arguments of diverse_search (where.py's lower_diverse: same rules, same errors as std::runtime_error, in the same order):
 // k < 1, fetch_k < k, fetch_k > QK_MAX_FETCH_K, a lambda_mult that is NaN or outside [0, 1] -> lambda_mult rounded to float32
 float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult);
@@ -121,6 +127,13 @@ public:
     shared_ptr<OrderedSearchResult> ordered_search(Tensor x, const std::string &order_by, shared_ptr<SearchParams> search_params,
                                                    std::optional<float> radius = std::nullopt, bool descending = false,
                                                    const std::string &missing = "exclude");
+    // extension: multi-vector (late interaction) search -- x [L, T, d]; per logical query the search_params->k best values of the
+    // attribute column `group_by` by the sum over the query's vectors of the best range hit among the value's vectors, `missing`
+    // where there is none (qk_maxsim_search)
+    shared_ptr<MultiVectorSearchResult> multi_vector_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> search_params,
+                                                            std::optional<float> radius = std::nullopt,
+                                                            const std::optional<std::vector<int64_t>> &n_tokens = std::nullopt,
+                                                            std::optional<double> missing = std::nullopt);
     // extension: diversified search -- search_params->k of the fetch_k nearest vectors of each query, chosen greedily by maximal
     // marginal relevance with weight lambda_mult in [0, 1] (qk_diverse_search)
     shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult = 0.5);

@@ -894,6 +894,101 @@ shared_ptr<OrderedSearchResult> QueryCoordinator::ordered_search(Tensor x, qk_at
     return res;
 }
 
+shared_ptr<MultiVectorSearchResult> QueryCoordinator::multi_vector_search(Tensor x, qk_attr *col, const std::vector<std::string> &known,
+                                                                          const std::string &group_by, shared_ptr<SearchParams> sp,
+                                                                          std::optional<float> radius_opt,
+                                                                          const std::optional<std::vector<int64_t>> &n_tokens,
+                                                                          std::optional<double> missing_opt) {
+    const std::string who = "[QuakeIndex::multi_vector_search()]";
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::multi_vector_search] partition_manager_ is null.");
+    if (!sp->filters.empty() || sp->query_filter.defined())
+        throw std::runtime_error(who + " SearchParams.filters / query_filter (one filter per query) are not supported by "
+                                       "multi_vector_search");
+    if (sp->filters_exact_rows != 0)
+        throw std::runtime_error(who + " SearchParams.filters_exact_rows (exact per-query filtered search) is not supported by "
+                                       "multi_vector_search");
+    if (sp->filter_exact_rows != 0)
+        throw std::runtime_error(who + " SearchParams.filter_exact_rows (exact filtered search) is not supported by multi_vector_search");
+    if (sp->max_nprobe > 0)
+        throw std::runtime_error(who + " SearchParams.max_nprobe (adaptive probing) is not supported by multi_vector_search");
+    if (sp->recall_target > 0.0f) throw std::runtime_error(who + " multi_vector_search is not supported with recall_target > 0");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group()) throw std::runtime_error(who + " multi_vector_search is not supported with num_workers > 0");
+    if (!store) throw std::runtime_error("[QueryCoordinator::multi_vector_search] partitions are not initialized.");
+    if (!x.defined() || x.dim() != 3) throw std::runtime_error(who + " x must be [L, T, d]");
+    const int64_t L = x.size(0), T = x.size(1), k = sp->k;
+    const float missing = (float)lower_maxsim(known, group_by, k, T, n_tokens, missing_opt, (int)metric_ == QK_METRIC_IP);
+    if (n_tokens && (int64_t)n_tokens->size() != L)
+        throw std::runtime_error(who + " n_tokens has " + std::to_string(n_tokens->size()) + " entries for " + std::to_string(L) + " queries");
+    qk_filter *flt = nullptr;
+    if (sp->filter) {
+        if (!sp->filter->h) throw std::runtime_error(who + " SearchParams.filter must come from make_filter()");
+        if (sp->filter->owner != store) throw std::runtime_error(who + " the filter was made for another index");
+        flt = sp->filter->h;
+    }
+    const float inf = std::numeric_limits<float>::infinity();
+    const float radius = radius_opt ? *radius_opt : ((int)metric_ == QK_METRIC_IP ? -inf : inf);
+    if (radius != radius) throw std::runtime_error(who + " the radius is NaN");
+    auto res = std::make_shared<MultiVectorSearchResult>();
+    res->column = group_by;
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->search_params = sp;
+    ti->n_clusters = partition_manager_->nlist();
+    if (L == 0) {
+        res->groups = torch::zeros({0, k}, torch::kInt64);
+        res->scores = torch::zeros({0, k}, torch::kFloat32);
+        res->matched = torch::zeros({0, k}, torch::kInt32);
+        res->n_groups = torch::zeros({0}, torch::kInt64);
+        res->hits = torch::zeros({0, T}, torch::kInt64);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = (on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x)).reshape({L * T, x.size(2)});
+    BoundToTorchStream bound(ctx, xq);
+    const int nprobe = std::max(sp->nprobe, 1);
+    const int mem = on_dev ? QK_MEM_DEVICE : QK_MEM_HOST;
+    ti->n_queries = L;
+    Tensor nt;  // int32 [L] in x's memory
+    if (n_tokens) {
+        nt = torch::empty({L}, torch::kInt32);
+        for (int64_t l = 0; l < L; l++) nt.data_ptr<int32_t>()[l] = (int32_t)(*n_tokens)[l];
+        if (on_dev) nt = nt.to(xq.device());
+    }
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
+    res->groups = torch::empty({L, k}, i64);
+    res->scores = torch::empty({L, k}, i64.dtype(torch::kFloat32));
+    res->matched = torch::empty({L, k}, i64.dtype(torch::kInt32));
+    res->n_groups = torch::empty({L}, i64);
+    res->hits = torch::empty({L, T}, i64);
+    qk_check(qk_maxsim_search(ctx, parent_ ? parent_->store() : nullptr, store, xq.data_ptr<float>(), L, (int)T,
+                              nt.defined() ? nt.data_ptr<int32_t>() : nullptr, nprobe, (int)metric_, radius, flt, col, missing, (int)k,
+                              res->groups.data_ptr<int64_t>(), res->scores.data_ptr<float>(), res->matched.data_ptr<int32_t>(),
+                              res->n_groups.data_ptr<int64_t>(), res->hits.data_ptr<int64_t>(), mem, &tm));
+    ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    if (parent_) {
+        ti->parent_info = std::make_shared<SearchTimingInfo>();
+        ti->parent_info->n_queries = L;
+        ti->parent_info->n_clusters = 1;
+        ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
+    }
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
 shared_ptr<DiverseSearchResult> QueryCoordinator::diverse_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, double lambda_mult) {
     const std::string who = "[QuakeIndex::diverse_search()]";
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::diverse_search] partition_manager_ is null.");

@@ -57,6 +57,13 @@ public:
     shared_ptr<OrderedSearchResult> ordered_search(Tensor x, qk_attr *col, const std::vector<std::string> &known, const std::string &order_by,
                                                    shared_ptr<SearchParams> search_params, std::optional<float> radius, bool descending,
                                                    const std::string &missing);
+    // extension (qk_maxsim_search): x [L, T, d], the search_params->k best values of `col` per logical query by the sum of the best
+    // hits of its vectors -- the column `group_by` of this index's store, nullptr: unknown; `known`: the names of the store's columns
+    // (lower_maxsim runs behind the refusals)
+    shared_ptr<MultiVectorSearchResult> multi_vector_search(Tensor x, qk_attr *col, const std::vector<std::string> &known,
+                                                            const std::string &group_by, shared_ptr<SearchParams> search_params,
+                                                            std::optional<float> radius, const std::optional<std::vector<int64_t>> &n_tokens,
+                                                            std::optional<double> missing);
     // extension (qk_diverse_search): search_params->k of the fetch_k nearest vectors of each query by maximal marginal relevance
     // (lower_diverse runs behind the refusals)
     shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult);

@@ -55,6 +55,27 @@ inline void facet_params_fill(FacetParams &F, const qk_emit_pass &p, const qk_st
     F.max_ids = 0;
 }
 
+// The slots a query's tables USE of the T + 1 reserved ones: the power of two >= max(16, 2 * min(hits of the query, max_ids)),
+// known once the hits are counted (k_facet_hits) and never more than T -- a query has no more distinct values than hits.  Clearing,
+// counting and selecting touch these slots only, so a call costs what its hits cost, not what the largest list of the store would.
+// (Also evaluated on the host by multi-vector search, which lays its tables out by it: qk_maxsim.hip.)
+__host__ __device__ __forceinline__ uint32_t facet_used_mask(uint64_t hits, int64_t max_ids, uint32_t tmask) {
+    const uint64_t ids = (uint64_t)(max_ids > 1 ? max_ids : 1);
+    const uint64_t distinct = hits < ids ? hits : ids;
+    uint64_t T = 16;
+    while (T < 2 * distinct) T <<= 1;
+    return (uint32_t)(T - 1 < (uint64_t)tmask ? T - 1 : (uint64_t)tmask);
+}
+
+__device__ __forceinline__ uint32_t facet_hash(unsigned long long v) {  // (the 64-bit finaliser of MurmurHash3, as grouped_hash)
+    v ^= v >> 33;
+    v *= 0xff51afd7ed558ccdull;
+    v ^= v >> 33;
+    v *= 0xc4ceb9fe1a85ec53ull;
+    v ^= v >> 33;
+    return (uint32_t)v;
+}
+
 // is the key at absolute position pos a hit (k_range_count's test); *row: its arena row when it passed the key interval
 __device__ __forceinline__ bool facet_hit(const FacetParams &F, const int64_t *pbase, const int64_t *qpids, int64_t pos, int64_t lim, int64_t *row) {
     const uint32_t key = pos < lim ? F.keys[pos] : 0xFFFFFFFFu;

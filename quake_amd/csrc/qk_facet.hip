@@ -43,24 +43,7 @@ constexpr unsigned long long FC_EMPTY = ~0ull;
 constexpr int FC_AGG_ROUNDS = 4;    // leaders a wave elects per column and step before the lanes that are left add for themselves
 constexpr int FC_SEL = QK_MAX_FACET_VALUES;  // entries the selection sorts in LDS
 
-// The slots a query's tables USE of the T + 1 reserved ones: the power of two >= max(16, 2 * min(hits of the query, max_ids)),
-// known once the hits are counted (k_facet_hits) and never more than T -- a query has no more distinct values than hits.  Clearing,
-// counting and selecting touch these slots only, so a call costs what its hits cost, not what the largest list of the store would.
-__device__ __forceinline__ uint32_t facet_used_mask(uint32_t hits, int64_t max_ids, uint32_t tmask) {
-    const uint64_t distinct = min((uint64_t)hits, (uint64_t)max(max_ids, (int64_t)1));
-    uint64_t T = 16;
-    while (T < 2 * distinct) T <<= 1;
-    return (uint32_t)min(T - 1, (uint64_t)tmask);
-}
-
-__device__ __forceinline__ uint32_t facet_hash(unsigned long long v) {  // (the 64-bit finaliser of MurmurHash3, as grouped_hash)
-    v ^= v >> 33;
-    v *= 0xff51afd7ed558ccdull;
-    v ^= v >> 33;
-    v *= 0xc4ceb9fe1a85ec53ull;
-    v ^= v >> 33;
-    return (uint32_t)v;
-}
+// facet_used_mask (the slots a query's tables USE of the reserved ones) and facet_hash: qk_facet.h
 
 // `add` hits of value v go to v's slot of the table at tv / tc.  Linear probing; the table holds at least twice the values a query
 // can meet, so an empty slot ends every chain -- and at most T probes whatever happens: this loop cannot spin.

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_diverse, lower_edges, lower_expr, lower_order
+from .where import lower_diverse, lower_edges, lower_expr, lower_maxsim, lower_order
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -370,6 +370,22 @@ class OrderedSearchResult:
         self.counts = None
         self.missing = None
         self.totals = None
+        self.column = None
+        self.timing_info = None
+
+
+class MultiVectorSearchResult:
+    """extension (QuakeIndex.multi_vector_search): per logical query the k best values of an attribute column by the sum over the
+    query's vectors of the best hit among the value's rows: groups [L, k] (padding 0), scores [L, k] (padding as search pads),
+    matched [L, k] int32 the query vectors that met the value (padding 0), n_groups [L] the values met, hits [L, T] the range hits
+    of every query vector; column the column's name"""
+
+    def __init__(self):
+        self.groups = None
+        self.scores = None
+        self.matched = None
+        self.n_groups = None
+        self.hits = None
         self.column = None
         self.timing_info = None
 
@@ -1366,6 +1382,93 @@ class QuakeIndex:
             ti.parent_info = pi
         ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
         res.ids, res.distances, res.values, res.counts, res.missing, res.totals = (o if on_dev else o.cpu() for o in out[:6])
+        return res
+
+    def multi_vector_search(self, x, group_by, search_params, radius=None, n_tokens=None, missing=None):
+        """extension (no reference counterpart): multi-vector (late interaction) search.  x is [L, T, d]: every logical query has T
+        vectors, of which the first n_tokens[l] take part (None: all).  A value of the attribute column `group_by` (a document) scores
+        the sum over the query's vectors of the best vector range_search(x[l, t], radius, search_params) returns among the value's
+        vectors (radius None: every vector of the probed partitions), `missing` where there is none (None: 0.0 for the inner
+        product; l2 needs an explicit value).  Returns the search_params.k best values per logical query, the better score first,
+        ties to the smaller value, as a MultiVectorSearchResult on x's device.  1 <= T <= 64, 1 <= k <= 1024.  Exact; the sum is
+        added in float32 in the order of the query's vectors (include/quake_hip.h, "multi-vector search")."""
+        who = "[QuakeIndex::multi_vector_search()]"
+        self._require_built(who + " No query coordinator. Did you build the index?")
+        sp = search_params
+        if (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None:
+            raise RuntimeError(who + " SearchParams.filters / query_filter (one filter per query) are not supported by "
+                               "multi_vector_search")
+        if int(getattr(sp, "filters_exact_rows", 0) or 0) != 0:
+            raise RuntimeError(who + " SearchParams.filters_exact_rows (exact per-query filtered search) is not supported by "
+                               "multi_vector_search")
+        if int(getattr(sp, "filter_exact_rows", 0) or 0) != 0:
+            raise RuntimeError(who + " SearchParams.filter_exact_rows (exact filtered search) is not supported by multi_vector_search")
+        if int(getattr(sp, "max_nprobe", 0) or 0) > 0:
+            raise RuntimeError(who + " SearchParams.max_nprobe (adaptive probing) is not supported by multi_vector_search")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise RuntimeError(who + " multi_vector_search is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise RuntimeError(who + " multi_vector_search is not supported with num_workers > 0")
+        if x is None or x.dim() != 3:
+            raise RuntimeError(who + " x must be [L, T, d]")
+        cols = self._attributes()
+        if n_tokens is not None and torch.is_tensor(n_tokens):
+            n_tokens = n_tokens.detach().cpu().reshape(-1).tolist()
+        name, k, T, n_tokens, missing = lower_maxsim(cols, group_by, sp.k, int(x.shape[1]), n_tokens, missing,
+                                                     "ip" if capi.metric_code(self.metric_) == capi.QK_METRIC_IP else "l2", who)
+        nq = int(x.shape[0])
+        if n_tokens is not None and len(n_tokens) != nq:
+            raise RuntimeError("%s n_tokens has %d entries for %d queries" % (who, len(n_tokens), nq))
+        flt = getattr(sp, "filter", None)
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError(who + " SearchParams.filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError(who + " the filter was made for another index")
+            flt = flt._h
+        if radius is None:
+            radius = float("-inf") if capi.metric_code(self.metric_) == capi.QK_METRIC_IP else float("inf")
+        radius = float(radius)
+        if radius != radius:
+            raise RuntimeError(who + " the radius is NaN")
+        res = MultiVectorSearchResult()
+        res.column = name
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        if nq == 0:
+            res.groups = torch.zeros((0, k), dtype=torch.int64)
+            res.scores = torch.zeros((0, k), dtype=torch.float32)
+            res.matched = torch.zeros((0, k), dtype=torch.int32)
+            res.n_groups = torch.zeros((0,), dtype=torch.int64)
+            res.hits = torch.zeros((0, T), dtype=torch.int64)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        nt = None if n_tokens is None else torch.tensor(n_tokens, dtype=torch.int32, device=xd.device)
+        was = self._ctx.get_timing()   # (a timing mode the caller had set is put back)
+        self._ctx.set_timing(1)
+        try:
+            out = self._ctx.maxsim_search(self.parent._store if self.parent is not None else None, self._store, xd, nprobe, radius,
+                                          self.metric_, cols[name], k, missing=missing, n_tokens=nt, filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(was)
+        tm = out[5]
+        ti.n_queries = nq
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        if self.parent is not None:
+            pi = SearchTimingInfo()
+            pi.n_queries = nq
+            pi.n_clusters = 1
+            pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+            ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.groups, res.scores, res.matched, res.n_groups, res.hits = (o if on_dev else o.cpu() for o in out[:5])
         return res
 
     def diverse_search(self, x, search_params, fetch_k, lambda_mult=0.5):

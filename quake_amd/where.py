@@ -6,7 +6,8 @@ Python integers of any size and are saturated, not wrapped: a comparison with a 
 integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
 lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search), lower_order
-the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search).
+the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_maxsim those of multi-vector search
+(QuakeIndex.multi_vector_search).
 Pure Python: importable without the library or a GPU."""
 
 INT64_MIN = -(1 << 63)
@@ -24,6 +25,7 @@ QK_MAX_ORDER_K = 1024
 QK_ORDER_DESC, QK_ORDER_MISSING_LAST = 1, 2
 MISSING = ("exclude", "last")
 QK_MAX_FETCH_K = 256
+QK_MAXSIM_MAX_TOKENS, QK_MAXSIM_MAX_K = 64, 1024
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
 SET_OPS = ("in", "not_in")  # lower_expr only
@@ -246,3 +248,40 @@ def lower_diverse(k, fetch_k, lambda_mult=0.5, who="[QuakeIndex::diverse_search(
     if not 0.0 <= lam <= 1.0:
         raise RuntimeError("%s lambda_mult=%g must lie in [0, 1]" % (who, lam))
     return k, fetch_k, _to_f32(lam)
+
+
+def lower_maxsim(columns, group_by, k, T, n_tokens=None, missing=None, metric="ip", who="[QuakeIndex::multi_vector_search()]"):
+    """The arguments of multi-vector search (include/quake_hip.h, "multi-vector search") -> (column name, k, T, n_tokens, missing):
+    `columns` are the names of the index's attribute columns, group_by one of them, 1 <= k <= QK_MAXSIM_MAX_K, 1 <= T <=
+    QK_MAXSIM_MAX_TOKENS, n_tokens None (T for every logical query) or a sequence of integers in [0, T] (returned as a list), missing
+    the term of a sub-query without a candidate: None means 0.0 for the inner product and is an error for L2, where no value is the
+    obvious one.  RuntimeError, in this order: a name that is no string, an unknown column, k outside its bounds, T outside its
+    bounds, a bad n_tokens, a `missing` that is no number, NaN, or None under L2."""
+    if not isinstance(group_by, str):
+        raise RuntimeError("%s group_by must be the name of one attribute column, got %r" % (who, group_by))
+    if group_by not in columns:
+        raise RuntimeError("%s unknown attribute column '%s'" % (who, group_by))
+    k = _int(k, who + " k:")
+    if not 1 <= k <= QK_MAXSIM_MAX_K:
+        raise RuntimeError("%s k=%d must be between 1 and %d" % (who, k, QK_MAXSIM_MAX_K))
+    T = _int(T, who + " T:")
+    if not 1 <= T <= QK_MAXSIM_MAX_TOKENS:
+        raise RuntimeError("%s T=%d vectors per query must be between 1 and %d" % (who, T, QK_MAXSIM_MAX_TOKENS))
+    if n_tokens is not None:
+        if isinstance(n_tokens, (str, bytes)) or not hasattr(n_tokens, "__len__") or not hasattr(n_tokens, "__getitem__"):
+            raise RuntimeError("%s n_tokens must be a sequence of integers, got %r" % (who, n_tokens))
+        n_tokens = [_int(n_tokens[i], who + " n_tokens:") for i in range(len(n_tokens))]
+        for i, n in enumerate(n_tokens):
+            if not 0 <= n <= T:
+                raise RuntimeError("%s n_tokens[%d]=%d must be between 0 and T=%d" % (who, i, n, T))
+    is_ip = str(metric).lower() == "ip"
+    if missing is None:
+        if not is_ip:
+            raise RuntimeError("%s missing must be given for the l2 metric: the term of a vector without a match has no default" % who)
+        missing = 0.0
+    if isinstance(missing, bool) or not isinstance(missing, (int, float)):
+        raise RuntimeError("%s missing must be a number, got %r" % (who, missing))
+    missing = float(missing)
+    if missing != missing:
+        raise RuntimeError("%s missing is NaN" % who)
+    return group_by, k, T, n_tokens, missing
