@@ -984,6 +984,20 @@ QK_API int qk_debug_merge_records(qk_ctx *ctx, int64_t Q, int P, int k, int metr
                                   const int32_t *pair_head, const int32_t *rec_hdr, const uint32_t *rec_ord, const int64_t *rec_id,
                                   int32_t max_recs, int64_t *out_ids, float *out_dist, uint32_t *next_key, int64_t *next_id,
                                   char *kernel_name, int name_len);
+/* Test and diagnosis hook: the exact finish of the fp16 shadow form (k_shadow_finish, through the launcher a search uses) on records
+ * the CALLER laid out over a real store, so that a test decides how many records, entries and candidates a query has.  HOST
+ * pointers only.  x [Q][d] queries (their norms come from the library's own preparation), E [Q] error bounds (negative or NaN: no
+ * bound), lists [Q] the probed list of every query (-1: none).  pair_slots [Q][32], pair_head [Q], rec_hdr [max_recs][2] as for
+ * qk_debug_merge_records with P = 1; rec_ord [max_recs][32] approximate keys, ascending within a record; ent_list / ent_pos
+ * [max_recs][32]: every entry's row as (list number, position in the list's arena order) -- the hook turns them into arena rows
+ * from the store's table.  out_ids / out_dist [Q][k] (out_dist may be NULL); counters [4]: what this call added to verified,
+ * fallback, candidates, queries with chained records (qk_ctx_shadow_stats).  A list or position out of range, a record number
+ * outside [-1, max_recs), an entry count outside [0, 32], a chain that does not end, k > 16 or d > 256: QK_ERR_INVALID, nothing is
+ * launched -- the kernel trusts well-formed structures as it trusts the scan.  No reference counterpart. */
+QK_API int qk_debug_shadow_finish(qk_ctx *ctx, qk_store *store, int64_t Q, int k, int metric, int sqrt_l2, const float *x, const float *E,
+                                  const int64_t *lists, const int32_t *pair_slots, const int32_t *pair_head, const int32_t *rec_hdr,
+                                  const uint32_t *rec_ord, const int64_t *ent_list, const int64_t *ent_pos, int32_t max_recs,
+                                  int64_t *out_ids, float *out_dist, int64_t *counters);
 /* When enabled, qk_scan/qk_search return squared L2 distances (the merge key) instead of sqrt distances. */
 QK_API int qk_ctx_set_squared_l2(qk_ctx *ctx, int enabled);
 

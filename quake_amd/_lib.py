@@ -169,6 +169,9 @@ SIGNATURES = {
     # merge stage on caller-built records: (ctx, Q, P, k, metric, sqrt_l2, form, pair_slots, pair_head, rec_hdr, rec_ord, rec_id,
     #                                        max_recs, out_ids, out_dist, next_key, next_id, kernel_name, name_len)
     "qk_debug_merge_records": (_int, [_vp, _i64, _int, _int, _int, _int, _int] + [_vp] * 5 + [C.c_int32] + [_vp] * 4 + [C.c_char_p, _int]),
+    # exact finish of the fp16 shadow form on caller-built records (host arrays): (ctx, store, Q, k, metric, sqrt_l2, x, E, lists,
+    #     pair_slots, pair_head, rec_hdr, rec_ord, ent_list, ent_pos, max_recs, out_ids, out_dist, counters)
+    "qk_debug_shadow_finish": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 9 + [C.c_int32] + [_vp] * 3),
     "qk_kmeans_assign": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _int]),
     "qk_kmeans_accumulate": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp, _int]),
     "qk_kmeans_accumulate_blocked": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp, _int]),

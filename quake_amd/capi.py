@@ -855,6 +855,33 @@ class Context:
             out.update(next_key=nk, next_id=ni)
         return out
 
+    def shadow_finish(self, store, x, E, lists, pair_slots, pair_head, rec_hdr, rec_ord, ent_list, ent_pos, k, metric, sqrt_l2=True, dist=True):
+        """the exact finish of the fp16 shadow form on caller-built records over `store` (qk_debug_shadow_finish; test and diagnosis
+        hook).  numpy arrays: x float32 [Q, d], E float32 [Q], lists int64 [Q] (the probed list, -1: none), pair_slots int32 [Q, 32],
+        pair_head int32 [Q], rec_hdr int32 [max_recs, 2], rec_ord uint32 [max_recs, 32], ent_list / ent_pos int64 [max_recs, 32]
+        (every entry's row: list number, position in the list).  Returns a dict: ids [Q, k], dist [Q, k] (None with dist=False) and
+        what the call added to the counters verified / fallback / candidates / chained.  Malformed records raise, nothing runs."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        Q = int(x.shape[0])
+        k = int(k)
+        max_recs = int(rec_hdr.shape[0])
+        arrs = []
+        for a, dt, shape in ((E, np.float32, (Q,)), (lists, np.int64, (Q,)), (pair_slots, np.int32, (Q, 32)), (pair_head, np.int32, (Q,)),
+                             (rec_hdr, np.int32, (max_recs, 2)), (rec_ord, np.uint32, (max_recs, 32)), (ent_list, np.int64, (max_recs, 32)),
+                             (ent_pos, np.int64, (max_recs, 32))):
+            a = np.ascontiguousarray(a, dtype=dt)
+            if tuple(a.shape) != shape:
+                raise ValueError("shadow_finish: expected a %s array of shape %s, got %s" % (np.dtype(dt).name, shape, tuple(a.shape)))
+            arrs.append(a)
+        if x.ndim != 2 or x.shape[1] != store.d:
+            raise ValueError("shadow_finish: x must be [Q, %d]" % store.d)
+        out_i = np.empty((Q, max(k, 0)), dtype=np.int64)
+        out_d = np.empty((Q, max(k, 0)), dtype=np.float32) if dist else None
+        cnt = np.zeros(4, dtype=np.int64)
+        check(self.lib.qk_debug_shadow_finish(self.h, store.h, Q, k, metric_code(metric), int(bool(sqrt_l2)), _ptr(x), *[_ptr(a) for a in arrs],
+                                              max_recs, _ptr(out_i), _ptr(out_d), _ptr(cnt)))
+        return dict(ids=out_i, dist=out_d, verified=int(cnt[0]), fallback=int(cnt[1]), candidates=int(cnt[2]), chained=int(cnt[3]))
+
     # ---- k-means ----------------------------------------------------------------------------------------
     def kmeans_assign(self, x, c, metric, values=True):
         """nearest centroid of every row (and, with values, its distance / dot product); values=False passes val = NULL, the

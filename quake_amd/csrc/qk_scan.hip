@@ -1079,10 +1079,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     float4 *sh_xqh = shadow ? (float4 *)qk_ws_alloc(ctx, (size_t)Q * nblk_scan * 64) : nullptr;  // fp16 copy of the prepared queries
     float *sh_E = shadow ? (float *)qk_ws_alloc(ctx, (size_t)Q * 4) : nullptr;                   // every query's error bound
     if (shadow && (!sh_xqh || !sh_E)) QK_FAIL(QK_ERR_OOM, "qk_scan: workspace exhausted");
-    if (shadow && !ctx->shadow_counters) {
-        QK_HIP(hipMalloc((void **)&ctx->shadow_counters, 4 * sizeof(unsigned long long)));
-        QK_HIP(hipMemsetAsync(ctx->shadow_counters, 0, 4 * sizeof(unsigned long long), st));
-    }
+    if (shadow) QK_TRY(qk_shadow_counters_ensure(ctx, st));
     if (!g_cnt || !active || !g_qoff || !act_hoff || !grouped_q || !pair_slots || !act_list || !gtau || !rec_hdr || !rec_ord || !rec_id)
         QK_FAIL(QK_ERR_OOM, "qk_scan: workspace exhausted");
 

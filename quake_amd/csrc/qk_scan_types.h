@@ -259,6 +259,8 @@ struct ShadowFinishParams {
 };
 int qk_launch_scan_shadow(int db, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
 int qk_launch_shadow_finish(hipStream_t st, const ShadowFinishParams &fp, int64_t Q);
+// the context's finish counters (ctx->shadow_counters): allocated and cleared on stream st by the first call that needs them
+int qk_shadow_counters_ensure(qk_ctx *ctx, hipStream_t st);
 // fp16 copy of the prepared queries in B-operand order ([Q][nblk_s][4] x 16 B) and every query's error bound
 int qk_launch_shadow_prep(hipStream_t st, const float4 *xq4, const float *xn, int64_t Q, int d, int nblk, int metric, float rho, float xmax,
                           float4 *xqh, float *E);
