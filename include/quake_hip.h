@@ -903,6 +903,43 @@ QK_API int qk_diverse_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, 
                            float lambda, int metric, qk_filter *filter /* or NULL */, int64_t *out_ids, float *out_dist, int32_t *out_rank,
                            int mem, qk_timing *timing);
 
+/* Funnel search: rank the probed rows by a column PREFIX, re-score a shortlist on the full vector.  An approximate
+ * search by design -- the use Matryoshka-trained embeddings are made for -- whose result is still defined bit for bit.
+ * The call takes prefix_dim = d', fetch_k, k and the probed lists, which are chosen exactly as qk_search chooses them: the coarse
+ * step uses the full query (qk_funnel_scan: the pids row, as qk_scan).
+ *   1. Prefix key.  The key of (query, row) is what qk_search would compute for them over a store that holds only columns
+ *      0 .. d'-1: the canonical chain over those columns in ascending order; for L2 the expanded form with the norms of the two
+ *      prefixes, computed the way the store computes a row norm; ord_from_l2 / ord_from_ip and the non-finite rule -- a NaN key is
+ *      never a candidate.
+ *   2. Candidates.  Per query, the fetch_k rows of its probed lists with the smallest prefix keys.  Rows with equal prefix keys that
+ *      straddle the fetch_k-th place are taken in arena order: deterministic for a given store state, not part of the contract.
+ *   3. Answer.  Every candidate gets its exact key -- the canonical full-d chain with the stored norms, bit for bit what qk_search
+ *      reports for that pair.  The k best under (exact key, id) are returned, padding as in qk_search (-1, +inf / -inf).  A
+ *      candidate whose exact key is NaN is not returned.  A row stored twice is two entries.
+ * Consequences: prefix_dim == d equals qk_search with the same k, bit for bit; so does a fetch_k that covers every probed row of
+ * a query; k == fetch_k returns the candidates re-ordered by exact key.
+ * Arguments: 16 <= prefix_dim <= d and prefix_dim a multiple of 16 or equal to d, else QK_ERR_INVALID; prefix_dim >
+ * QK_FUNNEL_MAX_PREFIX: QK_ERR_UNSUPPORTED (the prefix query tile must fit the LDS-staged tile form); 1 <= k <= fetch_k, else
+ * QK_ERR_INVALID; fetch_k > QK_MAX_K: QK_ERR_UNSUPPORTED; d up to QK_MAX_D; Q == 0: QK_OK.  Not served, each QK_ERR_UNSUPPORTED
+ * and never a silent full scan: a flat index without lists of its own (parent == NULL over a one-list store; the dense path).
+ * There is no form for filters, cursors, qk_search_aps or the device group.
+ * Inside (qk_funnel.hip), one enqueue without a host wait -- except the one-off build of the prefix norms: k_funnel_prep (the
+ * queries' prefix in B-operand order with its norms), the grouping, k_scan_prefix (the tile form's body walking the first d'/16
+ * blocks of every tile, tiles strided by the store's row width; no ids read; unseeded), the record merge over (prefix key, arena
+ * row) with k = fetch_k into a buffer of the context, and k_funnel_finish (one workgroup per query; a wave gathers 16 candidate
+ * rows as an MFMA A operand straight from the arena, the query broadcast from LDS as B, v_mfma_f32_16x16x4_f32 in ascending block
+ * order = the canonical chain; selection of the k best under (key, id) in LDS).
+ * Side data: 4 bytes per arena row of prefix norms for ONE prefix_dim at a time, built by the first L2 call for a (store version,
+ * prefix_dim) and invalid as soon as the store changes; counted in qk_store_device_bytes; not persisted.  No memory for it:
+ * QK_ERR_OOM, nothing else changed.
+ * timing: the candidate search's phases; the finish lies behind merge_ms and is part of total_ms only.  scan_bytes counts the
+ * prefix bytes of the unique probed rows.  qk_ctx_last_scan_kernel reports "k_scan (prefix)". */
+#define QK_FUNNEL_MAX_PREFIX 1024
+QK_API int qk_funnel_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k,
+                            int prefix_dim, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_funnel_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k,
+                          int prefix_dim, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

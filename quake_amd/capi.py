@@ -111,6 +111,7 @@ QK_ORDER_DESC = 1          # include/quake_hip.h: the flags of ordered search
 QK_ORDER_MISSING_LAST = 2
 QK_MAX_ORDER_K = 1024
 QK_MAX_FETCH_K = 256       # diversified search
+QK_FUNNEL_MAX_PREFIX = 1024  # funnel search
 QK_MAXSIM_MAX_TOKENS = 64  # multi-vector search
 QK_MAXSIM_MAX_K = 1024
 
@@ -772,6 +773,41 @@ class Context:
                                        _ptr(ids), _ptr(dist) if dist is not None else None, _ptr(rank) if rank is not None else None,
                                        mem, C.byref(t) if timing else None))
         return (ids, dist, rank, timing_dict(t)) if timing else (ids, dist, rank)
+
+    # ---- funnel search -----------------------------------------------------------------------------------
+    def funnel_search(self, parent, store, x, nprobe, k, fetch_k, prefix_dim, metric, want_dist=True, timing=False):
+        """qk_funnel_search: per query, the fetch_k rows of its probed lists with the smallest keys over the first prefix_dim
+        columns, re-scored on the full vector; the k best under (exact key, id).  Returns (ids [Q, k] padded with -1, dist [Q, k]
+        padded as search pads -- None where not wanted --[, timing]) on x's device."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1  # (the library refuses such a k before it writes: the buffers only have to exist)
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_funnel_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
+                                        int(prefix_dim), metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                                        C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
+
+    def funnel_scan(self, store, x, pids, k, fetch_k, prefix_dim, metric, want_dist=True, timing=False):
+        """qk_funnel_scan: funnel_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
+        nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        pids = _pids_rows(pids, Q)
+        mem = _mem_of(x, pids)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_funnel_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
+                                      fetch_k, int(prefix_dim), metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None,
+                                      mem, C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):

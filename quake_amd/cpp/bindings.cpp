@@ -208,6 +208,20 @@ PYBIND11_MODULE(_bindings, m) {
           },
           py::arg("k"), py::arg("fetch_k"), py::arg("lambda_mult") = 0.5,
           "the arguments of diverse_search -> (k, fetch_k, lambda_mult rounded to float32); needs no device (where.py's lower_diverse)");
+    m.def("lower_funnel",
+          [](int64_t d, int64_t k, int64_t prefix_dim, int64_t fetch_k) {
+              lower_funnel(d, k, prefix_dim, fetch_k);
+              return py::make_tuple(k, prefix_dim, fetch_k);
+          },
+          py::arg("d"), py::arg("k"), py::arg("prefix_dim"), py::arg("fetch_k"),
+          "the arguments of funnel_search -> (k, prefix_dim, fetch_k); needs no device (where.py's lower_funnel)");
+    py::register_exception_translator([](std::exception_ptr p) {
+        try {
+            if (p) std::rethrow_exception(p);
+        } catch (const NotImplemented &e) {
+            PyErr_SetString(PyExc_NotImplementedError, e.what());
+        }
+    });
     m.doc() = "quake_amd: MI355X-native Quake search path (same surface as quake._bindings)";
 
     py::class_<QuakeIndex, std::shared_ptr<QuakeIndex>>(m, "QuakeIndex")
@@ -318,6 +332,8 @@ PYBIND11_MODULE(_bindings, m) {
              "attribute column `group_by` by the sum over the query's vectors of the best vector range_search returns among the value's "
              "vectors; n_tokens [L]: the vectors of each query that take part; missing: the term of a vector without a match (None: 0 "
              "for the inner product)")
+        .def("funnel_search", &QuakeIndex::funnel_search, py::arg("x"), py::arg("search_params"), py::arg("prefix_dim"), py::arg("fetch_k"),
+             "extension: rank the probed rows by their first prefix_dim columns, re-score the fetch_k best on the full vector")
         .def("diverse_search", &QuakeIndex::diverse_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
              py::arg("lambda_mult") = 0.5,
              "extension: per query, search_params.k of its fetch_k nearest vectors (what search() returns with k = fetch_k) chosen "

@@ -231,6 +231,11 @@ struct MultiVectorSearchResult {
     shared_ptr<SearchTimingInfo> timing_info;
 };
 
+// a request the index does not serve (Python: NotImplementedError, a RuntimeError)
+struct NotImplemented : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
 // extension (QuakeIndex::diverse_search): per query k of its fetch_k nearest vectors chosen by maximal marginal relevance, in
 // selection order: ids [Q, k] (padding -1), distances [Q, k] (padding as search pads), ranks [Q, k] int32 (padding -1)
 struct DiverseSearchResult {

@@ -280,6 +280,23 @@ shared_ptr<DiverseSearchResult> QuakeIndex::diverse_search(Tensor x, shared_ptr<
     return query_coordinator_->diverse_search(x, sp, fetch_k, lambda_mult);
 }
 
+void lower_funnel(int64_t d, int64_t k, int64_t prefix_dim, int64_t fetch_k) {
+    const std::string who = "[QuakeIndex::funnel_search()]";
+    if (!(prefix_dim >= 16 && prefix_dim <= d) || (prefix_dim % 16 != 0 && prefix_dim != d))
+        throw std::runtime_error(who + " prefix_dim=" + std::to_string(prefix_dim) + " must lie in [16, d=" + std::to_string(d) +
+                                 "] and be a multiple of 16 or equal to d");
+    if (k < 1) throw std::runtime_error(who + " k=" + std::to_string(k) + " must be at least 1");
+    if (fetch_k < k) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must be at least k=" + std::to_string(k));
+    if (prefix_dim > QK_FUNNEL_MAX_PREFIX)
+        throw std::runtime_error(who + " prefix_dim=" + std::to_string(prefix_dim) + " must not exceed " + std::to_string(QK_FUNNEL_MAX_PREFIX));
+    if (fetch_k > QK_MAX_K) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must not exceed " + std::to_string(QK_MAX_K));
+}
+
+shared_ptr<SearchResult> QuakeIndex::funnel_search(Tensor x, shared_ptr<SearchParams> sp, int64_t prefix_dim, int64_t fetch_k) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::funnel_search()] No query coordinator. Did you build the index?");
+    return query_coordinator_->funnel_search(x, sp, prefix_dim, fetch_k);
+}
+
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?");
     qk_store *s = partition_manager_->store();

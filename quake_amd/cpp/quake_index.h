@@ -59,6 +59,8 @@ double lower_maxsim(const std::vector<std::string> &columns, const std::string &
 // the arguments of diverse_search (where.py's lower_diverse: same rules, same errors as std::runtime_error, in the same order):
 // k < 1, fetch_k < k, fetch_k > QK_MAX_FETCH_K, a lambda_mult that is NaN or outside [0, 1] -> lambda_mult rounded to float32
 float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult);
+// the arguments of funnel_search over vectors of d columns (where.py's lower_funnel: same rules, same errors, same order)
+void lower_funnel(int64_t d, int64_t k, int64_t prefix_dim, int64_t fetch_k);
 
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
@@ -137,6 +139,9 @@ public:
     // extension: diversified search -- search_params->k of the fetch_k nearest vectors of each query, chosen greedily by maximal
     // marginal relevance with weight lambda_mult in [0, 1] (qk_diverse_search)
     shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult = 0.5);
+    // extension: funnel search -- rank the probed rows by their first prefix_dim columns, re-score the fetch_k best on the full vector,
+    // return search_params->k of them under (exact distance, id) (qk_funnel_search)
+    shared_ptr<SearchResult> funnel_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t prefix_dim, int64_t fetch_k);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

@@ -67,6 +67,8 @@ public:
     // extension (qk_diverse_search): search_params->k of the fetch_k nearest vectors of each query by maximal marginal relevance
     // (lower_diverse runs behind the refusals)
     shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult);
+    // extension (qk_funnel_search): candidates by a column prefix, exact re-score (lower_funnel runs behind the refusals)
+    shared_ptr<SearchResult> funnel_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t prefix_dim, int64_t fetch_k);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

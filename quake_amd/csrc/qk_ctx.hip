@@ -77,6 +77,7 @@ int qk_ctx_destroy(qk_ctx *c) {
     if (c->after_buf) hipFree(c->after_buf);
     if (c->pool_buf) hipFree(c->pool_buf);
     if (c->div_buf) hipFree(c->div_buf);
+    if (c->fn_buf) hipFree(c->fn_buf);
     if (c->shadow_counters) hipFree(c->shadow_counters);
     if (c->xcd_host) hipHostFree(c->xcd_host);
     if (c->xcd_ev) hipEventDestroy(c->xcd_ev);

@@ -210,6 +210,10 @@ struct qk_ctx {
     // queries and the staging of a host caller's buffers; its own buffer because the candidate search recycles `ws` and `stage`
     char *div_buf = nullptr;
     size_t div_cap = 0;
+    // funnel search (qk_funnel.hip): the queries' prefix in B-operand order with its norms, and the candidates of a call (arena rows);
+    // its own buffer because the coarse step and the scan recycle `ws`
+    char *fn_buf = nullptr;
+    size_t fn_cap = 0;
 };
 
 int qk_ws_reserve(qk_ctx *ctx, size_t bytes);          // make sure the workspace can hold `bytes` (may sync+realloc)
@@ -294,7 +298,17 @@ struct qk_store {
     float shadow_rho = 0.f, shadow_xmax = 0.f;  // max ||x - fp16(x)||, max ||fp16(x)|| over the live rows, rounded up
     uint32_t *shadow_stats = nullptr;  // device [4]: what a conversion reduces (kept with the store: no allocation per build)
     int64_t shadow_builds = 0;
+    // funnel search (qk_funnel.hip): the canonical squared norm of the first pnorms_dim columns of every live row, in
+    // arena indexing.  Built lazily by qk_store_prefix_norms for one (version, prefix_dim) at a time; not persisted
+    float *pnorms = nullptr;
+    int64_t pnorms_cap_rows = 0;
+    uint64_t pnorms_version = 0;
+    int pnorms_dim = 0;  // 0: none
 };
+// the prefix norms of `s` (table synced) for prefix_dim, built on ctx's stream if the store or the dimension changed; QK_ERR_OOM and
+// nothing else changed where there is no memory for them
+int qk_store_prefix_norms(qk_ctx *ctx, qk_store *s, int prefix_dim, const float **out);
+void qk_store_prefix_free(qk_store *s);
 // the shadow of `s` for the search that is being planned on ctx (the store's table is synced): *usable = a valid shadow of the
 // current version exists (built here if the call count -- or force -- says so).  Never fails for want of memory or validity.
 int qk_store_shadow_consider(qk_ctx *ctx, qk_store *s, bool force, bool *usable);
@@ -381,6 +395,11 @@ struct qk_scan_args {
     const int64_t *after_id = nullptr;
     uint32_t *next_key = nullptr;
     int64_t *next_id = nullptr;
+    // funnel search (qk_funnel.hip): prefix_nblk > 0 -> the scan reads only the first prefix_nblk blocks of every tile (k_scan_prefix).
+    // xq4 / xn are then the queries' prefix ([Q][prefix_nblk][4] x 16 B) and its norms, prefix_norms the store's (qk_store_prefix_norms);
+    // out_ids receives ARENA ROWS, out_dist prefix keys.  Unseeded tile form only; no filter, cursor, per_pair or key emission
+    int prefix_nblk = 0;
+    const float *prefix_norms = nullptr;
 };
 // filters (qk_filter.hip)
 struct qk_filter;

@@ -917,6 +917,10 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     if (paged && (!filtered || a.qmasks || !a.after_id)) QK_FAIL(QK_ERR_UNSUPPORTED, "paged scan: needs one row mask and both cursor arrays");
     // (a flat index with a filter takes the grouped scan below: the dense forms know nothing of masks)
     const bool one_list = a.all_lists && s->nlist == 1 && !emit && !filtered;
+    // prefix form (qk_funnel.hip): the unseeded tile form over the first a.prefix_nblk blocks of every tile, nothing else
+    const bool prefix = a.prefix_nblk > 0;
+    if (prefix && (one_list || k > QK_MAX_K || emit || filtered || paged || a.per_pair || a.tau_init || a.prefix_nblk > s->nblk))
+        QK_FAIL(QK_ERR_UNSUPPORTED, "prefix scan: the tile form over several lists with k <= QK_MAX_K only");
     if (k > QK_MAX_K && !one_list) {
         if (a.per_pair) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: k=%d exceeds QK_MAX_K=%d", k, QK_MAX_K);
         QK_TRY(qk_prep_flush(ctx));
@@ -950,7 +954,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     // fp16 shadow form (qk_shadow.hip): the tile form's launch over the shadow -- blocks of 32 columns, records of k' entries that hold
     // approximate keys and arena rows -- and k_shadow_finish in the merge's place
     const bool shadow = plan.form == 3;
-    const int nblk_scan = shadow ? qk_shadow_nblk(nblk) : nblk;  // 1 KiB blocks per tile of what the scan kernel streams
+    const int nblk_scan = prefix ? a.prefix_nblk : shadow ? qk_shadow_nblk(nblk) : nblk;  // 1 KiB blocks per tile of what the scan kernel streams
     const int k_rec = shadow ? QK_SHADOW_KP : k;                 // entries per record
     const size_t q_bytes = (size_t)nblk_scan * 1024;
     int DB = plan.DB;
@@ -1001,7 +1005,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     if (use_rl) waves_per_cu = rl_waves;  // one wave per SIMD: 256+ registers of row data per wave
     // wide rows (d >= 256: the LDS query tile leaves room for <= 4 waves per CU): 16 blocks = 16 KB per load step, so
     // that the few resident waves still keep enough bytes in flight to cover the HBM latency
-    if (nblk % 16 == 0 && waves_per_cu <= 4 && !qshare && !use_rl && !shadow && !qk_env_set("QK_SCAN_NO_DB16")) DB = 16;
+    if (nblk % 16 == 0 && waves_per_cu <= 4 && !qshare && !use_rl && !shadow && !prefix && !qk_env_set("QK_SCAN_NO_DB16")) DB = 16;
     const int wgs_per_cu = waves_per_cu / nw;
     const int64_t n_wgs = (int64_t)num_cus * wgs_per_cu;
     const int64_t n_waves = n_wgs * nw;
@@ -1138,7 +1142,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     const int seed_cap = nblk <= 8 ? std::max(seed_max_k, 128) : seed_max_k;
     // (never for a filtered call: a sample bound comes from rows nobody tested against the filter, and a bound learnt from a
     //  disallowed row drops allowed ones.  The bounds the waves of one query share through gtau come from allowed rows only.)
-    const bool seeded = ((!no_seed && share_tau) || seed_pairs) && k <= std::min(seed_cap, 512) && npairs > 0 && npids > 0 && !filtered;
+    const bool seeded = ((!no_seed && share_tau) || seed_pairs) && k <= std::min(seed_cap, 512) && npairs > 0 && npids > 0 && !filtered && !prefix;
     bool fused_group = false, fused_count = false;
     if (seeded) {
         // bound seeding: for the first (nearest) partitions of every query, the k-th smallest distance of a 64-row
@@ -1272,6 +1276,11 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             sp.tau_refresh = 0;
             sp.tau_publish = 0;
         }
+        sp.nblk_row = nblk;
+        if (prefix) {  // the arena walked by its first nblk_scan blocks per tile, against the prefix norms (a.xq4 / a.xn are the prefix's already)
+            sp.nblk = nblk_scan;
+            sp.norms = a.prefix_norms;
+        }
         sp.k = k_rec;
         sp.C = C;
         sp.metric = a.metric;
@@ -1386,7 +1395,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         sp.xcd_stat = nullptr;
         for (int c = 0; c < 8; c++) sp.xcd_w[c] = 1024;
         // (a filtered launch neither uses nor feeds the weights: how long a class takes depends on the tiles its mask leaves)
-        if (xcd_adapt && !wide && !filtered && (sp.dyn_counter == nullptr || use_rl) && grid >= 64 && tiles_est >= (int64_t)grid * wpw * 32) {
+        if (xcd_adapt && !wide && !filtered && !prefix && (sp.dyn_counter == nullptr || use_rl) && grid >= 64 && tiles_est >= (int64_t)grid * wpw * 32) {
             const uint64_t xkey = s->uid ^ (shadow ? 0x8000000000000000ull : 0ull);  // (the shadow is another allocation: its own weights)
             qk_ctx::xcd_state &xs = ctx->xcd[xkey];
             sp.xcd_on = 1;
@@ -1409,12 +1418,14 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             QK_HIP(hipMemsetAsync(d_clock, 0, (size_t)grid * wpw * 64 * 2, st));
             sp.wave_clock = d_clock;
         }
-        ctx->last_scan_kernel = paged ? (wide ? "k_scan_wide (after)" : "k_scan (after)") : a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : shadow ? "k_scan (fp16 shadow)" : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
+        ctx->last_scan_kernel = paged ? (wide ? "k_scan_wide (after)" : "k_scan (after)") : a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : shadow ? "k_scan (fp16 shadow)" : prefix ? "k_scan (prefix)" : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
         // (until qk_finish_timing fills it in, qk_timing::scan_bytes holds MINUS the bytes per row of the form that ran, or 0 = fp32
         //  rows: the call's own result, not context state -- a later call cannot inherit it --, and a negative value is no byte count,
         //  so finishing the same struct twice cannot multiply rows by a total)
-        if (timing) timing->scan_bytes = shadow ? -(int64_t)nblk_scan * 64 : 0;
-        if (shadow)
+        if (timing) timing->scan_bytes = (shadow || prefix) ? -(int64_t)nblk_scan * 64 : 0;
+        if (prefix)
+            QK_TRY(qk_launch_scan_prefix(DB, maxch, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
+        else if (shadow)
             QK_TRY(qk_launch_scan_shadow(DB, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
         else if (wide)
             QK_TRY(qk_launch_scan_wide(maxch, (unsigned)grid, lds_launch, st, sp));

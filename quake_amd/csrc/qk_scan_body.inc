@@ -15,6 +15,9 @@
 // (P.nblk blocks of 32 columns per tile, 16 B per lane as before), P.xq4 the fp16 copy of the queries in the same lane order, one
 // v_mfma_f32_16x16x32_f16 per block; no ids are loaded -- a candidate's "id" is its arena row --, the start bound is the seed's
 // widened by the query's error bound P.sh_E, P.k is the k' of the form.  Everything it changes sits behind #ifdef QK_SCAN_SHADOW.
+// QK_SCAN_PREFIX (with QK_SCAN_FILT 0) = k_scan_prefix (qk_funnel.hip), the prefix form: P.vecs is the arena, whose tiles lie
+// P.nblk_row blocks apart, and the walk takes the first P.nblk blocks of each; P.norms / P.xn are norms of the prefixes, P.xq4 the
+// queries' prefix; no ids are loaded (a candidate's "id" is its arena row).  Everything it changes sits behind #ifdef QK_SCAN_PREFIX.
 // Expects: template parameters DB, MAXCH, MODE, L2 and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     // nw waves per workgroup (1, 2 or 4) share ONE LDS query tile and split every segment's tiles between them; each
@@ -167,7 +170,11 @@
         {
             // (a wave whose share is empty still issues the static loads: keep them inside the segment)
             const int64_t tile_abs0 = (row_off >> 4) + min(tl, tend_wg - 1);
+#ifdef QK_SCAN_PREFIX
+            const float4 *src = P.vecs + tile_abs0 * P.nblk_row * 64 + lane;  // (a tile is nblk_row blocks; the walk takes the first nblk)
+#else
             const float4 *src = P.vecs + tile_abs0 * nblk * 64 + lane;
+#endif
             const float4 *nsrc = (const float4 *)(P.norms + (tile_abs0 << 4)) + g;  // +4 float4 per tile
             // ids of this lane's 4 rows travel with the tile (static prefetch): an id load inside the append path
             // would force s_waitcnt vmcnt(0) and drain the prefetched tile every time a candidate passes
@@ -291,6 +298,23 @@
             }                                                         \
         }                                                             \
     }
+#elif defined(QK_SCAN_PREFIX)
+#define QK_EPI_M(Y)
+#define QK_NEXT_TILE tile++
+#define QK_LOAD(A, Y, I0, I1)                                         \
+    {                                                                 \
+        const float4 *pp_ = src + ((int64_t)ltile * P.nblk_row + ldch * DB) * 64; \
+        _Pragma("unroll") for (int b_ = 0; b_ < DB; b_++)             \
+            A[b_] = qk_ld_stream(pp_ + b_ * 64);                      \
+        Y = nsrc[(int64_t)ltile * 4];                                 \
+        if (lS < nsteps - 1) {                                        \
+            lS++;                                                     \
+            if (++ldch == ncd) {                                      \
+                ldch = 0;                                             \
+                ltile++;                                              \
+            }                                                         \
+        }                                                             \
+    }
 #else
 #define QK_EPI_M(Y)
 #define QK_NEXT_TILE tile++
@@ -357,7 +381,7 @@
 #endif
                 const int row0 = tl_ << 4;
                 const float yv[4] = {yn.x, yn.y, yn.z, yn.w};
-#ifdef QK_SCAN_SHADOW
+#if defined(QK_SCAN_SHADOW) || defined(QK_SCAN_PREFIX)
                 const int64_t row_abs_ = row_off + row0 + 4 * g;
                 const int64_t idv[4] = {row_abs_, row_abs_ + 1, row_abs_ + 2, row_abs_ + 3};
 #else

@@ -155,6 +155,9 @@ struct ScanParams {
     // fp16 shadow form (k_scan_shadow, qk_shadow.hip): vecs is the shadow, nblk its 32-column blocks, xq4 the fp16 query copy; sh_E
     // [Q] is the error bound of every query's approximate keys, negative = the query takes no part (the finish answers it exactly)
     const float *sh_E;
+    // prefix form (k_scan_prefix, qk_funnel.hip): vecs is the arena itself, whose tiles are nblk_row blocks apart; the kernel walks
+    // the first nblk of them.  norms / xn are the norms of the prefixes, xq4 the queries' prefix in B-operand order
+    int nblk_row;
 };
 
 // ---- merge stage (qk_merge.hip) ------------------------------------------------------------------------------------------
@@ -268,4 +271,6 @@ int qk_launch_shadow_prep(hipStream_t st, const float4 *xq4, const float *xn, in
 // bits of max err^2, bits of max ||fp16(x)||^2, "a value is not finite or beyond 65504"
 int qk_launch_shadow_convert(hipStream_t st, const float4 *vecs, int nblk, const int64_t *pt_off, const int32_t *pt_size, int npids, void *shadow,
                              uint32_t *stats);
+// prefix form (qk_funnel.hip): the tile form over the first sp.nblk blocks of every tile, launched like k_scan
+int qk_launch_scan_prefix(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
 int qk_launch_next_cursor(qk_ctx *ctx, const MergeParams &mp, int64_t Q, const int64_t *out_ids, uint32_t *next_key, int64_t *next_id);

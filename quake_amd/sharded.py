@@ -288,6 +288,11 @@ class ShardedIndex:
         self.dist.all_gather_into_tensor(buf.view(-1, t.shape[-1]), t.contiguous())
         return buf
 
+    def funnel_search(self, q, nprobe, k, prefix_dim, fetch_k):
+        """funnel search (QuakeIndex.funnel_search, qk_funnel_search) has no sharded form: a shard's candidates are its own fetch_k
+        best prefix keys, not the index's."""
+        raise NotImplementedError("[ShardedIndex::funnel_search()] funnel_search is not supported by sharded.py")
+
     def diverse_search(self, q, nprobe, k, fetch_k, lambda_mult=0.5):
         """diversified search (QuakeIndex.diverse_search, qk_diverse_search) has no sharded form: the re-ranking needs the vectors
         of every candidate of a query, which live on different ranks"""

@@ -6,7 +6,7 @@ Python integers of any size and are saturated, not wrapped: a comparison with a 
 integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
 lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search), lower_order
-the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_maxsim those of multi-vector search
+the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_funnel those of funnel search (QuakeIndex.funnel_search), lower_maxsim those of multi-vector search
 (QuakeIndex.multi_vector_search).
 Pure Python: importable without the library or a GPU."""
 
@@ -25,6 +25,8 @@ QK_MAX_ORDER_K = 1024
 QK_ORDER_DESC, QK_ORDER_MISSING_LAST = 1, 2
 MISSING = ("exclude", "last")
 QK_MAX_FETCH_K = 256
+QK_MAX_K = 448
+QK_FUNNEL_MAX_PREFIX = 1024
 QK_MAXSIM_MAX_TOKENS, QK_MAXSIM_MAX_K = 64, 1024
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
@@ -248,6 +250,27 @@ def lower_diverse(k, fetch_k, lambda_mult=0.5, who="[QuakeIndex::diverse_search(
     if not 0.0 <= lam <= 1.0:
         raise RuntimeError("%s lambda_mult=%g must lie in [0, 1]" % (who, lam))
     return k, fetch_k, _to_f32(lam)
+
+
+def lower_funnel(d, k, prefix_dim, fetch_k, who="[QuakeIndex::funnel_search()]"):
+    """The arguments of funnel search (include/quake_hip.h, "funnel search") over vectors of d columns -> (k, prefix_dim, fetch_k):
+    16 <= prefix_dim <= d, prefix_dim a multiple of 16 or d itself and at most QK_FUNNEL_MAX_PREFIX; 1 <= k <= fetch_k <= QK_MAX_K.
+    RuntimeError, in this order: a value that is no integer, prefix_dim outside [16, d] or neither a multiple of 16 nor d, k < 1,
+    fetch_k < k, prefix_dim above its limit, fetch_k above its limit."""
+    k = _int(k, who + " k:")
+    prefix_dim = _int(prefix_dim, who + " prefix_dim:")
+    fetch_k = _int(fetch_k, who + " fetch_k:")
+    if not 16 <= prefix_dim <= d or (prefix_dim % 16 != 0 and prefix_dim != d):
+        raise RuntimeError("%s prefix_dim=%d must lie in [16, d=%d] and be a multiple of 16 or equal to d" % (who, prefix_dim, d))
+    if k < 1:
+        raise RuntimeError("%s k=%d must be at least 1" % (who, k))
+    if fetch_k < k:
+        raise RuntimeError("%s fetch_k=%d must be at least k=%d" % (who, fetch_k, k))
+    if prefix_dim > QK_FUNNEL_MAX_PREFIX:
+        raise RuntimeError("%s prefix_dim=%d must not exceed %d" % (who, prefix_dim, QK_FUNNEL_MAX_PREFIX))
+    if fetch_k > QK_MAX_K:
+        raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_MAX_K))
+    return k, prefix_dim, fetch_k
 
 
 def lower_maxsim(columns, group_by, k, T, n_tokens=None, missing=None, metric="ip", who="[QuakeIndex::multi_vector_search()]"):
