@@ -940,6 +940,51 @@ QK_API int qk_funnel_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const fl
 QK_API int qk_funnel_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k,
                           int prefix_dim, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
 
+/* Quantized search: scalar quantization with oversampling and rescoring.  Every coordinate of the store is mirrored
+ * as one int8 code, all d coordinates are scanned at a quarter of the bytes, a shortlist of fetch_k rows is re-scored exactly.  An
+ * approximate search by design whose result is still defined bit for bit; all arithmetic below is float32 unless it says integer.
+ *   1. Code parameters of a store: a pure function of its live rows, independent of their order.
+ *      L2: lo_j / hi_j = min / max of column j over the live rows; m_j = 0.5f * lo_j + 0.5f * hi_j (two products, one sum);
+ *          w = max_j (hi_j - lo_j); s = w / 254.0f (IEEE division), or 1 where that quotient is 0.
+ *      IP: m_j = 0; a = max |x| over live rows and columns; s = a / 127.0f, or 1 where that quotient is 0.
+ *      A store with a live row that holds a non-finite value, or whose s is not finite, has no code mirror: QK_ERR_UNSUPPORTED, the
+ *      message names the list, nothing is written (the rule of the fp16 shadow for values beyond its range, as an error here
+ *      because the caller asked for this form).  An empty store is QK_OK with padding rows.
+ *   2. Row code: c_j = clamp(rint((x_j - m_j) / s), -127, 127): one subtraction, one IEEE division, round half to even.  Columns
+ *      from d up to the next multiple of 64 hold code 0.  L2: nx = sum c_j^2 is kept as an int32 per row.
+ *   3. Query code: L2 uses the store's m and s with the same formula.  IP gives every query its own scale: s_q = (max |q_j| over
+ *      its finite coordinates) / 127.0f, or 1 where that is 0.  A NaN coordinate codes as 0, +-inf as +-127.
+ *   4. Approximate key: L2: sum (cq_j - cx_j)^2 computed as nq + nx - 2 dot (below 2^31 for d <= 8192); IP: -dot.  Exact integers --
+ *      integer sums are associative, so no rule about summation order is needed.  The key enters the pools and the merge as a
+ *      strictly monotone uint32 image that is never 0xFFFFFFFF.
+ *   5. Candidates: per query, the fetch_k rows of its probed lists that are smallest under (approximate key, arena row).  The probed
+ *      lists are chosen exactly as qk_search chooses them, the coarse step on the float32 query (qk_sq8_scan: the pids row).
+ *   6. Answer: as funnel search, step 3 -- every candidate gets its canonical fp32 key, the k best under (exact key, id) are
+ *      returned, padding as in qk_search; a candidate whose exact key is NaN is not returned.
+ *   7. Consequence: a fetch_k that covers every probed row of a query gives qk_search's row, bit for bit.
+ * Arguments: 1 <= k <= fetch_k, else QK_ERR_INVALID; fetch_k > QK_MAX_K: QK_ERR_UNSUPPORTED; d > QK_SQ8_MAX_D: QK_ERR_UNSUPPORTED (at
+ * d = 2048 the code query tile is 32 KiB and the pools of fetch_k = 448 are 96 KiB of LDS; at 4096 the two fill all 160 KiB); a flat
+ * index without lists of its own: QK_ERR_UNSUPPORTED; Q == 0: QK_OK.  A refusal writes no output.  There is no form for filters,
+ * cursors, qk_search_aps or the device group.
+ * Inside (qk_sq8.hip), one enqueue without a host wait -- except the one-off build of the mirror: k_sq8_prep (the queries' codes in
+ * B-operand order, their nq), the grouping, k_scan_sq8 (the tile form's body over the code tiles: one v_mfma_i32_16x16x64_i8 per
+ * 64-column block into an int32 accumulator, the rows' nx in the norm stream, no ids read, unseeded), the record merge over
+ * (integer key, arena row) with k = fetch_k into a buffer of the context, and k_funnel_finish, unchanged.
+ * The mirror: 64 * ceil(d / 64) + 4 bytes per arena row, code row r = arena row r in the same 16-row tiles; built on the context's
+ * stream (k_sq8_range, k_sq8_encode) by the first call for a (store version, metric), invalid as soon as the store changes and
+ * then rebuilt in full (the scale depends on every row); freed with the store or by qk_store_sq8_drop; counted in
+ * qk_store_device_bytes; not persisted.  No memory for it: QK_ERR_OOM, nothing else changed.  qk_store_sq8_info: valid = a mirror of
+ * the current version exists, bytes = what it occupies, scale = its s (0 without a valid mirror).
+ * timing: the candidate search's phases; the finish lies behind merge_ms and is part of total_ms only.  scan_bytes counts the code
+ * bytes of the unique probed rows.  qk_ctx_last_scan_kernel reports "k_scan (int8 codes)". */
+#define QK_SQ8_MAX_D 2048
+QK_API int qk_sq8_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k, int metric,
+                         int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_sq8_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
+                       int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_store_sq8_info(qk_store *s, int *valid, int64_t *bytes, float *scale);
+QK_API int qk_store_sq8_drop(qk_store *s);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

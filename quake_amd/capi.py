@@ -112,6 +112,7 @@ QK_ORDER_MISSING_LAST = 2
 QK_MAX_ORDER_K = 1024
 QK_MAX_FETCH_K = 256       # diversified search
 QK_FUNNEL_MAX_PREFIX = 1024  # funnel search
+QK_SQ8_MAX_D = 2048        # quantized search
 QK_MAXSIM_MAX_TOKENS = 64  # multi-vector search
 QK_MAXSIM_MAX_K = 1024
 
@@ -809,6 +810,41 @@ class Context:
                                       mem, C.byref(t) if timing else None))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
+    # ---- quantized search --------------------------------------------------------------------------------
+    def sq8_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False):
+        """qk_sq8_search: per query, the fetch_k rows of its probed lists with the smallest integer keys over the store's int8
+        codes, re-scored on the float32 rows; the k best under (exact key, id).  Returns (ids [Q, k] padded with -1, dist [Q, k]
+        padded as search pads -- None where not wanted --[, timing]) on x's device."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1  # (the library refuses such a k before it writes: the buffers only have to exist)
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_sq8_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
+                                     metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                                     C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
+
+    def sq8_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False):
+        """qk_sq8_scan: sq8_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
+        nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        pids = _pids_rows(pids, Q)
+        mem = _mem_of(x, pids)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_sq8_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
+                                   fetch_k, metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                                   C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
+
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):
         """recall-target search (adaptive partition scanning).  Returns (ids, dist, nscanned[, timing])."""
@@ -1147,6 +1183,16 @@ class Store:
     def shadow_drop(self):
         """free the fp16 shadow (qk_store_shadow_drop); eligible searches build it again"""
         check(self.lib.qk_store_shadow_drop(self.h))
+
+    def sq8_info(self):
+        """{valid, bytes, scale} of the store's int8 code mirror of quantized search (qk_store_sq8_info)"""
+        v, b, s = C.c_int(), C.c_int64(), C.c_float()
+        check(self.lib.qk_store_sq8_info(self.h, C.byref(v), C.byref(b), C.byref(s)))
+        return {"valid": bool(v.value), "bytes": b.value, "scale": s.value}
+
+    def sq8_drop(self):
+        """free the int8 code mirror (qk_store_sq8_drop); the next quantized search builds it again"""
+        check(self.lib.qk_store_sq8_drop(self.h))
 
     def exact_pool_info(self):
         """{slots, rows, cap_rows, builds, evictions, device_bytes} of the candidate pool of exact per-query search

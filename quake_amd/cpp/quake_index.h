@@ -61,6 +61,8 @@ double lower_maxsim(const std::vector<std::string> &columns, const std::string &
 float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult);
 // the arguments of funnel_search over vectors of d columns (where.py's lower_funnel: same rules, same errors, same order)
 void lower_funnel(int64_t d, int64_t k, int64_t prefix_dim, int64_t fetch_k);
+// the arguments of quantized_search over vectors of d columns (where.py's lower_sq8: same rules, same errors, same order)
+void lower_sq8(int64_t d, int64_t k, int64_t fetch_k);
 
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
@@ -142,6 +144,9 @@ public:
     // extension: funnel search -- rank the probed rows by their first prefix_dim columns, re-score the fetch_k best on the full vector,
     // return search_params->k of them under (exact distance, id) (qk_funnel_search)
     shared_ptr<SearchResult> funnel_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t prefix_dim, int64_t fetch_k);
+    // extension: quantized search -- rank the probed rows by an exact integer key over one int8 code per coordinate, re-score the
+    // fetch_k best on the float32 rows, return search_params->k of them under (exact distance, id) (qk_sq8_search)
+    shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

@@ -1118,6 +1118,63 @@ shared_ptr<SearchResult> QueryCoordinator::funnel_search(Tensor x, shared_ptr<Se
     return res;
 }
 
+shared_ptr<SearchResult> QueryCoordinator::quantized_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k) {
+    const std::string who = "[QuakeIndex::quantized_search()]";
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::quantized_search] partition_manager_ is null.");
+    if (sp->filter || !sp->filters.empty() || sp->query_filter.defined() || sp->filters_exact_rows != 0 || sp->filter_exact_rows != 0 ||
+        sp->max_nprobe > 0)
+        throw NotImplemented(who + " filters of any kind are not supported by quantized_search");
+    if (sp->recall_target > 0.0f) throw NotImplemented(who + " quantized_search is not supported with recall_target > 0");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group()) throw NotImplemented(who + " quantized_search is not supported with num_workers > 0");
+    if (!store) throw std::runtime_error("[QueryCoordinator::quantized_search] partitions are not initialized.");
+    if (!parent_) throw NotImplemented(who + " quantized_search is not supported by a flat index (no lists of its own)");
+    lower_sq8(partition_manager_->d(), sp->k, fetch_k);
+    const int64_t k = sp->k;
+    auto res = std::make_shared<SearchResult>();
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->search_params = sp;
+    ti->n_clusters = partition_manager_->nlist();
+    if (!x.defined() || x.size(0) == 0) {
+        res->ids = torch::zeros({0, k}, torch::kInt64);
+        res->distances = torch::zeros({0, k}, torch::kFloat32);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x);
+    BoundToTorchStream bound(ctx, xq);
+    const int64_t Q = xq.size(0);
+    const int nprobe = std::max(sp->nprobe, 1);
+    const int mem = on_dev ? QK_MEM_DEVICE : QK_MEM_HOST;
+    ti->n_queries = Q;
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
+    res->ids = torch::empty({Q, k}, i64);
+    res->distances = torch::empty({Q, k}, i64.dtype(torch::kFloat32));
+    qk_check(qk_sq8_search(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, (int)k, (int)fetch_k, (int)metric_,
+                              res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, &tm));
+    ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
+    ti->parent_info = std::make_shared<SearchTimingInfo>();
+    ti->parent_info->n_queries = Q;
+    ti->parent_info->n_clusters = 1;
+    ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
 shared_ptr<SearchResult> QueryCoordinator::scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> sp) {  // :659-673
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::scan_partitions] partition_manager_ is null.");
     if (!x.defined() || x.size(0) == 0) return empty_result(sp);

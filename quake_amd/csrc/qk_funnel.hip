@@ -105,18 +105,6 @@ int launch_scan_prefix(dim3 grid, dim3 block, size_t lds, hipStream_t st, const 
 }
 
 // ---- the exact finish -------------------------------------------------------------------------------------------------------------
-struct FunnelFinishParams {
-    const int64_t *cand;  // [Q][C] arena rows in (prefix key, row) order, -1 behind the candidates
-    const float4 *xq4;    // [Q][nblk][4] the FULL queries in B-operand order
-    const float *xn;      // [Q] their norms
-    const float4 *vecs;   // arena
-    const float *norms;
-    const int64_t *ids;
-    int nblk, C, k, metric, sqrt_l2;
-    int64_t *out_ids;  // [Q][k]
-    float *out_dist;   // [Q][k] or nullptr
-};
-
 constexpr int FN_U = 4;  // blocks per load group: two groups of 4 x 16 B per lane in flight
 
 // One workgroup of four waves per query.  A wave takes 16 candidates at a time and gathers them as the A operand of
@@ -216,7 +204,15 @@ int launch_finish(hipStream_t st, const FunnelFinishParams &fp, int64_t Q) {
     return QK_OK;
 }
 
-int fn_reserve(qk_ctx *ctx, size_t need) {
+}  // namespace
+
+int qk_launch_funnel_finish(hipStream_t st, const FunnelFinishParams &fp, int64_t Q) {
+    const int maxch = pick_maxch(fp.C);
+    return maxch == 1 ? launch_finish<1>(st, fp, Q) : maxch == 2 ? launch_finish<2>(st, fp, Q) : maxch == 4 ? launch_finish<4>(st, fp, Q)
+                                                                                                       : launch_finish<8>(st, fp, Q);
+}
+
+int qk_fn_reserve(qk_ctx *ctx, size_t need) {
     if (need <= ctx->fn_cap) return QK_OK;
     // (an earlier call's kernels may still read the old buffer: hipFree waits for the device)
     if (ctx->fn_buf) QK_HIP(hipFree(ctx->fn_buf));
@@ -231,6 +227,8 @@ int fn_reserve(qk_ctx *ctx, size_t need) {
     ctx->fn_cap = cap;
     return QK_OK;
 }
+
+namespace {
 
 // the body of both entry points: parent == nullptr && pids == nullptr -> every list
 int funnel_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
@@ -270,7 +268,7 @@ int funnel_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     const float *pnorms = s->norms;  // (IP: the key reads no norm; the scan's norm stream still needs memory to load from)
     if (l2) QK_TRY(qk_store_prefix_norms(ctx, s, prefix_dim, &pnorms));
     const size_t b_q = qk_al256((size_t)Q * nbp * 64), b_n = qk_al256((size_t)Q * 4), b_c = qk_al256((size_t)Q * C * 8);
-    QK_TRY(fn_reserve(ctx, b_q + b_n + b_c));
+    QK_TRY(qk_fn_reserve(ctx, b_q + b_n + b_c));
     float4 *xq4p = (float4 *)ctx->fn_buf;
     float *xnp = (float *)(ctx->fn_buf + b_q);
     int64_t *cand = (int64_t *)(ctx->fn_buf + b_q + b_n);
@@ -311,9 +309,7 @@ int funnel_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     fp.sqrt_l2 = ctx->squared_l2 ? 0 : 1;
     fp.out_ids = d_ids;
     fp.out_dist = d_dist;
-    const int maxch = pick_maxch(C);
-    QK_TRY(maxch == 1 ? launch_finish<1>(st, fp, Q) : maxch == 2 ? launch_finish<2>(st, fp, Q) : maxch == 4 ? launch_finish<4>(st, fp, Q)
-                                                                                                          : launch_finish<8>(st, fp, Q));
+    QK_TRY(qk_launch_funnel_finish(st, fp, Q));
     const bool tm = ctx->timing && timing;
     hipEvent_t tail_end = nullptr;
     if (tm) {

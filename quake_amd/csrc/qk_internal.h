@@ -304,7 +304,23 @@ struct qk_store {
     int64_t pnorms_cap_rows = 0;
     uint64_t pnorms_version = 0;
     int pnorms_dim = 0;  // 0: none
+    // quantized search (qk_sq8.hip): one int8 code per coordinate in the arena's tile indexing -- code row r is arena
+    // row r, a 1 KiB code block holds 64 columns of a tile -- and, for L2, every row's int32 code norm.  Built lazily by
+    // qk_store_sq8_mirror for one (version, metric) at a time, in full (the scale depends on every live row); not persisted
+    void *sq8_codes = nullptr;
+    int32_t *sq8_nx = nullptr;
+    float *sq8_m = nullptr;          // device [64 nblk8]: the centre of every column (L2; 0 for IP and in the padding)
+    uint32_t *sq8_stats = nullptr;   // device [2 * 64 nblk8 + 4]: what k_sq8_range reduces
+    int64_t sq8_cap_rows = 0;
+    uint64_t sq8_version = 0;
+    int sq8_metric = -1;  // -1: none
+    float sq8_scale = 1.0f;
 };
+inline int qk_sq8_nblk(int d) { return (d + 63) / 64; }
+// the code mirror of `s` (table synced) for `metric`, built on ctx's stream if the store or the metric changed.  QK_ERR_UNSUPPORTED
+// where a live row holds a non-finite value or the scale is not finite; QK_ERR_OOM, and nothing else changed, without memory
+int qk_store_sq8_mirror(qk_ctx *ctx, qk_store *s, int metric);
+void qk_store_sq8_free(qk_store *s);
 // the prefix norms of `s` (table synced) for prefix_dim, built on ctx's stream if the store or the dimension changed; QK_ERR_OOM and
 // nothing else changed where there is no memory for them
 int qk_store_prefix_norms(qk_ctx *ctx, qk_store *s, int prefix_dim, const float **out);
@@ -400,6 +416,12 @@ struct qk_scan_args {
     // out_ids receives ARENA ROWS, out_dist prefix keys.  Unseeded tile form only; no filter, cursor, per_pair or key emission
     int prefix_nblk = 0;
     const float *prefix_norms = nullptr;
+    // quantized search (qk_sq8.hip): sq8_nblk > 0 -> the scan streams the store's int8 code mirror, sq8_nblk blocks of 64 columns per
+    // tile (k_scan_sq8).  xq4 / xn are then the queries' codes ([Q][sq8_nblk][4] x 16 B) and their int32 code norms as bits, sq8_nx
+    // the rows'; out_ids receives ARENA ROWS.  Unseeded tile form only, as the prefix form
+    int sq8_nblk = 0;
+    const void *sq8_codes = nullptr;
+    const int32_t *sq8_nx = nullptr;
 };
 // filters (qk_filter.hip)
 struct qk_filter;

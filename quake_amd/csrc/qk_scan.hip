@@ -918,9 +918,12 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     // (a flat index with a filter takes the grouped scan below: the dense forms know nothing of masks)
     const bool one_list = a.all_lists && s->nlist == 1 && !emit && !filtered;
     // prefix form (qk_funnel.hip): the unseeded tile form over the first a.prefix_nblk blocks of every tile, nothing else
-    const bool prefix = a.prefix_nblk > 0;
-    if (prefix && (one_list || k > QK_MAX_K || emit || filtered || paged || a.per_pair || a.tau_init || a.prefix_nblk > s->nblk))
-        QK_FAIL(QK_ERR_UNSUPPORTED, "prefix scan: the tile form over several lists with k <= QK_MAX_K only");
+    // int8 code form (qk_sq8.hip): the same launch over the store's code mirror, a.sq8_nblk blocks of 64 columns per tile
+    const bool sq8 = a.sq8_nblk > 0;
+    const bool prefix = a.prefix_nblk > 0 || sq8;
+    if (prefix && (one_list || k > QK_MAX_K || emit || filtered || paged || a.per_pair || a.tau_init || a.prefix_nblk > s->nblk ||
+                   (sq8 && (a.prefix_nblk > 0 || !a.sq8_codes || !a.sq8_nx))))
+        QK_FAIL(QK_ERR_UNSUPPORTED, "prefix / int8 code scan: the tile form over several lists with k <= QK_MAX_K only");
     if (k > QK_MAX_K && !one_list) {
         if (a.per_pair) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: k=%d exceeds QK_MAX_K=%d", k, QK_MAX_K);
         QK_TRY(qk_prep_flush(ctx));
@@ -954,7 +957,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     // fp16 shadow form (qk_shadow.hip): the tile form's launch over the shadow -- blocks of 32 columns, records of k' entries that hold
     // approximate keys and arena rows -- and k_shadow_finish in the merge's place
     const bool shadow = plan.form == 3;
-    const int nblk_scan = prefix ? a.prefix_nblk : shadow ? qk_shadow_nblk(nblk) : nblk;  // 1 KiB blocks per tile of what the scan kernel streams
+    const int nblk_scan = sq8 ? a.sq8_nblk : prefix ? a.prefix_nblk : shadow ? qk_shadow_nblk(nblk) : nblk;  // 1 KiB blocks per tile of what the scan kernel streams
     const int k_rec = shadow ? QK_SHADOW_KP : k;                 // entries per record
     const size_t q_bytes = (size_t)nblk_scan * 1024;
     int DB = plan.DB;
@@ -1281,6 +1284,10 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             sp.nblk = nblk_scan;
             sp.norms = a.prefix_norms;
         }
+        if (sq8) {  // the code mirror in the arena's place, the rows' code norms in the norms' (a.xq4 / a.xn are the queries' codes and norms)
+            sp.vecs = (const float4 *)a.sq8_codes;
+            sp.norms = (const float *)a.sq8_nx;
+        }
         sp.k = k_rec;
         sp.C = C;
         sp.metric = a.metric;
@@ -1418,12 +1425,14 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
             QK_HIP(hipMemsetAsync(d_clock, 0, (size_t)grid * wpw * 64 * 2, st));
             sp.wave_clock = d_clock;
         }
-        ctx->last_scan_kernel = paged ? (wide ? "k_scan_wide (after)" : "k_scan (after)") : a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : shadow ? "k_scan (fp16 shadow)" : prefix ? "k_scan (prefix)" : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
+        ctx->last_scan_kernel = paged ? (wide ? "k_scan_wide (after)" : "k_scan (after)") : a.qmasks ? (wide ? "k_scan_wide (filtered, per query)" : "k_scan (filtered, per query)") : filtered ? (wide ? "k_scan_wide (filtered)" : "k_scan (filtered)") : shadow ? "k_scan (fp16 shadow)" : sq8 ? "k_scan (int8 codes)" : prefix ? "k_scan (prefix)" : wide ? "k_scan_wide" : use_rl ? (hot.min > 0 ? "k_scan_rl (mixed)" : "k_scan_rl") : qshare ? "k_scan (query-sharing)" : "k_scan";
         // (until qk_finish_timing fills it in, qk_timing::scan_bytes holds MINUS the bytes per row of the form that ran, or 0 = fp32
         //  rows: the call's own result, not context state -- a later call cannot inherit it --, and a negative value is no byte count,
         //  so finishing the same struct twice cannot multiply rows by a total)
         if (timing) timing->scan_bytes = (shadow || prefix) ? -(int64_t)nblk_scan * 64 : 0;
-        if (prefix)
+        if (sq8)
+            QK_TRY(qk_launch_scan_sq8(DB, maxch, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
+        else if (prefix)
             QK_TRY(qk_launch_scan_prefix(DB, maxch, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
         else if (shadow)
             QK_TRY(qk_launch_scan_shadow(DB, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));

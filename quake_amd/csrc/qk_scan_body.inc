@@ -18,6 +18,10 @@
 // QK_SCAN_PREFIX (with QK_SCAN_FILT 0) = k_scan_prefix (qk_funnel.hip), the prefix form: P.vecs is the arena, whose tiles lie
 // P.nblk_row blocks apart, and the walk takes the first P.nblk blocks of each; P.norms / P.xn are norms of the prefixes, P.xq4 the
 // queries' prefix; no ids are loaded (a candidate's "id" is its arena row).  Everything it changes sits behind #ifdef QK_SCAN_PREFIX.
+// QK_SCAN_SQ8 (with QK_SCAN_FILT 0) = k_scan_sq8 (qk_sq8.hip), the int8 code form: P.vecs is the code mirror of the arena (P.nblk
+// blocks of 64 columns per tile, 16 B per lane as before), P.xq4 the queries' codes in the same lane order, one
+// v_mfma_i32_16x16x64_i8 per block into an int32 accumulator; P.norms / P.xn carry the int32 code norms as bits (L2); no ids are
+// loaded (a candidate's "id" is its arena row); the key is an exact integer.  Everything it changes sits behind #ifdef QK_SCAN_SQ8.
 // Expects: template parameters DB, MAXCH, MODE, L2 and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     // nw waves per workgroup (1, 2 or 4) share ONE LDS query tile and split every segment's tiles between them; each
@@ -164,6 +168,9 @@
         int cnt = 0;
         dbg_seg++;
         float xnj = 0.0f;
+#ifdef QK_SCAN_SQ8
+        int nqj = 0;  // this lane's query's code norm (L2)
+#endif
 #ifdef QK_SCAN_SHADOW
         bool sh_dead = false;  // this lane's query takes no part (its bound is negative: the finish answers it exactly)
 #endif
@@ -246,7 +253,13 @@
 #endif
             float4 a0[DB], a1[DB];
             float4 y0 = make_float4(0.f, 0.f, 0.f, 0.f), y1 = y0;
+#ifdef QK_SCAN_SQ8
+#define QK_ACC_ZERO (qk_i32x4){0, 0, 0, 0}
+            qk_i32x4 acc = {0, 0, 0, 0};
+#else
+#define QK_ACC_ZERO (f32x4){0.f, 0.f, 0.f, 0.f}
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#endif
             float probe_sink = 0.f;
             int dch = 0;    // d-chunk of the step being computed
 #if QK_SCAN_FILT
@@ -281,7 +294,7 @@
             }                                                         \
         }                                                             \
     }
-#elif defined(QK_SCAN_SHADOW)
+#elif defined(QK_SCAN_SHADOW) || defined(QK_SCAN_SQ8)
 #define QK_EPI_M(Y)
 #define QK_NEXT_TILE tile++
 #define QK_LOAD(A, Y, I0, I1)                                         \
@@ -342,6 +355,8 @@
 
 #ifdef QK_SCAN_SHADOW
 #define QK_DOT(A_, B_) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(qk_as_h8(A_), qk_as_h8(B_), acc, 0, 0, 0);
+#elif defined(QK_SCAN_SQ8)
+#define QK_DOT(A_, B_) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(qk_as_i4(A_), qk_as_i4(B_), acc, 0, 0, 0);
 #else
 #define QK_DOT(A_, B_)                                                        \
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A_.x, B_.x, acc, 0, 0, 0);     \
@@ -351,7 +366,7 @@
 #endif
 #define QK_STEP(A, Y, I0, I1, LIVE)                                                                                    \
     {                                                                                                      \
-        if (dch == 0) acc = (f32x4){0.f, 0.f, 0.f, 0.f};                                                   \
+        if (dch == 0) acc = QK_ACC_ZERO;                                                                   \
         _Pragma("unroll") for (int b_ = 0; b_ < DB; b_++) {                                                \
             if (MODE == 2) {                                                                               \
                 acc[0] += A[b_].x;                                                                         \
@@ -381,7 +396,7 @@
 #endif
                 const int row0 = tl_ << 4;
                 const float yv[4] = {yn.x, yn.y, yn.z, yn.w};
-#if defined(QK_SCAN_SHADOW) || defined(QK_SCAN_PREFIX)
+#if defined(QK_SCAN_SHADOW) || defined(QK_SCAN_PREFIX) || defined(QK_SCAN_SQ8)
                 const int64_t row_abs_ = row_off + row0 + 4 * g;
                 const int64_t idv[4] = {row_abs_, row_abs_ + 1, row_abs_ + 2, row_abs_ + 3};
 #else
@@ -418,8 +433,13 @@
 #else
                     const bool valid = live && (myq >= 0) && (row < size_p);
 #endif
+#ifdef QK_SCAN_SQ8
+                    // the exact integer key: sum (cq - cx)^2 = nq + nx - 2 dot in [0, 2^31), or -dot moved into the unsigned range
+                    const uint32_t o = l2 ? (uint32_t)(nqj + __float_as_int(yv[reg]) - 2 * acc[reg]) : (uint32_t)(-acc[reg]) ^ 0x80000000u;
+#else
                     const float v = acc[reg];
                     const uint32_t o = l2 ? ord_from_l2(l2_expanded(xnj, yv[reg], v)) : ord_from_ip(v);
+#endif
 #ifdef QK_SCAN_AFTER
                     // a row at or before the cursor is no candidate: it never reaches a pool, so it never sets a bound either
                     const bool cand = valid && qk_behind_cursor(o, idv[reg], cur_key, cur_id);
@@ -482,6 +502,9 @@
                 const float4 *qsrc = P.xq4 + (int64_t)qsafe * nblk * 4 + g;
                 if (P.gtau) tau = ~__hip_atomic_load(&P.gtau[qsafe], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (l2) xnj = P.xn[qsafe];
+#ifdef QK_SCAN_SQ8
+                nqj = l2 && myq >= 0 ? __float_as_int(xnj) : 0;
+#endif
 #ifdef QK_SCAN_SHADOW
                 {  // the seed's exact bound, widened by what an approximate key may lie above its exact one
                     const float she_ = P.sh_E[qsafe];
@@ -525,6 +548,7 @@
 #undef QK_LOAD
 #undef QK_STEP
 #undef QK_DOT
+#undef QK_ACC_ZERO
 #undef QK_EPI_M
 #undef QK_NEXT_TILE
 #if QK_SCAN_FILT

@@ -114,7 +114,8 @@ static int qk_pick_form(qk_ctx *ctx, uint64_t key, int form_static, const bool a
 int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int k, int P, int64_t npairs, ScanPlan *pl) {
     const int64_t Q = a.Q;
     // ---- geometry ----------------------------------------------------------------------------------
-    const int nblk = a.prefix_nblk > 0 ? a.prefix_nblk : s->nblk;  // (prefix form, qk_funnel.hip: the geometry of the blocks it walks)
+    // (prefix form, qk_funnel.hip, and int8 code form, qk_sq8.hip: the geometry of the 1 KiB blocks they walk)
+    const int nblk = a.sq8_nblk > 0 ? a.sq8_nblk : a.prefix_nblk > 0 ? a.prefix_nblk : s->nblk;
     int DB = (nblk % 8 == 0) ? 8 : (nblk % 4 == 0) ? 4 : (nblk % 2 == 0) ? 2 : 1;
     // pool capacity per query: k + slack, limited by LDS (one wave per workgroup, 160 KiB max)
     const size_t lds_budget = 160 * 1024 - 64;
@@ -129,7 +130,7 @@ int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int
         // the query tile and the pools do not fit side by side: k_scan_wide (qk_scan_wide.hip) keeps only the pools in LDS and
         // reads the queries from global memory.  The one form of these shapes -- no form feedback.
         if (s->d > QK_MAX_D) QK_FAIL(QK_ERR_UNSUPPORTED, "qk_scan: d=%d exceeds QK_MAX_D=%d", s->d, QK_MAX_D);
-        if (a.prefix_nblk > 0) QK_FAIL(QK_ERR_UNSUPPORTED, "prefix scan: the prefix query tile and the pools of k=%d do not fit the LDS", k);
+        if (a.prefix_nblk > 0 || a.sq8_nblk > 0) QK_FAIL(QK_ERR_UNSUPPORTED, "prefix / int8 code scan: the query tile and the pools of k=%d do not fit the LDS", k);
         C = qk_round_up(k + std::max(slack_min, std::min(k, QK_SLACK_CAP)), 4);
         while ((size_t)16 * C * 12 > lds_budget && C > k + 4) C -= 4;
         if ((size_t)16 * C * 12 > lds_budget || C < k + 4 || C > 512)
@@ -168,8 +169,8 @@ int qk_scan_plan(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, bool emit, int
             if ((w == 1 || w == 2 || w == 4) && waves_for(w, C) > 0) nw = w;
         }
     }
-    if (a.mask || a.prefix_nblk > 0) {
-        // (prefix form: as below -- the tile form with one query tile per workgroup; the static rule, its labels and the form feedback
+    if (a.mask || a.prefix_nblk > 0 || a.sq8_nblk > 0) {
+        // (prefix and int8 code forms: as below -- the tile form with one query tile per workgroup; the static rule, its labels and the form feedback
         //  are neither consulted nor fed)
         // filtered call: the tile form with one query tile per workgroup (k_scan_filt), nothing else.  The query-sharing, per-wave,
         // mixed and hot forms either learn bounds from rows they have not tested against the mask (bf16 prefilter) or have no

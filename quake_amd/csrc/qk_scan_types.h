@@ -273,4 +273,22 @@ int qk_launch_shadow_convert(hipStream_t st, const float4 *vecs, int nblk, const
                              uint32_t *stats);
 // prefix form (qk_funnel.hip): the tile form over the first sp.nblk blocks of every tile, launched like k_scan
 int qk_launch_scan_prefix(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
+// the exact finish of funnel search (k_funnel_finish, qk_funnel.hip), shared with quantized search (qk_sq8.hip): the candidates'
+// canonical fp32 keys by a gathered MFMA, the k best under (exact key, id)
+struct FunnelFinishParams {
+    const int64_t *cand;  // [Q][C] arena rows in (approximate key, row) order, -1 behind the candidates
+    const float4 *xq4;    // [Q][nblk][4] the FULL queries in B-operand order
+    const float *xn;      // [Q] their norms
+    const float4 *vecs;   // arena
+    const float *norms;
+    const int64_t *ids;
+    int nblk, C, k, metric, sqrt_l2;
+    int64_t *out_ids;  // [Q][k]
+    float *out_dist;   // [Q][k] or nullptr
+};
+int qk_launch_funnel_finish(hipStream_t st, const FunnelFinishParams &fp, int64_t Q);
+// the context's buffer for a call's approximate queries and candidates (ctx->fn_buf), grown to `need` bytes
+int qk_fn_reserve(qk_ctx *ctx, size_t need);
+// int8 code form (qk_sq8.hip): the tile form over the code mirror, sp.nblk blocks of 64 columns per tile, launched like k_scan
+int qk_launch_scan_sq8(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
 int qk_launch_next_cursor(qk_ctx *ctx, const MergeParams &mp, int64_t Q, const int64_t *out_ids, uint32_t *next_key, int64_t *next_id);

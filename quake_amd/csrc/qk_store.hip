@@ -204,6 +204,7 @@ int qk_store_sync_table(qk_store *s) {
     s->rowmajor_valid = false;
     s->shadow_valid = false;  // (the fp16 shadow mirrors one version; it is rebuilt once the store has been stable again)
     s->pnorms_dim = 0;        // (so do the prefix norms of funnel search: the next L2 funnel call rebuilds them)
+    s->sq8_metric = -1;       // (and the int8 codes of quantized search: the scale depends on every live row)
     qk_ctx *c = s->ctx;
     int64_t n = (int64_t)s->parts.size();
     if (n > s->table_cap) {
@@ -679,6 +680,7 @@ int qk_store_destroy(qk_store *s) {
     hipDeviceSynchronize();  // (as above: another context's search may still read the shadow)
     qk_store_shadow_free(s);
     qk_store_prefix_free(s);
+    qk_store_sq8_free(s);
     if (s->shadow_stats) hipFree(s->shadow_stats);
     delete s;
     return QK_OK;
@@ -1351,7 +1353,8 @@ int qk_store_counters(qk_store *s, int64_t *out, int n) {
 int64_t qk_store_device_bytes(qk_store *s) {
     if (!s) return 0;
     return s->cap_rows * ((int64_t)s->dpad * 4 + 4 + 8) + (s->shadow ? s->shadow_cap_rows * (int64_t)qk_shadow_nblk(s->nblk) * 64 : 0) +
-           (s->pnorms ? s->pnorms_cap_rows * 4 : 0);  // (+ the prefix norms of funnel search, qk_funnel.hip)
+           (s->pnorms ? s->pnorms_cap_rows * 4 : 0) +  // (+ the prefix norms of funnel search, qk_funnel.hip)
+           (s->sq8_codes ? s->sq8_cap_rows * ((int64_t)qk_sq8_nblk(s->d) * 64 + 4) : 0);  // (+ the int8 codes of quantized search, qk_sq8.hip)
 }
 
 int qk_store_shadow_info(qk_store *s, int *valid, int64_t *bytes, int64_t *builds) {

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order
+from .where import lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_sq8
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -1577,6 +1577,62 @@ class QuakeIndex:
         self._ctx.set_timing(1)
         try:
             out = self._ctx.funnel_search(self.parent._store, self._store, xd, nprobe, k, fetch_k, prefix_dim, self.metric_, timing=True)
+        finally:
+            self._ctx.set_timing(0)
+        tm = out[2]
+        ti.n_queries = nq
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.job_enqueue_time_ns = int(tm["group_ms"] * 1e6)
+        pi = SearchTimingInfo()
+        pi.n_queries = nq
+        pi.n_clusters = 1
+        pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
+        ti.parent_info = pi
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.ids, res.distances = (o if on_dev else o.cpu() for o in out[:2])
+        return res
+
+    def quantized_search(self, x, search_params, fetch_k):
+        """extension (no reference counterpart): quantized search, scalar quantization with oversampling and rescoring -- the rows
+        of each query's probed lists (chosen as search() chooses them, by the float32 query) are ranked by an exact integer key over
+        one int8 code per coordinate, a quarter of the bytes search() reads; the fetch_k best of them are re-scored on the float32
+        rows, and search_params.k of those are returned under (exact distance, id), with the distances search() reports.
+        Approximate by design, defined bit for bit (include/quake_hip.h, "quantized search"): a fetch_k that covers the probed rows
+        is search().  1 <= k <= fetch_k <= 448, d <= 2048; the codes (64 ceil(d / 64) + 4 bytes per row) are rebuilt by the first
+        call after the index changed.  Filters, recall_target, num_workers > 0 and a flat index are not served
+        (NotImplementedError); a stored value that is not finite is a RuntimeError.  Returns a SearchResult on x's device."""
+        who = "[QuakeIndex::quantized_search()]"
+        self._require_built(who + " No query coordinator. Did you build the index?")
+        sp = search_params
+        if (getattr(sp, "filter", None) is not None or (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None
+                or int(getattr(sp, "filters_exact_rows", 0) or 0) != 0 or int(getattr(sp, "filter_exact_rows", 0) or 0) != 0
+                or int(getattr(sp, "max_nprobe", 0) or 0) > 0):
+            raise NotImplementedError(who + " filters of any kind are not supported by quantized_search")
+        if sp.recall_target is not None and sp.recall_target > 0.0:
+            raise NotImplementedError(who + " quantized_search is not supported with recall_target > 0")
+        if isinstance(self._store, capi.Group):
+            raise NotImplementedError(who + " quantized_search is not supported with num_workers > 0")
+        if self.parent is None:
+            raise NotImplementedError(who + " quantized_search is not supported by a flat index (no lists of its own)")
+        k, fetch_k = lower_sq8(int(self._d), sp.k, fetch_k, who)
+        res = SearchResult()
+        ti = SearchTimingInfo()
+        ti.search_params = sp
+        ti.n_clusters = self.nlist()
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        nq = 0 if x is None else int(x.shape[0])
+        if nq == 0:
+            res.ids = torch.zeros((0, k), dtype=torch.int64)
+            res.distances = torch.zeros((0, k), dtype=torch.float32)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        nprobe = max(int(sp.nprobe), 1)
+        self._ctx.set_timing(1)
+        try:
+            out = self._ctx.sq8_search(self.parent._store, self._store, xd, nprobe, k, fetch_k, self.metric_, timing=True)
         finally:
             self._ctx.set_timing(0)
         tm = out[2]

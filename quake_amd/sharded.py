@@ -293,6 +293,11 @@ class ShardedIndex:
         best prefix keys, not the index's."""
         raise NotImplementedError("[ShardedIndex::funnel_search()] funnel_search is not supported by sharded.py")
 
+    def quantized_search(self, q, nprobe, k, fetch_k):
+        """quantized search (QuakeIndex.quantized_search, qk_sq8_search) has no sharded form: a shard's codes use its own scale, and
+        its candidates are its own fetch_k best, not the index's."""
+        raise NotImplementedError("[ShardedIndex::quantized_search()] quantized_search is not supported by sharded.py")
+
     def diverse_search(self, q, nprobe, k, fetch_k, lambda_mult=0.5):
         """diversified search (QuakeIndex.diverse_search, qk_diverse_search) has no sharded form: the re-ranking needs the vectors
         of every candidate of a query, which live on different ranks"""

@@ -6,7 +6,7 @@ Python integers of any size and are saturated, not wrapped: a comparison with a 
 integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
 lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search), lower_order
-the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_funnel those of funnel search (QuakeIndex.funnel_search), lower_maxsim those of multi-vector search
+the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_funnel those of funnel search (QuakeIndex.funnel_search), lower_sq8 those of quantized search (QuakeIndex.quantized_search), lower_maxsim those of multi-vector search
 (QuakeIndex.multi_vector_search).
 Pure Python: importable without the library or a GPU."""
 
@@ -27,6 +27,7 @@ MISSING = ("exclude", "last")
 QK_MAX_FETCH_K = 256
 QK_MAX_K = 448
 QK_FUNNEL_MAX_PREFIX = 1024
+QK_SQ8_MAX_D = 2048
 QK_MAXSIM_MAX_TOKENS, QK_MAXSIM_MAX_K = 64, 1024
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
@@ -271,6 +272,23 @@ def lower_funnel(d, k, prefix_dim, fetch_k, who="[QuakeIndex::funnel_search()]")
     if fetch_k > QK_MAX_K:
         raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_MAX_K))
     return k, prefix_dim, fetch_k
+
+
+def lower_sq8(d, k, fetch_k, who="[QuakeIndex::quantized_search()]"):
+    """The arguments of quantized search (include/quake_hip.h, "quantized search") over vectors of d columns -> (k, fetch_k):
+    1 <= k <= fetch_k <= QK_MAX_K, d <= QK_SQ8_MAX_D.  RuntimeError, in this order: a value that is no integer, k < 1, fetch_k < k,
+    fetch_k above its limit, d above its limit."""
+    k = _int(k, who + " k:")
+    fetch_k = _int(fetch_k, who + " fetch_k:")
+    if k < 1:
+        raise RuntimeError("%s k=%d must be at least 1" % (who, k))
+    if fetch_k < k:
+        raise RuntimeError("%s fetch_k=%d must be at least k=%d" % (who, fetch_k, k))
+    if fetch_k > QK_MAX_K:
+        raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_MAX_K))
+    if d > QK_SQ8_MAX_D:
+        raise RuntimeError("%s d=%d must not exceed %d" % (who, d, QK_SQ8_MAX_D))
+    return k, fetch_k
 
 
 def lower_maxsim(columns, group_by, k, T, n_tokens=None, missing=None, metric="ip", who="[QuakeIndex::multi_vector_search()]"):
