@@ -855,6 +855,51 @@ QK_API int qk_maxsim_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t L, i
                           int64_t *out_groups, float *out_scores, int32_t *out_matched, int64_t *out_n_groups, int64_t *out_hits,
                           int mem, qk_timing *timing);
 
+/* ---- multi-vector rerank ------------------------------------------------------------------------------
+ * No reference counterpart.  The exact stage behind multi-vector search: for a shortlist of candidate values per logical query,
+ * every participating sub-query is compared with EVERY row of the document and the sum of the per-token best ranks the shortlist
+ * (the last stage of ColBERT / ColPali / PLAID).  No parent and no nprobe take part, so a flat index is served; d up to QK_MAX_D.
+ * x, T, n_tokens, missing: as for qk_maxsim_search.
+ * Document: D(g) = the live arena rows whose id has the value g in group_by when the call runs (the per-row values grouped search
+ * keeps; liveness as for facets); with a filter only the rows it accepts.
+ * Pair key: key(l, t, row) = the uint32 search key qk_search computes for sub-query l * T + t and that row -- the canonical chain,
+ * the stored norms, the expanded L2 form with its clamp, the key maps of DESIGN 5.8.1.  A NaN pair never takes part.
+ * best(l, t, g) = the smallest key over D(g); term(l, t, g) = the float32 distance reported for it (sqrtf for L2 unless
+ * qk_ctx_set_squared_l2, the product for IP), `missing` where no pair of (t, D(g)) is a number.
+ * Score, order, ties, padding: word for word those of qk_maxsim_search.
+ * Candidates of l: cand[l][0 .. n_cand[l]), int64 [L][C] in `mem`; n_cand: int32 [L] in `mem` or NULL meaning C for every l (a host
+ * value outside [0, C] is QK_ERR_INVALID, a device value is clamped).  A value named twice counts once.  Every int64 is legal.  A
+ * value whose document has no row -- or no row with a non-NaN pair for a participating sub-query -- is not a candidate and is
+ * never returned.
+ * 0 <= C <= QK_MAXSIM_RERANK_MAX_CAND (stage one's largest k feeds it), 1 <= k; entries behind min(k, n_groups[l]) are padding.
+ * Returned:
+ *   out_groups, out_scores, out_matched   [L][k]   as qk_maxsim_search (matched: the sub-queries with a non-NaN pair)
+ *   out_rows      [L][k]   int32, may be NULL   |D(g)|; padding 0
+ *   out_n_groups  [L]      int64, may be NULL   the distinct candidates returned or cut off by k
+ * The identity that defines the call: the result equals that of qk_maxsim_scan over every list of the store with radius +inf (L2) /
+ * -inf (IP), the same `missing` and filter, restricted to the candidate values -- bit for bit, matched included -- and row l equals
+ * the call made with logical query l alone.
+ * There is no form for the device group.
+ * Inside (qk_rerank.hip), per group of at most 2^22 / C logical queries: k_rerank_insert (the distinct candidate values claim
+ * slots of one open-addressing table, atomicCAS: a document is its slot), k_rerank_count / k_rerank_offsets / k_rerank_fill (one sweep
+ * over the row values of the live rows, list by list, filter mask first; an exclusive scan; the same sweep writes every document's
+ * rows into its segment), k_rerank_score (work item = logical query x slice of its candidates; the tokens staged in LDS in B-operand
+ * order; a wave gathers 16 rows of a document as the A operand of v_mfma_f32_16x16x4_f32 straight from the tile-major arena and
+ * issues it once per 16-token column tile, the running minima of the ordered keys staying in registers; documents of more than 512
+ * rows are split over the workgroup's waves and joined by atomicMin in LDS; tokens wider than 64 KiB are walked in chunks of d with
+ * the accumulators live) and k_rerank_select (the <= 1024 records of a logical query sorted in LDS under qk_maxsim_search's order).
+ * No kernel waits or spins.  The host waits ONCE per group, for the 8 bytes that size the buffer of document rows.  Without memory:
+ * QK_ERR_OOM and nothing else changed.
+ * timing: scan_ms = the sweep (table clear, insert, count, offsets, fill), merge_ms = score + select, scan_bytes = the gathered row
+ * bytes, n_items = the groups of the call.  A call of one group -- L * C <= 2^22 -- reports exactly that.  With several groups only
+ * two marks separate the phases: merge_ms is the LAST group's score + select and scan_ms covers everything in front of it, the
+ * earlier groups' score + select included; total_ms is right either way. */
+#define QK_MAXSIM_RERANK_MAX_CAND 1024
+QK_API int qk_maxsim_rerank(qk_ctx *ctx, qk_store *s, const float *x, int64_t L, int T, const int32_t *n_tokens, int metric,
+                            qk_filter *filter, qk_attr *group_by, float missing, const int64_t *cand, const int32_t *n_cand, int C, int k,
+                            int64_t *out_groups, float *out_scores, int32_t *out_matched, int32_t *out_rows, int64_t *out_n_groups,
+                            int mem, qk_timing *timing);
+
 /* ---- diversified search ------------------------------------------------------------------------------
  * No reference counterpart.  Maximal marginal relevance (MMR): of the fetch_k nearest rows of a query keep k, chosen greedily -- each
  * step takes the candidate that is close to the query and far from everything already taken (the near-duplicate chunks of a

@@ -154,6 +154,10 @@ SIGNATURES = {
                          [_int, C.POINTER(QkTiming)]),
     "qk_maxsim_scan": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _int, _int, C.c_float, _vp, _vp, C.c_float, _int] + [_vp] * 5 +
                        [_int, C.POINTER(QkTiming)]),
+    # multi-vector rerank: (ctx, s, x, L, T, n_tokens, metric, filter, group_by, missing, cand, n_cand, C, k, groups, scores, matched, rows,
+    # n_groups, mem, timing)
+    "qk_maxsim_rerank": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _int, _vp, _vp, C.c_float, _vp, _vp, _int, _int] + [_vp] * 5 +
+                         [_int, C.POINTER(QkTiming)]),
     # diversified search: (.., k, fetch_k, lambda, metric, filter, ids, dist, rank, mem, timing)
     "qk_diverse_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, C.c_float, _int, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_diverse_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, C.c_float, _int, _vp, _vp, _vp, _vp, _int, C.POINTER(QkTiming)]),

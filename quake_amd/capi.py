@@ -115,6 +115,7 @@ QK_FUNNEL_MAX_PREFIX = 1024  # funnel search
 QK_SQ8_MAX_D = 2048        # quantized search
 QK_MAXSIM_MAX_TOKENS = 64  # multi-vector search
 QK_MAXSIM_MAX_K = 1024
+QK_MAXSIM_RERANK_MAX_CAND = 1024  # multi-vector rerank
 
 
 def timing_dict(t):
@@ -731,6 +732,36 @@ class Context:
                                       int(pids.shape[1]), metric_code(metric), float(radius), filter.h if filter is not None else None,
                                       group_by.h if group_by is not None else None, float(missing), k, *[_ptr(o) for o in out], mem,
                                       C.byref(t) if timing else None))
+        return (*out, timing_dict(t)) if timing else tuple(out)
+
+    def maxsim_rerank(self, store, x, metric, group_by, candidates, k, missing=0.0, n_tokens=None, n_candidates=None, filter=None,
+                      timing=False):
+        """qk_maxsim_rerank: the exact stage of multi-vector search.  x [L, T, d]; candidates [L, C] int64 values of the Attr column
+        `group_by` (n_candidates [L]: only the first n_candidates[l] count); per logical query the k best candidates by the sum over
+        the sub-queries of the best pair among ALL live rows of the value's document.  Returns (groups [L, k] padded with 0, scores
+        [L, k] padded as search pads, matched [L, k] int32, rows [L, k] int32, n_groups [L][, timing]) on x's device."""
+        if x.ndim != 3:
+            raise ValueError("multi-vector queries are [L, T, d], got %d dimensions" % x.ndim)
+        L, T = int(x.shape[0]), int(x.shape[1])
+        xf = _f32(x).reshape(L * T, x.shape[2])
+        cand = _i64(candidates)
+        if cand.ndim != 2 or cand.shape[0] != L:
+            raise ValueError("candidates are [L, C], got %s for %d logical queries" % (tuple(cand.shape), L))
+        Cn = int(cand.shape[1])
+        nt = _i32_with(n_tokens, xf) if n_tokens is not None else None
+        nc = _i32_with(n_candidates, xf) if n_candidates is not None else None
+        for name, a in (("n_tokens", nt), ("n_candidates", nc)):
+            if a is not None and a.shape[0] != L:
+                raise ValueError("%s has %d entries for %d logical queries" % (name, a.shape[0], L))
+        k = int(k)
+        kk = max(k, 1)  # (the library refuses k < 1 before it writes: the buffers of such a call only have to exist)
+        out = [_empty_like_mem((L, kk), np.int64, xf), _empty_like_mem((L, kk), np.float32, xf), _empty_like_mem((L, kk), np.int32, xf),
+               _empty_like_mem((L, kk), np.int32, xf), _empty_like_mem((L,), np.int64, xf)]
+        mem = _mem_of(xf, cand)
+        t = QkTiming()
+        check(self.lib.qk_maxsim_rerank(self.h, store.h, _ptr(xf), L, T, _ptr(nt), metric_code(metric), filter.h if filter is not None else None,
+                                        group_by.h if group_by is not None else None, float(missing), _ptr(cand) if Cn > 0 else None,
+                                        _ptr(nc), Cn, k, *[_ptr(o) for o in out], mem, C.byref(t) if timing else None))
         return (*out, timing_dict(t)) if timing else tuple(out)
 
     # ---- diversified search ------------------------------------------------------------------------------

@@ -201,6 +201,24 @@ PYBIND11_MODULE(_bindings, m) {
           py::arg("columns"), py::arg("group_by"), py::arg("k"), py::arg("T"), py::arg("n_tokens") = py::none(), py::arg("missing") = py::none(),
           py::arg("metric") = "ip",
           "the arguments of multi_vector_search -> (column name, k, T, n_tokens, missing); needs no device (where.py's lower_maxsim)");
+    m.def("lower_rerank",
+          [](const std::vector<std::string> &columns, const std::string &group_by, int64_t k, int64_t T, py::object n_tokens, py::object missing,
+             const std::string &metric, int64_t C, py::object n_candidates) {
+              std::optional<std::vector<int64_t>> nt, nc;
+              if (!n_tokens.is_none()) nt = n_tokens.cast<std::vector<int64_t>>();
+              if (!n_candidates.is_none()) nc = n_candidates.cast<std::vector<int64_t>>();
+              std::optional<double> ms;
+              if (!missing.is_none()) ms = missing.cast<double>();
+              std::string m = metric;
+              std::transform(m.begin(), m.end(), m.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
+              const double mv = lower_rerank(columns, group_by, k, T, nt, ms, m == "ip", C, nc);
+              return py::make_tuple(group_by, k, T, nt ? py::object(py::cast(*nt)) : py::object(py::none()), mv,
+                                    nc ? py::object(py::cast(*nc)) : py::object(py::none()));
+          },
+          py::arg("columns"), py::arg("group_by"), py::arg("k"), py::arg("T"), py::arg("n_tokens") = py::none(), py::arg("missing") = py::none(),
+          py::arg("metric") = "ip", py::arg("C") = 0, py::arg("n_candidates") = py::none(),
+          "the arguments of multi_vector_rerank -> (column name, k, T, n_tokens, missing, n_candidates); needs no device (where.py's "
+          "lower_rerank)");
     m.def("lower_diverse",
           [](int64_t k, int64_t fetch_k, double lambda_mult) {
               const float lambda = lower_diverse(k, fetch_k, lambda_mult);
@@ -321,7 +339,7 @@ PYBIND11_MODULE(_bindings, m) {
              "'exclude' or 'last'")
         .def("multi_vector_search",
              [](QuakeIndex &self, Tensor x, const std::string &group_by, shared_ptr<SearchParams> sp, py::object radius, py::object n_tokens,
-                py::object missing) {
+                py::object missing, py::object fetch_k) {
                  std::optional<float> r;
                  if (!radius.is_none()) r = radius.cast<float>();
                  std::optional<std::vector<int64_t>> nt;
@@ -331,14 +349,35 @@ PYBIND11_MODULE(_bindings, m) {
                  }
                  std::optional<double> ms;
                  if (!missing.is_none()) ms = missing.cast<double>();
-                 return self.multi_vector_search(x, group_by, sp, r, nt, ms);
+                 std::optional<int64_t> fk;
+                 if (!fetch_k.is_none()) fk = fetch_k.cast<int64_t>();
+                 return self.multi_vector_search(x, group_by, sp, r, nt, ms, fk);
              },
              py::arg("x"), py::arg("group_by"), py::arg("search_params"), py::arg("radius") = py::none(), py::arg("n_tokens") = py::none(),
-             py::arg("missing") = py::none(),
+             py::arg("missing") = py::none(), py::arg("fetch_k") = py::none(),
              "extension: multi-vector (late interaction) search -- x [L, T, d]; per logical query the search_params.k best values of the "
              "attribute column `group_by` by the sum over the query's vectors of the best vector range_search returns among the value's "
              "vectors; n_tokens [L]: the vectors of each query that take part; missing: the term of a vector without a match (None: 0 "
              "for the inner product)")
+        .def("multi_vector_rerank",
+             [](QuakeIndex &self, Tensor x, const std::string &group_by, Tensor candidates, int64_t k, py::object n_tokens, py::object missing,
+                py::object n_candidates, shared_ptr<SearchFilter> filter) {
+                 auto ints = [](py::object o) {
+                     std::optional<std::vector<int64_t>> v;
+                     if (!o.is_none()) {
+                         if (py::hasattr(o, "tolist")) o = o.attr("reshape")(-1).attr("tolist")();
+                         v = o.cast<std::vector<int64_t>>();
+                     }
+                     return v;
+                 };
+                 std::optional<double> ms;
+                 if (!missing.is_none()) ms = missing.cast<double>();
+                 return self.multi_vector_rerank(x, group_by, candidates, k, ints(n_tokens), ms, ints(n_candidates), filter);
+             },
+             py::arg("x"), py::arg("group_by"), py::arg("candidates"), py::arg("k"), py::arg("n_tokens") = py::none(),
+             py::arg("missing") = py::none(), py::arg("n_candidates") = py::none(), py::arg("filter") = nullptr,
+             "extension: the exact stage of multi-vector search -- candidates [L, C] int64 values of `group_by`; every query vector "
+             "against every vector of a candidate's document, the k best candidates; multi_vector_search(fetch_k=) runs both stages")
         .def("funnel_search", &QuakeIndex::funnel_search, py::arg("x"), py::arg("search_params"), py::arg("prefix_dim"), py::arg("fetch_k"),
              "extension: rank the probed rows by their first prefix_dim columns, re-score the fetch_k best on the full vector")
         .def("quantized_search", &QuakeIndex::quantized_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
@@ -602,6 +641,9 @@ PYBIND11_MODULE(_bindings, m) {
         .def_readwrite("matched", &MultiVectorSearchResult::matched)
         .def_readwrite("n_groups", &MultiVectorSearchResult::n_groups)
         .def_readwrite("hits", &MultiVectorSearchResult::hits)
+        .def_property_readonly("rows", [](const MultiVectorSearchResult &r) -> py::object {
+            return r.rows.defined() ? py::cast(r.rows) : py::none();
+        })
         .def_readwrite("column", &MultiVectorSearchResult::column)
         .def_readwrite("timing_info", &MultiVectorSearchResult::timing_info);
     py::class_<OrderedSearchResult, std::shared_ptr<OrderedSearchResult>>(m, "OrderedSearchResult")

@@ -227,6 +227,7 @@ struct MultiVectorSearchResult {
     Tensor matched;
     Tensor n_groups;
     Tensor hits;
+    Tensor rows;  // multi_vector_rerank and multi_vector_search with fetch_k: the documents' row counts [L, k] int32; hits undefined
     std::string column;
     shared_ptr<SearchTimingInfo> timing_info;
 };

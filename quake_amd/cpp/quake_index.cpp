@@ -247,7 +247,7 @@ double lower_maxsim(const std::vector<std::string> &columns, const std::string &
 shared_ptr<MultiVectorSearchResult> QuakeIndex::multi_vector_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> sp,
                                                                     std::optional<float> radius,
                                                                     const std::optional<std::vector<int64_t>> &n_tokens,
-                                                                    std::optional<double> missing) {
+                                                                    std::optional<double> missing, std::optional<int64_t> fetch_k) {
     if (!query_coordinator_)
         throw std::runtime_error("[QuakeIndex::multi_vector_search()] No query coordinator. Did you build the index?");
     std::vector<std::string> known;
@@ -257,7 +257,47 @@ shared_ptr<MultiVectorSearchResult> QuakeIndex::multi_vector_search(Tensor x, co
             known.push_back(kv.first);
             if (kv.first == group_by) col = kv.second;
         }
-    return query_coordinator_->multi_vector_search(x, col, known, group_by, sp, radius, n_tokens, missing);
+    return query_coordinator_->multi_vector_search(x, col, known, group_by, sp, radius, n_tokens, missing, fetch_k);
+}
+
+double lower_rerank(const std::vector<std::string> &columns, const std::string &group_by, int64_t k, int64_t T,
+                    const std::optional<std::vector<int64_t>> &n_tokens, std::optional<double> missing, bool is_ip, int64_t C,
+                    const std::optional<std::vector<int64_t>> &n_candidates) {
+    const std::string who = "[QuakeIndex::multi_vector_rerank()]";
+    if (k < 1) throw std::runtime_error(who + " k=" + std::to_string(k) + " must be at least 1");
+    double mv = 0.0;
+    try {
+        mv = lower_maxsim(columns, group_by, 1, T, n_tokens, missing, is_ip);
+    } catch (const std::runtime_error &e) {  // (the same rules under this call's name)
+        const std::string was = "[QuakeIndex::multi_vector_search()]", msg = e.what();
+        throw std::runtime_error(msg.compare(0, was.size(), was) == 0 ? who + msg.substr(was.size()) : msg);
+    }
+    if (C < 0 || C > QK_MAXSIM_RERANK_MAX_CAND)
+        throw std::runtime_error(who + " C=" + std::to_string(C) + " candidates per query must be between 0 and " +
+                                 std::to_string(QK_MAXSIM_RERANK_MAX_CAND));
+    if (n_candidates)
+        for (size_t i = 0; i < n_candidates->size(); i++)
+            if ((*n_candidates)[i] < 0 || (*n_candidates)[i] > C)
+                throw std::runtime_error(who + " n_candidates[" + std::to_string(i) + "]=" + std::to_string((*n_candidates)[i]) +
+                                         " must be between 0 and C=" + std::to_string(C));
+    return mv;
+}
+
+shared_ptr<MultiVectorSearchResult> QuakeIndex::multi_vector_rerank(Tensor x, const std::string &group_by, Tensor candidates, int64_t k,
+                                                                    const std::optional<std::vector<int64_t>> &n_tokens,
+                                                                    std::optional<double> missing,
+                                                                    const std::optional<std::vector<int64_t>> &n_candidates,
+                                                                    shared_ptr<SearchFilter> filter) {
+    if (!query_coordinator_)
+        throw std::runtime_error("[QuakeIndex::multi_vector_rerank()] No query coordinator. Did you build the index?");
+    std::vector<std::string> known;
+    qk_attr *col = nullptr;
+    if (partition_manager_ && partition_manager_->has_lists() && partition_manager_->store() && partition_manager_->store() == attrs_store_)
+        for (const auto &kv : attrs_) {
+            known.push_back(kv.first);
+            if (kv.first == group_by) col = kv.second;
+        }
+    return query_coordinator_->multi_vector_rerank(x, col, known, group_by, candidates, k, n_tokens, missing, n_candidates, filter);
 }
 
 float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult) {

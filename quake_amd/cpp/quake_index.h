@@ -56,6 +56,13 @@ int lower_order(const std::vector<std::string> &columns, const std::string &orde
 double lower_maxsim(const std::vector<std::string> &columns, const std::string &group_by, int64_t k, int64_t T,
                     const std::optional<std::vector<int64_t>> &n_tokens, std::optional<double> missing, bool is_ip);
 
+// the arguments of multi_vector_rerank (where.py's lower_rerank: same rules, same errors, same order): k < 1, then lower_maxsim's
+// rules for the column, T, n_tokens and missing, then C outside 0 .. QK_MAXSIM_RERANK_MAX_CAND, an n_candidates entry outside [0, C]
+// -> missing
+double lower_rerank(const std::vector<std::string> &columns, const std::string &group_by, int64_t k, int64_t T,
+                    const std::optional<std::vector<int64_t>> &n_tokens, std::optional<double> missing, bool is_ip, int64_t C,
+                    const std::optional<std::vector<int64_t>> &n_candidates);
+
 // the arguments of diverse_search (where.py's lower_diverse: same rules, same errors as std::runtime_error, in the same order):
 // k < 1, fetch_k < k, fetch_k > QK_MAX_FETCH_K, a lambda_mult that is NaN or outside [0, 1] -> lambda_mult rounded to float32
 float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult);
@@ -137,7 +144,15 @@ public:
     shared_ptr<MultiVectorSearchResult> multi_vector_search(Tensor x, const std::string &group_by, shared_ptr<SearchParams> search_params,
                                                             std::optional<float> radius = std::nullopt,
                                                             const std::optional<std::vector<int64_t>> &n_tokens = std::nullopt,
-                                                            std::optional<double> missing = std::nullopt);
+                                                            std::optional<double> missing = std::nullopt,
+                                                            std::optional<int64_t> fetch_k = std::nullopt);
+    // extension: multi-vector rerank, the exact stage -- candidates [L, C] int64 values of `group_by`; every query vector against
+    // every vector of a candidate's document, the k best candidates (qk_maxsim_rerank).  fetch_k above runs both stages
+    shared_ptr<MultiVectorSearchResult> multi_vector_rerank(Tensor x, const std::string &group_by, Tensor candidates, int64_t k,
+                                                            const std::optional<std::vector<int64_t>> &n_tokens = std::nullopt,
+                                                            std::optional<double> missing = std::nullopt,
+                                                            const std::optional<std::vector<int64_t>> &n_candidates = std::nullopt,
+                                                            shared_ptr<SearchFilter> filter = nullptr);
     // extension: diversified search -- search_params->k of the fetch_k nearest vectors of each query, chosen greedily by maximal
     // marginal relevance with weight lambda_mult in [0, 1] (qk_diverse_search)
     shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult = 0.5);

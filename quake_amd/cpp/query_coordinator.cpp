@@ -898,7 +898,7 @@ shared_ptr<MultiVectorSearchResult> QueryCoordinator::multi_vector_search(Tensor
                                                                           const std::string &group_by, shared_ptr<SearchParams> sp,
                                                                           std::optional<float> radius_opt,
                                                                           const std::optional<std::vector<int64_t>> &n_tokens,
-                                                                          std::optional<double> missing_opt) {
+                                                                          std::optional<double> missing_opt, std::optional<int64_t> fetch_k) {
     const std::string who = "[QuakeIndex::multi_vector_search()]";
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::multi_vector_search] partition_manager_ is null.");
     if (!sp->filters.empty() || sp->query_filter.defined())
@@ -917,8 +917,12 @@ shared_ptr<MultiVectorSearchResult> QueryCoordinator::multi_vector_search(Tensor
     if (partition_manager_->group()) throw std::runtime_error(who + " multi_vector_search is not supported with num_workers > 0");
     if (!store) throw std::runtime_error("[QueryCoordinator::multi_vector_search] partitions are not initialized.");
     if (!x.defined() || x.dim() != 3) throw std::runtime_error(who + " x must be [L, T, d]");
-    const int64_t L = x.size(0), T = x.size(1), k = sp->k;
-    const float missing = (float)lower_maxsim(known, group_by, k, T, n_tokens, missing_opt, (int)metric_ == QK_METRIC_IP);
+    const int64_t L = x.size(0), T = x.size(1), k_out = sp->k;
+    const float missing = (float)lower_maxsim(known, group_by, k_out, T, n_tokens, missing_opt, (int)metric_ == QK_METRIC_IP);
+    if (fetch_k && (*fetch_k < k_out || *fetch_k > QK_MAXSIM_MAX_K))
+        throw std::runtime_error(who + " fetch_k=" + std::to_string(*fetch_k) + " must be between k=" + std::to_string(k_out) + " and " +
+                                 std::to_string(QK_MAXSIM_MAX_K));
+    const int64_t k = fetch_k ? *fetch_k : k_out;  // (stage one's k)
     if (n_tokens && (int64_t)n_tokens->size() != L)
         throw std::runtime_error(who + " n_tokens has " + std::to_string(n_tokens->size()) + " entries for " + std::to_string(L) + " queries");
     qk_filter *flt = nullptr;
@@ -936,11 +940,12 @@ shared_ptr<MultiVectorSearchResult> QueryCoordinator::multi_vector_search(Tensor
     ti->search_params = sp;
     ti->n_clusters = partition_manager_->nlist();
     if (L == 0) {
-        res->groups = torch::zeros({0, k}, torch::kInt64);
-        res->scores = torch::zeros({0, k}, torch::kFloat32);
-        res->matched = torch::zeros({0, k}, torch::kInt32);
+        res->groups = torch::zeros({0, k_out}, torch::kInt64);
+        res->scores = torch::zeros({0, k_out}, torch::kFloat32);
+        res->matched = torch::zeros({0, k_out}, torch::kInt32);
         res->n_groups = torch::zeros({0}, torch::kInt64);
         res->hits = torch::zeros({0, T}, torch::kInt64);
+        if (fetch_k) res->rows = torch::zeros({0, k_out}, torch::kInt32);
         return res;
     }
     auto t0 = clk::now();
@@ -985,6 +990,99 @@ shared_ptr<MultiVectorSearchResult> QueryCoordinator::multi_vector_search(Tensor
         ti->parent_info->n_clusters = 1;
         ti->parent_info->total_time_ns = (int64_t)(tm.coarse_ms * 1e6);
     }
+    if (fetch_k) {
+        // stage two: the values stage one found, still in x's memory, against every vector of their documents; its sweep and its
+        // score + select are added to stage one's scan and aggregate times
+        auto two = multi_vector_rerank(x, col, known, group_by, res->groups, k_out, n_tokens, (double)missing, std::nullopt, sp->filter,
+                                       res->n_groups.clamp_max(k).to(torch::kInt32));
+        res->groups = two->groups, res->scores = two->scores, res->matched = two->matched, res->n_groups = two->n_groups;
+        res->rows = two->rows;
+        ti->job_wait_time_ns += two->timing_info->job_wait_time_ns;
+        ti->result_aggregate_time_ns += two->timing_info->result_aggregate_time_ns;
+    }
+    ti->total_time_ns = ns_since(t0);
+    return res;
+}
+
+shared_ptr<MultiVectorSearchResult> QueryCoordinator::multi_vector_rerank(Tensor x, qk_attr *col, const std::vector<std::string> &known,
+                                                                          const std::string &group_by, Tensor candidates, int64_t k,
+                                                                          const std::optional<std::vector<int64_t>> &n_tokens,
+                                                                          std::optional<double> missing_opt,
+                                                                          const std::optional<std::vector<int64_t>> &n_candidates,
+                                                                          shared_ptr<SearchFilter> filter, Tensor d_n_cand) {
+    const std::string who = "[QuakeIndex::multi_vector_rerank()]";
+    if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::multi_vector_rerank] partition_manager_ is null.");
+    qk_ctx *ctx = partition_manager_->ctx();
+    qk_store *store = partition_manager_->store();
+    if (partition_manager_->group())
+        throw NotImplemented(who + " multi_vector_rerank is not supported with num_workers > 0 (QK_ERR_UNSUPPORTED)");
+    if (!store) throw std::runtime_error("[QueryCoordinator::multi_vector_rerank] partitions are not initialized.");
+    if (!x.defined() || x.dim() != 3) throw std::runtime_error(who + " x must be [L, T, d]");
+    if (!candidates.defined() || candidates.dim() != 2 || candidates.size(0) != x.size(0))
+        throw std::runtime_error(who + " candidates must be an int64 tensor [L, C]");
+    const int64_t L = x.size(0), T = x.size(1), C = candidates.size(1);
+    const float missing = (float)lower_rerank(known, group_by, k, T, n_tokens, missing_opt, (int)metric_ == QK_METRIC_IP, C, n_candidates);
+    if (n_tokens && (int64_t)n_tokens->size() != L)
+        throw std::runtime_error(who + " n_tokens has " + std::to_string(n_tokens->size()) + " entries for " + std::to_string(L) + " queries");
+    if (n_candidates && (int64_t)n_candidates->size() != L)
+        throw std::runtime_error(who + " n_candidates has " + std::to_string(n_candidates->size()) + " entries for " + std::to_string(L) +
+                                 " queries");
+    qk_filter *flt = nullptr;
+    if (filter) {
+        if (!filter->h) throw std::runtime_error(who + " filter must come from make_filter()");
+        if (filter->owner != store) throw std::runtime_error(who + " the filter was made for another index");
+        flt = filter->h;
+    }
+    auto res = std::make_shared<MultiVectorSearchResult>();
+    res->column = group_by;
+    auto ti = res->timing_info = std::make_shared<SearchTimingInfo>();
+    ti->n_clusters = partition_manager_->nlist();
+    ti->n_queries = L;
+    if (L == 0) {
+        res->groups = torch::zeros({0, k}, torch::kInt64);
+        res->scores = torch::zeros({0, k}, torch::kFloat32);
+        res->matched = torch::zeros({0, k}, torch::kInt32);
+        res->rows = torch::zeros({0, k}, torch::kInt32);
+        res->n_groups = torch::zeros({0}, torch::kInt64);
+        return res;
+    }
+    auto t0 = clk::now();
+    const bool on_dev = x.is_cuda();
+    Tensor xq = (on_dev ? x.to(torch::kFloat32).contiguous() : host_f32(x)).reshape({L * T, x.size(2)});
+    Tensor cd = candidates.to(xq.device(), torch::kInt64).contiguous();
+    BoundToTorchStream bound(ctx, xq);
+    auto i32_of = [&](const std::optional<std::vector<int64_t>> &v) {  // int32 [L] in x's memory
+        Tensor t;
+        if (v) {
+            t = torch::empty({L}, torch::kInt32);
+            for (int64_t l = 0; l < L; l++) t.data_ptr<int32_t>()[l] = (int32_t)(*v)[l];
+            if (on_dev) t = t.to(xq.device());
+        }
+        return t;
+    };
+    Tensor nt = i32_of(n_tokens), nc = d_n_cand.defined() ? d_n_cand.to(xq.device(), torch::kInt32).contiguous() : i32_of(n_candidates);
+    int was = 0;
+    qk_check(qk_ctx_get_timing(ctx, &was));
+    struct Restore {
+        qk_ctx *c;
+        int was;
+        ~Restore() { (void)qk_ctx_set_timing(c, was); }
+    } restore{ctx, was};
+    qk_check(qk_ctx_set_timing(ctx, 1));
+    qk_timing tm;
+    std::memset(&tm, 0, sizeof(tm));
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
+    res->groups = torch::empty({L, k}, i64);
+    res->scores = torch::empty({L, k}, i64.dtype(torch::kFloat32));
+    res->matched = torch::empty({L, k}, i64.dtype(torch::kInt32));
+    res->rows = torch::empty({L, k}, i64.dtype(torch::kInt32));
+    res->n_groups = torch::empty({L}, i64);
+    qk_check(qk_maxsim_rerank(ctx, store, xq.data_ptr<float>(), L, (int)T, nt.defined() ? nt.data_ptr<int32_t>() : nullptr, (int)metric_, flt,
+                              col, missing, C > 0 ? cd.data_ptr<int64_t>() : nullptr, nc.defined() ? nc.data_ptr<int32_t>() : nullptr, (int)C,
+                              (int)k, res->groups.data_ptr<int64_t>(), res->scores.data_ptr<float>(), res->matched.data_ptr<int32_t>(),
+                              res->rows.data_ptr<int32_t>(), res->n_groups.data_ptr<int64_t>(), on_dev ? QK_MEM_DEVICE : QK_MEM_HOST, &tm));
+    ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
+    ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);
     ti->total_time_ns = ns_since(t0);
     return res;
 }

@@ -63,7 +63,14 @@ public:
     shared_ptr<MultiVectorSearchResult> multi_vector_search(Tensor x, qk_attr *col, const std::vector<std::string> &known,
                                                             const std::string &group_by, shared_ptr<SearchParams> search_params,
                                                             std::optional<float> radius, const std::optional<std::vector<int64_t>> &n_tokens,
-                                                            std::optional<double> missing);
+                                                            std::optional<double> missing, std::optional<int64_t> fetch_k = std::nullopt);
+    // extension (qk_maxsim_rerank): the k best of candidates [L, C] by every vector of their documents (lower_rerank runs behind the
+    // refusals); d_n_cand: int32 [L] in x's memory instead of n_candidates (stage two of multi_vector_search with fetch_k)
+    shared_ptr<MultiVectorSearchResult> multi_vector_rerank(Tensor x, qk_attr *col, const std::vector<std::string> &known,
+                                                            const std::string &group_by, Tensor candidates, int64_t k,
+                                                            const std::optional<std::vector<int64_t>> &n_tokens, std::optional<double> missing,
+                                                            const std::optional<std::vector<int64_t>> &n_candidates,
+                                                            shared_ptr<SearchFilter> filter, Tensor d_n_cand = Tensor());
     // extension (qk_diverse_search): search_params->k of the fetch_k nearest vectors of each query by maximal marginal relevance
     // (lower_diverse runs behind the refusals)
     shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult);

@@ -78,6 +78,8 @@ int qk_ctx_destroy(qk_ctx *c) {
     if (c->pool_buf) hipFree(c->pool_buf);
     if (c->div_buf) hipFree(c->div_buf);
     if (c->fn_buf) hipFree(c->fn_buf);
+    if (c->rr_buf) hipFree(c->rr_buf);
+    if (c->rr_rows) hipFree(c->rr_rows);
     if (c->shadow_counters) hipFree(c->shadow_counters);
     if (c->xcd_host) hipHostFree(c->xcd_host);
     if (c->xcd_ev) hipEventDestroy(c->xcd_ev);

@@ -214,6 +214,10 @@ struct qk_ctx {
     // its own buffer because the coarse step and the scan recycle `ws`
     char *fn_buf = nullptr;
     size_t fn_cap = 0;
+    // multi-vector rerank (qk_rerank.hip): the value -> document table of a group of logical queries with its counts and
+    // offsets, the group's records and a host caller's candidates; and the arena rows of the group's documents, sized by the sweep
+    char *rr_buf = nullptr, *rr_rows = nullptr;
+    size_t rr_cap = 0, rr_rows_cap = 0;
 };
 
 int qk_ws_reserve(qk_ctx *ctx, size_t bytes);          // make sure the workspace can hold `bytes` (may sync+realloc)

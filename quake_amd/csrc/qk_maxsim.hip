@@ -23,17 +23,13 @@
 // No thread waits for another, every loop is bounded, phases are separated by kernel boundaries, only commutative minima decide a
 // key word and values are distinct, so order keys are: the result is a pure function of the store, the column, the filter and the
 // call.  The host side is one description, maxsim_call, for qk_emit_run (qk_emit.hip) and maxsim_device in qk_emit_device's skeleton.
-#include "qk_facet.h"
+#include "qk_maxsim.h"
 
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 namespace {
-
-constexpr unsigned long long MS_EMPTY = ~0ull;
-constexpr unsigned long long MS_SIGN = 0x8000000000000000ull;
-constexpr int MS_SEL = QK_MAXSIM_MAX_K;  // records the selection sorts in LDS
 
 struct MaxsimParams {
     FacetParams F;             // keys, segments, mask, has[0] / rowval[0], nq, P, Sg, the key interval, tmask, max_ids; total = the
@@ -138,19 +134,7 @@ __global__ __launch_bounds__(256) void k_maxsim_claim(MaxsimParams M) {
     }
 }
 
-// the score as an unsigned word that orders as asked (smaller = better): -0 counts as +0, a NaN is 0xFFFFFFFF, the word no number has
-__device__ __forceinline__ uint32_t maxsim_score_word(float s, int metric) {
-    if (s != s) return 0xFFFFFFFFu;
-    uint32_t b = __float_as_uint(s);
-    b = b == 0x80000000u ? 0u : b;
-    const uint32_t asc = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-    return metric == QK_METRIC_IP ? ~asc : asc;
-}
-__device__ __forceinline__ float maxsim_score_of(uint32_t w, int metric) {
-    if (w == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
-    const uint32_t asc = metric == QK_METRIC_IP ? ~w : w;
-    return __uint_as_float((asc & 0x80000000u) ? (asc ^ 0x80000000u) : ~asc);
-}
+// (the score word, maxsim_score_word / maxsim_score_of: qk_maxsim.h)
 
 struct MaxsimSelectParams {
     MaxsimParams M;
@@ -164,18 +148,7 @@ struct MaxsimSelectParams {
     int64_t *out_hits;         // [L][T] or nullptr
 };
 
-// a record of the selection: (score word, value ^ sign bit) is the 96-bit order key; m (the matched count, all ones for padding)
-// only separates a record from padding that looks like it
-struct MKey {
-    uint32_t hi;
-    unsigned long long lo;
-    uint32_t m;
-};
-__device__ __forceinline__ bool mkey_less(const MKey &a, const MKey &b) {
-    if (a.hi != b.hi) return a.hi < b.hi;
-    if (a.lo != b.lo) return a.lo < b.lo;
-    return a.m < b.m;
-}
+// (a record of the selection and its order, MKey / mkey_less: qk_maxsim.h)
 // byte d (0 = most significant, 11 = least) of an order key, and whether the bytes in front of d equal those of p (fkey_byte /
 // fkey_prefix of qk_facet.hip)
 __device__ __forceinline__ uint32_t mkey_byte(uint32_t hi, unsigned long long lo, int d) {

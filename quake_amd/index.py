@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_sq8
+from .where import lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_rerank, lower_sq8
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -378,7 +378,9 @@ class MultiVectorSearchResult:
     """extension (QuakeIndex.multi_vector_search): per logical query the k best values of an attribute column by the sum over the
     query's vectors of the best hit among the value's rows: groups [L, k] (padding 0), scores [L, k] (padding as search pads),
     matched [L, k] int32 the query vectors that met the value (padding 0), n_groups [L] the values met, hits [L, T] the range hits
-    of every query vector; column the column's name"""
+    of every query vector; column the column's name.  From multi_vector_rerank (and multi_vector_search with fetch_k): matched counts
+    the query vectors with a non-NaN pair in the document, rows [L, k] int32 holds the documents' row counts (padding 0) and hits
+    is None"""
 
     def __init__(self):
         self.groups = None
@@ -388,6 +390,7 @@ class MultiVectorSearchResult:
         self.hits = None
         self.column = None
         self.timing_info = None
+        self.rows = None
 
 
 class DiverseSearchResult:
@@ -1384,14 +1387,16 @@ class QuakeIndex:
         res.ids, res.distances, res.values, res.counts, res.missing, res.totals = (o if on_dev else o.cpu() for o in out[:6])
         return res
 
-    def multi_vector_search(self, x, group_by, search_params, radius=None, n_tokens=None, missing=None):
+    def multi_vector_search(self, x, group_by, search_params, radius=None, n_tokens=None, missing=None, fetch_k=None):
         """extension (no reference counterpart): multi-vector (late interaction) search.  x is [L, T, d]: every logical query has T
         vectors, of which the first n_tokens[l] take part (None: all).  A value of the attribute column `group_by` (a document) scores
         the sum over the query's vectors of the best vector range_search(x[l, t], radius, search_params) returns among the value's
         vectors (radius None: every vector of the probed partitions), `missing` where there is none (None: 0.0 for the inner
         product; l2 needs an explicit value).  Returns the search_params.k best values per logical query, the better score first,
         ties to the smaller value, as a MultiVectorSearchResult on x's device.  1 <= T <= 64, 1 <= k <= 1024.  Exact; the sum is
-        added in float32 in the order of the query's vectors (include/quake_hip.h, "multi-vector search")."""
+        added in float32 in the order of the query's vectors (include/quake_hip.h, "multi-vector search").
+        fetch_k (None: the call above, untouched): two stages -- the search runs with k = fetch_k, its values stay on the device and
+        multi_vector_rerank scores them against every vector of their documents; the search_params.k best of that are returned."""
         who = "[QuakeIndex::multi_vector_search()]"
         self._require_built(who + " No query coordinator. Did you build the index?")
         sp = search_params
@@ -1416,6 +1421,11 @@ class QuakeIndex:
             n_tokens = n_tokens.detach().cpu().reshape(-1).tolist()
         name, k, T, n_tokens, missing = lower_maxsim(cols, group_by, sp.k, int(x.shape[1]), n_tokens, missing,
                                                      "ip" if capi.metric_code(self.metric_) == capi.QK_METRIC_IP else "l2", who)
+        k_out = k
+        if fetch_k is not None:
+            k = fetch_k.__index__() if hasattr(fetch_k, "__index__") and not isinstance(fetch_k, bool) else -1
+            if not k_out <= k <= capi.QK_MAXSIM_MAX_K:
+                raise RuntimeError("%s fetch_k=%r must be between k=%d and %d" % (who, fetch_k, k_out, capi.QK_MAXSIM_MAX_K))
         nq = int(x.shape[0])
         if n_tokens is not None and len(n_tokens) != nq:
             raise RuntimeError("%s n_tokens has %d entries for %d queries" % (who, len(n_tokens), nq))
@@ -1443,7 +1453,10 @@ class QuakeIndex:
             res.scores = torch.zeros((0, k), dtype=torch.float32)
             res.matched = torch.zeros((0, k), dtype=torch.int32)
             res.n_groups = torch.zeros((0,), dtype=torch.int64)
+            res.groups, res.scores, res.matched = res.groups[:, :k_out], res.scores[:, :k_out], res.matched[:, :k_out]
             res.hits = torch.zeros((0, T), dtype=torch.int64)
+            if fetch_k is not None:
+                res.rows = torch.zeros((0, k_out), dtype=torch.int32)
             return res
         on_dev = x.is_cuda
         xd = self._to_dev(x, torch.float32)
@@ -1467,8 +1480,89 @@ class QuakeIndex:
             pi.n_clusters = 1
             pi.total_time_ns = int(tm["coarse_ms"] * 1e6)
             ti.parent_info = pi
+        if fetch_k is not None:
+            # stage two: the values stage one found, still on the device, against every vector of their documents
+            # (its sweep and its score + select are added to stage one's scan and aggregate times)
+            self._ctx.set_timing(1)
+            try:
+                two = self._ctx.maxsim_rerank(self._store, xd, self.metric_, cols[name], out[0], k_out, missing=missing, n_tokens=nt,
+                                              n_candidates=torch.clamp(out[3], max=k).to(torch.int32), filter=flt, timing=True)
+            finally:
+                self._ctx.set_timing(was)
+            ti.job_wait_time_ns += int(two[5]["scan_ms"] * 1e6)
+            ti.result_aggregate_time_ns += int(two[5]["merge_ms"] * 1e6)
+            res.rows = two[3] if on_dev else two[3].cpu()
+            out = (two[0], two[1], two[2], two[4], out[4])
         ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
         res.groups, res.scores, res.matched, res.n_groups, res.hits = (o if on_dev else o.cpu() for o in out[:5])
+        return res
+
+    def multi_vector_rerank(self, x, group_by, candidates, k, n_tokens=None, missing=None, n_candidates=None, filter=None):
+        """extension (no reference counterpart): the exact stage of multi-vector search.  x is [L, T, d] as for multi_vector_search;
+        candidates [L, C] int64 are values of the attribute column `group_by` (documents), of which the first n_candidates[l] count
+        (None: all C; C <= 1024).  Every query vector is compared with EVERY vector of a candidate's document -- no partitions are
+        probed, so a flat index is served --, the document scores the float32 sum of the per-vector best, `missing` where a vector
+        has no pair that is a number, and the k best candidates are returned in multi_vector_search's order.  A value named twice
+        counts once; a value without vectors (or none the filter of make_filter() accepts) is never returned.  Returns a
+        MultiVectorSearchResult on x's device with rows set and hits None (include/quake_hip.h, "multi-vector rerank")."""
+        who = "[QuakeIndex::multi_vector_rerank()]"
+        self._require_built(who + " No query coordinator. Did you build the index?")
+        if isinstance(self._store, capi.Group):
+            raise NotImplementedError(who + " multi_vector_rerank is not supported with num_workers > 0 (QK_ERR_UNSUPPORTED)")
+        if x is None or x.dim() != 3:
+            raise RuntimeError(who + " x must be [L, T, d]")
+        if candidates is None or not torch.is_tensor(candidates) or candidates.dim() != 2 or candidates.shape[0] != x.shape[0]:
+            raise RuntimeError(who + " candidates must be an int64 tensor [L, C]")
+        cols = self._attributes()
+        if n_tokens is not None and torch.is_tensor(n_tokens):
+            n_tokens = n_tokens.detach().cpu().reshape(-1).tolist()
+        if n_candidates is not None and torch.is_tensor(n_candidates):
+            n_candidates = n_candidates.detach().cpu().reshape(-1).tolist()
+        name, k, T, n_tokens, missing, n_candidates = lower_rerank(
+            cols, group_by, k, int(x.shape[1]), n_tokens, missing, "ip" if capi.metric_code(self.metric_) == capi.QK_METRIC_IP else "l2",
+            int(candidates.shape[1]), n_candidates, who)
+        nq = int(x.shape[0])
+        for what, a in (("n_tokens", n_tokens), ("n_candidates", n_candidates)):
+            if a is not None and len(a) != nq:
+                raise RuntimeError("%s %s has %d entries for %d queries" % (who, what, len(a), nq))
+        flt = filter
+        if flt is not None:
+            if not isinstance(flt, SearchFilter):
+                raise RuntimeError(who + " filter must come from make_filter()")
+            if flt._store is not self._store:
+                raise RuntimeError(who + " the filter was made for another index")
+            flt = flt._h
+        res = MultiVectorSearchResult()
+        res.column = name
+        ti = SearchTimingInfo()
+        ti.n_clusters = self.nlist()
+        ti.n_queries = nq
+        res.timing_info = ti
+        t0 = time.perf_counter()
+        if nq == 0:
+            res.groups = torch.zeros((0, k), dtype=torch.int64)
+            res.scores = torch.zeros((0, k), dtype=torch.float32)
+            res.matched = torch.zeros((0, k), dtype=torch.int32)
+            res.rows = torch.zeros((0, k), dtype=torch.int32)
+            res.n_groups = torch.zeros((0,), dtype=torch.int64)
+            return res
+        on_dev = x.is_cuda
+        xd = self._to_dev(x, torch.float32)
+        cd = self._to_dev(candidates, torch.int64)
+        nt = None if n_tokens is None else torch.tensor(n_tokens, dtype=torch.int32, device=xd.device)
+        nc = None if n_candidates is None else torch.tensor(n_candidates, dtype=torch.int32, device=xd.device)
+        was = self._ctx.get_timing()   # (a timing mode the caller had set is put back)
+        self._ctx.set_timing(1)
+        try:
+            out = self._ctx.maxsim_rerank(self._store, xd, self.metric_, cols[name], cd, k, missing=missing, n_tokens=nt, n_candidates=nc,
+                                          filter=flt, timing=True)
+        finally:
+            self._ctx.set_timing(was)
+        tm = out[5]
+        ti.job_wait_time_ns = int(tm["scan_ms"] * 1e6)
+        ti.result_aggregate_time_ns = int(tm["merge_ms"] * 1e6)
+        ti.total_time_ns = int((time.perf_counter() - t0) * 1e9)
+        res.groups, res.scores, res.matched, res.rows, res.n_groups = (o if on_dev else o.cpu() for o in out[:5])
         return res
 
     def diverse_search(self, x, search_params, fetch_k, lambda_mult=0.5):

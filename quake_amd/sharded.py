@@ -293,6 +293,11 @@ class ShardedIndex:
         best prefix keys, not the index's."""
         raise NotImplementedError("[ShardedIndex::funnel_search()] funnel_search is not supported by sharded.py")
 
+    def multi_vector_rerank(self, x, group_by, candidates, k, n_tokens=None, missing=None, n_candidates=None, filter=None):
+        """multi-vector rerank (QuakeIndex.multi_vector_rerank, qk_maxsim_rerank) has no sharded form: a document's rows lie on
+        several shards, and the best pair of a query vector is a minimum over all of them (QK_ERR_UNSUPPORTED)."""
+        raise NotImplementedError("[ShardedIndex::multi_vector_rerank()] multi_vector_rerank is not supported by sharded.py")
+
     def quantized_search(self, q, nprobe, k, fetch_k):
         """quantized search (QuakeIndex.quantized_search, qk_sq8_search) has no sharded form: a shard's codes use its own scale, and
         its candidates are its own fetch_k best, not the index's."""

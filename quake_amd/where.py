@@ -7,7 +7,7 @@ integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr add
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
 lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search), lower_order
 the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_funnel those of funnel search (QuakeIndex.funnel_search), lower_sq8 those of quantized search (QuakeIndex.quantized_search), lower_maxsim those of multi-vector search
-(QuakeIndex.multi_vector_search).
+(QuakeIndex.multi_vector_search), lower_rerank those of multi-vector rerank (QuakeIndex.multi_vector_rerank).
 Pure Python: importable without the library or a GPU."""
 
 INT64_MIN = -(1 << 63)
@@ -29,6 +29,7 @@ QK_MAX_K = 448
 QK_FUNNEL_MAX_PREFIX = 1024
 QK_SQ8_MAX_D = 2048
 QK_MAXSIM_MAX_TOKENS, QK_MAXSIM_MAX_K = 64, 1024
+QK_MAXSIM_RERANK_MAX_CAND = 1024
 
 OPS = ("==", "!=", "<", "<=", ">", ">=", "between", "any_bits", "all_bits", "no_bits")
 SET_OPS = ("in", "not_in")  # lower_expr only
@@ -326,3 +327,26 @@ def lower_maxsim(columns, group_by, k, T, n_tokens=None, missing=None, metric="i
     if missing != missing:
         raise RuntimeError("%s missing is NaN" % who)
     return group_by, k, T, n_tokens, missing
+
+
+def lower_rerank(columns, group_by, k, T, n_tokens=None, missing=None, metric="ip", C=0, n_candidates=None,
+                 who="[QuakeIndex::multi_vector_rerank()]"):
+    """The arguments of multi-vector rerank (include/quake_hip.h, "multi-vector rerank") -> (column name, k, T, n_tokens, missing,
+    n_candidates): lower_maxsim's rules and errors for group_by, T, n_tokens and missing, in its order, except that k only has to be at
+    least 1; then C, the candidates per logical query, in [0, QK_MAXSIM_RERANK_MAX_CAND], and n_candidates None (C for every logical
+    query) or a sequence of integers in [0, C] (returned as a list)."""
+    k = _int(k, who + " k:")
+    if k < 1:
+        raise RuntimeError("%s k=%d must be at least 1" % (who, k))
+    name, _, T, n_tokens, missing = lower_maxsim(columns, group_by, 1, T, n_tokens, missing, metric, who)
+    C = _int(C, who + " C:")
+    if not 0 <= C <= QK_MAXSIM_RERANK_MAX_CAND:
+        raise RuntimeError("%s C=%d candidates per query must be between 0 and %d" % (who, C, QK_MAXSIM_RERANK_MAX_CAND))
+    if n_candidates is not None:
+        if isinstance(n_candidates, (str, bytes)) or not hasattr(n_candidates, "__len__") or not hasattr(n_candidates, "__getitem__"):
+            raise RuntimeError("%s n_candidates must be a sequence of integers, got %r" % (who, n_candidates))
+        n_candidates = [_int(n_candidates[i], who + " n_candidates:") for i in range(len(n_candidates))]
+        for i, n in enumerate(n_candidates):
+            if not 0 <= n <= C:
+                raise RuntimeError("%s n_candidates[%d]=%d must be between 0 and C=%d" % (who, i, n, C))
+    return name, k, T, n_tokens, missing, n_candidates
