@@ -1030,6 +1030,34 @@ QK_API int qk_sq8_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, cons
 QK_API int qk_store_sq8_info(qk_store *s, int *valid, int64_t *bytes, float *scale);
 QK_API int qk_store_sq8_drop(qk_store *s);
 
+/* Deep quantized search: quantized search for long shortlists.  The arguments are qk_sq8_search's / qk_sq8_scan's,
+ * and steps 1-7 of the definition above hold word for word -- code parameters, codes, integer keys, the candidates (the fetch_k
+ * smallest under (approximate key, arena row)), funnel search's answer step.  Only the limits differ:
+ *   1 <= k <= min(fetch_k, QK_MAX_K) and 1 <= fetch_k <= QK_SQ8_MAX_FETCH; beyond either: QK_ERR_UNSUPPORTED, no output written.
+ *   QK_SQ8_MAX_D and the refusals of a flat index, filters, cursors, qk_search_aps and the device group are unchanged.
+ * Consequences: at fetch_k <= QK_MAX_K the call returns bit for bit what qk_sq8_search returns for the same arguments; a fetch_k
+ * that covers a query's probed rows gives qk_search's row.
+ * The definition holds for every finite store, including one where more rows share the key at the cut than any buffer holds (a
+ * store of identical rows): there the rows with the smallest arena numbers win.  There is no "incomplete result" outcome.
+ * Inside (qk_sq8_deep.hip) the candidates are selected by counting, not in LDS pools: k_sq8_bound (a true upper bound U_q of the
+ * fetch_k-th key from a strided sample of the probed lists, and 1024 bins under it), k_scan_sq8_deep pass A (the k_scan_sq8 stream;
+ * a key <= U_q adds one to its bin), k_sq8_cut (prefix sum: the cut bin and c0 < fetch_k keys under it), pass B (the same stream;
+ * bins under the cut append their row to the candidates, the cut bin its (key, row) to a contested slice of 4096 entries),
+ * k_sq8_resolve (the fetch_k - c0 smallest contested entries under (key, row) by byte-wise selection; a cut bin of more than 4096
+ * rows is selected from the probed rows themselves, keys recomputed, in a fixed number of walks), then the exact finish
+ * (k_funnel_finish up to QK_MAX_K candidates, k_sq8_deep_finish -- the same gather, selection by counting -- above).  One enqueue, no
+ * host wait on any path, no data-dependent memory: besides the queries' codes the call uses
+ *   Q * (8 * fetch_k + 12 * 4096 + 4 * 1024 + 40) bytes (each of its seven arrays rounded up to 256)
+ * of the context's candidate buffer.
+ * timing: scan phase = bound + pass A + cut + pass B; the resolve and the finish lie behind merge_ms and are part of total_ms only;
+ * scan_bytes counts the code bytes of the unique probed rows twice.  qk_ctx_last_scan_kernel reports
+ * "k_scan (int8 codes, counting)". */
+#define QK_SQ8_MAX_FETCH 4096
+QK_API int qk_sq8_search_deep(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k,
+                              int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_sq8_scan_deep(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
+                            int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

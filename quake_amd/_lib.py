@@ -166,6 +166,8 @@ SIGNATURES = {
     # quantized search: (.., k, fetch_k, metric, ids, dist, mem, timing)
     "qk_sq8_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_sq8_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_sq8_search_deep": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_sq8_scan_deep": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_store_sq8_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(C.c_float)]),
     "qk_store_sq8_drop": (_int, [_vp]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

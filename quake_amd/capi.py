@@ -842,10 +842,11 @@ class Context:
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
     # ---- quantized search --------------------------------------------------------------------------------
-    def sq8_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False):
+    def sq8_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False, deep=False):
         """qk_sq8_search: per query, the fetch_k rows of its probed lists with the smallest integer keys over the store's int8
         codes, re-scored on the float32 rows; the k best under (exact key, id).  Returns (ids [Q, k] padded with -1, dist [Q, k]
-        padded as search pads -- None where not wanted --[, timing]) on x's device."""
+        padded as search pads -- None where not wanted --[, timing]) on x's device.  deep: qk_sq8_search_deep, the same definition
+        with the candidates selected by counting, fetch_k up to QK_SQ8_MAX_FETCH."""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
@@ -854,14 +855,14 @@ class Context:
         ids = _empty_like_mem((Q, kk), np.int64, x)
         dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
         t = QkTiming()
-        check(self.lib.qk_sq8_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
-                                     metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
-                                     C.byref(t) if timing else None))
+        fn = self.lib.qk_sq8_search_deep if deep else self.lib.qk_sq8_search
+        check(fn(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
+                 metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem, C.byref(t) if timing else None))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
-    def sq8_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False):
+    def sq8_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False, deep=False):
         """qk_sq8_scan: sq8_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
-        nothing."""
+        nothing.  deep: qk_sq8_scan_deep."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
         pids = _pids_rows(pids, Q)
@@ -871,9 +872,10 @@ class Context:
         ids = _empty_like_mem((Q, kk), np.int64, x)
         dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
         t = QkTiming()
-        check(self.lib.qk_sq8_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
-                                   fetch_k, metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
-                                   C.byref(t) if timing else None))
+        fn = self.lib.qk_sq8_scan_deep if deep else self.lib.qk_sq8_scan
+        check(fn(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
+                 fetch_k, metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                 C.byref(t) if timing else None))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,

@@ -234,11 +234,11 @@ PYBIND11_MODULE(_bindings, m) {
           py::arg("d"), py::arg("k"), py::arg("prefix_dim"), py::arg("fetch_k"),
           "the arguments of funnel_search -> (k, prefix_dim, fetch_k); needs no device (where.py's lower_funnel)");
     m.def("lower_sq8",
-          [](int64_t d, int64_t k, int64_t fetch_k) {
-              lower_sq8(d, k, fetch_k);
+          [](int64_t d, int64_t k, int64_t fetch_k, bool deep) {
+              lower_sq8(d, k, fetch_k, deep);
               return py::make_tuple(k, fetch_k);
           },
-          py::arg("d"), py::arg("k"), py::arg("fetch_k"),
+          py::arg("d"), py::arg("k"), py::arg("fetch_k"), py::arg("deep") = false,
           "the arguments of quantized_search -> (k, fetch_k); needs no device (where.py's lower_sq8)");
     py::register_exception_translator([](std::exception_ptr p) {
         try {
@@ -380,7 +380,7 @@ PYBIND11_MODULE(_bindings, m) {
              "against every vector of a candidate's document, the k best candidates; multi_vector_search(fetch_k=) runs both stages")
         .def("funnel_search", &QuakeIndex::funnel_search, py::arg("x"), py::arg("search_params"), py::arg("prefix_dim"), py::arg("fetch_k"),
              "extension: rank the probed rows by their first prefix_dim columns, re-score the fetch_k best on the full vector")
-        .def("quantized_search", &QuakeIndex::quantized_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
+        .def("quantized_search", &QuakeIndex::quantized_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"), py::arg("deep") = false,
              "extension: rank the probed rows by exact integer keys over int8 codes, re-score the fetch_k best on the float32 rows")
         .def("diverse_search", &QuakeIndex::diverse_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
              py::arg("lambda_mult") = 0.5,

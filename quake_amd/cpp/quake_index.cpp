@@ -337,17 +337,19 @@ shared_ptr<SearchResult> QuakeIndex::funnel_search(Tensor x, shared_ptr<SearchPa
     return query_coordinator_->funnel_search(x, sp, prefix_dim, fetch_k);
 }
 
-void lower_sq8(int64_t d, int64_t k, int64_t fetch_k) {
+void lower_sq8(int64_t d, int64_t k, int64_t fetch_k, bool deep) {
     const std::string who = "[QuakeIndex::quantized_search()]";
+    const int64_t max_fetch = deep ? QK_SQ8_MAX_FETCH : QK_MAX_K;
     if (k < 1) throw std::runtime_error(who + " k=" + std::to_string(k) + " must be at least 1");
     if (fetch_k < k) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must be at least k=" + std::to_string(k));
-    if (fetch_k > QK_MAX_K) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must not exceed " + std::to_string(QK_MAX_K));
+    if (deep && k > QK_MAX_K) throw std::runtime_error(who + " k=" + std::to_string(k) + " must not exceed " + std::to_string(QK_MAX_K));
+    if (fetch_k > max_fetch) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must not exceed " + std::to_string(max_fetch));
     if (d > QK_SQ8_MAX_D) throw std::runtime_error(who + " d=" + std::to_string(d) + " must not exceed " + std::to_string(QK_SQ8_MAX_D));
 }
 
-shared_ptr<SearchResult> QuakeIndex::quantized_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k) {
+shared_ptr<SearchResult> QuakeIndex::quantized_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, bool deep) {
     if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::quantized_search()] No query coordinator. Did you build the index?");
-    return query_coordinator_->quantized_search(x, sp, fetch_k);
+    return query_coordinator_->quantized_search(x, sp, fetch_k, deep);
 }
 
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {

@@ -76,8 +76,8 @@ public:
     shared_ptr<DiverseSearchResult> diverse_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, double lambda_mult);
     // extension (qk_funnel_search): candidates by a column prefix, exact re-score (lower_funnel runs behind the refusals)
     shared_ptr<SearchResult> funnel_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t prefix_dim, int64_t fetch_k);
-    // extension (qk_sq8_search): candidates by int8 codes, exact re-score (lower_sq8 runs behind the refusals)
-    shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
+    // extension (qk_sq8_search; deep: qk_sq8_search_deep): candidates by int8 codes, exact re-score (lower_sq8 runs behind the refusals)
+    shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, bool deep = false);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

@@ -426,6 +426,9 @@ struct qk_scan_args {
     int sq8_nblk = 0;
     const void *sq8_codes = nullptr;
     const int32_t *sq8_nx = nullptr;
+    // deep quantized search (qk_sq8_deep.hip): with sq8_nblk > 0, the counting form in the pool form's place -- bound, count, cut and
+    // emit launches over the same grouping, the candidates left in sq8_deep's buffers; k only sizes the (unused) pools, no merge runs
+    const struct Sq8DeepParams *sq8_deep = nullptr;
 };
 // filters (qk_filter.hip)
 struct qk_filter;

@@ -1430,7 +1430,10 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         //  rows: the call's own result, not context state -- a later call cannot inherit it --, and a negative value is no byte count,
         //  so finishing the same struct twice cannot multiply rows by a total)
         if (timing) timing->scan_bytes = (shadow || prefix) ? -(int64_t)nblk_scan * 64 : 0;
-        if (sq8)
+        if (sq8 && a.sq8_deep) {
+            ctx->last_scan_kernel = "k_scan (int8 codes, counting)";
+            QK_TRY(qk_launch_scan_sq8_deep(s, a, DB, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
+        } else if (sq8)
             QK_TRY(qk_launch_scan_sq8(DB, maxch, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
         else if (prefix)
             QK_TRY(qk_launch_scan_prefix(DB, maxch, dim3((unsigned)grid), dim3(64 * wpw), lds_launch, st, sp));
@@ -1587,7 +1590,9 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     mp.out_dist = a.out_dist;
     mp.sqrt_l2 = a.sqrt_l2 ? 1 : 0;
     const dim3 mgrid((unsigned)(a.per_pair ? Q * P : Q));
-    if (shadow) {  // the exact finish (qk_shadow.hip): candidates re-scored in fp32, verified, or the list scanned exactly
+    if (sq8 && a.sq8_deep) {
+        // counting form: the candidates are in the call's own buffers; its resolve and finish follow in qk_sq8_deep.hip
+    } else if (shadow) {  // the exact finish (qk_shadow.hip): candidates re-scored in fp32, verified, or the list scanned exactly
         ShadowFinishParams fp;
         fp.pair_head = pair_head;
         fp.pair_slots = pair_slots;

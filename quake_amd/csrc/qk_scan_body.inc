@@ -22,6 +22,9 @@
 // blocks of 64 columns per tile, 16 B per lane as before), P.xq4 the queries' codes in the same lane order, one
 // v_mfma_i32_16x16x64_i8 per block into an int32 accumulator; P.norms / P.xn carry the int32 code norms as bits (L2); no ids are
 // loaded (a candidate's "id" is its arena row); the key is an exact integer.  Everything it changes sits behind #ifdef QK_SCAN_SQ8.
+// QK_SCAN_SQ8_DEEP (with QK_SCAN_SQ8) = k_scan_sq8_deep (qk_sq8_deep.hip), the counting form: the same walk and load stream, no pools
+// and no records.  A key at or under its query's bound P.dp.qst[q].x goes into the query's bin histogram (PASS 0) or, by its bin,
+// into the query's candidate or contested slice through an atomic cursor (PASS 1).  Everything it changes sits behind the #ifdef.
 // Expects: template parameters DB, MAXCH, MODE, L2 and the kernel argument `ScanParams P` in scope.
     extern __shared__ __align__(16) unsigned char smem[];
     // nw waves per workgroup (1, 2 or 4) share ONE LDS query tile and split every segment's tiles between them; each
@@ -170,6 +173,9 @@
         float xnj = 0.0f;
 #ifdef QK_SCAN_SQ8
         int nqj = 0;  // this lane's query's code norm (L2)
+#endif
+#ifdef QK_SCAN_SQ8_DEEP
+        uint4 dq = make_uint4(0u, 0u, 0u, 0u);  // this lane's query: bound U, bin origin, bin shift, cut bin (qk_sq8_deep.hip)
 #endif
 #ifdef QK_SCAN_SHADOW
         bool sh_dead = false;  // this lane's query takes no part (its bound is negative: the finish answers it exactly)
@@ -402,6 +408,30 @@
 #else
                 const int64_t idv[4] = {ia.x, ia.y, ib.x, ib.y};
 #endif
+#ifdef QK_SCAN_SQ8_DEEP
+                // a survivor (key <= U_q) does one global atomic, exact whatever the order of arrival; how many survive is set by the
+                // sample behind U_q: about fetch_k x probed rows / sample rows per query (DESIGN.md 5.25)
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    if (!(live && myq >= 0 && row0 + 4 * g + reg < size_p)) continue;
+                    const uint32_t o = l2 ? (uint32_t)(nqj + __float_as_int(yv[reg]) - 2 * acc[reg]) : (uint32_t)(-acc[reg]) ^ 0x80000000u;
+                    if (o > dq.x) continue;
+                    const uint32_t bin = o < dq.y ? 0u : 1u + ((o - dq.y) >> dq.z);
+                    if (PASS == 0) {
+                        atomicAdd(&P.dp.hist[(int64_t)myq * QK_SQ8_DEEP_BINS + bin], 1u);
+                    } else if (bin < dq.w) {  // definitely in: exactly c0 <= fetch_k of these exist
+                        const uint32_t slot = atomicAdd(&P.dp.cur[2 * (int64_t)myq], 1u);
+                        if (slot < (uint32_t)P.dp.C) P.dp.cand[(int64_t)myq * P.dp.C + slot] = idv[reg];
+                    } else if (bin == dq.w) {  // contested: what does not fit is counted, and found again by the resolve's own walk
+                        const uint32_t slot = atomicAdd(&P.dp.cur[2 * (int64_t)myq + 1], 1u);
+                        if (slot < (uint32_t)QK_SQ8_DEEP_CAP) {
+                            P.dp.ckey[(int64_t)myq * QK_SQ8_DEEP_CAP + slot] = o;
+                            P.dp.crow[(int64_t)myq * QK_SQ8_DEEP_CAP + slot] = idv[reg];
+                        }
+                    }
+                }
+                return;
+#endif
                 if (EMIT) {
                     if (live && myq >= 0) {
                         uint32_t *dst = P.key_out + P.pair_base[mypair] + row0 + 4 * g;
@@ -504,6 +534,9 @@
                 if (l2) xnj = P.xn[qsafe];
 #ifdef QK_SCAN_SQ8
                 nqj = l2 && myq >= 0 ? __float_as_int(xnj) : 0;
+#endif
+#ifdef QK_SCAN_SQ8_DEEP
+                dq = P.dp.qst[qsafe];
 #endif
 #ifdef QK_SCAN_SHADOW
                 {  // the seed's exact bound, widened by what an approximate key may lie above its exact one

@@ -77,6 +77,20 @@ __host__ __device__ inline long long hot_units_of(int cnt, int size, const HotCo
     return u;
 }
 
+// ---- counting form of the int8 code scan (k_scan_sq8_deep, qk_sq8_deep.hip) ----------------------------------------
+constexpr int QK_SQ8_DEEP_BINS = 1024;  // bins per query: bin 0 = keys under the origin, bin 1 + ((key - origin) >> shift) above
+constexpr int QK_SQ8_DEEP_CAP = 4096;   // entries of a query's contested slice (the keys of the cut bin)
+struct Sq8DeepParams {
+    uint4 *qst;         // [Q] {bound U, bin origin, bin shift, cut bin} (k_sq8_bound; .w by k_sq8_cut)
+    uint4 *stt;         // [Q] {c0 = keys in the bins under the cut, keys in the cut bin, cut bin, -} (k_sq8_cut)
+    uint32_t *hist;     // [Q][QK_SQ8_DEEP_BINS]
+    uint32_t *cur;      // [Q][2] cursors of the candidate and the contested slice
+    int64_t *cand;      // [Q][C] arena rows
+    uint32_t *ckey;     // [Q][QK_SQ8_DEEP_CAP] keys of the contested entries
+    int64_t *crow;      // [Q][QK_SQ8_DEEP_CAP] their arena rows
+    int C;              // fetch_k
+};
+
 struct ScanParams {
     const float4 *vecs;
     const float *norms;
@@ -158,6 +172,8 @@ struct ScanParams {
     // prefix form (k_scan_prefix, qk_funnel.hip): vecs is the arena itself, whose tiles are nblk_row blocks apart; the kernel walks
     // the first nblk of them.  norms / xn are the norms of the prefixes, xq4 the queries' prefix in B-operand order
     int nblk_row;
+    // counting form of the int8 code scan (k_scan_sq8_deep only; unset elsewhere)
+    Sq8DeepParams dp;
 };
 
 // ---- merge stage (qk_merge.hip) ------------------------------------------------------------------------------------------
@@ -291,4 +307,16 @@ int qk_launch_funnel_finish(hipStream_t st, const FunnelFinishParams &fp, int64_
 int qk_fn_reserve(qk_ctx *ctx, size_t need);
 // int8 code form (qk_sq8.hip): the tile form over the code mirror, sp.nblk blocks of 64 columns per tile, launched like k_scan
 int qk_launch_scan_sq8(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
+// counting form (qk_sq8_deep.hip): k_sq8_bound, k_scan_sq8_deep pass A, k_sq8_cut, pass B -- both passes launched like k_scan_sq8
+int qk_launch_scan_sq8_deep(qk_store *s, const qk_scan_args &a, int db, dim3 grid, dim3 block, size_t lds, hipStream_t st, ScanParams &sp);
+// its buffers: bytes for Q queries (a function of Q and fetch_k alone), their places in a region of that size, the per-query state
+// a call starts from; k_sq8_resolve behind the scan; the exact finish (k_funnel_finish up to QK_MAX_K candidates, k_sq8_deep_finish above)
+size_t qk_sq8_deep_bytes(int64_t Q, int fetch_k);
+void qk_sq8_deep_carve(char *buf, int64_t Q, int fetch_k, Sq8DeepParams *dp);
+int qk_launch_sq8_deep_init(hipStream_t st, const Sq8DeepParams &dp, int64_t Q);
+int qk_launch_sq8_resolve(qk_store *s, const qk_scan_args &a, hipStream_t st);
+int qk_launch_sq8_deep_finish(hipStream_t st, const FunnelFinishParams &fp, int64_t Q);
+// the body of qk_sq8_search / qk_sq8_scan (qk_sq8.hip) and of their deep siblings (deep: the counting form, fetch_k up to QK_SQ8_MAX_FETCH)
+int qk_sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
+               int k, int fetch_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool deep);
 int qk_launch_next_cursor(qk_ctx *ctx, const MergeParams &mp, int64_t Q, const int64_t *out_ids, uint32_t *next_key, int64_t *next_id);

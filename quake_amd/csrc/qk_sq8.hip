@@ -239,16 +239,20 @@ int launch_scan_sq8(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Sca
     return QK_OK;
 }
 
-// the body of both entry points: parent == nullptr && pids == nullptr -> every list
-int sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe, int k,
-            int fetch_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+}  // namespace
+
+// the body of the entry points: parent == nullptr && pids == nullptr -> every list; deep: the candidates by counting (qk_sq8_deep.hip)
+int qk_sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe, int k,
+               int fetch_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool deep) {
     const int d = s->d;
     if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
     if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
     if (fetch_k < k) QK_FAIL(QK_ERR_INVALID, "%s: fetch_k=%d must be at least k=%d", who, fetch_k, k);
     if (Q < 0 || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
     if (mem != QK_MEM_HOST && mem != QK_MEM_DEVICE) QK_FAIL(QK_ERR_INVALID, "%s: mem must be QK_MEM_HOST or QK_MEM_DEVICE", who);
-    if (fetch_k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: fetch_k=%d exceeds QK_MAX_K=%d", who, fetch_k, QK_MAX_K);
+    if (deep && k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds QK_MAX_K=%d", who, k, QK_MAX_K);
+    if (deep && fetch_k > QK_SQ8_MAX_FETCH) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: fetch_k=%d exceeds QK_SQ8_MAX_FETCH=%d", who, fetch_k, QK_SQ8_MAX_FETCH);
+    if (!deep && fetch_k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: fetch_k=%d exceeds QK_MAX_K=%d", who, fetch_k, QK_MAX_K);
     if (d > QK_SQ8_MAX_D) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: d=%d exceeds QK_SQ8_MAX_D=%d", who, d, QK_SQ8_MAX_D);
     if (!parent && !pids && s->nlist == 1)
         QK_FAIL(QK_ERR_UNSUPPORTED, "%s: a flat index without lists of its own takes the dense path, which has no int8 code form", who);
@@ -271,11 +275,13 @@ int sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const f
     // ---- the mirror and the call's buffer: what can refuse or fail for want of memory comes first -----------------------------------
     QK_TRY(qk_store_sync_table(s));
     QK_TRY(qk_store_sq8_mirror(ctx, s, metric));
-    const size_t b_q = qk_al256((size_t)Q * nb8 * 64), b_n = qk_al256((size_t)Q * 4), b_c = qk_al256((size_t)Q * C * 8);
+    const size_t b_q = qk_al256((size_t)Q * nb8 * 64), b_n = qk_al256((size_t)Q * 4), b_c = deep ? qk_sq8_deep_bytes(Q, C) : qk_al256((size_t)Q * C * 8);
     QK_TRY(qk_fn_reserve(ctx, b_q + b_n + b_c));
     uint4 *xq = (uint4 *)ctx->fn_buf;
     int32_t *nq = (int32_t *)(ctx->fn_buf + b_q);
     int64_t *cand = (int64_t *)(ctx->fn_buf + b_q + b_n);
+    Sq8DeepParams dd;
+    if (deep) qk_sq8_deep_carve(ctx->fn_buf + b_q + b_n, Q, C, &dd);  // (the candidates first: cand as above)
     // ---- staging, full query preparation, coarse (the unfiltered qk_search's, on the float32 queries) -------------------------------
     const size_t b_oi = qk_al256((size_t)Q * k * 8), b_od = qk_al256((size_t)Q * k * 4);
     qk_scan_args sa;
@@ -297,11 +303,16 @@ int sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const f
     sa.sq8_nblk = nb8;
     sa.sq8_codes = s->sq8_codes;
     sa.sq8_nx = s->sq8_nx;
-    sa.k = C;
+    sa.k = deep ? 1 : C;  // (counting form: no pools; k sizes nothing that is used)
+    if (deep) {
+        sa.sq8_deep = &dd;
+        QK_TRY(qk_launch_sq8_deep_init(st, dd, Q));
+    }
     sa.out_ids = cand;
     sa.out_dist = nullptr;
     sa.record_events = timing != nullptr;
     QK_TRY(qk_scan_device(ctx, s, sa, timing, 4));
+    if (deep) QK_TRY(qk_launch_sq8_resolve(s, sa, st));
     // ---- the exact finish: funnel search's ------------------------------------------------------------------------------------------
     FunnelFinishParams fp;
     fp.cand = cand;
@@ -317,7 +328,7 @@ int sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const f
     fp.sqrt_l2 = ctx->squared_l2 ? 0 : 1;
     fp.out_ids = d_ids;
     fp.out_dist = d_dist;
-    QK_TRY(qk_launch_funnel_finish(st, fp, Q));
+    QK_TRY(deep ? qk_launch_sq8_deep_finish(st, fp, Q) : qk_launch_funnel_finish(st, fp, Q));
     const bool tm = ctx->timing && timing;
     hipEvent_t tail_end = nullptr;
     if (tm) {
@@ -343,14 +354,13 @@ int sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const f
         rc = qk_finish_timing(ctx, s, timing, have_coarse, 4);
         float ms = 0.f;
         if (rc == QK_OK && tm && hipEventElapsedTime(&ms, ctx->ev[7], tail_end) == hipSuccess) timing->total_ms += ms;
+        if (rc == QK_OK && deep) timing->scan_bytes *= 2;  // (the codes are streamed twice)
     }
     if (tail_end) (void)hipEventDestroy(tail_end);
     QK_TRY(rc);
     if (timing || host) QK_TRY(qk_check_overflow(ctx));
     return QK_OK;
 }
-
-}  // namespace
 
 int qk_launch_scan_sq8(int db, int maxch, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp) {
 #define QK_CASEQ(D, M) \
@@ -455,14 +465,14 @@ int qk_sq8_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
                   int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_sq8_search: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_sq8_search: nprobe must be positive");
-    return sq8_run("qk_sq8_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, metric, out_ids, out_dist, mem, timing);
+    return qk_sq8_run("qk_sq8_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, metric, out_ids, out_dist, mem, timing, false);
 }
 
 int qk_sq8_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
                 int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_sq8_scan: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_sq8_scan: bad partition id list");
-    return sq8_run("qk_sq8_scan", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, metric, out_ids, out_dist, mem, timing);
+    return qk_sq8_run("qk_sq8_scan", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, metric, out_ids, out_dist, mem, timing, false);
 }
 
 int qk_store_sq8_info(qk_store *s, int *valid, int64_t *bytes, float *scale) {

@@ -1687,14 +1687,16 @@ class QuakeIndex:
         res.ids, res.distances = (o if on_dev else o.cpu() for o in out[:2])
         return res
 
-    def quantized_search(self, x, search_params, fetch_k):
+    def quantized_search(self, x, search_params, fetch_k, deep=False):
         """extension (no reference counterpart): quantized search, scalar quantization with oversampling and rescoring -- the rows
         of each query's probed lists (chosen as search() chooses them, by the float32 query) are ranked by an exact integer key over
         one int8 code per coordinate, a quarter of the bytes search() reads; the fetch_k best of them are re-scored on the float32
         rows, and search_params.k of those are returned under (exact distance, id), with the distances search() reports.
         Approximate by design, defined bit for bit (include/quake_hip.h, "quantized search"): a fetch_k that covers the probed rows
-        is search().  1 <= k <= fetch_k <= 448, d <= 2048; the codes (64 ceil(d / 64) + 4 bytes per row) are rebuilt by the first
-        call after the index changed.  Filters, recall_target, num_workers > 0 and a flat index are not served
+        is search().  1 <= k <= fetch_k <= 448, d <= 2048.
+        deep=True (include/quake_hip.h, "deep quantized search"): the same definition with the shortlist selected by counting
+        instead of in LDS pools; 1 <= k <= 448, k <= fetch_k <= 4096, d <= 2048.
+        The codes (64 ceil(d / 64) + 4 bytes per row) are rebuilt by the first call after the index changed.  Filters, recall_target, num_workers > 0 and a flat index are not served
         (NotImplementedError); a stored value that is not finite is a RuntimeError.  Returns a SearchResult on x's device."""
         who = "[QuakeIndex::quantized_search()]"
         self._require_built(who + " No query coordinator. Did you build the index?")
@@ -1709,7 +1711,7 @@ class QuakeIndex:
             raise NotImplementedError(who + " quantized_search is not supported with num_workers > 0")
         if self.parent is None:
             raise NotImplementedError(who + " quantized_search is not supported by a flat index (no lists of its own)")
-        k, fetch_k = lower_sq8(int(self._d), sp.k, fetch_k, who)
+        k, fetch_k = lower_sq8(int(self._d), sp.k, fetch_k, who, deep=bool(deep))
         res = SearchResult()
         ti = SearchTimingInfo()
         ti.search_params = sp
@@ -1726,7 +1728,7 @@ class QuakeIndex:
         nprobe = max(int(sp.nprobe), 1)
         self._ctx.set_timing(1)
         try:
-            out = self._ctx.sq8_search(self.parent._store, self._store, xd, nprobe, k, fetch_k, self.metric_, timing=True)
+            out = self._ctx.sq8_search(self.parent._store, self._store, xd, nprobe, k, fetch_k, self.metric_, timing=True, deep=bool(deep))
         finally:
             self._ctx.set_timing(0)
         tm = out[2]

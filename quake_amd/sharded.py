@@ -298,9 +298,9 @@ class ShardedIndex:
         several shards, and the best pair of a query vector is a minimum over all of them (QK_ERR_UNSUPPORTED)."""
         raise NotImplementedError("[ShardedIndex::multi_vector_rerank()] multi_vector_rerank is not supported by sharded.py")
 
-    def quantized_search(self, q, nprobe, k, fetch_k):
-        """quantized search (QuakeIndex.quantized_search, qk_sq8_search) has no sharded form: a shard's codes use its own scale, and
-        its candidates are its own fetch_k best, not the index's."""
+    def quantized_search(self, q, nprobe, k, fetch_k, deep=False):
+        """quantized search (QuakeIndex.quantized_search, qk_sq8_search / qk_sq8_search_deep) has no sharded form: a shard's codes use
+        its own scale, and its candidates are its own fetch_k best, not the index's."""
         raise NotImplementedError("[ShardedIndex::quantized_search()] quantized_search is not supported by sharded.py")
 
     def diverse_search(self, q, nprobe, k, fetch_k, lambda_mult=0.5):

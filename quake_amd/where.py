@@ -28,6 +28,7 @@ QK_MAX_FETCH_K = 256
 QK_MAX_K = 448
 QK_FUNNEL_MAX_PREFIX = 1024
 QK_SQ8_MAX_D = 2048
+QK_SQ8_MAX_FETCH = 4096
 QK_MAXSIM_MAX_TOKENS, QK_MAXSIM_MAX_K = 64, 1024
 QK_MAXSIM_RERANK_MAX_CAND = 1024
 
@@ -275,18 +276,21 @@ def lower_funnel(d, k, prefix_dim, fetch_k, who="[QuakeIndex::funnel_search()]")
     return k, prefix_dim, fetch_k
 
 
-def lower_sq8(d, k, fetch_k, who="[QuakeIndex::quantized_search()]"):
+def lower_sq8(d, k, fetch_k, who="[QuakeIndex::quantized_search()]", deep=False):
     """The arguments of quantized search (include/quake_hip.h, "quantized search") over vectors of d columns -> (k, fetch_k):
     1 <= k <= fetch_k <= QK_MAX_K, d <= QK_SQ8_MAX_D.  RuntimeError, in this order: a value that is no integer, k < 1, fetch_k < k,
-    fetch_k above its limit, d above its limit."""
+    fetch_k above its limit, d above its limit.  deep ("deep quantized search"): k <= QK_MAX_K (checked before fetch_k's limit) and
+    fetch_k <= QK_SQ8_MAX_FETCH."""
     k = _int(k, who + " k:")
     fetch_k = _int(fetch_k, who + " fetch_k:")
     if k < 1:
         raise RuntimeError("%s k=%d must be at least 1" % (who, k))
     if fetch_k < k:
         raise RuntimeError("%s fetch_k=%d must be at least k=%d" % (who, fetch_k, k))
-    if fetch_k > QK_MAX_K:
-        raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_MAX_K))
+    if deep and k > QK_MAX_K:
+        raise RuntimeError("%s k=%d must not exceed %d" % (who, k, QK_MAX_K))
+    if fetch_k > (QK_SQ8_MAX_FETCH if deep else QK_MAX_K):
+        raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_SQ8_MAX_FETCH if deep else QK_MAX_K))
     if d > QK_SQ8_MAX_D:
         raise RuntimeError("%s d=%d must not exceed %d" % (who, d, QK_SQ8_MAX_D))
     return k, fetch_k
