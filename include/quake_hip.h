@@ -1058,6 +1058,53 @@ QK_API int qk_sq8_search_deep(qk_ctx *ctx, qk_store *parent, qk_store *s, const 
 QK_API int qk_sq8_scan_deep(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
                             int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
 
+/* Binary search: binary quantization with oversampling and rescoring.  Every coordinate of the store is mirrored as
+ * one sign bit, 1/32 of the bytes, the probed rows are ranked by Hamming distance, a shortlist of fetch_k rows is re-scored exactly.
+ * An approximate search by design whose result is still defined bit for bit; comparisons below are float32, keys are integers.
+ *   1. Centres of a store.  L2: m_j = 0.5f * lo_j + 0.5f * hi_j with lo_j / hi_j = min / max of column j over the live rows --
+ *      quantized search's centre, step 1 above, found by the same kernel; a store with a live row that holds a non-finite value has
+ *      no mirror: QK_ERR_UNSUPPORTED, the message names the list, nothing is written.  IP: m_j = 0; no pass over the rows, no
+ *      refusal.  An empty store is QK_OK with padding rows.
+ *   2. Code bit: b_j = (x_j > m_j), an ordered float32 comparison: NaN gives 0, and -0 and +0 against the centre 0 give 0.  Queries
+ *      use the same rule with the same m.  Bits from column d up to the next multiple of 128 are 0 in rows and queries.
+ *   3. Approximate key: the Hamming distance h = popcount(bq ^ bx), an integer in [0, d], for both metrics (for +-1 codes the
+ *      squared L2 distance is 4 h and the negated inner product 2 h - d: h orders both).
+ *   4. Candidates: per query, the fetch_k rows of its probed lists that are smallest under (h, arena row).  The probed lists are
+ *      chosen exactly as qk_search chooses them, the coarse step on the float32 query (qk_bin_scan: the pids row; -1, absent and
+ *      empty lists contribute nothing).
+ *   5. Answer: as funnel search, step 3 -- every candidate gets its canonical fp32 key, the k best under (exact key, id) are
+ *      returned, padding as in qk_search; a candidate whose exact key is NaN is not returned.
+ *   6. Consequence: a fetch_k that covers every probed row of a query gives qk_search's row, bit for bit.
+ * Arguments: k < 1 or fetch_k < k: QK_ERR_INVALID; k > QK_MAX_K, fetch_k > QK_BIN_MAX_FETCH, d > QK_MAX_D, nprobe after its clamp to the parent's rows (qk_bin_scan: P;
+ * no parent and no pids: the lists of the store) > QK_BIN_MAX_NPROBE, a query whose probed rows could number 2^32 or more, a flat index
+ * without lists of its own: QK_ERR_UNSUPPORTED; Q == 0: QK_OK.  A refusal writes no output.  There is no form for filters, cursors,
+ * qk_search_aps or the device group.
+ * Inside (qk_bin.hip), one enqueue without a host wait -- except the one-off build of the mirror: k_bin_prep (the queries' bit
+ * words), the coarse step, k_bin_select -- one workgroup per query, no global atomics: the query's lists ordered by arena offset,
+ * pass A (Hamming keys of every probed row by popcount, a histogram of d + 1 bins in LDS, the keys kept in LDS as uint16 where the
+ * probed rows fit), the cut key by a prefix sum, pass B (rows under the cut key and the first ties at it, in arena order, compacted
+ * into the query's candidates; -1 behind) -- and the exact finish (k_funnel_finish up to QK_MAX_K candidates, k_sq8_deep_finish
+ * above), both unchanged.
+ * The mirror: 16 * ceil(d / 128) bytes per arena row, code row r = arena row r; built on the context's stream (k_sq8_range for L2,
+ * k_bin_encode) by the first call for a (store version, metric), invalid as soon as the store changes; a mirror of its own beside
+ * the int8 codes (a store may hold both); freed with the store or by qk_store_bin_drop; counted in qk_store_device_bytes; not
+ * persisted.  No memory for it: QK_ERR_OOM, nothing else changed.  qk_store_bin_info: valid = a mirror of the current version
+ * exists, bytes = what it occupies, cache_rows = the most probed rows of one query whose keys pass A keeps in LDS for pass B (a
+ * function of d alone; beyond it pass B recomputes them from the codes; 0 in a build without the key cache, QK_BIN_KEY_CACHE=0, which
+ * is the product build: DESIGN.md 5.26 has the measurement).
+ * timing: group_ms = k_bin_prep, scan_ms = k_bin_select; no merge runs, the finish lies behind merge_ms and is part of total_ms
+ * only, as in quantized search.  scan_bytes counts the code bytes of every
+ * query's probed rows once per query (this form does not share lists), partitions_scanned the (query, list) pairs walked, n_items
+ * the queries.  qk_ctx_last_scan_kernel reports "k_bin_select (sign codes)". */
+#define QK_BIN_MAX_FETCH 4096
+#define QK_BIN_MAX_NPROBE 1024
+QK_API int qk_bin_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k, int metric,
+                         int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_bin_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
+                       int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_store_bin_info(qk_store *s, int *valid, int64_t *bytes, int64_t *cache_rows);
+QK_API int qk_store_bin_drop(qk_store *s);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

@@ -170,6 +170,11 @@ SIGNATURES = {
     "qk_sq8_scan_deep": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_store_sq8_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(C.c_float)]),
     "qk_store_sq8_drop": (_int, [_vp]),
+    # binary search: (.., k, fetch_k, metric, ids, dist, mem, timing)
+    "qk_bin_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_bin_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_store_bin_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64)]),
+    "qk_store_bin_drop": (_int, [_vp]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
     "qk_filter_create_expr": (_int, [_vp, C.POINTER(QkExprClause), C.POINTER(_int), _int, C.POINTER(_vp)]),

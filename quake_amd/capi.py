@@ -113,6 +113,8 @@ QK_MAX_ORDER_K = 1024
 QK_MAX_FETCH_K = 256       # diversified search
 QK_FUNNEL_MAX_PREFIX = 1024  # funnel search
 QK_SQ8_MAX_D = 2048        # quantized search
+QK_BIN_MAX_FETCH = 4096    # binary search
+QK_BIN_MAX_NPROBE = 1024
 QK_MAXSIM_MAX_TOKENS = 64  # multi-vector search
 QK_MAXSIM_MAX_K = 1024
 QK_MAXSIM_RERANK_MAX_CAND = 1024  # multi-vector rerank
@@ -878,6 +880,41 @@ class Context:
                  C.byref(t) if timing else None))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
+    # ---- binary search -----------------------------------------------------------------------------------
+    def bin_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False):
+        """qk_bin_search: per query, the fetch_k rows of its probed lists with the smallest Hamming distance over the store's sign
+        bits -- ties by arena row --, re-scored on the float32 rows; the k best under (exact key, id).  Returns (ids [Q, k] padded
+        with -1, dist [Q, k] padded as search pads -- None where not wanted --[, timing]) on x's device."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1  # (the library refuses such a k before it writes: the buffers only have to exist)
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_bin_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
+                                     metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                                     C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
+
+    def bin_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False):
+        """qk_bin_scan: bin_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
+        nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        pids = _pids_rows(pids, Q)
+        mem = _mem_of(x, pids)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_bin_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
+                                   fetch_k, metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                                   C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
+
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):
         """recall-target search (adaptive partition scanning).  Returns (ids, dist, nscanned[, timing])."""
@@ -1222,6 +1259,17 @@ class Store:
         v, b, s = C.c_int(), C.c_int64(), C.c_float()
         check(self.lib.qk_store_sq8_info(self.h, C.byref(v), C.byref(b), C.byref(s)))
         return {"valid": bool(v.value), "bytes": b.value, "scale": s.value}
+
+    def bin_info(self):
+        """{valid, bytes, cache_rows} of the store's sign-bit mirror of binary search (qk_store_bin_info); cache_rows: the most
+        probed rows of one query whose keys the selection keeps in LDS between its two passes"""
+        v, b, c = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        check(self.lib.qk_store_bin_info(self.h, C.byref(v), C.byref(b), C.byref(c)))
+        return {"valid": bool(v.value), "bytes": int(b.value), "cache_rows": int(c.value)}
+
+    def bin_drop(self):
+        """free the sign-bit mirror (qk_store_bin_drop); the next binary search builds it again"""
+        check(self.lib.qk_store_bin_drop(self.h))
 
     def sq8_drop(self):
         """free the int8 code mirror (qk_store_sq8_drop); the next quantized search builds it again"""

@@ -240,6 +240,12 @@ PYBIND11_MODULE(_bindings, m) {
           },
           py::arg("d"), py::arg("k"), py::arg("fetch_k"), py::arg("deep") = false,
           "the arguments of quantized_search -> (k, fetch_k); needs no device (where.py's lower_sq8)");
+    m.def("lower_bin",
+          [](int64_t d, int64_t k, int64_t fetch_k) {
+              lower_bin(d, k, fetch_k);
+              return py::make_tuple(k, fetch_k);
+          },
+          py::arg("d"), py::arg("k"), py::arg("fetch_k"), "the arguments of binary_search -> (k, fetch_k); needs no device (where.py's lower_bin)");
     py::register_exception_translator([](std::exception_ptr p) {
         try {
             if (p) std::rethrow_exception(p);
@@ -382,6 +388,8 @@ PYBIND11_MODULE(_bindings, m) {
              "extension: rank the probed rows by their first prefix_dim columns, re-score the fetch_k best on the full vector")
         .def("quantized_search", &QuakeIndex::quantized_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"), py::arg("deep") = false,
              "extension: rank the probed rows by exact integer keys over int8 codes, re-score the fetch_k best on the float32 rows")
+        .def("binary_search", &QuakeIndex::binary_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
+             "extension: rank the probed rows by Hamming distance over one sign bit per coordinate, re-score the fetch_k best on the float32 rows")
         .def("diverse_search", &QuakeIndex::diverse_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
              py::arg("lambda_mult") = 0.5,
              "extension: per query, search_params.k of its fetch_k nearest vectors (what search() returns with k = fetch_k) chosen "

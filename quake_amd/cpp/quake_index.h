@@ -70,6 +70,8 @@ float lower_diverse(int64_t k, int64_t fetch_k, double lambda_mult);
 void lower_funnel(int64_t d, int64_t k, int64_t prefix_dim, int64_t fetch_k);
 // the arguments of quantized_search over vectors of d columns (where.py's lower_sq8: same rules, same errors, same order)
 void lower_sq8(int64_t d, int64_t k, int64_t fetch_k, bool deep = false);
+// the arguments of binary_search over vectors of d columns (where.py's lower_bin: same rules, same errors, same order)
+void lower_bin(int64_t d, int64_t k, int64_t fetch_k);
 
 class QuakeIndex : public std::enable_shared_from_this<QuakeIndex> {
 public:
@@ -162,6 +164,9 @@ public:
     // extension: quantized search -- rank the probed rows by an exact integer key over one int8 code per coordinate, re-score the
     // fetch_k best on the float32 rows, return search_params->k of them under (exact distance, id) (qk_sq8_search)
     shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, bool deep = false);
+    // extension: binary search -- rank the probed rows by the Hamming distance over one sign bit per coordinate, re-score the fetch_k
+    // best on the float32 rows, return search_params->k of them under (exact distance, id) (qk_bin_search)
+    shared_ptr<SearchResult> binary_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
     // the reference never feeds its hit tracker from search(): with this switch on, search() records the
     // partitions every query probed, so maintenance() has a window to act on
     void set_track_hits(bool on);

@@ -78,6 +78,10 @@ public:
     shared_ptr<SearchResult> funnel_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t prefix_dim, int64_t fetch_k);
     // extension (qk_sq8_search; deep: qk_sq8_search_deep): candidates by int8 codes, exact re-score (lower_sq8 runs behind the refusals)
     shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, bool deep = false);
+    // extension (qk_bin_search): candidates by sign bits and Hamming distance, exact re-score (lower_bin runs behind the refusals)
+    shared_ptr<SearchResult> binary_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
+    // the body of both: form 0 quantized_search, 1 its deep form, 2 binary_search
+    shared_ptr<SearchResult> code_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, int form);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

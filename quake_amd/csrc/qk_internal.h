@@ -319,8 +319,26 @@ struct qk_store {
     uint64_t sq8_version = 0;
     int sq8_metric = -1;  // -1: none
     float sq8_scale = 1.0f;
+    // binary search (qk_bin.hip): one sign bit per coordinate -- code row r is arena row r, the 16 rows of a tile hold
+    // their 16-byte words of a 128-column block side by side (256 B), the blocks of a tile one after the other.  Built lazily by
+    // qk_store_bin_mirror for one (version, metric) at a time; a mirror of its own beside the int8 codes; not persisted
+    void *bin_codes = nullptr;
+    float *bin_m = nullptr;          // device [128 nbw]: the centre of every column (L2; 0 for IP and in the padding)
+    uint32_t *bin_stats = nullptr;   // device [2 * 128 nbw + 4]: what k_sq8_range reduces
+    int64_t bin_cap_rows = 0;
+    uint64_t bin_version = 0;
+    int bin_metric = -1;  // -1: none
 };
 inline int qk_sq8_nblk(int d) { return (d + 63) / 64; }
+inline int qk_bin_nbw(int d) { return (d + 127) / 128; }
+// the sign-bit mirror of `s` (table synced) for `metric`, built on ctx's stream if the store or the metric changed.  L2:
+// QK_ERR_UNSUPPORTED where a live row holds a non-finite value; QK_ERR_OOM, and nothing else changed, without memory
+int qk_store_bin_mirror(qk_ctx *ctx, qk_store *s, int metric);
+void qk_store_bin_free(qk_store *s);
+// quantized search's L2 centres for another mirror (qk_sq8.hip: k_sq8_range<true> over the live rows): stats is device memory of
+// 2 ncol + 4 words, ncol >= 16 nblk; h_m [ncol] receives m_j = 0.5f lo_j + 0.5f hi_j for j < d and 0 behind.  Waits for the stream.
+// *bad_list >= 0: the smallest list that holds a non-finite value (h_m is then not filled)
+int qk_sq8_l2_centres(qk_ctx *ctx, qk_store *s, uint32_t *stats, int ncol, float *h_m, int64_t *bad_list);
 // the code mirror of `s` (table synced) for `metric`, built on ctx's stream if the store or the metric changed.  QK_ERR_UNSUPPORTED
 // where a live row holds a non-finite value or the scale is not finite; QK_ERR_OOM, and nothing else changed, without memory
 int qk_store_sq8_mirror(qk_ctx *ctx, qk_store *s, int metric);

@@ -459,6 +459,24 @@ int qk_store_sq8_mirror(qk_ctx *ctx, qk_store *s, int metric) {
     return QK_OK;
 }
 
+int qk_sq8_l2_centres(qk_ctx *ctx, qk_store *s, uint32_t *stats, int ncol, float *h_m, int64_t *bad_list) {
+    hipStream_t st = ctx->stream;
+    const int nstat = 2 * ncol + 4;
+    const int64_t nl = (int64_t)s->parts.size();
+    const unsigned gy = nl >= 2048 ? 4 : nl >= 256 ? 16 : 64;
+    std::vector<uint32_t> h_stats(nstat, 0u);
+    hipLaunchKernelGGL(k_sq8_init, dim3((unsigned)((nstat + 255) / 256)), dim3(256), 0, st, stats, ncol);
+    hipLaunchKernelGGL(k_sq8_range<true>, dim3((unsigned)nl, gy), dim3(256), 0, st, (const float4 *)s->vecs, s->nblk, ncol,
+                       (const int64_t *)s->d_off, (const int32_t *)s->d_size, stats);
+    QK_HIP(hipGetLastError());
+    QK_HIP(hipMemcpyAsync(h_stats.data(), stats, (size_t)nstat * 4, hipMemcpyDeviceToHost, st));
+    QK_HIP(hipStreamSynchronize(st));
+    *bad_list = h_stats[2 * ncol] != 0 ? (int64_t)h_stats[2 * ncol + 1] : -1;
+    if (*bad_list >= 0) return QK_OK;
+    for (int j = 0; j < ncol; j++) h_m[j] = j < s->d ? 0.5f * sq8_from_img(h_stats[j]) + 0.5f * sq8_from_img(h_stats[ncol + j]) : 0.0f;
+    return QK_OK;
+}
+
 extern "C" {
 
 int qk_sq8_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k, int metric,

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_rerank, lower_sq8
+from .where import lower_bin, lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_rerank, lower_sq8
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -1698,20 +1698,42 @@ class QuakeIndex:
         instead of in LDS pools; 1 <= k <= 448, k <= fetch_k <= 4096, d <= 2048.
         The codes (64 ceil(d / 64) + 4 bytes per row) are rebuilt by the first call after the index changed.  Filters, recall_target, num_workers > 0 and a flat index are not served
         (NotImplementedError); a stored value that is not finite is a RuntimeError.  Returns a SearchResult on x's device."""
-        who = "[QuakeIndex::quantized_search()]"
+        return self._code_search(x, search_params, "quantized_search", lambda d, k, who: lower_sq8(d, k, fetch_k, who, deep=bool(deep)),
+                                 lambda xd, nprobe, k, fk: self._ctx.sq8_search(self.parent._store, self._store, xd, nprobe, k, fk, self.metric_,
+                                                                                timing=True, deep=bool(deep)))
+
+    def binary_search(self, x, search_params, fetch_k):
+        """extension (no reference counterpart): binary search, binary quantization with oversampling and rescoring -- the rows of
+        each query's probed lists (chosen as search() chooses them, by the float32 query) are ranked by the Hamming distance over one
+        sign bit per coordinate (x_j above the column's centre: the middle of its range for L2, 0 for the inner product), 1 / 32 of
+        the bytes search() reads; the fetch_k best of them -- ties by position in the index -- are re-scored on the float32 rows, and
+        search_params.k of those are returned under (exact distance, id), with the distances search() reports.
+        Approximate by design, defined bit for bit (include/quake_hip.h, "binary search"): a fetch_k that covers the probed rows is
+        search().  1 <= k <= 448, k <= fetch_k <= 4096, d <= 8192, nprobe <= 1024.
+        The bits (16 ceil(d / 128) bytes per row) are rebuilt by the first call after the index changed.  Filters, recall_target,
+        num_workers > 0 and a flat index are not served (NotImplementedError); under L2 a stored value that is not finite is a
+        RuntimeError.  Returns a SearchResult on x's device."""
+        return self._code_search(x, search_params, "binary_search", lambda d, k, who: lower_bin(d, k, fetch_k, who),
+                                 lambda xd, nprobe, k, fk: self._ctx.bin_search(self.parent._store, self._store, xd, nprobe, k, fk, self.metric_,
+                                                                                timing=True))
+
+    def _code_search(self, x, search_params, name, lower, call):
+        """the body of quantized_search and binary_search: the refusals, lower(d, k, who) -> (k, fetch_k), call(x, nprobe, k, fetch_k)
+        -> (ids, distances, timing)"""
+        who = "[QuakeIndex::%s()]" % name
         self._require_built(who + " No query coordinator. Did you build the index?")
         sp = search_params
         if (getattr(sp, "filter", None) is not None or (getattr(sp, "filters", None) or []) or getattr(sp, "query_filter", None) is not None
                 or int(getattr(sp, "filters_exact_rows", 0) or 0) != 0 or int(getattr(sp, "filter_exact_rows", 0) or 0) != 0
                 or int(getattr(sp, "max_nprobe", 0) or 0) > 0):
-            raise NotImplementedError(who + " filters of any kind are not supported by quantized_search")
+            raise NotImplementedError(who + " filters of any kind are not supported by " + name)
         if sp.recall_target is not None and sp.recall_target > 0.0:
-            raise NotImplementedError(who + " quantized_search is not supported with recall_target > 0")
+            raise NotImplementedError(who + " %s is not supported with recall_target > 0" % name)
         if isinstance(self._store, capi.Group):
-            raise NotImplementedError(who + " quantized_search is not supported with num_workers > 0")
+            raise NotImplementedError(who + " %s is not supported with num_workers > 0" % name)
         if self.parent is None:
-            raise NotImplementedError(who + " quantized_search is not supported by a flat index (no lists of its own)")
-        k, fetch_k = lower_sq8(int(self._d), sp.k, fetch_k, who, deep=bool(deep))
+            raise NotImplementedError(who + " %s is not supported by a flat index (no lists of its own)" % name)
+        k, fetch_k = lower(int(self._d), sp.k, who)
         res = SearchResult()
         ti = SearchTimingInfo()
         ti.search_params = sp
@@ -1728,7 +1750,7 @@ class QuakeIndex:
         nprobe = max(int(sp.nprobe), 1)
         self._ctx.set_timing(1)
         try:
-            out = self._ctx.sq8_search(self.parent._store, self._store, xd, nprobe, k, fetch_k, self.metric_, timing=True, deep=bool(deep))
+            out = call(xd, nprobe, k, fetch_k)
         finally:
             self._ctx.set_timing(0)
         tm = out[2]

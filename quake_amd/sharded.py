@@ -303,6 +303,11 @@ class ShardedIndex:
         its own scale, and its candidates are its own fetch_k best, not the index's."""
         raise NotImplementedError("[ShardedIndex::quantized_search()] quantized_search is not supported by sharded.py")
 
+    def binary_search(self, q, nprobe, k, fetch_k):
+        """binary search (QuakeIndex.binary_search, qk_bin_search) has no sharded form: a shard's sign bits use its own centres,
+        and its candidates are its own fetch_k best, not the index's."""
+        raise NotImplementedError("[ShardedIndex::binary_search()] binary_search is not supported by sharded.py")
+
     def diverse_search(self, q, nprobe, k, fetch_k, lambda_mult=0.5):
         """diversified search (QuakeIndex.diverse_search, qk_diverse_search) has no sharded form: the re-ranking needs the vectors
         of every candidate of a query, which live on different ranks"""
