@@ -1105,6 +1105,65 @@ QK_API int qk_bin_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, cons
 QK_API int qk_store_bin_info(qk_store *s, int *valid, int64_t *bytes, int64_t *cache_rows);
 QK_API int qk_store_bin_drop(qk_store *s);
 
+/* Product-quantized search: product quantization with oversampling and rescoring.  The d columns are cut into M
+ * sub-spaces, each with a learned codebook of 256 codewords; a row is mirrored as M bytes, a query becomes a lookup table, the probed
+ * rows are ranked by a sum of M table entries, a shortlist of fetch_k rows is re-scored exactly.  An approximate search by design
+ * whose result is still defined bit for bit.  dot(a, b) over n columns is the canonical chain acc = 0; acc = fmaf(a_j, b_j, acc), j
+ * ascending; zero-padded columns change nothing.  All arithmetic below is float32.
+ *   1. Codebooks: M sub-quantizers, 1 <= M <= QK_PQ_MAX_M, d % M == 0, dsub = d / M <= QK_PQ_MAX_DSUB, each 256 codewords
+ *      w[m][c][dsub].  State of the store: supplied by qk_store_pq_set_codebooks (host [M][256][dsub]; a value that is not finite:
+ *      QK_ERR_INVALID) or trained by qk_store_pq_train, read back by qk_store_pq_codebooks.  They are data, not part of the bit
+ *      contract: training need not be reproducible across builds, everything after it is.  They survive every mutation of the
+ *      store -- only the codes are re-derived -- and are the same for both metrics, as is the mirror.
+ *   2. Code of a row: for sub-vector m, e(c) = fmaf(-2, dot(x_m, w[m][c]), n[m][c]) with n[m][c] = dot(w[m][c], w[m][c]); the code
+ *      byte is the c smallest under (e is NaN, e, c): equal e, -0 / +0 included, goes to the smaller c.  A store with a live row
+ *      that holds a non-finite value has no mirror: QK_ERR_UNSUPPORTED, the message names the list, nothing is written.
+ *   3. Table of a query: T[m][c] = fmaf(-2, dot(q_m, w[m][c]), n[m][c]) (L2; the query's own norm orders nothing), -dot(q_m,
+ *      w[m][c]) (IP).  lo_m / hi_m = min / max of T[m][.]; R = sum over m ascending of (hi_m - lo_m); delta = R / 8000.0f;
+ *      u[m][c] = (uint16) rintf((T[m][c] - lo_m) / delta), an IEEE division.  Any entry of T not finite, or R 0 or not finite:
+ *      every u of that query is 0.  sum_m max_c u[m][c] < QK_PQ_KEY_BINS for every M <= 128.
+ *   4. Key: h = sum_m u[m][code_m(row)], an exact integer in [0, 8191].
+ *   5. Candidates: per query, the fetch_k rows of its probed lists smallest under (h, arena row).  The lists are qk_search's: the
+ *      coarse step on the float32 query (qk_pq_scan: the pids row; -1, absent and empty lists contribute nothing).
+ *   6. Answer: as funnel search, step 3.  A fetch_k that covers every probed row of a query gives qk_search's row, bit for bit.
+ * Arguments: k < 1 or fetch_k < k: QK_ERR_INVALID; k > QK_MAX_K, fetch_k > QK_PQ_MAX_FETCH, more than QK_PQ_MAX_NPROBE lists per
+ * query, 2^32 or more probed rows per query, a flat index without lists of its own, a store without codebooks ("train or set
+ * codebooks first"): QK_ERR_UNSUPPORTED; Q == 0: QK_OK.  A refusal writes no output.  No form for filters, cursors, qk_search_aps or
+ * the device group.
+ * qk_store_pq_train(ctx, s, M, max_rows, niter, seed): a seeded sample (qk_rand_perm over the live rows in arena order) of up to
+ * max_rows rows, per sub-space its [n][dsub] matrix gathered from the arena and qk_kmeans (256 centroids, L2, niter iterations, seed
+ * + m).  Fewer than 256 live rows: QK_ERR_UNSUPPORTED ("supply codebooks").  Setting or training codebooks drops the codes.
+ * Inside (qk_pq.hip), one enqueue without a host wait -- except the one-off build of the mirror: k_pq_lut (T for 16 queries x 16
+ * codewords per v_mfma_f32_16x16x4_f32, float32 [Q][M][256] in the call's workspace), the coarse step, k_pq_select -- one workgroup
+ * per query, no global atomics: lo / hi / R / delta and the uint16 table into LDS, the lists ordered by arena offset, pass A (keys
+ * by byte-indexed LDS reads into a histogram of 8192 bins), the cut key by a prefix sum, pass B (rows under the cut and the first
+ * ties in arena order; -1 behind) -- and the exact finish (k_funnel_finish / k_sq8_deep_finish), unchanged.
+ * Workspace of a call: 1024 M + 8 fetch_k + 8 bytes per query, the float32 table first -- 128 KiB per query at M = 128, 134 MB for
+ * 1024 queries, where the sibling forms take a few KB per query.  It grows with Q without a bound and stays with the context; a
+ * caller for whom that is too much sends its queries in slices.  No memory for it: QK_ERR_OOM, nothing written.
+ * The mirror: 16 * ceil(M / 16) bytes per arena row, code row r = arena row r, 16-byte words of 16 sub-quantizers (padding bytes 0),
+ * the 16 words of a tile side by side; built by k_pq_encode (an assign on the same MFMA, the sub-space's codebook in LDS, the
+ * non-finite check in the same pass) by the first call for a store version, invalid as soon as the store changes, rebuilt in full;
+ * counted in qk_store_device_bytes; not persisted.  No memory for it: QK_ERR_OOM, nothing else changed.  qk_store_pq_info: M, dsub
+ * (0 without codebooks), has_codebooks, valid = codes of the current version exist, bytes = what they occupy.  qk_store_pq_drop
+ * frees the codes and, with drop_codebooks != 0, the codebooks.
+ * timing: group_ms = k_pq_lut, scan_ms = k_pq_select; the finish is part of total_ms only.  scan_bytes counts the code bytes of
+ * every query's probed rows.  qk_ctx_last_scan_kernel reports "k_pq_select (PQ codes)". */
+#define QK_PQ_MAX_M 128
+#define QK_PQ_MAX_DSUB 64
+#define QK_PQ_KEY_BINS 8192
+#define QK_PQ_MAX_FETCH 4096
+#define QK_PQ_MAX_NPROBE 1024
+QK_API int qk_pq_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k, int metric,
+                        int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_pq_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
+                      int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_store_pq_set_codebooks(qk_store *s, int M, const float *codebooks);
+QK_API int qk_store_pq_codebooks(qk_store *s, float *out_codebooks);
+QK_API int qk_store_pq_train(qk_ctx *ctx, qk_store *s, int M, int64_t max_rows, int niter, uint64_t seed);
+QK_API int qk_store_pq_info(qk_store *s, int *M, int *dsub, int *has_codebooks, int *valid, int64_t *bytes);
+QK_API int qk_store_pq_drop(qk_store *s, int drop_codebooks);
+
 /* Paged search: continue a search behind a cursor.  Results are totally ordered by (key, id): the key is the 32-bit integer the
  * top-k compares (a monotone image of the squared L2 distance / of the negated inner product), ids are unique and non-negative,
  * and the key 0xFFFFFFFF (a NaN value) is never a candidate.  A cursor (ck, cid) is a position in that order, not a snapshot.

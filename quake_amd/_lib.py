@@ -175,6 +175,14 @@ SIGNATURES = {
     "qk_bin_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_store_bin_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_store_bin_drop": (_int, [_vp]),
+    # product-quantized search: the arguments of binary search; codebooks are host float32 [M][256][d / M]
+    "qk_pq_search": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_pq_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_store_pq_set_codebooks": (_int, [_vp, _int, _vp]),
+    "qk_store_pq_codebooks": (_int, [_vp, _vp]),
+    "qk_store_pq_train": (_int, [_vp, _vp, _int, _i64, _int, C.c_uint64]),
+    "qk_store_pq_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_i64)]),
+    "qk_store_pq_drop": (_int, [_vp, _int]),
     "qk_attr_group_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_filter_create_where": (_int, [_vp, C.POINTER(QkClause), _int, C.POINTER(_vp)]),
     "qk_filter_create_expr": (_int, [_vp, C.POINTER(QkExprClause), C.POINTER(_int), _int, C.POINTER(_vp)]),

@@ -115,6 +115,8 @@ QK_FUNNEL_MAX_PREFIX = 1024  # funnel search
 QK_SQ8_MAX_D = 2048        # quantized search
 QK_BIN_MAX_FETCH = 4096    # binary search
 QK_BIN_MAX_NPROBE = 1024
+QK_PQ_MAX_M, QK_PQ_MAX_DSUB = 128, 64  # product-quantized search
+QK_PQ_MAX_FETCH, QK_PQ_MAX_NPROBE = 4096, 1024
 QK_MAXSIM_MAX_TOKENS = 64  # multi-vector search
 QK_MAXSIM_MAX_K = 1024
 QK_MAXSIM_RERANK_MAX_CAND = 1024  # multi-vector rerank
@@ -915,6 +917,41 @@ class Context:
                                    C.byref(t) if timing else None))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
+    # ---- product-quantized search -----------------------------------------------------------------------------------
+    def pq_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False):
+        """qk_pq_search: per query, the fetch_k rows of its probed lists with the smallest sum of lookup-table entries over the
+        store's PQ codes -- ties by arena row --, re-scored on the float32 rows; the k best under (exact key, id).  Returns (ids [Q, k] padded
+        with -1, dist [Q, k] padded as search pads -- None where not wanted --[, timing]) on x's device."""
+        x = _f32(x)
+        Q = x.shape[0]
+        mem = _mem_of(x)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1  # (the library refuses such a k before it writes: the buffers only have to exist)
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_pq_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
+                                     metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                                     C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
+
+    def pq_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False):
+        """qk_pq_scan: pq_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
+        nothing."""
+        x, pids = _f32(x), _i64(pids)
+        Q = x.shape[0]
+        pids = _pids_rows(pids, Q)
+        mem = _mem_of(x, pids)
+        k, fetch_k = int(k), int(fetch_k)
+        kk = k if k >= 1 else 1
+        ids = _empty_like_mem((Q, kk), np.int64, x)
+        dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
+        t = QkTiming()
+        check(self.lib.qk_pq_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
+                                   fetch_k, metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
+                                   C.byref(t) if timing else None))
+        return (ids, dist, timing_dict(t)) if timing else (ids, dist)
+
     def search_aps(self, parent, store, x, k, metric, recall_target, recompute_threshold=0.001, use_precomputed=True,
                    initial_search_fraction=0.02, timing=False):
         """recall-target search (adaptive partition scanning).  Returns (ids, dist, nscanned[, timing])."""
@@ -1270,6 +1307,34 @@ class Store:
     def bin_drop(self):
         """free the sign-bit mirror (qk_store_bin_drop); the next binary search builds it again"""
         check(self.lib.qk_store_bin_drop(self.h))
+
+    def pq_set_codebooks(self, codebooks):
+        """the codebooks of product-quantized search (qk_store_pq_set_codebooks): float32 [M, 256, d / M], kept until pq_drop(True)"""
+        cb = np.ascontiguousarray(codebooks.cpu().numpy() if hasattr(codebooks, "cpu") else codebooks, np.float32)
+        if cb.ndim != 3 or cb.shape[1] != 256 or cb.shape[0] * cb.shape[2] != self.d:
+            raise ValueError("codebooks must be [M, 256, d / M] with d = %d, got %s" % (self.d, tuple(cb.shape)))
+        check(self.lib.qk_store_pq_set_codebooks(self.h, int(cb.shape[0]), _ptr(cb)))
+
+    def pq_codebooks(self):
+        """the store's codebooks as float32 [M, 256, d / M] (qk_store_pq_codebooks)"""
+        info = self.pq_info()
+        cb = np.empty((max(info["M"], 1), 256, max(info["dsub"], 1)), np.float32)
+        check(self.lib.qk_store_pq_codebooks(self.h, _ptr(cb)))
+        return cb
+
+    def pq_train(self, ctx, M, max_rows=65536, niter=10, seed=0):
+        """train M codebooks of 256 codewords on a seeded sample of up to max_rows live rows (qk_store_pq_train)"""
+        check(self.lib.qk_store_pq_train(ctx.h, self.h, int(M), int(max_rows), int(niter), int(seed)))
+
+    def pq_info(self):
+        """{M, dsub, codebooks, valid, bytes} of product-quantized search's state on the store (qk_store_pq_info)"""
+        m, ds, hc, v, b = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+        check(self.lib.qk_store_pq_info(self.h, C.byref(m), C.byref(ds), C.byref(hc), C.byref(v), C.byref(b)))
+        return {"M": m.value, "dsub": ds.value, "codebooks": bool(hc.value), "valid": bool(v.value), "bytes": int(b.value)}
+
+    def pq_drop(self, drop_codebooks=False):
+        """free the PQ codes and, where asked, the codebooks (qk_store_pq_drop); the next call builds the codes again"""
+        check(self.lib.qk_store_pq_drop(self.h, 1 if drop_codebooks else 0))
 
     def sq8_drop(self):
         """free the int8 code mirror (qk_store_sq8_drop); the next quantized search builds it again"""

@@ -246,6 +246,18 @@ PYBIND11_MODULE(_bindings, m) {
               return py::make_tuple(k, fetch_k);
           },
           py::arg("d"), py::arg("k"), py::arg("fetch_k"), "the arguments of binary_search -> (k, fetch_k); needs no device (where.py's lower_bin)");
+    m.def("lower_pq",
+          [](int64_t d, int64_t k, int64_t fetch_k) {
+              lower_pq(d, k, fetch_k);
+              return py::make_tuple(k, fetch_k);
+          },
+          py::arg("d"), py::arg("k"), py::arg("fetch_k"), "the arguments of pq_search -> (k, fetch_k); needs no device (where.py's lower_pq)");
+    m.def("lower_pq_codebooks",
+          [](int64_t d, int64_t num_codebooks) {
+              lower_pq_codebooks(d, num_codebooks);
+              return num_codebooks;
+          },
+          py::arg("d"), py::arg("num_codebooks"), "the number of sub-quantizers of train_pq -> M; needs no device (where.py's lower_pq_codebooks)");
     py::register_exception_translator([](std::exception_ptr p) {
         try {
             if (p) std::rethrow_exception(p);
@@ -390,6 +402,12 @@ PYBIND11_MODULE(_bindings, m) {
              "extension: rank the probed rows by exact integer keys over int8 codes, re-score the fetch_k best on the float32 rows")
         .def("binary_search", &QuakeIndex::binary_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
              "extension: rank the probed rows by Hamming distance over one sign bit per coordinate, re-score the fetch_k best on the float32 rows")
+        .def("pq_search", &QuakeIndex::pq_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
+             "extension: rank the probed rows by a sum of lookup-table entries over one PQ code byte per sub-space, re-score the fetch_k best on the float32 rows")
+        .def("train_pq", &QuakeIndex::train_pq, py::arg("num_codebooks"), py::arg("max_rows") = 65536, py::arg("niter") = 10, py::arg("seed") = 0,
+             "extension: train the codebooks of pq_search on a seeded sample of the index's rows")
+        .def("set_pq_codebooks", &QuakeIndex::set_pq_codebooks, py::arg("codebooks"),
+             "extension: supply the codebooks of pq_search, float32 [num_codebooks, 256, d / num_codebooks]")
         .def("diverse_search", &QuakeIndex::diverse_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
              py::arg("lambda_mult") = 0.5,
              "extension: per query, search_params.k of its fetch_k nearest vectors (what search() returns with k = fetch_k) chosen "

@@ -367,6 +367,49 @@ shared_ptr<SearchResult> QuakeIndex::binary_search(Tensor x, shared_ptr<SearchPa
     return query_coordinator_->binary_search(x, sp, fetch_k);
 }
 
+void lower_pq(int64_t d, int64_t k, int64_t fetch_k) {
+    const std::string who = "[QuakeIndex::pq_search()]";
+    if (k < 1) throw std::runtime_error(who + " k=" + std::to_string(k) + " must be at least 1");
+    if (fetch_k < k) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must be at least k=" + std::to_string(k));
+    if (k > QK_MAX_K) throw std::runtime_error(who + " k=" + std::to_string(k) + " must not exceed " + std::to_string(QK_MAX_K));
+    if (fetch_k > QK_PQ_MAX_FETCH)
+        throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must not exceed " + std::to_string(QK_PQ_MAX_FETCH));
+    if (d > QK_MAX_D) throw std::runtime_error(who + " d=" + std::to_string(d) + " must not exceed " + std::to_string(QK_MAX_D));
+}
+
+void lower_pq_codebooks(int64_t d, int64_t M, const std::string &who) {
+    if (M < 1) throw std::runtime_error(who + " num_codebooks=" + std::to_string(M) + " must be at least 1");
+    if (M > QK_PQ_MAX_M) throw std::runtime_error(who + " num_codebooks=" + std::to_string(M) + " must not exceed " + std::to_string(QK_PQ_MAX_M));
+    if (d % M != 0) throw std::runtime_error(who + " num_codebooks=" + std::to_string(M) + " must divide d=" + std::to_string(d));
+    if (d / M > QK_PQ_MAX_DSUB)
+        throw std::runtime_error(who + " d / num_codebooks = " + std::to_string(d / M) + " must not exceed " + std::to_string(QK_PQ_MAX_DSUB));
+}
+
+shared_ptr<SearchResult> QuakeIndex::pq_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k) {
+    if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::pq_search()] No query coordinator. Did you build the index?");
+    return query_coordinator_->pq_search(x, sp, fetch_k);
+}
+
+void QuakeIndex::train_pq(int64_t num_codebooks, int64_t max_rows, int64_t niter, int64_t seed) {
+    const std::string who = "[QuakeIndex::train_pq()]";
+    require_built((who + " No partition manager. Index not built?").c_str());
+    if (partition_manager_->group()) throw NotImplemented(who + " product quantization is not supported with num_workers > 0");
+    lower_pq_codebooks(partition_manager_->d(), num_codebooks, who);
+    qk_check(qk_store_pq_train(partition_manager_->ctx(), partition_manager_->store(), (int)num_codebooks, max_rows, (int)niter, (uint64_t)seed));
+}
+
+void QuakeIndex::set_pq_codebooks(Tensor codebooks) {
+    const std::string who = "[QuakeIndex::set_pq_codebooks()]";
+    require_built((who + " No partition manager. Index not built?").c_str());
+    if (partition_manager_->group()) throw NotImplemented(who + " product quantization is not supported with num_workers > 0");
+    Tensor cb = codebooks.to(torch::kCPU).to(torch::kFloat32).contiguous();
+    const int64_t d = partition_manager_->d();
+    if (cb.dim() != 3 || cb.size(1) != 256 || cb.size(0) * cb.size(2) != d)
+        throw std::runtime_error(who + " codebooks must be [num_codebooks, 256, d / num_codebooks] with d=" + std::to_string(d));
+    lower_pq_codebooks(d, cb.size(0), who);
+    qk_check(qk_store_pq_set_codebooks(partition_manager_->store(), (int)cb.size(0), cb.data_ptr<float>()));
+}
+
 shared_ptr<SearchFilter> QuakeIndex::make_filter(Tensor ids, bool exclude) {
     require_built("[QuakeIndex::make_filter()] No partition manager. Index not built?");
     qk_store *s = partition_manager_->store();

@@ -1224,8 +1224,12 @@ shared_ptr<SearchResult> QueryCoordinator::binary_search(Tensor x, shared_ptr<Se
     return code_search(x, sp, fetch_k, 2);
 }
 
+shared_ptr<SearchResult> QueryCoordinator::pq_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k) {
+    return code_search(x, sp, fetch_k, 3);
+}
+
 shared_ptr<SearchResult> QueryCoordinator::code_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, int form) {
-    const std::string name = form == 2 ? "binary_search" : "quantized_search";
+    const std::string name = form == 3 ? "pq_search" : form == 2 ? "binary_search" : "quantized_search";
     const std::string who = "[QuakeIndex::" + name + "()]";
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::" + name + "] partition_manager_ is null.");
     if (sp->filter || !sp->filters.empty() || sp->query_filter.defined() || sp->filters_exact_rows != 0 || sp->filter_exact_rows != 0 ||
@@ -1237,7 +1241,9 @@ shared_ptr<SearchResult> QueryCoordinator::code_search(Tensor x, shared_ptr<Sear
     if (partition_manager_->group()) throw NotImplemented(who + " " + name + " is not supported with num_workers > 0");
     if (!store) throw std::runtime_error("[QueryCoordinator::" + name + "] partitions are not initialized.");
     if (!parent_) throw NotImplemented(who + " " + name + " is not supported by a flat index (no lists of its own)");
-    if (form == 2)
+    if (form == 3)
+        lower_pq(partition_manager_->d(), sp->k, fetch_k);
+    else if (form == 2)
         lower_bin(partition_manager_->d(), sp->k, fetch_k);
     else
         lower_sq8(partition_manager_->d(), sp->k, fetch_k, form == 1);
@@ -1272,7 +1278,7 @@ shared_ptr<SearchResult> QueryCoordinator::code_search(Tensor x, shared_ptr<Sear
     auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
     res->ids = torch::empty({Q, k}, i64);
     res->distances = torch::empty({Q, k}, i64.dtype(torch::kFloat32));
-    qk_check((form == 2 ? qk_bin_search : form == 1 ? qk_sq8_search_deep : qk_sq8_search)(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, (int)k, (int)fetch_k, (int)metric_,
+    qk_check((form == 3 ? qk_pq_search : form == 2 ? qk_bin_search : form == 1 ? qk_sq8_search_deep : qk_sq8_search)(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, (int)k, (int)fetch_k, (int)metric_,
                                                          res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, &tm));
     ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
     ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);

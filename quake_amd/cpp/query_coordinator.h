@@ -80,7 +80,9 @@ public:
     shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, bool deep = false);
     // extension (qk_bin_search): candidates by sign bits and Hamming distance, exact re-score (lower_bin runs behind the refusals)
     shared_ptr<SearchResult> binary_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
-    // the body of both: form 0 quantized_search, 1 its deep form, 2 binary_search
+    // extension (qk_pq_search): candidates by PQ codes and a lookup table per query, exact re-score (lower_pq runs behind the refusals)
+    shared_ptr<SearchResult> pq_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
+    // the body of all three: form 0 quantized_search, 1 its deep form, 2 binary_search, 3 pq_search
     shared_ptr<SearchResult> code_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, int form);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

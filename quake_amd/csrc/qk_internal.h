@@ -328,7 +328,24 @@ struct qk_store {
     int64_t bin_cap_rows = 0;
     uint64_t bin_version = 0;
     int bin_metric = -1;  // -1: none
+    // product-quantized search (qk_pq.hip): M sub-quantizers of 256 float32 codewords over dsub = d / M columns each.
+    // The codebooks are state of the store -- set or trained, kept across every mutation, for both metrics --, the codes a mirror
+    // with bin_*'s life cycle: code row r is arena row r, a row's codes are 16-byte words of 16 sub-quantizers (padding bytes 0), the
+    // 16 words of a tile side by side, the words of a tile one after the other.  Not persisted
+    int pq_M = 0;                    // 0: no codebooks
+    float *pq_cb = nullptr;          // device [M][256][dsub]
+    float *pq_cbn = nullptr;         // device [M][256]: dot(w, w), the canonical chain
+    int32_t *pq_bad = nullptr;       // device [1]: the smallest list that holds a non-finite value (k_pq_encode)
+    void *pq_codes = nullptr;
+    int64_t pq_cap_rows = 0;
+    uint64_t pq_version = 0;
+    bool pq_valid = false;
 };
+inline int qk_pq_nw(int M) { return (M + 15) / 16; }
+// the PQ code mirror of `s` (table synced, codebooks present), built on ctx's stream if the store or the codebooks changed.
+// QK_ERR_UNSUPPORTED where a live row holds a non-finite value; QK_ERR_OOM, and nothing else changed, without memory
+int qk_store_pq_mirror(qk_ctx *ctx, qk_store *s);
+void qk_store_pq_free(qk_store *s, bool codebooks);
 inline int qk_sq8_nblk(int d) { return (d + 63) / 64; }
 inline int qk_bin_nbw(int d) { return (d + 127) / 128; }
 // the sign-bit mirror of `s` (table synced) for `metric`, built on ctx's stream if the store or the metric changed.  L2:

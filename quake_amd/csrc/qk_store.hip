@@ -206,6 +206,7 @@ int qk_store_sync_table(qk_store *s) {
     s->pnorms_dim = 0;        // (so do the prefix norms of funnel search: the next L2 funnel call rebuilds them)
     s->sq8_metric = -1;       // (and the int8 codes of quantized search: the scale depends on every live row)
     s->bin_metric = -1;       // (and the sign bits of binary search)
+    s->pq_valid = false;      // (and the PQ codes of product-quantized search; the codebooks stay)
     qk_ctx *c = s->ctx;
     int64_t n = (int64_t)s->parts.size();
     if (n > s->table_cap) {
@@ -683,6 +684,7 @@ int qk_store_destroy(qk_store *s) {
     qk_store_prefix_free(s);
     qk_store_sq8_free(s);
     qk_store_bin_free(s);
+    qk_store_pq_free(s, true);
     if (s->shadow_stats) hipFree(s->shadow_stats);
     delete s;
     return QK_OK;
@@ -1357,7 +1359,8 @@ int64_t qk_store_device_bytes(qk_store *s) {
     return s->cap_rows * ((int64_t)s->dpad * 4 + 4 + 8) + (s->shadow ? s->shadow_cap_rows * (int64_t)qk_shadow_nblk(s->nblk) * 64 : 0) +
            (s->pnorms ? s->pnorms_cap_rows * 4 : 0) +  // (+ the prefix norms of funnel search, qk_funnel.hip)
            (s->sq8_codes ? s->sq8_cap_rows * ((int64_t)qk_sq8_nblk(s->d) * 64 + 4) : 0) +  // (+ the int8 codes of quantized search, qk_sq8.hip)
-           (s->bin_codes ? s->bin_cap_rows * (int64_t)qk_bin_nbw(s->d) * 16 : 0);  // (+ the sign bits of binary search, qk_bin.hip)
+           (s->bin_codes ? s->bin_cap_rows * (int64_t)qk_bin_nbw(s->d) * 16 : 0) +  // (+ the sign bits of binary search, qk_bin.hip)
+           (s->pq_codes ? s->pq_cap_rows * (int64_t)qk_pq_nw(s->pq_M) * 16 : 0);  // (+ the PQ codes of product-quantized search, qk_pq.hip)
 }
 
 int qk_store_shadow_info(qk_store *s, int *valid, int64_t *bytes, int64_t *builds) {

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_bin, lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_rerank, lower_sq8
+from .where import lower_bin, lower_pq, lower_pq_codebooks, lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_rerank, lower_sq8
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -1717,8 +1717,46 @@ class QuakeIndex:
                                  lambda xd, nprobe, k, fk: self._ctx.bin_search(self.parent._store, self._store, xd, nprobe, k, fk, self.metric_,
                                                                                 timing=True))
 
+    def pq_search(self, x, search_params, fetch_k):
+        """extension (no reference counterpart): product-quantized search, product quantization with oversampling and rescoring --
+        the rows of each query's probed lists (chosen as search() chooses them) are ranked by the sum of M lookup-table entries over
+        one code byte per sub-space (train_pq / set_pq_codebooks first), 16 ceil(M / 16) bytes per row; the fetch_k best of them --
+        ties by position in the index -- are re-scored on the float32 rows, and search_params.k of those are returned under (exact
+        distance, id), with the distances search() reports.  Approximate by design, defined bit for bit (include/quake_hip.h,
+        "product-quantized search"): a fetch_k that covers the probed rows is search().  1 <= k <= 448, k <= fetch_k <= 4096, nprobe
+        <= 1024.  The codes are rebuilt by the first call after the index changed; the codebooks stay.  Filters, recall_target,
+        num_workers > 0 and a flat index are not served (NotImplementedError); an index without codebooks or with a stored value that
+        is not finite is a RuntimeError.  Returns a SearchResult on x's device."""
+        return self._code_search(x, search_params, "pq_search", lambda d, k, who: lower_pq(d, k, fetch_k, who),
+                                 lambda xd, nprobe, k, fk: self._ctx.pq_search(self.parent._store, self._store, xd, nprobe, k, fk, self.metric_,
+                                                                               timing=True))
+
+    def _pq_store(self, who):
+        self._require_built(who + " No partition manager. Index not built?")
+        if isinstance(self._store, capi.Group):
+            raise NotImplementedError(who + " product quantization is not supported with num_workers > 0")
+        return self._store
+
+    def train_pq(self, num_codebooks, max_rows=65536, niter=10, seed=0):
+        """extension: train the codebooks of pq_search -- num_codebooks sub-quantizers of 256 codewords each, k-means (niter Lloyd
+        iterations) on a seeded sample of up to max_rows of the index's rows.  They stay until they are replaced, whatever is added
+        to or removed from the index; they are not saved with it."""
+        who = "[QuakeIndex::train_pq()]"
+        s = self._pq_store(who)
+        s.pq_train(self._ctx, lower_pq_codebooks(int(self._d), num_codebooks, who), max_rows, niter, seed)
+
+    def set_pq_codebooks(self, codebooks):
+        """extension: supply the codebooks of pq_search, float32 [num_codebooks, 256, d / num_codebooks]"""
+        who = "[QuakeIndex::set_pq_codebooks()]"
+        s = self._pq_store(who)
+        cb = torch.as_tensor(codebooks, dtype=torch.float32).cpu().contiguous()
+        if cb.dim() != 3 or cb.shape[1] != 256 or cb.shape[0] * cb.shape[2] != int(self._d):
+            raise RuntimeError("%s codebooks must be [num_codebooks, 256, d / num_codebooks] with d=%d" % (who, int(self._d)))
+        lower_pq_codebooks(int(self._d), int(cb.shape[0]), who)
+        s.pq_set_codebooks(cb.numpy())
+
     def _code_search(self, x, search_params, name, lower, call):
-        """the body of quantized_search and binary_search: the refusals, lower(d, k, who) -> (k, fetch_k), call(x, nprobe, k, fetch_k)
+        """the body of quantized_search, binary_search and pq_search: the refusals, lower(d, k, who) -> (k, fetch_k), call(x, nprobe, k, fetch_k)
         -> (ids, distances, timing)"""
         who = "[QuakeIndex::%s()]" % name
         self._require_built(who + " No query coordinator. Did you build the index?")

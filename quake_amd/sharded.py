@@ -308,6 +308,11 @@ class ShardedIndex:
         and its candidates are its own fetch_k best, not the index's."""
         raise NotImplementedError("[ShardedIndex::binary_search()] binary_search is not supported by sharded.py")
 
+    def pq_search(self, q, nprobe, k, fetch_k):
+        """product-quantized search (QuakeIndex.pq_search, qk_pq_search) has no sharded form: a shard's candidates are its own
+        fetch_k best, not the index's, and its codebooks would be trained on its own rows."""
+        raise NotImplementedError("[ShardedIndex::pq_search()] pq_search is not supported by sharded.py")
+
     def diverse_search(self, q, nprobe, k, fetch_k, lambda_mult=0.5):
         """diversified search (QuakeIndex.diverse_search, qk_diverse_search) has no sharded form: the re-ranking needs the vectors
         of every candidate of a query, which live on different ranks"""

@@ -6,7 +6,7 @@ Python integers of any size and are saturated, not wrapped: a comparison with a 
 integers (x < 2^70 holds for every int64 x, x == 2^70 for none).  lower_expr adds the OR of up to 8 such conjunctions (`any_of`) and
 the value sets ("col", "in" | "not_in", [v, ...]) of qk_filter_create_expr; a set value outside int64 is dropped by the same rule.
 lower_edges normalises the histogram edges of facet statistics (QuakeIndex.facet_stats, Context.facet_stats_search), lower_order
-the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_funnel those of funnel search (QuakeIndex.funnel_search), lower_sq8 those of quantized search (QuakeIndex.quantized_search), lower_bin those of binary search (QuakeIndex.binary_search), lower_maxsim those of multi-vector search
+the arguments of ordered search (QuakeIndex.ordered_search), lower_diverse those of diversified search (QuakeIndex.diverse_search), lower_funnel those of funnel search (QuakeIndex.funnel_search), lower_sq8 those of quantized search (QuakeIndex.quantized_search), lower_bin those of binary search (QuakeIndex.binary_search), lower_pq / lower_pq_codebooks those of product-quantized search (QuakeIndex.pq_search, train_pq), lower_maxsim those of multi-vector search
 (QuakeIndex.multi_vector_search), lower_rerank those of multi-vector rerank (QuakeIndex.multi_vector_rerank).
 Pure Python: importable without the library or a GPU."""
 
@@ -30,6 +30,8 @@ QK_FUNNEL_MAX_PREFIX = 1024
 QK_SQ8_MAX_D = 2048
 QK_SQ8_MAX_FETCH = 4096
 QK_BIN_MAX_FETCH = 4096
+QK_PQ_MAX_FETCH = 4096
+QK_PQ_MAX_M, QK_PQ_MAX_DSUB = 128, 64
 QK_MAX_D = 8192
 QK_MAXSIM_MAX_TOKENS, QK_MAXSIM_MAX_K = 64, 1024
 QK_MAXSIM_RERANK_MAX_CAND = 1024
@@ -315,6 +317,40 @@ def lower_bin(d, k, fetch_k, who="[QuakeIndex::binary_search()]"):
     if d > QK_MAX_D:
         raise RuntimeError("%s d=%d must not exceed %d" % (who, d, QK_MAX_D))
     return k, fetch_k
+
+
+def lower_pq(d, k, fetch_k, who="[QuakeIndex::pq_search()]"):
+    """The arguments of product-quantized search (include/quake_hip.h, "product-quantized search") over vectors of d columns ->
+    (k, fetch_k): 1 <= k <= min(fetch_k, QK_MAX_K), fetch_k <= QK_PQ_MAX_FETCH, d <= QK_MAX_D.  RuntimeError, in this order: a value
+    that is no integer, k < 1, fetch_k < k, k above its limit, fetch_k above its limit, d above its limit."""
+    k = _int(k, who + " k:")
+    fetch_k = _int(fetch_k, who + " fetch_k:")
+    if k < 1:
+        raise RuntimeError("%s k=%d must be at least 1" % (who, k))
+    if fetch_k < k:
+        raise RuntimeError("%s fetch_k=%d must be at least k=%d" % (who, fetch_k, k))
+    if k > QK_MAX_K:
+        raise RuntimeError("%s k=%d must not exceed %d" % (who, k, QK_MAX_K))
+    if fetch_k > QK_PQ_MAX_FETCH:
+        raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_PQ_MAX_FETCH))
+    if d > QK_MAX_D:
+        raise RuntimeError("%s d=%d must not exceed %d" % (who, d, QK_MAX_D))
+    return k, fetch_k
+
+
+def lower_pq_codebooks(d, num_codebooks, who="[QuakeIndex::train_pq()]"):
+    """The number of sub-quantizers M of product-quantized search over vectors of d columns -> M.  RuntimeError, in this order: no
+    integer, M < 1, M > QK_PQ_MAX_M, M does not divide d, d / M > QK_PQ_MAX_DSUB."""
+    M = _int(num_codebooks, who + " num_codebooks:")
+    if M < 1:
+        raise RuntimeError("%s num_codebooks=%d must be at least 1" % (who, M))
+    if M > QK_PQ_MAX_M:
+        raise RuntimeError("%s num_codebooks=%d must not exceed %d" % (who, M, QK_PQ_MAX_M))
+    if d % M != 0:
+        raise RuntimeError("%s num_codebooks=%d must divide d=%d" % (who, M, d))
+    if d // M > QK_PQ_MAX_DSUB:
+        raise RuntimeError("%s d / num_codebooks = %d must not exceed %d" % (who, d // M, QK_PQ_MAX_DSUB))
+    return M
 
 
 def lower_maxsim(columns, group_by, k, T, n_tokens=None, missing=None, metric="ip", who="[QuakeIndex::multi_vector_search()]"):
