@@ -1105,6 +1105,35 @@ QK_API int qk_bin_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, cons
 QK_API int qk_store_bin_info(qk_store *s, int *valid, int64_t *bytes, int64_t *cache_rows);
 QK_API int qk_store_bin_drop(qk_store *s);
 
+/* Binary search, rescored: a cascade bits -> int8 -> float32.  The shortlist that the sign bits rank is re-ranked on
+ * the store's int8 codes -- a quarter of the bytes per gathered row -- and float32 rows are fetched only for the rescore_k rows that
+ * survive.  The arguments are qk_bin_search's / qk_bin_scan's with rescore_k behind fetch_k; 1 <= k <= rescore_k <= fetch_k.
+ *   1. Stage 1: steps 1-4 of binary search, unchanged -- per query, the fetch_k rows of its probed lists that are smallest under
+ *      (Hamming key, arena row).
+ *   2. Stage 2: each of those rows gets quantized search's approximate key, steps 1-4 of "quantized search" -- the store's code
+ *      parameters, row codes, query codes (IP: the query's own scale) and the exact integer key nq + nx - 2 dot / -dot.  The
+ *      rescore_k smallest under (integer key, arena row) survive.
+ *   3. Stage 3: the answer step of binary search -- canonical fp32 key, the k best under (exact key, id), a candidate whose exact
+ *      key is NaN is not returned, padding as in qk_search.
+ *   4. Consequences: rescore_k == fetch_k gives qk_bin_search's row, bit for bit; a fetch_k that covers a query's probed rows gives
+ *      qk_sq8_scan's row for fetch_k = rescore_k; a rescore_k that covers them as well gives qk_search's row.
+ * Arguments: k < 1, fetch_k < k, rescore_k < k or rescore_k > fetch_k: QK_ERR_INVALID; k or rescore_k > QK_MAX_K, fetch_k >
+ * QK_BIN_MAX_FETCH, d > QK_SQ8_MAX_D, more than QK_BIN_MAX_NPROBE lists per query, a flat index without lists of its own:
+ * QK_ERR_UNSUPPORTED; a store with a live row that holds a non-finite value: QK_ERR_UNSUPPORTED in quantized search's words, the
+ * message names the list, for both metrics; Q == 0: QK_OK.  A refusal writes no output.  There is no form for filters, cursors,
+ * qk_search_aps or the device group.
+ * Inside (qk_bin.hip, qk_cascade.hip), one enqueue without a host wait -- except the one-off build of the two mirrors, both before
+ * any launch of the call: k_bin_prep and k_sq8_prep, the coarse step, k_bin_select with fetch_k candidates, k_sq8_rerank -- one
+ * workgroup per query, no global atomics: the query's code tile in LDS, the candidates' code rows gathered 16 per wave and step
+ * with several blocks in flight, v_dot4_i32_i8, the keys in LDS by candidate position, the rescore_k-th key by four rounds of 256
+ * bins, an ordered compaction (ties by position, which is arena order) -- and the exact finish over rescore_k candidates.
+ * timing: as binary search; the re-rank lies behind merge_ms with the finish and is part of total_ms only.  scan_bytes stays the
+ * sign-code bytes.  qk_ctx_last_scan_kernel reports "k_bin_select (sign codes) + k_sq8_rerank (int8 codes)". */
+QK_API int qk_bin_search_rescored(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k,
+                                  int rescore_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_bin_scan_rescored(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k,
+                                int rescore_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+
 /* Product-quantized search: product quantization with oversampling and rescoring.  The d columns are cut into M
  * sub-spaces, each with a learned codebook of 256 codewords; a row is mirrored as M bytes, a query becomes a lookup table, the probed
  * rows are ranked by a sum of M table entries, a shortlist of fetch_k rows is re-scored exactly.  An approximate search by design

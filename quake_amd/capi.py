@@ -883,10 +883,12 @@ class Context:
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
     # ---- binary search -----------------------------------------------------------------------------------
-    def bin_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False):
+    def bin_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False, rescore_k=None):
         """qk_bin_search: per query, the fetch_k rows of its probed lists with the smallest Hamming distance over the store's sign
         bits -- ties by arena row --, re-scored on the float32 rows; the k best under (exact key, id).  Returns (ids [Q, k] padded
-        with -1, dist [Q, k] padded as search pads -- None where not wanted --[, timing]) on x's device."""
+        with -1, dist [Q, k] padded as search pads -- None where not wanted --[, timing]) on x's device.
+        rescore_k: qk_bin_search_rescored -- the fetch_k rows are re-ranked by the integer key over their int8 codes, ties by arena
+        row, and only the rescore_k best are re-scored; None is the call without it."""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
@@ -895,14 +897,17 @@ class Context:
         ids = _empty_like_mem((Q, kk), np.int64, x)
         dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
         t = QkTiming()
-        check(self.lib.qk_bin_search(self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k,
-                                     metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
-                                     C.byref(t) if timing else None))
+        head = (self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k)
+        tail = (metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem, C.byref(t) if timing else None)
+        if rescore_k is None:
+            check(self.lib.qk_bin_search(*head, *tail))
+        else:
+            check(self.lib.qk_bin_search_rescored(*head, int(rescore_k), *tail))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
-    def bin_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False):
+    def bin_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False, rescore_k=None):
         """qk_bin_scan: bin_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
-        nothing."""
+        nothing.  rescore_k: qk_bin_scan_rescored."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
         pids = _pids_rows(pids, Q)
@@ -912,9 +917,12 @@ class Context:
         ids = _empty_like_mem((Q, kk), np.int64, x)
         dist = _empty_like_mem((Q, kk), np.float32, x) if want_dist else None
         t = QkTiming()
-        check(self.lib.qk_bin_scan(self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k,
-                                   fetch_k, metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem,
-                                   C.byref(t) if timing else None))
+        head = (self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k, fetch_k)
+        tail = (metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem, C.byref(t) if timing else None)
+        if rescore_k is None:
+            check(self.lib.qk_bin_scan(*head, *tail))
+        else:
+            check(self.lib.qk_bin_scan_rescored(*head, int(rescore_k), *tail))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
     # ---- product-quantized search -----------------------------------------------------------------------------------

@@ -246,6 +246,13 @@ PYBIND11_MODULE(_bindings, m) {
               return py::make_tuple(k, fetch_k);
           },
           py::arg("d"), py::arg("k"), py::arg("fetch_k"), "the arguments of binary_search -> (k, fetch_k); needs no device (where.py's lower_bin)");
+    m.def("lower_bin_rescored",
+          [](int64_t d, int64_t k, int64_t fetch_k, int64_t rescore_k) {
+              lower_bin_rescored(d, k, fetch_k, rescore_k);
+              return py::make_tuple(k, fetch_k, rescore_k);
+          },
+          py::arg("d"), py::arg("k"), py::arg("fetch_k"), py::arg("rescore_k"),
+          "the arguments of binary_search with rescore_k -> (k, fetch_k, rescore_k); needs no device (where.py's lower_bin_rescored)");
     m.def("lower_pq",
           [](int64_t d, int64_t k, int64_t fetch_k) {
               lower_pq(d, k, fetch_k);
@@ -400,8 +407,16 @@ PYBIND11_MODULE(_bindings, m) {
              "extension: rank the probed rows by their first prefix_dim columns, re-score the fetch_k best on the full vector")
         .def("quantized_search", &QuakeIndex::quantized_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"), py::arg("deep") = false,
              "extension: rank the probed rows by exact integer keys over int8 codes, re-score the fetch_k best on the float32 rows")
-        .def("binary_search", &QuakeIndex::binary_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
-             "extension: rank the probed rows by Hamming distance over one sign bit per coordinate, re-score the fetch_k best on the float32 rows")
+        .def(
+            "binary_search",
+            [](QuakeIndex &self, Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, std::optional<int64_t> rescore_k) {
+                // (None is the call without the option; any number, a negative one included, goes through lower_bin_rescored)
+                if (rescore_k && *rescore_k < 0) lower_bin_rescored(0, sp->k, fetch_k, *rescore_k);
+                return self.binary_search(x, sp, fetch_k, rescore_k ? *rescore_k : -1);
+            },
+            py::arg("x"), py::arg("search_params"), py::arg("fetch_k"), py::arg("rescore_k") = py::none(),
+            "extension: rank the probed rows by Hamming distance over one sign bit per coordinate, re-score the fetch_k best on the float32 rows; "
+            "rescore_k: re-rank the fetch_k rows on their int8 codes in between and re-score only the rescore_k best")
         .def("pq_search", &QuakeIndex::pq_search, py::arg("x"), py::arg("search_params"), py::arg("fetch_k"),
              "extension: rank the probed rows by a sum of lookup-table entries over one PQ code byte per sub-space, re-score the fetch_k best on the float32 rows")
         .def("train_pq", &QuakeIndex::train_pq, py::arg("num_codebooks"), py::arg("max_rows") = 65536, py::arg("niter") = 10, py::arg("seed") = 0,

@@ -362,9 +362,24 @@ void lower_bin(int64_t d, int64_t k, int64_t fetch_k) {
     if (d > QK_MAX_D) throw std::runtime_error(who + " d=" + std::to_string(d) + " must not exceed " + std::to_string(QK_MAX_D));
 }
 
-shared_ptr<SearchResult> QuakeIndex::binary_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k) {
+void lower_bin_rescored(int64_t d, int64_t k, int64_t fetch_k, int64_t rescore_k) {
+    const std::string who = "[QuakeIndex::binary_search()]";
+    if (k < 1) throw std::runtime_error(who + " k=" + std::to_string(k) + " must be at least 1");
+    if (fetch_k < k) throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must be at least k=" + std::to_string(k));
+    if (rescore_k < k) throw std::runtime_error(who + " rescore_k=" + std::to_string(rescore_k) + " must be at least k=" + std::to_string(k));
+    if (rescore_k > fetch_k)
+        throw std::runtime_error(who + " rescore_k=" + std::to_string(rescore_k) + " must be at most fetch_k=" + std::to_string(fetch_k));
+    if (k > QK_MAX_K) throw std::runtime_error(who + " k=" + std::to_string(k) + " must not exceed " + std::to_string(QK_MAX_K));
+    if (rescore_k > QK_MAX_K)
+        throw std::runtime_error(who + " rescore_k=" + std::to_string(rescore_k) + " must not exceed " + std::to_string(QK_MAX_K));
+    if (fetch_k > QK_BIN_MAX_FETCH)
+        throw std::runtime_error(who + " fetch_k=" + std::to_string(fetch_k) + " must not exceed " + std::to_string(QK_BIN_MAX_FETCH));
+    if (d > QK_SQ8_MAX_D) throw std::runtime_error(who + " d=" + std::to_string(d) + " must not exceed " + std::to_string(QK_SQ8_MAX_D));
+}
+
+shared_ptr<SearchResult> QuakeIndex::binary_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, int64_t rescore_k) {
     if (!query_coordinator_) throw std::runtime_error("[QuakeIndex::binary_search()] No query coordinator. Did you build the index?");
-    return query_coordinator_->binary_search(x, sp, fetch_k);
+    return query_coordinator_->binary_search(x, sp, fetch_k, rescore_k);
 }
 
 void lower_pq(int64_t d, int64_t k, int64_t fetch_k) {

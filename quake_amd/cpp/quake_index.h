@@ -72,6 +72,8 @@ void lower_funnel(int64_t d, int64_t k, int64_t prefix_dim, int64_t fetch_k);
 void lower_sq8(int64_t d, int64_t k, int64_t fetch_k, bool deep = false);
 // the arguments of binary_search over vectors of d columns (where.py's lower_bin: same rules, same errors, same order)
 void lower_bin(int64_t d, int64_t k, int64_t fetch_k);
+// the arguments of binary_search with rescore_k (where.py's lower_bin_rescored: same rules, same errors, same order)
+void lower_bin_rescored(int64_t d, int64_t k, int64_t fetch_k, int64_t rescore_k);
 // the arguments of pq_search, and the number of sub-quantizers of train_pq / set_pq_codebooks (where.py's lower_pq, lower_pq_codebooks)
 void lower_pq(int64_t d, int64_t k, int64_t fetch_k);
 void lower_pq_codebooks(int64_t d, int64_t num_codebooks, const std::string &who = "[QuakeIndex::train_pq()]");
@@ -169,7 +171,8 @@ public:
     shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, bool deep = false);
     // extension: binary search -- rank the probed rows by the Hamming distance over one sign bit per coordinate, re-score the fetch_k
     // best on the float32 rows, return search_params->k of them under (exact distance, id) (qk_bin_search)
-    shared_ptr<SearchResult> binary_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
+    // rescore_k >= 0: the fetch_k rows are re-ranked on their int8 codes and only the rescore_k best are re-scored (qk_bin_search_rescored)
+    shared_ptr<SearchResult> binary_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, int64_t rescore_k = -1);
     // extension: product-quantized search -- rank the probed rows by the sum of num_codebooks lookup-table entries over one code byte
     // per sub-space, re-score the fetch_k best on the float32 rows (qk_pq_search); the codebooks are trained on a seeded sample of the
     // index's rows (qk_store_pq_train) or supplied as [num_codebooks, 256, d / num_codebooks] and stay until replaced

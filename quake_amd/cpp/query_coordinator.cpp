@@ -1220,15 +1220,16 @@ shared_ptr<SearchResult> QueryCoordinator::quantized_search(Tensor x, shared_ptr
     return code_search(x, sp, fetch_k, deep ? 1 : 0);
 }
 
-shared_ptr<SearchResult> QueryCoordinator::binary_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k) {
-    return code_search(x, sp, fetch_k, 2);
+shared_ptr<SearchResult> QueryCoordinator::binary_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, int64_t rescore_k) {
+    return code_search(x, sp, fetch_k, 2, rescore_k);
 }
 
 shared_ptr<SearchResult> QueryCoordinator::pq_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k) {
     return code_search(x, sp, fetch_k, 3);
 }
 
-shared_ptr<SearchResult> QueryCoordinator::code_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, int form) {
+shared_ptr<SearchResult> QueryCoordinator::code_search(Tensor x, shared_ptr<SearchParams> sp, int64_t fetch_k, int form, int64_t rescore_k) {
+    const bool rescored = form == 2 && rescore_k >= 0;
     const std::string name = form == 3 ? "pq_search" : form == 2 ? "binary_search" : "quantized_search";
     const std::string who = "[QuakeIndex::" + name + "()]";
     if (!partition_manager_) throw std::runtime_error("[QueryCoordinator::" + name + "] partition_manager_ is null.");
@@ -1243,6 +1244,8 @@ shared_ptr<SearchResult> QueryCoordinator::code_search(Tensor x, shared_ptr<Sear
     if (!parent_) throw NotImplemented(who + " " + name + " is not supported by a flat index (no lists of its own)");
     if (form == 3)
         lower_pq(partition_manager_->d(), sp->k, fetch_k);
+    else if (rescored)
+        lower_bin_rescored(partition_manager_->d(), sp->k, fetch_k, rescore_k);
     else if (form == 2)
         lower_bin(partition_manager_->d(), sp->k, fetch_k);
     else
@@ -1278,8 +1281,12 @@ shared_ptr<SearchResult> QueryCoordinator::code_search(Tensor x, shared_ptr<Sear
     auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(xq.device());
     res->ids = torch::empty({Q, k}, i64);
     res->distances = torch::empty({Q, k}, i64.dtype(torch::kFloat32));
-    qk_check((form == 3 ? qk_pq_search : form == 2 ? qk_bin_search : form == 1 ? qk_sq8_search_deep : qk_sq8_search)(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, (int)k, (int)fetch_k, (int)metric_,
-                                                         res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, &tm));
+    if (rescored)
+        qk_check(qk_bin_search_rescored(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, (int)k, (int)fetch_k, (int)rescore_k, (int)metric_,
+                                        res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, &tm));
+    else
+        qk_check((form == 3 ? qk_pq_search : form == 2 ? qk_bin_search : form == 1 ? qk_sq8_search_deep : qk_sq8_search)(ctx, parent_->store(), store, xq.data_ptr<float>(), Q, nprobe, (int)k, (int)fetch_k, (int)metric_,
+                                                             res->ids.data_ptr<int64_t>(), res->distances.data_ptr<float>(), mem, &tm));
     ti->job_enqueue_time_ns = (int64_t)(tm.group_ms * 1e6);
     ti->job_wait_time_ns = (int64_t)(tm.scan_ms * 1e6);
     ti->result_aggregate_time_ns = (int64_t)(tm.merge_ms * 1e6);

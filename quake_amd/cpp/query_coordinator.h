@@ -79,11 +79,12 @@ public:
     // extension (qk_sq8_search; deep: qk_sq8_search_deep): candidates by int8 codes, exact re-score (lower_sq8 runs behind the refusals)
     shared_ptr<SearchResult> quantized_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, bool deep = false);
     // extension (qk_bin_search): candidates by sign bits and Hamming distance, exact re-score (lower_bin runs behind the refusals)
-    shared_ptr<SearchResult> binary_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
+    // rescore_k >= 0: qk_bin_search_rescored, a re-rank on the int8 codes in between (lower_bin_rescored)
+    shared_ptr<SearchResult> binary_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, int64_t rescore_k = -1);
     // extension (qk_pq_search): candidates by PQ codes and a lookup table per query, exact re-score (lower_pq runs behind the refusals)
     shared_ptr<SearchResult> pq_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k);
     // the body of all three: form 0 quantized_search, 1 its deep form, 2 binary_search, 3 pq_search
-    shared_ptr<SearchResult> code_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, int form);
+    shared_ptr<SearchResult> code_search(Tensor x, shared_ptr<SearchParams> search_params, int64_t fetch_k, int form, int64_t rescore_k = -1);
     shared_ptr<SearchResult> scan_partitions(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);
     shared_ptr<SearchResult> batched_serial_scan(Tensor x, Tensor partition_ids, shared_ptr<SearchParams> search_params);

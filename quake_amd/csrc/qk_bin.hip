@@ -14,6 +14,7 @@
 //   k_bin_select       one workgroup per query, no global atomics: the query's lists ordered by arena offset, pass A (keys by
 //                      popcount, a histogram of d + 1 bins and -- where the probed rows fit -- the keys themselves in LDS), the cut key
 //                      by a prefix sum, pass B (the rows under the cut and the first ties at it, compacted in walk order)
+//   (k_sq8_prep, k_sq8_rerank: the rescored form only -- "binary search, rescored"; qk_sq8.hip, qk_cascade.hip)
 //   (k_funnel_finish / k_sq8_deep_finish: the exact finish of funnel search and of deep quantized search, unchanged.  Neither reads
 //    anything from the order of its candidates: both pool (exact key, id) by order of arrival and select under (key, id))
 #include "qk_internal.h"
@@ -356,17 +357,23 @@ __global__ __launch_bounds__(256) void k_bin_select(BinSelectParams B) {
     if (B.stat && tid == 0) B.stat[q] = make_uint2(total, nlists);
 }
 
-// the body of both entry points: parent == nullptr && pids == nullptr -> every list
+// the body of the entry points: parent == nullptr && pids == nullptr -> every list.  rescore_k >= 0: the rescored form ("binary search,
+// rescored") -- k_sq8_rerank (qk_cascade.hip) between the selection and the finish, which then sees rescore_k candidates
 int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe, int k,
-               int fetch_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+               int fetch_k, int rescore_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     const int d = s->d;
+    const bool rescored = rescore_k >= 0;
     if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
     if (k < 1) QK_FAIL(QK_ERR_INVALID, "%s: k=%d must be at least 1", who, k);
     if (fetch_k < k) QK_FAIL(QK_ERR_INVALID, "%s: fetch_k=%d must be at least k=%d", who, fetch_k, k);
+    if (rescored && rescore_k < k) QK_FAIL(QK_ERR_INVALID, "%s: rescore_k=%d must be at least k=%d", who, rescore_k, k);
+    if (rescored && rescore_k > fetch_k) QK_FAIL(QK_ERR_INVALID, "%s: rescore_k=%d must be at most fetch_k=%d", who, rescore_k, fetch_k);
     if (Q < 0 || (Q > 0 && (!x || !out_ids))) QK_FAIL(QK_ERR_INVALID, "%s: null argument", who);
     if (mem != QK_MEM_HOST && mem != QK_MEM_DEVICE) QK_FAIL(QK_ERR_INVALID, "%s: mem must be QK_MEM_HOST or QK_MEM_DEVICE", who);
     if (k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: k=%d exceeds QK_MAX_K=%d", who, k, QK_MAX_K);
+    if (rescored && rescore_k > QK_MAX_K) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: rescore_k=%d exceeds QK_MAX_K=%d", who, rescore_k, QK_MAX_K);
     if (fetch_k > QK_BIN_MAX_FETCH) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: fetch_k=%d exceeds QK_BIN_MAX_FETCH=%d", who, fetch_k, QK_BIN_MAX_FETCH);
+    if (rescored && d > QK_SQ8_MAX_D) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: d=%d exceeds QK_SQ8_MAX_D=%d", who, d, QK_SQ8_MAX_D);
     if (d > QK_MAX_D) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: d=%d exceeds QK_MAX_D=%d", who, d, QK_MAX_D);
     if (!parent && !pids && s->nlist == 1)
         QK_FAIL(QK_ERR_UNSUPPORTED, "%s: a flat index without lists of its own takes the dense path, which has no sign code form", who);
@@ -388,17 +395,24 @@ int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     hipStream_t st = ctx->stream;
     const bool host = mem == QK_MEM_HOST;
     const bool l2 = metric == QK_METRIC_L2;
-    const int C = fetch_k, nblk = s->nblk, nbw = qk_bin_nbw(d);
+    const int C = fetch_k, R = rescored ? rescore_k : fetch_k, nblk = s->nblk, nbw = qk_bin_nbw(d), nb8 = qk_sq8_nblk(d);
     // ---- the mirror and the call's buffer: what can refuse or fail for want of memory comes first -----------------------------------
     QK_TRY(qk_store_sync_table(s));
     const int64_t rows_ub = Pq * std::max<int64_t>(s->max_size, 0);  // (walk positions and bin counts are 32-bit)
     if (rows_ub >= ((int64_t)1 << 32)) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: a query could probe %lld rows, 2^32 or more", who, (long long)rows_ub);
+    // (the int8 codes first: a store with a non-finite row is refused in quantized search's words, for both metrics)
+    if (rescored) QK_TRY(qk_store_sq8_mirror(ctx, s, metric));
     QK_TRY(qk_store_bin_mirror(ctx, s, metric));
     const size_t b_q = qk_al256((size_t)Q * nbw * 16), b_c = qk_al256((size_t)Q * C * 8), b_s = qk_al256((size_t)Q * 8);
-    QK_TRY(qk_fn_reserve(ctx, b_q + b_c + b_s));
+    const size_t b_q8 = rescored ? qk_al256((size_t)Q * nb8 * 64) : 0, b_n8 = rescored ? qk_al256((size_t)Q * 4) : 0,
+                 b_c2 = rescored ? qk_al256((size_t)Q * R * 8) : 0;
+    QK_TRY(qk_fn_reserve(ctx, b_q + b_c + b_s + b_q8 + b_n8 + b_c2));
     uint4 *xq = (uint4 *)ctx->fn_buf;
     int64_t *cand = (int64_t *)(ctx->fn_buf + b_q);
     uint2 *stat = (uint2 *)(ctx->fn_buf + b_q + b_c);
+    uint4 *xq8 = (uint4 *)(ctx->fn_buf + b_q + b_c + b_s);
+    int32_t *nq8 = (int32_t *)(ctx->fn_buf + b_q + b_c + b_s + b_q8);
+    int64_t *cand2 = (int64_t *)(ctx->fn_buf + b_q + b_c + b_s + b_q8 + b_n8);
     // ---- staging, full query preparation, coarse (the unfiltered qk_search's, on the float32 queries) -------------------------------
     const size_t b_oi = qk_al256((size_t)Q * k * 8), b_od = qk_al256((size_t)Q * k * 4);
     qk_scan_args sa;
@@ -414,6 +428,7 @@ int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     else
         hipLaunchKernelGGL(k_bin_prep<false>, dim3((unsigned)Q), dim3(64), 0, st, sa.x, d, nbw, (const float *)s->bin_m, xq);
     QK_HIP(hipGetLastError());
+    if (rescored) QK_TRY(qk_launch_sq8_prep(st, s, sa.x, Q, metric, xq8, nq8));
     // ---- the candidates ---------------------------------------------------------------------------------------------------------------
     BinSelectParams bp;
     bp.codes = (const uint4 *)s->bin_codes;
@@ -435,21 +450,36 @@ int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     if (tm) QK_HIP(hipEventRecord(ctx->ev[5], st));
     hipLaunchKernelGGL(k_bin_select, dim3((unsigned)Q), dim3(256), lds, st, bp);
     QK_HIP(hipGetLastError());
-    ctx->last_scan_kernel = "k_bin_select (sign codes)";
+    ctx->last_scan_kernel = rescored ? "k_bin_select (sign codes) + k_sq8_rerank (int8 codes)" : "k_bin_select (sign codes)";
     if (tm) {
         QK_HIP(hipEventRecord(ctx->ev[6], st));
         QK_HIP(hipEventRecord(ctx->ev[7], st));  // (no merge)
     }
+    // ---- rescored: the R best of the C candidates on the int8 codes, behind the phase events like the finish -----------------------
+    if (rescored) {
+        Sq8RerankParams rp;
+        rp.cand = cand;
+        rp.cand2 = cand2;
+        rp.codes = (const uint4 *)s->sq8_codes;
+        rp.nx = s->sq8_nx;
+        rp.xq = xq8;
+        rp.nq = nq8;
+        rp.nb8 = nb8;
+        rp.C = C;
+        rp.R = R;
+        rp.metric = metric;
+        QK_TRY(qk_launch_sq8_rerank(st, rp, Q));
+    }
     // ---- the exact finish: funnel search's, or its sibling for more candidates than that one pools ---------------------------------
     FunnelFinishParams fp;
-    fp.cand = cand;
+    fp.cand = rescored ? cand2 : cand;
     fp.xq4 = sa.xq4;
     fp.xn = sa.xn;
     fp.vecs = (const float4 *)s->vecs;
     fp.norms = s->norms;
     fp.ids = s->ids;
     fp.nblk = nblk;
-    fp.C = C;
+    fp.C = R;
     fp.k = k;
     fp.metric = metric;
     fp.sqrt_l2 = ctx->squared_l2 ? 0 : 1;
@@ -567,14 +597,30 @@ int qk_bin_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
                   int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_search: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search: nprobe must be positive");
-    return qk_bin_run("qk_bin_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, metric, out_ids, out_dist, mem, timing);
+    return qk_bin_run("qk_bin_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, -1, metric, out_ids, out_dist, mem, timing);
+}
+
+int qk_bin_search_rescored(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k, int rescore_k,
+                           int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_rescored: null argument");
+    if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_rescored: nprobe must be positive");
+    if (rescore_k < 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_rescored: rescore_k=%d must be at least k=%d", rescore_k, k);
+    return qk_bin_run("qk_bin_search_rescored", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, rescore_k, metric, out_ids, out_dist, mem, timing);
 }
 
 int qk_bin_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
                 int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan: bad partition id list");
-    return qk_bin_run("qk_bin_scan", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, metric, out_ids, out_dist, mem, timing);
+    return qk_bin_run("qk_bin_scan", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, -1, metric, out_ids, out_dist, mem, timing);
+}
+
+int qk_bin_scan_rescored(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int rescore_k,
+                         int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_rescored: null argument");
+    if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_rescored: bad partition id list");
+    if (rescore_k < 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_rescored: rescore_k=%d must be at least k=%d", rescore_k, k);
+    return qk_bin_run("qk_bin_scan_rescored", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, rescore_k, metric, out_ids, out_dist, mem, timing);
 }
 
 int qk_store_bin_info(qk_store *s, int *valid, int64_t *bytes, int64_t *cache_rows) {

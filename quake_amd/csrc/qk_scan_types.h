@@ -319,4 +319,19 @@ int qk_launch_sq8_deep_finish(hipStream_t st, const FunnelFinishParams &fp, int6
 // the body of qk_sq8_search / qk_sq8_scan (qk_sq8.hip) and of their deep siblings (deep: the counting form, fetch_k up to QK_SQ8_MAX_FETCH)
 int qk_sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe,
                int k, int fetch_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing, bool deep);
+// k_sq8_prep for Q queries (qk_sq8.hip): their codes in B-operand order ([Q][nb8][4] x 16 B) and their int32 code norms, with the
+// parameters of the store's code mirror (which is current for `metric`)
+int qk_launch_sq8_prep(hipStream_t st, const qk_store *s, const float *x, int64_t Q, int metric, uint4 *xq, int32_t *nq);
+// rescored binary search (qk_cascade.hip): k_sq8_rerank, the R best of every query's C candidates under (integer key over the int8
+// codes, arena row)
+struct Sq8RerankParams {
+    const int64_t *cand;  // [Q][C] ascending arena rows, -1 behind the candidates (k_bin_select's)
+    int64_t *cand2;       // [Q][R] the same form
+    const uint4 *codes;   // the store's code mirror and its rows' code norms
+    const int32_t *nx;
+    const uint4 *xq;      // [Q][nb8][4] the queries' codes
+    const int32_t *nq;    // [Q]
+    int nb8, C, R, metric;
+};
+int qk_launch_sq8_rerank(hipStream_t st, const Sq8RerankParams &rp, int64_t Q);
 int qk_launch_next_cursor(qk_ctx *ctx, const MergeParams &mp, int64_t Q, const int64_t *out_ids, uint32_t *next_key, int64_t *next_id);

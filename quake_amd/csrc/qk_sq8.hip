@@ -292,11 +292,7 @@ int qk_sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     float *d_dist = host ? (out_dist ? (float *)(stage + b_oi) : nullptr) : out_dist;
     const float4 *xq4_full = sa.xq4;
     const float *xn_full = sa.xn;
-    if (l2)
-        hipLaunchKernelGGL(k_sq8_prep<true>, dim3((unsigned)Q), dim3(64), 0, st, sa.x, d, nb8, s->sq8_m, s->sq8_scale, xq, nq);
-    else
-        hipLaunchKernelGGL(k_sq8_prep<false>, dim3((unsigned)Q), dim3(64), 0, st, sa.x, d, nb8, s->sq8_m, s->sq8_scale, xq, nq);
-    QK_HIP(hipGetLastError());
+    QK_TRY(qk_launch_sq8_prep(st, s, sa.x, Q, metric, xq, nq));
     // ---- the candidates: the code scan with k = fetch_k; the merge leaves arena rows in the call's buffer ----------------------------
     sa.xq4 = (const float4 *)xq;
     sa.xn = (const float *)nq;
@@ -359,6 +355,16 @@ int qk_sq8_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     if (tail_end) (void)hipEventDestroy(tail_end);
     QK_TRY(rc);
     if (timing || host) QK_TRY(qk_check_overflow(ctx));
+    return QK_OK;
+}
+
+int qk_launch_sq8_prep(hipStream_t st, const qk_store *s, const float *x, int64_t Q, int metric, uint4 *xq, int32_t *nq) {
+    const int d = s->d, nb8 = qk_sq8_nblk(d);
+    if (metric == QK_METRIC_L2)
+        hipLaunchKernelGGL(k_sq8_prep<true>, dim3((unsigned)Q), dim3(64), 0, st, x, d, nb8, s->sq8_m, s->sq8_scale, xq, nq);
+    else
+        hipLaunchKernelGGL(k_sq8_prep<false>, dim3((unsigned)Q), dim3(64), 0, st, x, d, nb8, s->sq8_m, s->sq8_scale, xq, nq);
+    QK_HIP(hipGetLastError());
     return QK_OK;
 }
 

@@ -19,7 +19,7 @@ import torch
 
 from . import capi
 from ._lib import QuakeHipError, header_constant
-from .where import lower_bin, lower_pq, lower_pq_codebooks, lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_rerank, lower_sq8
+from .where import lower_bin, lower_bin_rescored, lower_pq, lower_pq_codebooks, lower_diverse, lower_edges, lower_funnel, lower_expr, lower_maxsim, lower_order, lower_rerank, lower_sq8
 
 # defaults: src/cpp/include/common.h:66-99
 DEFAULT_NLIST = 0
@@ -1702,7 +1702,7 @@ class QuakeIndex:
                                  lambda xd, nprobe, k, fk: self._ctx.sq8_search(self.parent._store, self._store, xd, nprobe, k, fk, self.metric_,
                                                                                 timing=True, deep=bool(deep)))
 
-    def binary_search(self, x, search_params, fetch_k):
+    def binary_search(self, x, search_params, fetch_k, rescore_k=None):
         """extension (no reference counterpart): binary search, binary quantization with oversampling and rescoring -- the rows of
         each query's probed lists (chosen as search() chooses them, by the float32 query) are ranked by the Hamming distance over one
         sign bit per coordinate (x_j above the column's centre: the middle of its range for L2, 0 for the inner product), 1 / 32 of
@@ -1712,7 +1712,15 @@ class QuakeIndex:
         search().  1 <= k <= 448, k <= fetch_k <= 4096, d <= 8192, nprobe <= 1024.
         The bits (16 ceil(d / 128) bytes per row) are rebuilt by the first call after the index changed.  Filters, recall_target,
         num_workers > 0 and a flat index are not served (NotImplementedError); under L2 a stored value that is not finite is a
-        RuntimeError.  Returns a SearchResult on x's device."""
+        RuntimeError.  Returns a SearchResult on x's device.
+        rescore_k (include/quake_hip.h, "binary search, rescored"): a cascade bits -> int8 -> float32.  The fetch_k rows are
+        re-ranked by quantized_search's integer key over their int8 codes, and only the rescore_k best of them -- ties by position in
+        the index -- are re-scored on the float32 rows.  k <= rescore_k <= min(fetch_k, 448), d <= 2048; both code mirrors are kept,
+        and a stored value that is not finite is a RuntimeError under either metric.  rescore_k == fetch_k is the call without it."""
+        if rescore_k is not None:
+            return self._code_search(x, search_params, "binary_search", lambda d, k, who: lower_bin_rescored(d, k, fetch_k, rescore_k, who),
+                                     lambda xd, nprobe, k, fk, rk: self._ctx.bin_search(self.parent._store, self._store, xd, nprobe, k, fk,
+                                                                                        self.metric_, timing=True, rescore_k=rk))
         return self._code_search(x, search_params, "binary_search", lambda d, k, who: lower_bin(d, k, fetch_k, who),
                                  lambda xd, nprobe, k, fk: self._ctx.bin_search(self.parent._store, self._store, xd, nprobe, k, fk, self.metric_,
                                                                                 timing=True))
@@ -1771,7 +1779,7 @@ class QuakeIndex:
             raise NotImplementedError(who + " %s is not supported with num_workers > 0" % name)
         if self.parent is None:
             raise NotImplementedError(who + " %s is not supported by a flat index (no lists of its own)" % name)
-        k, fetch_k = lower(int(self._d), sp.k, who)
+        k, *depths = lower(int(self._d), sp.k, who)  # (fetch_k; binary_search with rescore_k: fetch_k, rescore_k)
         res = SearchResult()
         ti = SearchTimingInfo()
         ti.search_params = sp
@@ -1788,7 +1796,7 @@ class QuakeIndex:
         nprobe = max(int(sp.nprobe), 1)
         self._ctx.set_timing(1)
         try:
-            out = call(xd, nprobe, k, fetch_k)
+            out = call(xd, nprobe, k, *depths)
         finally:
             self._ctx.set_timing(0)
         tm = out[2]

@@ -303,9 +303,9 @@ class ShardedIndex:
         its own scale, and its candidates are its own fetch_k best, not the index's."""
         raise NotImplementedError("[ShardedIndex::quantized_search()] quantized_search is not supported by sharded.py")
 
-    def binary_search(self, q, nprobe, k, fetch_k):
-        """binary search (QuakeIndex.binary_search, qk_bin_search) has no sharded form: a shard's sign bits use its own centres,
-        and its candidates are its own fetch_k best, not the index's."""
+    def binary_search(self, q, nprobe, k, fetch_k, rescore_k=None):
+        """binary search (QuakeIndex.binary_search, qk_bin_search / qk_bin_search_rescored) has no sharded form, with or without
+        rescore_k: a shard's sign bits use its own centres, and its candidates are its own fetch_k best, not the index's."""
         raise NotImplementedError("[ShardedIndex::binary_search()] binary_search is not supported by sharded.py")
 
     def pq_search(self, q, nprobe, k, fetch_k):

@@ -319,6 +319,33 @@ def lower_bin(d, k, fetch_k, who="[QuakeIndex::binary_search()]"):
     return k, fetch_k
 
 
+def lower_bin_rescored(d, k, fetch_k, rescore_k, who="[QuakeIndex::binary_search()]"):
+    """The arguments of rescored binary search (include/quake_hip.h, "binary search, rescored") over vectors of d columns ->
+    (k, fetch_k, rescore_k): 1 <= k <= rescore_k <= min(fetch_k, QK_MAX_K), fetch_k <= QK_BIN_MAX_FETCH, d <= QK_SQ8_MAX_D.
+    RuntimeError, in this order: a value that is no integer, k < 1, fetch_k < k, rescore_k < k, rescore_k > fetch_k, k above its
+    limit, rescore_k above its limit, fetch_k above its limit, d above its limit."""
+    k = _int(k, who + " k:")
+    fetch_k = _int(fetch_k, who + " fetch_k:")
+    rescore_k = _int(rescore_k, who + " rescore_k:")
+    if k < 1:
+        raise RuntimeError("%s k=%d must be at least 1" % (who, k))
+    if fetch_k < k:
+        raise RuntimeError("%s fetch_k=%d must be at least k=%d" % (who, fetch_k, k))
+    if rescore_k < k:
+        raise RuntimeError("%s rescore_k=%d must be at least k=%d" % (who, rescore_k, k))
+    if rescore_k > fetch_k:
+        raise RuntimeError("%s rescore_k=%d must be at most fetch_k=%d" % (who, rescore_k, fetch_k))
+    if k > QK_MAX_K:
+        raise RuntimeError("%s k=%d must not exceed %d" % (who, k, QK_MAX_K))
+    if rescore_k > QK_MAX_K:
+        raise RuntimeError("%s rescore_k=%d must not exceed %d" % (who, rescore_k, QK_MAX_K))
+    if fetch_k > QK_BIN_MAX_FETCH:
+        raise RuntimeError("%s fetch_k=%d must not exceed %d" % (who, fetch_k, QK_BIN_MAX_FETCH))
+    if d > QK_SQ8_MAX_D:
+        raise RuntimeError("%s d=%d must not exceed %d" % (who, d, QK_SQ8_MAX_D))
+    return k, fetch_k, rescore_k
+
+
 def lower_pq(d, k, fetch_k, who="[QuakeIndex::pq_search()]"):
     """The arguments of product-quantized search (include/quake_hip.h, "product-quantized search") over vectors of d columns ->
     (k, fetch_k): 1 <= k <= min(fetch_k, QK_MAX_K), fetch_k <= QK_PQ_MAX_FETCH, d <= QK_MAX_D.  RuntimeError, in this order: a value
