@@ -1134,6 +1134,55 @@ QK_API int qk_bin_search_rescored(qk_ctx *ctx, qk_store *parent, qk_store *s, co
 QK_API int qk_bin_scan_rescored(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k,
                                 int rescore_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
 
+/* Binary search, asymmetric: 4-bit query planes and a norm-corrected estimate.  The stored row stays one sign bit
+ * per coordinate -- binary search's mirror, byte for byte --, the query keeps four bits per coordinate, and two float32 factors per
+ * row (8 bytes) turn the popcounts into an estimate of the inner product itself instead of an angle between sign vectors.  An
+ * approximate search by design whose result is still defined bit for bit.  Below, (+) (-) (*) (/) are separately rounded IEEE
+ * float32 operations (__fadd_rn, __fsub_rn, __fmul_rn, __fdiv_rn); nothing is contracted into an fma.  The centres m_j and the bits
+ * b_j = (x_j > m_j) are binary search's, steps 1 and 2 above, unchanged: L2 the mid-range column centre, IP 0.
+ *   1. Row factors, two float32 per arena row: v_j = x_j (-) m_j for j < d.  Four chains g = 0..3 over the columns j = g (mod 4)
+ *      in ascending j, from +0: a_g = a_g (+) (v_j (*) v_j), l_g = l_g (+) |v_j|.  r2 = (a_0 (+) a_1) (+) (a_2 (+) a_3),
+ *      l1 = (l_0 (+) l_1) (+) (l_2 (+) l_3), w = r2 (/) l1, and w = 0 where l1 == 0.  A store in which a live row has an r2 or a w
+ *      that is not finite has no factors: QK_ERR_UNSUPPORTED under either metric, the message names the list.
+ *   2. Query: q'_j = q_j (-) m_j, a q'_j that is not finite -- or is -0 -- replaced by +0 (so lo and hi below are one bit pattern
+ *      whatever the order of the comparison).  lo = min_j q'_j, hi = max_j q'_j over j < d.  delta = (hi (-) lo) (/) 15, and
+ *      delta = 1 where that is 0.  u_j = clamp(rint((q'_j (-) lo) (/) delta), 0, 15), round half to even, a NaN (infinite over
+ *      infinite, where hi (-) lo overflows) giving 0.  sumU = sum_j u_j.  The query is four bit planes in the mirror's word layout:
+ *      plane b holds bit b of every u_j, columns from d on are 0.
+ *   3. Key of (query, row).  Exact integers: S = sum_j u_j b_j = sum_b 2^b popcount(plane_b & code), pop = popcount(code),
+ *      t = 2 S - sumU, p = 2 pop - d (both below 2^24 in magnitude: their float32 images are exact).  Then
+ *      e = (delta (*) float(t)) (+) (lo (*) float(p)), which estimates <q', sign(x')>;
+ *      L2: key = r2 (-) (2 (*) (w (*) e));   IP: key = -(w (*) e).
+ *   4. Candidates: per query, the fetch_k rows of its probed lists that are smallest under (image(key), arena row); image is the
+ *      order-preserving unsigned image of a float32 (bits ^ 0x80000000 for a clear sign bit, ~bits for a set one: -0 lies directly
+ *      below +0), and a NaN key has the image 0xFFFFFFFF.  The probed lists are binary search's, step 4.
+ *   5. Everything behind the candidates is the existing call: rescore_k == 0 the answer step of binary search, rescore_k > 0 stages
+ *      2 and 3 of "binary search, rescored".
+ *   6. Consequence: a fetch_k that covers every probed row of a query (with rescore_k == 0, or a rescore_k that covers them as
+ *      well) gives qk_search's row, bit for bit.
+ * Arguments: qk_bin_search_rescored's / qk_bin_scan_rescored's.  rescore_k == 0: no int8 stage, the limits of qk_bin_search (d <=
+ * QK_MAX_D, fetch_k <= QK_BIN_MAX_FETCH); rescore_k > 0: the cascade under the rescored call's limits and refusals; rescore_k < 0:
+ * QK_ERR_INVALID.  A refusal writes no output.  There is no form for filters, cursors, qk_search_aps or the device group.
+ * Inside (qk_bin_asym.hip; the host side is qk_bin.hip's), one enqueue without a host wait -- except the one-off builds, all before
+ * any launch of the call: the int8 codes (rescore_k > 0), the sign mirror, the factors.  k_bin_prep_asym: one wave per query, lo /
+ * hi by shuffles, the planes by ballots.  k_bin_select_asym: one workgroup per query, no global atomics, no scratch; the lists
+ * ordered by arena offset as k_bin_select orders them; per row and 128 columns one 16-byte load, per dword four v_and_b32 and five
+ * v_bcnt_u32_b32, then the six float operations; the cut by a radix selection over the images, three walks over digits of 11 / 11 /
+ * 10 bits with one LDS histogram, and a fourth walk that compacts the rows under the cut image and the first ties at it in walk
+ * order -- every walk recomputes the keys, so any number of probed rows is served.
+ * The factors: 8 bytes per arena row, built on the context's stream (k_bin_factors) by the first asymmetric call for a (store
+ * version, metric) -- a caller of qk_bin_search alone never pays for them --, invalid as soon as the store changes; freed with the
+ * store or by qk_store_bin_drop; counted in qk_store_device_bytes; not persisted.  qk_store_bin_asym_info: valid = factors of the
+ * current version exist, bytes = what they occupy.
+ * timing: as binary search, group_ms = k_bin_prep_asym, scan_ms = k_bin_select_asym; scan_bytes counts the code bytes and the 8
+ * factor bytes of every query's probed rows once (each of the four walks reads them).  qk_ctx_last_scan_kernel reports
+ * "k_bin_select_asym (sign codes)", with " + k_sq8_rerank (int8 codes)" behind it for rescore_k > 0. */
+QK_API int qk_bin_search_asym(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k,
+                              int rescore_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_bin_scan_asym(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k,
+                            int rescore_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing);
+QK_API int qk_store_bin_asym_info(qk_store *s, int *valid, int64_t *bytes);
+
 /* Product-quantized search: product quantization with oversampling and rescoring.  The d columns are cut into M
  * sub-spaces, each with a learned codebook of 256 codewords; a row is mirrored as M bytes, a query becomes a lookup table, the probed
  * rows are ranked by a sum of M table entries, a shortlist of fetch_k rows is re-scored exactly.  An approximate search by design

@@ -175,6 +175,9 @@ SIGNATURES = {
     "qk_bin_scan": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_bin_search_rescored": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
     "qk_bin_scan_rescored": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_bin_search_asym": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_bin_scan_asym": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _int, _int, _int, _int, _vp, _vp, _int, C.POINTER(QkTiming)]),
+    "qk_store_bin_asym_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64)]),
     "qk_store_bin_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64)]),
     "qk_store_bin_drop": (_int, [_vp]),
     # product-quantized search: the arguments of binary search; codebooks are host float32 [M][256][d / M]

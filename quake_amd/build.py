@@ -14,16 +14,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libquake_hip.so")
-SOURCES = ["qk_ctx.hip", "qk_store.hip", "qk_scan.hip", "qk_scan_plan.hip", "qk_merge.hip", "qk_scan_rl.hip", "qk_small.hip", "qk_dense.hip", "qk_dense_pf.hip", "qk_dense_fused.hip", "qk_kmeans.hip", "qk_assign_pf.hip", "qk_aps.hip", "qk_api.hip", "qk_group.hip", "qk_scan_wide.hip", "qk_filter.hip", "qk_emit.hip", "qk_range.hip", "qk_attr.hip", "qk_grouped.hip", "qk_after.hip", "qk_facet.hip", "qk_order.hip", "qk_maxsim.hip", "qk_rerank.hip", "qk_diverse.hip", "qk_shadow.hip", "qk_funnel.hip", "qk_sq8.hip", "qk_sq8_deep.hip", "qk_bin.hip", "qk_pq.hip", "qk_cascade.hip"]
+SOURCES = ["qk_ctx.hip", "qk_store.hip", "qk_scan.hip", "qk_scan_plan.hip", "qk_merge.hip", "qk_scan_rl.hip", "qk_small.hip", "qk_dense.hip", "qk_dense_pf.hip", "qk_dense_fused.hip", "qk_kmeans.hip", "qk_assign_pf.hip", "qk_aps.hip", "qk_api.hip", "qk_group.hip", "qk_scan_wide.hip", "qk_filter.hip", "qk_emit.hip", "qk_range.hip", "qk_attr.hip", "qk_grouped.hip", "qk_after.hip", "qk_facet.hip", "qk_order.hip", "qk_maxsim.hip", "qk_rerank.hip", "qk_diverse.hip", "qk_shadow.hip", "qk_funnel.hip", "qk_sq8.hip", "qk_sq8_deep.hip", "qk_bin.hip", "qk_bin_asym.hip", "qk_pq.hip", "qk_cascade.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value"]
 # per-source flags on top of FLAGS.  qk_funnel.hip is compiled without packed fp32 instructions (v_pk_*_f32): every chain in it is a
 # sequence of separately rounded scalar operations; so is qk_sq8.hip, whose codes are one subtraction and one division each, and
 # qk_rerank.hip, whose sums are one rounded addition after the other, and qk_sq8_deep.hip, whose finish repeats qk_funnel.hip's chain,
-# and qk_pq.hip, whose table entries are one subtraction and one division each
+# and qk_pq.hip, whose table entries are one subtraction and one division each, and qk_bin_asym.hip, whose row factors and keys are
+# chains of separately rounded operations
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"qk_funnel.hip": _NO_PK_F32, "qk_sq8.hip": _NO_PK_F32, "qk_rerank.hip": _NO_PK_F32, "qk_sq8_deep.hip": _NO_PK_F32, "qk_pq.hip": _NO_PK_F32}
+SOURCE_FLAGS = {"qk_funnel.hip": _NO_PK_F32, "qk_sq8.hip": _NO_PK_F32, "qk_rerank.hip": _NO_PK_F32, "qk_sq8_deep.hip": _NO_PK_F32, "qk_pq.hip": _NO_PK_F32, "qk_bin_asym.hip": _NO_PK_F32}
 # QK_BUILD_PROBES=1: the tuning build -- QK_* environment switches and the wave-clock printouts compiled in (qk_internal.h).
 # The product build has none of them.
 if os.environ.get("QK_BUILD_PROBES", "0") not in ("", "0"):

@@ -883,12 +883,14 @@ class Context:
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
     # ---- binary search -----------------------------------------------------------------------------------
-    def bin_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False, rescore_k=None):
+    def bin_search(self, parent, store, x, nprobe, k, fetch_k, metric, want_dist=True, timing=False, rescore_k=None, asymmetric=False):
         """qk_bin_search: per query, the fetch_k rows of its probed lists with the smallest Hamming distance over the store's sign
         bits -- ties by arena row --, re-scored on the float32 rows; the k best under (exact key, id).  Returns (ids [Q, k] padded
         with -1, dist [Q, k] padded as search pads -- None where not wanted --[, timing]) on x's device.
         rescore_k: qk_bin_search_rescored -- the fetch_k rows are re-ranked by the integer key over their int8 codes, ties by arena
-        row, and only the rescore_k best are re-scored; None is the call without it."""
+        row, and only the rescore_k best are re-scored; None is the call without it.
+        asymmetric: qk_bin_search_asym -- the fetch_k rows are the smallest under a float32 estimate from the same sign bits, four
+        bits per query coordinate and two factors per row (include/quake_hip.h, "binary search, asymmetric")."""
         x = _f32(x)
         Q = x.shape[0]
         mem = _mem_of(x)
@@ -899,15 +901,17 @@ class Context:
         t = QkTiming()
         head = (self.h, parent.h if parent is not None else None, store.h, _ptr(x), Q, int(nprobe), k, fetch_k)
         tail = (metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem, C.byref(t) if timing else None)
-        if rescore_k is None:
+        if asymmetric:
+            check(self.lib.qk_bin_search_asym(*head, 0 if rescore_k is None else int(rescore_k), *tail))
+        elif rescore_k is None:
             check(self.lib.qk_bin_search(*head, *tail))
         else:
             check(self.lib.qk_bin_search_rescored(*head, int(rescore_k), *tail))
         return (ids, dist, timing_dict(t)) if timing else (ids, dist)
 
-    def bin_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False, rescore_k=None):
+    def bin_scan(self, store, x, pids, k, fetch_k, metric, want_dist=True, timing=False, rescore_k=None, asymmetric=False):
         """qk_bin_scan: bin_search over the given lists -- pids [Q, P] (or [P] for every query); -1 / empty lists contribute
-        nothing.  rescore_k: qk_bin_scan_rescored."""
+        nothing.  rescore_k: qk_bin_scan_rescored; asymmetric: qk_bin_scan_asym."""
         x, pids = _f32(x), _i64(pids)
         Q = x.shape[0]
         pids = _pids_rows(pids, Q)
@@ -919,7 +923,9 @@ class Context:
         t = QkTiming()
         head = (self.h, store.h, _ptr(x), Q, _ptr(pids) if pids.shape[1] > 0 else None, int(pids.shape[1]), k, fetch_k)
         tail = (metric_code(metric), _ptr(ids), _ptr(dist) if dist is not None else None, mem, C.byref(t) if timing else None)
-        if rescore_k is None:
+        if asymmetric:
+            check(self.lib.qk_bin_scan_asym(*head, 0 if rescore_k is None else int(rescore_k), *tail))
+        elif rescore_k is None:
             check(self.lib.qk_bin_scan(*head, *tail))
         else:
             check(self.lib.qk_bin_scan_rescored(*head, int(rescore_k), *tail))
@@ -1312,8 +1318,15 @@ class Store:
         check(self.lib.qk_store_bin_info(self.h, C.byref(v), C.byref(b), C.byref(c)))
         return {"valid": bool(v.value), "bytes": int(b.value), "cache_rows": int(c.value)}
 
+    def bin_asym_info(self):
+        """{valid, bytes} of the row factors of asymmetric binary search (qk_store_bin_asym_info): 8 bytes per row, built by the
+        first asymmetric call"""
+        v, b = C.c_int(0), C.c_int64(0)
+        check(self.lib.qk_store_bin_asym_info(self.h, C.byref(v), C.byref(b)))
+        return {"valid": bool(v.value), "bytes": int(b.value)}
+
     def bin_drop(self):
-        """free the sign-bit mirror (qk_store_bin_drop); the next binary search builds it again"""
+        """free the sign-bit mirror and the row factors of the asymmetric form (qk_store_bin_drop); the next binary search builds them again"""
         check(self.lib.qk_store_bin_drop(self.h))
 
     def pq_set_codebooks(self, codebooks):

@@ -358,9 +358,11 @@ __global__ __launch_bounds__(256) void k_bin_select(BinSelectParams B) {
 }
 
 // the body of the entry points: parent == nullptr && pids == nullptr -> every list.  rescore_k >= 0: the rescored form ("binary search,
-// rescored") -- k_sq8_rerank (qk_cascade.hip) between the selection and the finish, which then sees rescore_k candidates
+// rescored") -- k_sq8_rerank (qk_cascade.hip) between the selection and the finish, which then sees rescore_k candidates.
+// asym: the candidates by k_bin_prep_asym / k_bin_select_asym over the same sign mirror and the row factors ("binary search,
+// asymmetric"; qk_bin_asym.hip); everything else is the same call
 int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int nprobe, int k,
-               int fetch_k, int rescore_k, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+               int fetch_k, int rescore_k, bool asym, int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     const int d = s->d;
     const bool rescored = rescore_k >= 0;
     if (metric != QK_METRIC_L2 && metric != QK_METRIC_IP) QK_FAIL(QK_ERR_INVALID, "Metric type not supported");
@@ -403,7 +405,8 @@ int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     // (the int8 codes first: a store with a non-finite row is refused in quantized search's words, for both metrics)
     if (rescored) QK_TRY(qk_store_sq8_mirror(ctx, s, metric));
     QK_TRY(qk_store_bin_mirror(ctx, s, metric));
-    const size_t b_q = qk_al256((size_t)Q * nbw * 16), b_c = qk_al256((size_t)Q * C * 8), b_s = qk_al256((size_t)Q * 8);
+    if (asym) QK_TRY(qk_store_bin_factors(ctx, s, metric));
+    const size_t b_q = asym ? qk_bin_asym_query_bytes(Q, d) : qk_al256((size_t)Q * nbw * 16), b_c = qk_al256((size_t)Q * C * 8), b_s = qk_al256((size_t)Q * 8);
     const size_t b_q8 = rescored ? qk_al256((size_t)Q * nb8 * 64) : 0, b_n8 = rescored ? qk_al256((size_t)Q * 4) : 0,
                  b_c2 = rescored ? qk_al256((size_t)Q * R * 8) : 0;
     QK_TRY(qk_fn_reserve(ctx, b_q + b_c + b_s + b_q8 + b_n8 + b_c2));
@@ -423,34 +426,43 @@ int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
     float *d_dist = host ? (out_dist ? (float *)(stage + b_oi) : nullptr) : out_dist;
     const bool tm = ctx->timing && timing;
     if (tm) QK_HIP(hipEventRecord(ctx->ev[4], st));
-    if (l2)
+    char *qf = !asym ? nullptr : (char *)xq + qk_al256((size_t)Q * nbw * 64);  // (asym: the queries' (lo, delta, sumU) behind their four planes)
+    if (asym)
+        QK_TRY(qk_launch_bin_prep_asym(st, s, sa.x, Q, metric, xq, qf));
+    else if (l2)
         hipLaunchKernelGGL(k_bin_prep<true>, dim3((unsigned)Q), dim3(64), 0, st, sa.x, d, nbw, (const float *)s->bin_m, xq);
     else
         hipLaunchKernelGGL(k_bin_prep<false>, dim3((unsigned)Q), dim3(64), 0, st, sa.x, d, nbw, (const float *)s->bin_m, xq);
     QK_HIP(hipGetLastError());
     if (rescored) QK_TRY(qk_launch_sq8_prep(st, s, sa.x, Q, metric, xq8, nq8));
     // ---- the candidates ---------------------------------------------------------------------------------------------------------------
-    BinSelectParams bp;
-    bp.codes = (const uint4 *)s->bin_codes;
-    bp.pt_off = (const int64_t *)s->d_off;
-    bp.pt_size = (const int32_t *)s->d_size;
-    bp.npids = (int)s->parts.size();
-    bp.pids = sa.all_lists ? nullptr : sa.pids;
-    bp.P = sa.all_lists ? bp.npids : sa.P;
-    bp.nbw = nbw;
-    bp.nbins = d + 1;
-    bp.xq = xq;
-    bp.C = C;
-    bp.cand = cand;
-    bp.cache_rows = QK_BIN_KEY_CACHE ? (int)std::min<int64_t>(bin_cache_rows(d), (rows_ub + 7) & ~(int64_t)7) : 0;
-    bp.stat = timing ? stat : nullptr;
-    if (bp.P < 1 || bp.P > QK_BIN_MAX_NPROBE) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: %d lists per query exceed QK_BIN_MAX_NPROBE=%d", who, bp.P, QK_BIN_MAX_NPROBE);
-    const size_t lds = bin_lds_bytes(d, bp.P, bp.cache_rows);
-    QK_HIP(hipFuncSetAttribute((const void *)k_bin_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (tm) QK_HIP(hipEventRecord(ctx->ev[5], st));
-    hipLaunchKernelGGL(k_bin_select, dim3((unsigned)Q), dim3(256), lds, st, bp);
-    QK_HIP(hipGetLastError());
-    ctx->last_scan_kernel = rescored ? "k_bin_select (sign codes) + k_sq8_rerank (int8 codes)" : "k_bin_select (sign codes)";
+    if (asym) {
+        if (tm) QK_HIP(hipEventRecord(ctx->ev[5], st));
+        QK_TRY(qk_launch_bin_select_asym(st, s, sa, metric, xq, qf, C, cand, timing ? stat : nullptr, Q));
+        ctx->last_scan_kernel = rescored ? "k_bin_select_asym (sign codes) + k_sq8_rerank (int8 codes)" : "k_bin_select_asym (sign codes)";
+    } else {
+        BinSelectParams bp;
+        bp.codes = (const uint4 *)s->bin_codes;
+        bp.pt_off = (const int64_t *)s->d_off;
+        bp.pt_size = (const int32_t *)s->d_size;
+        bp.npids = (int)s->parts.size();
+        bp.pids = sa.all_lists ? nullptr : sa.pids;
+        bp.P = sa.all_lists ? bp.npids : sa.P;
+        bp.nbw = nbw;
+        bp.nbins = d + 1;
+        bp.xq = xq;
+        bp.C = C;
+        bp.cand = cand;
+        bp.cache_rows = QK_BIN_KEY_CACHE ? (int)std::min<int64_t>(bin_cache_rows(d), (rows_ub + 7) & ~(int64_t)7) : 0;
+        bp.stat = timing ? stat : nullptr;
+        if (bp.P < 1 || bp.P > QK_BIN_MAX_NPROBE) QK_FAIL(QK_ERR_UNSUPPORTED, "%s: %d lists per query exceed QK_BIN_MAX_NPROBE=%d", who, bp.P, QK_BIN_MAX_NPROBE);
+        const size_t lds = bin_lds_bytes(d, bp.P, bp.cache_rows);
+        QK_HIP(hipFuncSetAttribute((const void *)k_bin_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (tm) QK_HIP(hipEventRecord(ctx->ev[5], st));
+        hipLaunchKernelGGL(k_bin_select, dim3((unsigned)Q), dim3(256), lds, st, bp);
+        QK_HIP(hipGetLastError());
+        ctx->last_scan_kernel = rescored ? "k_bin_select (sign codes) + k_sq8_rerank (int8 codes)" : "k_bin_select (sign codes)";
+    }
     if (tm) {
         QK_HIP(hipEventRecord(ctx->ev[6], st));
         QK_HIP(hipEventRecord(ctx->ev[7], st));  // (no merge)
@@ -517,7 +529,7 @@ int qk_bin_run(const char *who, qk_ctx *ctx, qk_store *parent, qk_store *s, cons
             for (const uint2 &v : h_stat) rows += v.x, lists += v.y;
             timing->n_items = Q;
             timing->partitions_scanned = lists;
-            timing->scan_bytes = rows * (int64_t)nbw * 16;
+            timing->scan_bytes = rows * ((int64_t)nbw * 16 + (asym ? 8 : 0));
             rc = qk_read_phase_ms(ctx, timing, have_coarse, 4);
             float ms = 0.f;
             if (rc == QK_OK && tm && hipEventElapsedTime(&ms, ctx->ev[7], tail_end) == hipSuccess) timing->total_ms += ms;
@@ -540,6 +552,7 @@ void qk_store_bin_free(qk_store *s) {
     s->bin_stats = nullptr;
     s->bin_cap_rows = 0;
     s->bin_metric = -1;
+    qk_store_bin_fac_free(s);  // (the row factors of the asymmetric form live and die with the centres they were built from)
 }
 
 int qk_store_bin_mirror(qk_ctx *ctx, qk_store *s, int metric) {
@@ -597,7 +610,7 @@ int qk_bin_search(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, in
                   int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_search: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search: nprobe must be positive");
-    return qk_bin_run("qk_bin_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, -1, metric, out_ids, out_dist, mem, timing);
+    return qk_bin_run("qk_bin_search", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, -1, false, metric, out_ids, out_dist, mem, timing);
 }
 
 int qk_bin_search_rescored(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k, int rescore_k,
@@ -605,14 +618,14 @@ int qk_bin_search_rescored(qk_ctx *ctx, qk_store *parent, qk_store *s, const flo
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_rescored: null argument");
     if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_rescored: nprobe must be positive");
     if (rescore_k < 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_rescored: rescore_k=%d must be at least k=%d", rescore_k, k);
-    return qk_bin_run("qk_bin_search_rescored", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, rescore_k, metric, out_ids, out_dist, mem, timing);
+    return qk_bin_run("qk_bin_search_rescored", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, rescore_k, false, metric, out_ids, out_dist, mem, timing);
 }
 
 int qk_bin_scan(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int metric,
                 int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan: bad partition id list");
-    return qk_bin_run("qk_bin_scan", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, -1, metric, out_ids, out_dist, mem, timing);
+    return qk_bin_run("qk_bin_scan", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, -1, false, metric, out_ids, out_dist, mem, timing);
 }
 
 int qk_bin_scan_rescored(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int rescore_k,
@@ -620,7 +633,25 @@ int qk_bin_scan_rescored(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, co
     if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_rescored: null argument");
     if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_rescored: bad partition id list");
     if (rescore_k < 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_rescored: rescore_k=%d must be at least k=%d", rescore_k, k);
-    return qk_bin_run("qk_bin_scan_rescored", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, rescore_k, metric, out_ids, out_dist, mem, timing);
+    return qk_bin_run("qk_bin_scan_rescored", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, rescore_k, false, metric, out_ids, out_dist, mem, timing);
+}
+
+int qk_bin_search_asym(qk_ctx *ctx, qk_store *parent, qk_store *s, const float *x, int64_t Q, int nprobe, int k, int fetch_k, int rescore_k,
+                       int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_asym: null argument");
+    if (parent && nprobe <= 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_asym: nprobe must be positive");
+    if (rescore_k < 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_search_asym: rescore_k=%d must be 0 (no int8 stage) or at least k=%d", rescore_k, k);
+    return qk_bin_run("qk_bin_search_asym", ctx, parent, s, x, Q, nullptr, 0, nprobe, k, fetch_k, rescore_k > 0 ? rescore_k : -1, true, metric, out_ids,
+                      out_dist, mem, timing);
+}
+
+int qk_bin_scan_asym(qk_ctx *ctx, qk_store *s, const float *x, int64_t Q, const int64_t *pids, int P, int k, int fetch_k, int rescore_k,
+                     int metric, int64_t *out_ids, float *out_dist, int mem, qk_timing *timing) {
+    if (!ctx || !s) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_asym: null argument");
+    if (P <= 0 || (Q > 0 && !pids)) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_asym: bad partition id list");
+    if (rescore_k < 0) QK_FAIL(QK_ERR_INVALID, "qk_bin_scan_asym: rescore_k=%d must be 0 (no int8 stage) or at least k=%d", rescore_k, k);
+    return qk_bin_run("qk_bin_scan_asym", ctx, nullptr, s, x, Q, pids, P, 0, k, fetch_k, rescore_k > 0 ? rescore_k : -1, true, metric, out_ids, out_dist,
+                      mem, timing);
 }
 
 int qk_store_bin_info(qk_store *s, int *valid, int64_t *bytes, int64_t *cache_rows) {

@@ -328,6 +328,13 @@ struct qk_store {
     int64_t bin_cap_rows = 0;
     uint64_t bin_version = 0;
     int bin_metric = -1;  // -1: none
+    // binary search, asymmetric (qk_bin_asym.hip): float2 (r2, w) per arena row beside the sign mirror, with its
+    // validity rule (version, metric); built lazily by qk_store_bin_factors, by the first asymmetric call only; not persisted
+    void *bin_fac = nullptr;
+    uint32_t *bin_fac_flag = nullptr;  // device [2]: "a factor is not finite", the smallest list that holds such a row
+    int64_t bin_fac_cap_rows = 0;
+    uint64_t bin_fac_version = 0;
+    int bin_fac_metric = -1;  // -1: none
     // product-quantized search (qk_pq.hip): M sub-quantizers of 256 float32 codewords over dsub = d / M columns each.
     // The codebooks are state of the store -- set or trained, kept across every mutation, for both metrics --, the codes a mirror
     // with bin_*'s life cycle: code row r is arena row r, a row's codes are 16-byte words of 16 sub-quantizers (padding bytes 0), the
@@ -352,6 +359,11 @@ inline int qk_bin_nbw(int d) { return (d + 127) / 128; }
 // QK_ERR_UNSUPPORTED where a live row holds a non-finite value; QK_ERR_OOM, and nothing else changed, without memory
 int qk_store_bin_mirror(qk_ctx *ctx, qk_store *s, int metric);
 void qk_store_bin_free(qk_store *s);
+// the row factors of asymmetric binary search (qk_bin_asym.hip) for `metric`, whose sign mirror is current: built on ctx's stream if
+// the store or the metric changed.  QK_ERR_UNSUPPORTED where a live row's r2 or w is not finite; QK_ERR_OOM, and nothing else
+// changed, without memory.  qk_store_bin_free frees them with the mirror
+int qk_store_bin_factors(qk_ctx *ctx, qk_store *s, int metric);
+void qk_store_bin_fac_free(qk_store *s);
 // quantized search's L2 centres for another mirror (qk_sq8.hip: k_sq8_range<true> over the live rows): stats is device memory of
 // 2 ncol + 4 words, ncol >= 16 nblk; h_m [ncol] receives m_j = 0.5f lo_j + 0.5f hi_j for j < d and 0 behind.  Waits for the stream.
 // *bad_list >= 0: the smallest list that holds a non-finite value (h_m is then not filled)

@@ -334,4 +334,11 @@ struct Sq8RerankParams {
     int nb8, C, R, metric;
 };
 int qk_launch_sq8_rerank(hipStream_t st, const Sq8RerankParams &rp, int64_t Q);
+// asymmetric binary search (qk_bin_asym.hip): the bytes of Q queries' bit planes ([Q][4][nbw] x 16 B) and of their (lo, delta,
+// sumU) records behind them, both rounded to 256; k_bin_prep_asym; k_bin_select_asym -- fetch_k candidates per query in ascending
+// arena rows, -1 behind, as k_bin_select leaves them (the sign mirror and the row factors are current for `metric`)
+size_t qk_bin_asym_query_bytes(int64_t Q, int d);
+int qk_launch_bin_prep_asym(hipStream_t st, const qk_store *s, const float *x, int64_t Q, int metric, void *planes, void *qf);
+int qk_launch_bin_select_asym(hipStream_t st, const qk_store *s, const qk_scan_args &sa, int metric, const void *planes, const void *qf,
+                              int fetch_k, int64_t *cand, uint2 *stat, int64_t Q);
 int qk_launch_next_cursor(qk_ctx *ctx, const MergeParams &mp, int64_t Q, const int64_t *out_ids, uint32_t *next_key, int64_t *next_id);

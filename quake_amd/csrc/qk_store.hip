@@ -1360,6 +1360,7 @@ int64_t qk_store_device_bytes(qk_store *s) {
            (s->pnorms ? s->pnorms_cap_rows * 4 : 0) +  // (+ the prefix norms of funnel search, qk_funnel.hip)
            (s->sq8_codes ? s->sq8_cap_rows * ((int64_t)qk_sq8_nblk(s->d) * 64 + 4) : 0) +  // (+ the int8 codes of quantized search, qk_sq8.hip)
            (s->bin_codes ? s->bin_cap_rows * (int64_t)qk_bin_nbw(s->d) * 16 : 0) +  // (+ the sign bits of binary search, qk_bin.hip)
+           (s->bin_fac ? s->bin_fac_cap_rows * 8 : 0) +  // (+ the row factors of its asymmetric form, qk_bin_asym.hip)
            (s->pq_codes ? s->pq_cap_rows * (int64_t)qk_pq_nw(s->pq_M) * 16 : 0);  // (+ the PQ codes of product-quantized search, qk_pq.hip)
 }
 
