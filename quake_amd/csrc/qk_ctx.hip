@@ -164,7 +164,9 @@ int qk_ctx_shadow_stats(qk_ctx *c, int64_t *verified, int64_t *fallback, int64_t
     if (c->shadow_counters) {
         QK_HIP(hipSetDevice(c->device));
         QK_HIP(hipStreamSynchronize(c->stream));
-        QK_HIP(hipMemcpy(h, c->shadow_counters, sizeof(h), hipMemcpyDeviceToHost));
+        unsigned long long stripes[QK_SHADOW_COUNTER_WORDS];
+        QK_HIP(hipMemcpy(stripes, c->shadow_counters, sizeof(stripes), hipMemcpyDeviceToHost));
+        qk_shadow_counters_total(stripes, h);
     }
     if (verified) *verified = (int64_t)h[0];
     if (fallback) *fallback = (int64_t)h[1];

@@ -66,6 +66,19 @@ constexpr int QK_QT = 16;              // queries per query tile (MFMA N)
 static inline int qk_round_up(int64_t v, int m) { return (int)(((v + m - 1) / m) * m); }
 static inline int64_t qk_round_up64(int64_t v, int64_t m) { return ((v + m - 1) / m) * m; }
 
+// ---- finish counters of the fp16 shadow form (qk_ctx::shadow_counters, qk_shadow.hip) ---------
+// Striped: one word that every query of a launch adds to is 1024 device-scope atomics in a row on one L2 line (20 us of the
+// bench's finish); 64 lines take 16 queries of such a launch each.  A power of two.
+constexpr int QK_SHADOW_STRIPES = 64;
+constexpr int QK_SHADOW_STRIPE_WORDS = 8;  // 64 bytes: the four counters and four unused words
+constexpr size_t QK_SHADOW_COUNTER_WORDS = (size_t)QK_SHADOW_STRIPES * QK_SHADOW_STRIPE_WORDS;
+// the four totals of a host copy of the whole array
+static inline void qk_shadow_counters_total(const unsigned long long *stripes, unsigned long long total[4]) {
+    for (int i = 0; i < 4; i++) total[i] = 0;
+    for (int s = 0; s < QK_SHADOW_STRIPES; s++)
+        for (int i = 0; i < 4; i++) total[i] += stripes[(size_t)s * QK_SHADOW_STRIPE_WORDS + i];
+}
+
 // ---- context ---------------------------------------------------------------------------------
 struct qk_ctx {
     int device = 0;
@@ -137,7 +150,10 @@ struct qk_ctx {
     // one missing the form is not admissible)
     int shadow_mode = 1;
     float shadow_form_time = 0.f;
-    unsigned long long *shadow_counters = nullptr;  // device [4]: verified, fallback, candidates (qk_ctx_shadow_stats)
+    // device [QK_SHADOW_STRIPES][QK_SHADOW_STRIPE_WORDS]: a 64-byte line per stripe, its first four words verified, fallback,
+    // candidates, queries with chained records.  The finish wave of query q adds to stripe q % QK_SHADOW_STRIPES only; the
+    // totals are the sums over the stripes, taken on the host (qk_shadow_counters_total; qk_ctx_shadow_stats)
+    unsigned long long *shadow_counters = nullptr;
     int *overflow_host = nullptr;    // pinned, device-visible: a scan kernel sets it when its record buffer overflows
     int *overflow_dev = nullptr;
     char *qprep_zero = nullptr;      // region cleared by the prep kernel for the scan of the same batch

@@ -542,6 +542,12 @@ struct SeedParams {
     uint32_t *gtau;
     int seed_ranks;      // pairs with r < seed_ranks are sampled (the nearest partitions give the tight bound)
     int strict_first;    // 1: the sample comes from the query's FIRST list or there is no bound (qk_scan_args::seed_first)
+    // fp16 shadow call through k_group_seed: rank 0's seed wave of query q also writes the query's fp16 copy and error bound
+    // (qk_shadow_prep_query: what k_shadow_prep writes).  sh_xqh null: not such a call.  Read by k_group_seed only.
+    const float4 *sh_xq4 = nullptr;
+    uint4 *sh_xqh = nullptr;
+    float *sh_E = nullptr;
+    float sh_rho = 0.f, sh_xmax = 0.f;
 };
 
 // grid = Q * seed_ranks waves: wave w -> query w / seed_ranks, rank w % seed_ranks.  M rows per lane: the sample is the
@@ -665,7 +671,12 @@ __global__ __launch_bounds__(1024) void k_group_seed(GroupParams G, SeedParams S
         return;
     }
     const int64_t w = ((int64_t)blockIdx.x - 1) * 16 + (threadIdx.x >> 6);
-    if (w < n_seed_waves) seed_tau_body<1, 4>(S, w, threadIdx.x & 63);
+    if (w >= n_seed_waves) return;
+    // (before the seed: its wave may leave early -- no list, fewer than k rows -- and the query still needs its copy and bound)
+    if (S.sh_xqh && w % S.seed_ranks == 0)
+        qk_shadow_prep_query(S.sh_xq4, S.xn, w / S.seed_ranks, S.d, S.nblk, S.metric == QK_METRIC_L2 ? 1 : 0, S.sh_rho, S.sh_xmax, S.sh_xqh, S.sh_E,
+                             threadIdx.x & 63);
+    seed_tau_body<1, 4>(S, w, threadIdx.x & 63);
 }
 
 
@@ -767,6 +778,9 @@ __global__ __launch_bounds__(64 * W) void k_seed_tau_wg(SeedParams S) {
 // the bytes of the tile form's, so more waves are needed to keep the same bytes in flight.  Measured on the bench index, forced mode,
 // ms per step at 4 / 6 / 8 waves per CU: 0.2566 / 0.2342 / 0.2412 (profiles/shadow_bench_parent_branch.txt).
 #define QK_SHADOW_WAVES_PER_CU_DEFAULT 6
+#endif
+#ifndef QK_SHADOW_FUSED_PREP
+#define QK_SHADOW_FUSED_PREP 1   // fp16 query copy and error bound from the seed waves of k_group_seed (0: always the k_shadow_prep launch)
 #endif
 #ifndef QK_DYN_CHUNK_DEFAULT
 #define QK_DYN_CHUNK_DEFAULT 16  // tiles per dynamic chunk
@@ -1146,7 +1160,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
     // (never for a filtered call: a sample bound comes from rows nobody tested against the filter, and a bound learnt from a
     //  disallowed row drops allowed ones.  The bounds the waves of one query share through gtau come from allowed rows only.)
     const bool seeded = ((!no_seed && share_tau) || seed_pairs) && k <= std::min(seed_cap, 512) && npairs > 0 && npids > 0 && !filtered && !prefix;
-    bool fused_group = false, fused_count = false;
+    bool fused_group = false, fused_count = false, fused_prep = false;
     if (seeded) {
         // bound seeding: for the first (nearest) partitions of every query, the k-th smallest distance of a 64-row
         // sample goes into gtau[q]
@@ -1186,6 +1200,15 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         static const bool no_fuse = qk_env_set("QK_NO_GROUP_SEED");
         if (k <= 64 && seed_waves == 1 && npairs <= QK_GROUP_SMALL && !no_small_f && !no_fuse) {
             const int64_t nsw = Q * sd.seed_ranks;
+            // (a side build with -DQK_SHADOW_FUSED_PREP=0 keeps the separate launch: the A/B of profiles/shadow_counters_bench_parent_branch.txt)
+            if (shadow && QK_SHADOW_FUSED_PREP) {  // the seed wave of a query holds what k_shadow_prep would load: no launch of its own
+                sd.sh_xq4 = xq4;
+                sd.sh_xqh = (uint4 *)sh_xqh;
+                sd.sh_E = sh_E;
+                sd.sh_rho = s->shadow_rho;
+                sd.sh_xmax = s->shadow_xmax;
+                fused_prep = true;
+            }
             QK_HIP(hipFuncSetAttribute((const void *)k_group_seed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QK_GROUP_SMALL_LDS));
             hipLaunchKernelGGL(k_group_seed, dim3((unsigned)(1 + (nsw + 15) / 16)), dim3(1024), group_small_lds(npairs), st, G, sd, nsw);
             fused_group = true;
@@ -1228,7 +1251,7 @@ int qk_scan_device(qk_ctx *ctx, qk_store *s, const qk_scan_args &a, qk_timing *t
         hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(1024), 0, st, G);
         if (npairs > 0) hipLaunchKernelGGL(k_group_scatter, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, G);
     }
-    if (shadow && npairs > 0 && npids > 0)
+    if (shadow && npairs > 0 && npids > 0 && !fused_prep)
         QK_TRY(qk_launch_shadow_prep(st, xq4, xn, Q, s->d, nblk, a.metric, s->shadow_rho, s->shadow_xmax, sh_xqh, sh_E));
     QK_TRY(pe.mark(1));
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "qk_shadow_bound.h"
 
 constexpr int QK_SLOTS = 32;  // ints per pair slot line: count + 31 record ids
 
@@ -274,7 +275,7 @@ struct ShadowFinishParams {
     const int64_t *pt_off;
     const int32_t *pt_size;
     int npids;
-    unsigned long long *counters;  // [4] verified, fallback, candidates, queries with chained records
+    unsigned long long *counters;  // [QK_SHADOW_STRIPES] lines of verified, fallback, candidates, queries with chained records (qk_internal.h)
 };
 int qk_launch_scan_shadow(int db, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ScanParams &sp);
 int qk_launch_shadow_finish(hipStream_t st, const ShadowFinishParams &fp, int64_t Q);
@@ -283,6 +284,53 @@ int qk_shadow_counters_ensure(qk_ctx *ctx, hipStream_t st);
 // fp16 copy of the prepared queries in B-operand order ([Q][nblk_s][4] x 16 B) and every query's error bound
 int qk_launch_shadow_prep(hipStream_t st, const float4 *xq4, const float *xn, int64_t Q, int d, int nblk, int metric, float rho, float xmax,
                           float4 *xqh, float *E);
+// fp16 image of x (round to nearest even) and the distance from x to it -- to the farther of the image and zero where the image is
+// subnormal: the bound must hold whether or not the matrix unit flushes such inputs
+__device__ __forceinline__ uint32_t qk_h_bits(float x, float &err, float &himg) {
+    const _Float16 h = (_Float16)x;
+    const float hf = (float)h;
+    float e = fabsf(x - hf);
+    if (hf != 0.0f && fabsf(hf) < 6.103515625e-05f) e = fmaxf(e, fabsf(x));
+    err = e;
+    himg = hf;
+    return (uint32_t)__builtin_bit_cast(unsigned short, h);
+}
+
+// The fp16 copy of query q in B-operand order and its error bound, by one whole wave (lane = 0..63).  xq4[(q * nblk + c) * 4 + g] holds
+// columns 16c + g + {0, 4, 8, 12}; lane (c, g) converts that float4, the lanes of an even c write their 8 B and those of c + 1 behind
+// them: xqh[(q * nbs + b) * 4 + g], which the scan stages like xq4.  E[q] < 0: a component is not finite or beyond 65504, or there is
+// no bound -- the finish answers the query by the exact scan.  Called by k_shadow_prep (qk_shadow.hip) and by the seed waves of
+// k_group_seed (qk_scan.hip): one function, the same bits.
+__device__ __forceinline__ void qk_shadow_prep_query(const float4 *__restrict__ xq4, const float *__restrict__ xn, int64_t q, int d, int nblk,
+                                                     int metric_l2, float rho, float xmax, uint4 *__restrict__ xqh, float *__restrict__ E, int lane) {
+    const int nbs = (nblk + 1) >> 1;
+    float e2 = 0.0f;
+    uint32_t bad = 0;
+    for (int c0 = 0; c0 < 2 * nbs; c0 += 16) {  // 16 arena blocks (64 float4) per round; d <= 256: one round
+        const int c = c0 + (lane >> 2), g = lane & 3;
+        const float4 a = c < nblk ? xq4[(q * nblk + c) * 4 + g] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float v[4] = {a.x, a.y, a.z, a.w};
+        uint32_t hb[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            float e, hf;
+            hb[i] = qk_h_bits(v[i], e, hf);
+            e2 = __fmaf_rn(e, e, e2);
+            bad |= fabsf(v[i]) <= 65504.0f ? 0u : 1u;
+        }
+        const uint32_t lo = hb[0] | (hb[1] << 16), hi = hb[2] | (hb[3] << 16);
+        const uint32_t plo = __shfl_down(lo, 4), phi = __shfl_down(hi, 4);  // lane (c + 1, g)
+        if ((c & 1) == 0 && c < 2 * nbs) xqh[(q * nbs + (c >> 1)) * 4 + g] = make_uint4(lo, hi, plo, phi);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) e2 += __shfl_xor(e2, o);
+    const bool anybad = __ballot(bad != 0) != 0;
+    if (lane == 0) {
+        const float up = 1.0009765625f;
+        float b = anybad ? -1.0f : qk_shadow_bound(metric_l2, d, sqrtf(xn[q]) * up, sqrtf(e2) * up, rho, xmax);
+        E[q] = b >= 0.0f ? b : -1.0f;  // (NaN: no bound)
+    }
+}
 // fp32 arena -> shadow for the lists of the table (device: pt_off / pt_size), statistics into stats [4] (zeroed by the caller):
 // bits of max err^2, bits of max ||fp16(x)||^2, "a value is not finite or beyond 65504"
 int qk_launch_shadow_convert(hipStream_t st, const float4 *vecs, int nblk, const int64_t *pt_off, const int32_t *pt_size, int npids, void *shadow,

@@ -21,18 +21,6 @@ typedef _Float16 qk_h8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ qk_h8 qk_as_h8(const float4 v) { return __builtin_bit_cast(qk_h8, v); }
 
-// fp16 image of x (round to nearest even) and the distance from x to it -- to the farther of the image and zero where the image is
-// subnormal: the bound must hold whether or not the matrix unit flushes such inputs
-__device__ __forceinline__ uint32_t qk_h_bits(float x, float &err, float &himg) {
-    const _Float16 h = (_Float16)x;
-    const float hf = (float)h;
-    float e = fabsf(x - hf);
-    if (hf != 0.0f && fabsf(hf) < 6.103515625e-05f) e = fmaxf(e, fabsf(x));
-    err = e;
-    himg = hf;
-    return (uint32_t)__builtin_bit_cast(unsigned short, h);
-}
-
 // a bound (integer key, smaller = better) moved by E towards "worse", rounded outwards; 0xFFFFFFFF (none) stays
 __device__ __forceinline__ uint32_t qk_ord_widen(uint32_t ord, float E, bool l2) {
     if (ord == 0xFFFFFFFFu) return ord;
@@ -111,40 +99,14 @@ int qk_launch_shadow_convert(hipStream_t st, const float4 *vecs, int nblk, const
 }
 
 // ---- the queries: fp16 copy in B-operand order, and every query's error bound -----------------------------------------------------
-// One wave per query.  xq4[(q * nblk + c) * 4 + g] holds columns 16c + g + {0, 4, 8, 12}; lane (c, g) converts that float4, the lanes of
-// an even c write their 8 B and those of c + 1 behind them: xqh[(q * nbs + b) * 4 + g], which the scan stages like xq4.
+// One wave per query: qk_shadow_prep_query (qk_scan_types.h).  This launch serves every grouping path but the small-batch one, whose
+// seed waves do the same work (k_group_seed, qk_scan.hip).
 __global__ __launch_bounds__(256) void k_shadow_prep(const float4 *__restrict__ xq4, const float *__restrict__ xn, int64_t Q, int d, int nblk,
                                                      int metric_l2, float rho, float xmax, uint4 *__restrict__ xqh, float *__restrict__ E) {
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= Q) return;
-    const int nbs = (nblk + 1) >> 1;
-    float e2 = 0.0f;
-    uint32_t bad = 0;
-    for (int c0 = 0; c0 < 2 * nbs; c0 += 16) {  // 16 arena blocks (64 float4) per round; d <= 256: one round
-        const int c = c0 + (lane >> 2), g = lane & 3;
-        const float4 a = c < nblk ? xq4[(q * nblk + c) * 4 + g] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float v[4] = {a.x, a.y, a.z, a.w};
-        uint32_t hb[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            float e, hf;
-            hb[i] = qk_h_bits(v[i], e, hf);
-            e2 = __fmaf_rn(e, e, e2);
-            bad |= fabsf(v[i]) <= 65504.0f ? 0u : 1u;
-        }
-        const uint32_t lo = hb[0] | (hb[1] << 16), hi = hb[2] | (hb[3] << 16);
-        const uint32_t plo = __shfl_down(lo, 4), phi = __shfl_down(hi, 4);  // lane (c + 1, g)
-        if ((c & 1) == 0 && c < 2 * nbs) xqh[(q * nbs + (c >> 1)) * 4 + g] = make_uint4(lo, hi, plo, phi);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) e2 += __shfl_xor(e2, o);
-    const bool anybad = __ballot(bad != 0) != 0;
-    if (lane == 0) {
-        const float up = 1.0009765625f;
-        float b = anybad ? -1.0f : qk_shadow_bound(metric_l2, d, sqrtf(xn[q]) * up, sqrtf(e2) * up, rho, xmax);
-        E[q] = b >= 0.0f ? b : -1.0f;  // (NaN: no bound)
-    }
+    qk_shadow_prep_query(xq4, xn, q, d, nblk, metric_l2, rho, xmax, xqh, E, lane);
 }
 
 int qk_launch_shadow_prep(hipStream_t st, const float4 *xq4, const float *xn, int64_t Q, int d, int nblk, int metric, float rho, float xmax,
@@ -512,18 +474,19 @@ __global__ __launch_bounds__(64, QK_SF_WAVES) void k_shadow_finish(ShadowFinishP
         F.out_ids[q * k + e] = oid;
         if (F.out_dist) F.out_dist[q * k + e] = od;
     }
-    if (lane == 0) {
-        if (verified) atomicAdd(&F.counters[0], 1ull);
-        if (fell_back) atomicAdd(&F.counters[1], 1ull);
-        if (ncand) atomicAdd(&F.counters[2], (unsigned long long)ncand);
-        if (!flagged && chained) atomicAdd(&F.counters[3], 1ull);  // (the serial walk of the chained records ran)
+    if (lane == 0) {  // the query's stripe: a launch of 1024 queries puts 16 adds on a line, not 1024 (qk_internal.h)
+        unsigned long long *c = F.counters + (size_t)(q & (QK_SHADOW_STRIPES - 1)) * QK_SHADOW_STRIPE_WORDS;
+        if (verified) atomicAdd(&c[0], 1ull);
+        if (fell_back) atomicAdd(&c[1], 1ull);
+        if (ncand) atomicAdd(&c[2], (unsigned long long)ncand);
+        if (!flagged && chained) atomicAdd(&c[3], 1ull);  // (the serial walk of the chained records ran)
     }
 }
 
 int qk_shadow_counters_ensure(qk_ctx *ctx, hipStream_t st) {
     if (ctx->shadow_counters) return QK_OK;
-    QK_HIP(hipMalloc((void **)&ctx->shadow_counters, 4 * sizeof(unsigned long long)));
-    QK_HIP(hipMemsetAsync(ctx->shadow_counters, 0, 4 * sizeof(unsigned long long), st));
+    QK_HIP(hipMalloc((void **)&ctx->shadow_counters, QK_SHADOW_COUNTER_WORDS * sizeof(unsigned long long)));
+    QK_HIP(hipMemsetAsync(ctx->shadow_counters, 0, QK_SHADOW_COUNTER_WORDS * sizeof(unsigned long long), st));
     return QK_OK;
 }
 
@@ -623,7 +586,7 @@ int qk_debug_shadow_finish(qk_ctx *ctx, qk_store *s, int64_t Q, int k, int metri
     const float4 *xq4 = nullptr;
     const float *xn = nullptr;
     QK_TRY(qk_prep_queries(ctx, d_x, Q, s->d, &xq4, &xn));  // (the library's own preparation: the norms)
-    unsigned long long c0[4], c1[4];
+    unsigned long long c0[QK_SHADOW_COUNTER_WORDS], c1[QK_SHADOW_COUNTER_WORDS];  // every stripe before and after; summed behind the synchronisation
     QK_HIP(hipMemcpyAsync(c0, ctx->shadow_counters, sizeof(c0), hipMemcpyDeviceToHost, st));
     ShadowFinishParams fp;
     fp.pair_head = d_head;
@@ -656,7 +619,10 @@ int qk_debug_shadow_finish(qk_ctx *ctx, qk_store *s, int64_t Q, int k, int metri
     QK_HIP(hipMemcpyAsync(out_ids, d_ids, (size_t)Q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (out_dist) QK_HIP(hipMemcpyAsync(out_dist, d_dist, (size_t)Q * k * sizeof(float), hipMemcpyDeviceToHost, st));
     QK_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < 4; i++) counters[i] = (int64_t)(c1[i] - c0[i]);
+    unsigned long long t0[4], t1[4];
+    qk_shadow_counters_total(c0, t0);
+    qk_shadow_counters_total(c1, t1);
+    for (int i = 0; i < 4; i++) counters[i] = (int64_t)(t1[i] - t0[i]);
     return QK_OK;
 }
 
